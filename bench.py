@@ -10,8 +10,9 @@ touches the GPU (spawn_ranks: free master port on 127.0.0.1, rank 0's JSON line 
 is re-exec'ed).  The line says what the collectives saw: `ranks_seen` (dist.get_world_size()), `backend`, and `devices`, one
 (rank, device index, device name) entry per rank.
 
-WORKLOAD.  `--images` (default 5120 = BASELINE configs[1]'s "5k") calibration images PER GPU; --steps only decides how
-they are cut into batches (batch = images / steps: 256 at the driver's 20 steps, 128 at 40), never how many there are.
+WORKLOAD.  K = --steps batches of 256 images PER GPU (--batch to change the size): the step is a fixed amount of work and
+K sets how many are timed; the default 20 steps are BASELINE configs[1]'s "5k" (5 120 images).  `--images I` instead fixes
+the images per GPU and cuts them into K batches (batch = ceil(I / K)).
 `--total-images T` instead fixes the WHOLE job (strong scaling, "scaling": "strong"; `--gpus 8 --total-images 50000` is
 BASELINE configs[3] verbatim): ceil(T / 256) batches of 256 images (--batch to change it) dealt round-robin to the ranks, the
 SAME batch at every N -- so that the N = 1 and the N = 8 point of the curve time the same kernels -- and --steps is derived
@@ -21,9 +22,15 @@ A "step" is one calibration batch taken through the whole hot path: forward -> a
 histograms (pass 2); the timed region is ONE complete Quantity.activation_quantize() over the K batches of every GPU:
 both passes, the MAX / SUM all-reduces, the KL threshold sweep of all 71 rows and the feat.table write.  Inputs are
 synthetic fp32 images generated on the device BEFORE the timed region.  value = images processed by all ranks / wall
-time (max over ranks, bracketed by barrier + synchronize).
+time (max over ranks, bracketed by barrier + synchronize); ms_per_step = that wall time / K.
 
-The JSON line also carries
+A plain run does only that: set up, warm up, time the K steps and print the line (the headline keys, the workload, the
+phases, feat_table_sha256 / statistics_sha256 and what the timed region's own HIP events measured: `roofline`,
+`roofline_hist_chain`, `roofline_hist_pair`).  `--dump-outputs DIR` also writes what the timed calibration computed as
+DIR/<name>.npy (rank 0, dump_outputs()); the same arguments give the same inputs, so two builds can be compared array by
+array.  Everything else is measured with `--full` only (the --no-* switches select within it).
+
+With --full the JSON line also carries
   value_cold   : the same workload in a FRESH process whose allocator pool is empty when the clock starts (no activation
                  cache: the engine never grows its pool for one; every hipMalloc inside the clock) -- what a one-shot
                  calibration script gets; `value` itself runs in a process that holds a warm pool (a long-running calibration service);
@@ -79,12 +86,19 @@ F32_MFMA_PEAK_TFLOPS = 157.3                 # dense fp32 MFMA peak (v_mfma_f32_
 
 class DeviceBatches(object):
     """Sequence of (images, None) pairs indexed by GLOBAL batch index; only this rank's batches
-    (i % world == rank) exist, pre-generated in HBM from generator seed 1234 + i."""
+    (i % world == rank) exist, pre-generated in HBM from generator seed 1234 + i.  A rank holds at most DISTINCT of them
+    (39 GB at 256 images of 224^2): its k-th batch for k >= DISTINCT is its (k % DISTINCT)-th again, so that a long run
+    (large --steps) does not have to fit all its inputs in HBM beside the pool."""
+    DISTINCT = 256
 
     def __init__(self, total, batch, hw, rank, world, device, on_host=False):
         self._items = {}
         self._total = total
-        for i in range(rank, total, world):
+        owned = list(range(rank, total, world))
+        for k, i in enumerate(owned):
+            if k >= self.DISTINCT:
+                self._items[i] = self._items[owned[k % self.DISTINCT]]
+                continue
             g = torch.Generator(device=device).manual_seed(1234 + i)
             t = torch.randn(batch, 3, hw, hw, generator=g, device=device)
             self._items[i] = t.cpu() if on_host else t       # --host-inputs: pageable host memory
@@ -518,18 +532,37 @@ def cpu_baseline(model_cpu_ctor, hw, n_images_full, q, log):
                                                                                      len(names), n_images_full)}
 
 
+def dump_outputs(out_dir, q, bits):
+    """--dump-outputs: what the timed calibration handed back and the statistics it was decided on, one row per tensor in the
+    calibration's order ("image" first, then the cared layers, as in feat.table):
+      bits.npy      float64[T]     the bit of every tensor, what activation_quantize() returns (feat.table is written from it);
+      absmax.npy    float32[T]     the running abs-max after pass 1 (and its MAX all-reduce);
+      hist.npy      float64[T, B]  the histogram counts after pass 2 (and its SUM all-reduce), exact as float64;
+      threshold.npy float64[T]     the KL threshold of every tensor, (t* + 0.5) x its bin width."""
+    names = list(q._quantizer._tensor_list)
+    arrays = {"bits": np.array([bits[n] for n in names], dtype=np.float64),
+              "absmax": q._collector.max_device.cpu().numpy().astype(np.float32),
+              "hist": q._collector.hist_device.cpu().numpy().astype(np.float64),
+              "threshold": np.array([q._quantizer.threshold_value[n] for n in names], dtype=np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--images", type=int, default=5120,
-                    help="calibration images PER GPU (weak scaling); BASELINE configs[1] = 5k")
+    ap.add_argument("--images", type=int, default=0,
+                    help="calibration images PER GPU (weak scaling), cut into --steps batches; default: --steps x --batch "
+                         "(20 x 256 = BASELINE configs[1]'s 5k)")
     ap.add_argument("--total-images", type=int, default=0,
                     help="calibration images of the WHOLE job (strong scaling; overrides --images): "
                          "--gpus 8 --total-images 50000 is BASELINE configs[3]")
-    ap.add_argument("--batch", type=int, default=0, help="images per step; default: images per GPU / steps")
+    ap.add_argument("--batch", type=int, default=0, help="images per step; default: 256, or --images / --steps")
     ap.add_argument("--model", default="r50", choices=["r50", "r101"])
     ap.add_argument("--image", type=int, default=224)
     ap.add_argument("--host-inputs", action="store_true",
@@ -550,7 +583,15 @@ def parse_args():
     ap.add_argument("--dry-launch", action="store_true",
                     help="launch plumbing only (no GPU needed): every rank joins a gloo group and rank 0 prints a JSON line with "
                          "ranks_seen / devices / the workload split -- what tests/test_bench_launch_cpu.py runs")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the fresh-process run (value_cold), the split-bf16 calibration, the "
+                         "producer / fake-quant rooflines, the int8-sim / fake-quant / float forwards, the CPU baseline, file inputs "
+                         "and the per-channel calibration (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed calibration computed (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)          # the bench changes its working directory
     world = max(args.gpus, 1)
     if args.total_images:
         # STRONG scaling (BASELINE configs[3]): the whole job is fixed and so is the batch -- 256 images per forward at EVERY N, so that
@@ -562,8 +603,11 @@ def parse_args():
         args.total_batches = -(-args.total_images // args.batch)
         args.steps = -(-args.total_batches // world)
     else:
+        # WEAK scaling: a step is one batch of a fixed size (256 unless --batch says otherwise), so that --steps sets how much
+        # work is timed and ms_per_step is the time of the same unit of work at any K; --images I instead fixes the images
+        # per GPU and cuts them into K batches.
         if args.batch <= 0:
-            args.batch = max(1, -(-args.images // max(args.steps, 1)))
+            args.batch = max(1, -(-args.images // max(args.steps, 1))) if args.images else 256
         args.total_batches = args.steps * world
     args.scaling = "strong" if args.total_images else "weak"
     args.images_per_gpu = args.batch * args.steps            # the busiest rank's share (== --images when steps divides it)
@@ -716,7 +760,7 @@ def main():
 
     # the fresh-process run goes FIRST, before this process touches the GPU: it needs the device's memory to itself
     cold = None
-    if world == 1 and not args.no_cold and not args.host_inputs:
+    if args.full and world == 1 and not args.no_cold and not args.host_inputs:
         cold = run_cold_child(args, log)
 
     assert torch.cuda.is_available(), "bench.py needs an MI355X"
@@ -803,7 +847,7 @@ def main():
         kt_hist.enabled = kt_chain.enabled = kt_pair.enabled = True
         barrier()
         t0 = time.perf_counter()
-        q.activation_quantize(data)
+        bits = q.activation_quantize(data)
         barrier()
         elapsed = time.perf_counter() - t0
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -832,7 +876,7 @@ def main():
         "metric": BASELINE_METRIC,
         "metric_note": "value = calibration images/s (both passes + KL sweep + feat.table, end to end) in SERVICE MODE: a process that "
                        "has calibrated before and holds a warm allocator pool of 80 % of HBM (230 GB), which pass 1's activations are kept "
-                       "in for pass 2; value_cold = the same workload in a fresh process (allocation inside the clock); "
+                       "in for pass 2; with --full: value_cold = the same workload in a fresh process (allocation inside the clock); "
                        "int8-sim images/s is reported beside it as int8_sim_images_per_s (resident integer activations, logits "
                        "bit-identical to int8_sim_fp32_boundary_images_per_s, the reference's module-boundary form)",
         "value": round(value, 2), "unit": "images/s", "n_gpus": world, "ranks_seen": ranks_seen,
@@ -844,7 +888,7 @@ def main():
                                "(batch %d x %d steps), %d images in the whole job, %d histogram rows x 2048 bins" %
                                ("50" if args.model == "r50" else "101", K * B, HW, HW, B, K, images, rows),
                    "batch": B, "images_per_gpu": K * B, "images_total": images, "batches_total": TB,
-                   "images_requested": args.total_images or args.images * world, "parallelism": "dp%d" % world,
+                   "images_requested": args.total_images or (args.images or args.images_per_gpu) * world, "parallelism": "dp%d" % world,
                    "sharding": "batch i -> rank i %% %d; one MAX all-reduce of fp32[%d] after pass 1, one SUM all-reduce of "
                                "int64[%d] after pass 2 (RCCL); KL replicated; rank 0 writes feat.table" % (world, rows, rows * 2048),
                    "activation_cache": "pass-1 activations kept in a warm allocator pool (80 % of HBM, grown during warm-up); "
@@ -911,6 +955,24 @@ def main():
         sm = kt.summary()
         if sm:
             result[key] = hbm_roofline(kernel, sm, {"note": note, "launches_are": "calls of the entry point (a chain call launches one kernel per chain)"})
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, q, bits)
+
+    def finish():
+        sys.stdout = real_stdout
+        sys.stdout.flush()
+        os.dup2(stdout_fd, 1)
+        if rank == 0:
+            log("feat.table head:", feat_table.split("\n")[:4])
+            print(json.dumps(result), flush=True)
+        if distributed:
+            barrier()
+            dist.destroy_process_group()
+        return 0 if own_everywhere else 3
+
+    if not args.full:
+        return finish()
 
     # ---- the same calibration with the float 1x1 layers on the split-bf16 kernels (FQ_CONV_SPLIT_BF16=1: every fp32 operand as three
     # bf16 pieces, six of the nine products on the bf16 matrix cores, fp32 accumulation -- as accurate as the fp32 fma chain, DESIGN.md
@@ -1326,16 +1388,7 @@ def main():
         except Exception as e:
             result["per_channel_calibration"] = {"error": repr(e)}
 
-    sys.stdout = real_stdout
-    sys.stdout.flush()
-    os.dup2(stdout_fd, 1)
-    if rank == 0:
-        log("feat.table head:", feat_table.split("\n")[:4])
-        print(json.dumps(result), flush=True)
-    if distributed:
-        barrier()
-        dist.destroy_process_group()
-    return 0 if own_everywhere else 3
+    return finish()
 
 
 if __name__ == "__main__":

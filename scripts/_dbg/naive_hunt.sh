@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/naive
 mkdir -p $OUT
 for V in 0 1; do
   export FQ_OWN_CONV1X1=$V
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/own$V -- python3 $R/bench.py --steps 4 --warmup 2 --images 512 --no-cold --no-cpu-baseline --no-recon --no-per-channel > $OUT/own$V.json 2> $OUT/own$V.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/own$V -- python3 $R/bench.py --full --steps 4 --warmup 2 --images 512 --no-cold --no-cpu-baseline --no-recon --no-per-channel > $OUT/own$V.json 2> $OUT/own$V.err
   echo "== FQ_OWN_CONV1X1=$V"; grep -h -i "naive\|grouped_conv" $(find $OUT/own$V -name "*kernel_stats.csv") | cut -c1-60,200-260
   python3 - $OUT/own$V <<'PY'
 import csv, glob, sys

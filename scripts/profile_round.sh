@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box: rocprofv3 evidence for bench.py (kernel trace + stats, then HBM counters in their own passes).
 # usage: scripts/profile_round.sh <tag>      (writes gpurun_out/prof_<tag>/...)
-# The traced command is the driver's (`--steps 20 --warmup 5`: 5 120 images per GPU, batch 256) minus the fresh-process
+# The traced command is the driver's with --full (`--steps 20 --warmup 5`: 5 120 images per GPU, batch 256) minus the fresh-process
 # run behind value_cold (--no-cold): a child process of a profiled program would be profiled as well, and the box does
 # not allow a program that has initialised the GPU (the profiler's preload has) to start another one that way.
 set -u
@@ -12,7 +12,7 @@ make -C $R/oracle -s                     # the cpu_baseline leg must not compile
 cd /tmp
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
-ARGS="--steps 20 --warmup 5 --no-cold"
+ARGS="--full --steps 20 --warmup 5 --no-cold"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py $ARGS > $OUT/bench_line.json 2> $OUT/trace_err.log
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -- python3 $R/bench.py $ARGS --no-cpu-baseline --no-recon --no-file-input > $OUT/bench_line_pmc.json 2> $OUT/pmc_fetch_err.log
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -- python3 $R/bench.py $ARGS --no-cpu-baseline --no-recon --no-file-input > /dev/null 2> $OUT/pmc_write_err.log

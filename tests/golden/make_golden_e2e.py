@@ -2,9 +2,9 @@
 """Capture end-to-end golden fixtures (G3, G4, G6, G7 of SURVEY.md section 8c) by running the imported
 reference in the build container:
 
-    python tests/golden/make_golden_e2e.py [r18] [g6] [g7] [dkl] [small] [random]
+    python tests/golden/make_golden_e2e.py [r18] [g6] [g7] [dkl] [small] [random] [bnsqrt]
 
-Writes tests/golden/g3_r18_e2e.json (+ g4_r18_recon.npz), g6_rewriter.json, g7_netinfo.json.
+Writes tests/golden/g3_r18_e2e.json (+ g4_r18_recon.npz), g6_rewriter.json, g7_netinfo.json; `bnsqrt` g15_bn_sqrt.npz.
 Fixtures hold inputs' recipes and the reference's outputs only.
 """
 import hashlib
@@ -334,9 +334,40 @@ def capture_g7(cq, tl):
         json.dump(out, fh, indent=1, sort_keys=True)
 
 
+def capture_bn_sqrt(cq, tl):
+    """G15 (g15_bn_sqrt.npz): torch.sqrt(running_var + 1e-5), the one machine-dependent operation of merge_bn (utils.py:37:
+    torch.sqrt on CPU tensors goes through MKL, whose last bit differs between hosts), for every BatchNorm that the CPU goldens
+    fold with merge_bn itself: the seeded ResNet-18 of G3 / G12 and the two G8 cases.  x: the inputs, y: what torch.sqrt
+    returns for them on the golden host.  Checked on the spot: under cases.torch_sqrt_as_captured the reference's merge_bn gives the
+    parameters it gives without, and G8's merged weights and biases, bit for bit."""
+    import torch
+    import torch.nn as nn
+    from model.resnet.ResNet_18_fabu import ResNet18          # the REFERENCE's model file (first on sys.path)
+    g8 = np.load(os.path.join(HERE, "g8_merge_bn.npz"))
+    xs = [layer.running_var + 1e-5 for layer in cases.seed_model(ResNet18()).modules() if type(layer).__name__ == "BatchNorm2d"]
+    xs += [torch.from_numpy(g8[tag + "/pre/1.running_var"]) + 1e-5 for tag in ("nobias", "bias")]
+    x = torch.cat([t.reshape(-1) for t in xs])
+    x = torch.from_numpy(np.unique(x.numpy().view(np.uint32)).view(np.float32))
+    np.savez_compressed(os.path.join(HERE, "g15_bn_sqrt.npz"), x=x.numpy(), y=torch.sqrt(x).numpy())
+    plain = cq.merge_bn(cases.seed_model(ResNet18()).eval(), "cpu").state_dict()
+    with cases.torch_sqrt_as_captured():
+        pinned = cq.merge_bn(cases.seed_model(ResNet18()).eval(), "cpu").state_dict()
+    assert plain.keys() == pinned.keys() and all(torch.equal(plain[k], pinned[k]) for k in plain)
+    for tag in ("nobias", "bias"):
+        seq = nn.Sequential(nn.Conv2d(3, 8, 3, padding=1, bias=(tag == "bias")), nn.BatchNorm2d(8), nn.ReLU(False))
+        seq.load_state_dict({k[len(tag) + 5:]: torch.from_numpy(g8[k]) for k in g8.files if k.startswith(tag + "/pre/")})
+        with cases.torch_sqrt_as_captured():
+            merged = cq.merge_bn(seq.eval(), "cpu")
+        assert np.array_equal(merged[0].weight.detach().numpy(), g8[tag + "/w"])
+        assert np.array_equal(merged[0].bias.detach().numpy(), g8[tag + "/b"])
+    print("G15 written:", x.numel(), "torch.sqrt inputs; merge_bn under them == merge_bn, G8 bit for bit")
+
+
 def main():
     which = sys.argv[1:] or ["r18", "g6", "g7"]
     cq, tl = _refenv.import_reference()
+    if "bnsqrt" in which:
+        capture_bn_sqrt(cq, tl)
     if "g6" in which:
         capture_g6(cq, tl)
     if "g7" in which:

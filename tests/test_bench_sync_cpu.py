@@ -71,7 +71,7 @@ def test_bench_recon_section_helpers_keep_two_ranks_in_step(tmp_path):
 @pytest.mark.parametrize("argv,per_gpu,batch,scaling", [
     ([], 5120, 256, "weak"),                                        # the default: BASELINE configs[1], 20 steps
     (["--steps", "20", "--warmup", "5"], 5120, 256, "weak"),        # the driver's command: same 5 120 images
-    (["--steps", "40"], 5120, 128, "weak"),                         # --steps only cuts the same images differently
+    (["--steps", "40", "--images", "5120"], 5120, 128, "weak"),     # with --images, --steps cuts the same images differently
     (["--steps", "10", "--images", "1000"], 1000, 100, "weak"),
     # config 4 (strong scaling): the batch stays 256 at every N; ceil(50 000 / 256) = 196 batches, the busiest of 8 ranks owns 25
     (["--gpus", "8", "--total-images", "50000"], 6400, 256, "strong"),
@@ -79,13 +79,67 @@ def test_bench_recon_section_helpers_keep_two_ranks_in_step(tmp_path):
     (["--gpus", "2", "--total-images", "1024", "--steps", "2"], 512, 256, "strong"),
     (["--gpus", "8", "--total-images", "1024", "--batch", "64"], 128, 64, "strong"),
     (["--batch", "64", "--steps", "4"], 256, 64, "weak"),
+    (["--steps", "40"], 10240, 256, "weak"),                        # --steps alone: that many batches of 256
+    (["--gpus", "1", "--steps", "3", "--warmup", "1"], 768, 256, "weak"),
 ])
 def test_bench_workload_arithmetic(monkeypatch, argv, per_gpu, batch, scaling):
-    """`--steps` must not change the workload (round-1 review): images per GPU come from --images / --total-images, the
-    batch follows from them."""
+    """--steps alone sets how many batches of a fixed size (256, or --batch) are timed; --images / --total-images fix the
+    images instead and the batch follows from them."""
     sys.path.insert(0, ROOT)
     import bench
     monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
     args = bench.parse_args()
     assert (args.images_per_gpu, args.batch, args.scaling) == (per_gpu, batch, scaling)
     assert args.images_per_gpu == args.batch * args.steps
+
+
+def test_steps_scale_the_timed_work_at_the_same_batch(monkeypatch):
+    """What a step is does not depend on how many are run: --steps 40 times twice the images of --steps 20, in batches of the
+    same size (so N x ms_per_step grows with N, and the headline batch stays 256 whatever N is chosen)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    got = {}
+    for n in (20, 40, 3):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", str(n), "--warmup", "2"])
+        args = bench.parse_args()
+        got[n] = (args.steps, args.batch, args.images_per_gpu, args.total_batches)
+    assert got[20] == (20, 256, 5120, 20)
+    assert got[40] == (40, 256, 2 * 5120, 40)
+    assert got[3] == (3, 256, 768, 3)
+
+
+def test_bench_plain_run_by_default_and_dump_dir_made_absolute(monkeypatch, tmp_path):
+    """A plain run times the headline only (--full adds the rest); --dump-outputs is resolved before the bench changes its
+    working directory into its scratch tree."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.chdir(tmp_path)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1"])
+    args = bench.parse_args()
+    assert args.full is False and args.dump_outputs is None and args.steps == 4
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = bench.parse_args()
+    assert args.full is True and args.dump_outputs == os.path.join(os.getcwd(), "out")
+
+
+def test_dump_outputs_writes_the_calibration_rows_in_table_order(tmp_path):
+    """bench.dump_outputs on a calibration's result: one row per tensor in the calibration's order, bits as returned, the
+    maxima as fp32, the int64 histogram counts exactly as float64, the KL thresholds."""
+    import types
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    names = ["image", "Conv2d_1", "ReLU_2"]
+    hist = torch.arange(3 * 2048, dtype=torch.int64).reshape(3, 2048) * (1 << 40)
+    q = types.SimpleNamespace(
+        _quantizer=types.SimpleNamespace(_tensor_list=names, threshold_value={"image": 2.5, "Conv2d_1": np.float32(0.75),
+                                                                              "ReLU_2": 11.0}),
+        _collector=types.SimpleNamespace(max_device=torch.tensor([3.0, 1.5, 20.0]), hist_device=hist))
+    bench.dump_outputs(str(tmp_path / "d"), q, {"ReLU_2": 3, "image": 5, "Conv2d_1": 7})
+    got = {n: np.load(tmp_path / "d" / (n + ".npy")) for n in ("bits", "absmax", "hist", "threshold")}
+    assert sorted(os.listdir(tmp_path / "d")) == ["absmax.npy", "bits.npy", "hist.npy", "threshold.npy"]
+    assert got["bits"].dtype == np.float64 and got["bits"].tolist() == [5, 7, 3]
+    assert got["absmax"].dtype == np.float32 and got["absmax"].tolist() == [3.0, 1.5, 20.0]
+    assert got["hist"].dtype == np.float64 and np.array_equal(got["hist"].astype(np.int64), hist.numpy())
+    assert got["threshold"].dtype == np.float64 and got["threshold"].tolist() == [2.5, 0.75, 11.0]

@@ -46,7 +46,8 @@ def run(oracle):
 
     out = {}
     with product_workdir(input_shape="1,3,32,32", device="cpu", max_cali_img_num=1) as tmp:
-        model = merge_bn(cases.seed_model(ResNet18()).eval())
+        with cases.torch_sqrt_as_captured():      # G3 holds the golden host's torch.sqrt bits (G15)
+            model = merge_bn(cases.seed_model(ResNet18()).eval())
         q = CpuQuantity(model)
         out["net_info"] = dict(q.net_info)
         out["net_info_order"] = list(q.net_info.keys())
@@ -126,7 +127,8 @@ def test_kl_weight_branch_matches_reference(golden_dir, g3, oracle):
     with open(os.path.join(golden_dir, "g3b_r18_dkl_weights.json")) as fh:
         ref = json.load(fh)
     with product_workdir(input_shape="1,3,32,32", device="cpu", max_cali_img_num=1) as tmp:
-        q = CpuQuantity(merge_bn(cases.seed_model(ResNet18()).eval()))
+        with cases.torch_sqrt_as_captured():
+            q = CpuQuantity(merge_bn(cases.seed_model(ResNet18()).eval()))
         wd = os.path.join(tmp, "test", "workdir")
         with open(os.path.join(wd, "feat.table"), "w") as fh:
             fh.write(g3["feat_table"])

@@ -95,7 +95,7 @@ def test_single_rank_rccl_calibration_gives_the_reference_tables(tmp_path, golde
 def test_bench_runs_under_the_distributed_launcher_with_rccl():
     """bench.py exactly as the driver launches it for N > 1, with N = 1: RCCL init, barriers, the MAX of the elapsed times,
     the table broadcast and the agreement all-reduces of the int8 section all execute; small workload."""
-    r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--images", "256", "--steps", "2", "--warmup", "1",
+    r = _torchrun([os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--images", "256", "--steps", "2", "--warmup", "1",
                    "--int8-batch", "64", "--no-cold", "--no-cpu-baseline"], 29672)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.strip().split("\n") if ln.startswith("{")][-1]
@@ -117,7 +117,7 @@ def test_bench_eight_rank_flow_runs_to_its_json_line_on_one_gpu():
     and no error key -- so that the first real 8-GPU run cannot die on plumbing."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", FQ_BENCH_BACKEND="gloo", FQ_BENCH_POOL_FRAC="0.05", OMP_NUM_THREADS="2")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--total-images", "1024", "--batch", "64",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--total-images", "1024", "--batch", "64",
                         "--steps", "2", "--warmup", "1", "--int8-batch", "32", "--no-cold", "--no-cpu-baseline", "--no-per-channel"],
                        env=env, capture_output=True, text=True, timeout=1400)
     assert r.returncode == 0, r.stderr[-3000:]
