@@ -225,6 +225,12 @@ int fq_add_sat_f32(const float* a, const float* b, float* y, size_t n, int bitwi
  *   y = clamp( RightShift(acc, rs) + qbias[c] ) / 2^ob      (qbias fp32[C], integer valued) */
 int fq_recon_epilogue_f32(const float* acc, const float* qbias, float* y, size_t outer, size_t C,
                           size_t inner, int rs, int ob, int bitwidth, fq_stream_t stream);
+/* fq_recon_epilogue_f32 for a layer whose shift is one per output channel (per-channel weight bits):
+ *   y = clamp( RightShift(acc, rs_k[c]) + qbias[c] ) / 2^ob
+ * rs_k: device int32[C]; rs_min <= rs_k[c] <= rs_max (the caller's bounds; FQ_ERR_INVALID_ARG unless
+ * -120 <= rs_min <= rs_max <= 120; a shift outside the bounds it gives is undefined behaviour of the caller). */
+int fq_recon_epilogue_pcs_f32(const float* acc, const float* qbias, const int32_t* rs_k, int rs_min, int rs_max, float* y,
+                              size_t outer, size_t C, size_t inner, int ob, int bitwidth, fq_stream_t stream);
 /* weight quantiser, pytorch_quantizer.py:656-657,:663: (int32) clip(around(w * 2^bit), -128, 127) */
 int fq_quantize_param_i32(const float* w, int32_t* q, size_t n, int bit, fq_stream_t stream);
 
@@ -467,6 +473,52 @@ int fq_conv2d_i8_add_resident(const int8_t* x_nhwc, const int8_t* w_krsc, const 
                               int relu, int Kpad, int N, int H, int W, int C, int K, int R, int S, int stride_h,
                               int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int rs, int ob,
                               fq_stream_t stream);
+
+/* Per-channel weight bits: fq_conv2d_i8 / _resident / _add_resident with the shift taken per output channel,
+ *   RightShift(acc[k], rs_k[k])   in place of   RightShift(acc[k], rs),
+ * everything else (arguments, outputs, limits, the kernel the dispatch picks) as in the per-tensor entry point.
+ * rs_k: device int32[K], 16-byte aligned.  rs_min / rs_max: bounds of rs_k that the caller knows on the host
+ * (-120 <= rs_min <= rs_max <= 120, FQ_ERR_INVALID_ARG otherwise); a shift outside them is undefined behaviour of the
+ * caller.  The integer tail runs when rs_min >= 1, rs_max <= 16 and the accumulator bound holds at rs_max, the fp32 tail
+ * otherwise -- both give the reference's integers.  A constant vector rs_k[k] = rs gives the bytes of the per-tensor entry
+ * point with rs.  fq_conv2d_i8_last_variant reports the same numbers.  Two exceptions to "the same kernel": the opt-in
+ * conv1x1_i8_stream (FQ_CONV_STREAM=1) declines per-channel layers, and the halo / c64 kernels' per-channel forms declare
+ * 4 x TK more static LDS, so near their two-workgroups-per-CU LDS budget a per-channel layer may take the halo form with
+ * a shorter weight ring, or the DMA kernel, where the per-tensor layer takes the halo form (same integers either way). */
+int fq_conv2d_i8_pcs(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, const int32_t* rs_k, int rs_min,
+                     int rs_max, float* y_nchw, int N, int H, int W, int C, int K, int R, int S, int stride_h, int stride_w,
+                     int pad_h, int pad_w, int dil_h, int dil_w, int ob, int bitwidth, fq_stream_t stream);
+int fq_conv2d_i8_resident_pcs(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, const int32_t* rs_k, int rs_min,
+                              int rs_max, float* y_nchw, int8_t* q_nhwc, int Kpad, int relu, int N, int H, int W, int C, int K,
+                              int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int ob,
+                              fq_stream_t stream);
+int fq_conv2d_i8_add_resident_pcs(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, const int32_t* rs_k,
+                                  int rs_min, int rs_max, const void* res, int res_bytes, int g_res, int16_t* wide, int g_wide,
+                                  int8_t* narrow, int ib, int relu, int Kpad, int N, int H, int W, int C, int K, int R, int S,
+                                  int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int ob,
+                                  fq_stream_t stream);
+
+/* fq_block_tail_i8 / fq_block_tail_proj_i8 / fq_conv2d_i8_stem with one shift per output channel: each `int rs*` becomes
+ * `const int32_t* rs*_k, int rs*_min, int rs*_max` (device int32, K3 / C2 / K entries; a per-tensor layer passes a constant
+ * vector).  These kernels have the integer tail only: every shift in [1, 16] (the _supported checks say no otherwise, and
+ * fq_conv2d_i8_resident_pcs / _add_resident_pcs compute the same integers).  Same variants reported as the per-tensor forms. */
+int fq_block_tail_i8_pcs_supported(int C, int K3, int C2, int rs3_min, int rs3_max, int rs1_min, int rs1_max, int ob3, int g_res,
+                                   int res_bytes, int ib);
+int fq_block_tail_i8_pcs(const int8_t* x_nhwc, const int8_t* w3_krsc, const float* qbias3, const int32_t* rs3_k, int rs3_min,
+                         int rs3_max, int ob3, const void* res, int res_bytes, int g_res, int16_t* wide, int g_wide, int8_t* narrow,
+                         int ib, int relu, const int8_t* w1_krsc, const float* qbias1, const int32_t* rs1_k, int rs1_min, int rs1_max,
+                         int relu1, int8_t* q1_nhwc, long M, int C, int K3, int C2, fq_stream_t stream);
+int fq_block_tail_proj_i8_pcs_supported(int C, int K3, int C2, int CP, int rs3_min, int rs3_max, int rs1_min, int rs1_max,
+                                        int rsp_min, int rsp_max, int stride_p);
+int fq_block_tail_proj_i8_pcs(const int8_t* x_nhwc, const int8_t* w3_krsc, const float* qbias3, const int32_t* rs3_k, int rs3_min,
+                              int rs3_max, int ob3, const int8_t* xp_nhwc, const int8_t* wp_krsc, const float* qbiasp,
+                              const int32_t* rsp_k, int rsp_min, int rsp_max, int obp, int stride_p, int Hp, int Wp, int16_t* wide,
+                              int g_wide, int8_t* narrow, int ib, int relu, const int8_t* w1_krsc, const float* qbias1,
+                              const int32_t* rs1_k, int rs1_min, int rs1_max, int relu1, int8_t* q1_nhwc, int N, int H, int W, int C,
+                              int K3, int C2, int CP, fq_stream_t stream);
+int fq_conv2d_i8_stem_pcs(const float* x_nchw, const int8_t* w_stem, const float* qbias, const int32_t* rs_k, int rs_min, int rs_max,
+                          int8_t* q_nhwc, int Kpad, int relu, int N, int C, int H, int W, int K, int R, int S, int stride_h,
+                          int stride_w, int pad_h, int pad_w, int ib, int ob, fq_stream_t stream);
 
 /* The tail of a bottleneck block and the head of the next one in ONE kernel (round 4):
  *   NewConv2d.forward of conv3 (1x1, C -> K3; new_quantity_op.py:124-133)  ->  NewAdd.forward with the shortcut (:166-174)

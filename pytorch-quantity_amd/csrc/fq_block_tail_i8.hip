@@ -53,6 +53,10 @@ struct BtParams {
     TailParams tp;
     unsigned xp_bytes;
     int sp, Ho, Wo, Hp, Wp;              // stride of the projection; output plane; the plane of xp
+    // per-channel shifts (kPcs): [K3] for conv3 and the projection, [C2] for the next conv1; t3 / tp / t1.rs are then unused
+    const int* rs3_k;
+    const int* rsp_k;
+    const int* rs1_k;
 };
 
 // LDS rows of RB bytes hold RB / 16 chunks of 16 bytes; position c of row r holds chunk c ^ swz_of(r), chosen so that the 16 lanes
@@ -65,24 +69,43 @@ template <int RB> __device__ __forceinline__ int swz_of(int row) {
 // The four-instruction tail (fq_int_tail.h) of four consecutive channels: their constants are three 16-byte LDS reads (G = 4), or
 // two rounds of three 8-byte reads (G = 2) where twelve constant registers at a time are more than the kernel has left
 typedef int v2i_t __attribute__((ext_vector_type(2)));
-template <int G, int N>
+// kPcs: the shift is per channel, packed into the lower clamp bound (conv_tail_kp); rs is unused.
+template <int G, int N, bool kPcs = false>
 __device__ __forceinline__ void tail4(int (&v)[4], int a0, int a1, int a2, int a3, const int (&t)[3][N], int ch, int rs) {
     const int acc[4] = {a0, a1, a2, a3};
     if constexpr (G == 4) {
         const v4i cB = *reinterpret_cast<const v4i*>(&t[0][ch]), cL = *reinterpret_cast<const v4i*>(&t[1][ch]),
                   cH = *reinterpret_cast<const v4i*>(&t[2][ch]);
+        if constexpr (kPcs) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = conv_tail_k(acc[e], cB[e], cL[e], cH[e], rs);
+            for (int e = 0; e < 4; ++e) v[e] = conv_tail_kp(acc[e], cB[e], cL[e], cH[e]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = conv_tail_k(acc[e], cB[e], cL[e], cH[e], rs);
+        }
     } else {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const v2i_t cB = *reinterpret_cast<const v2i_t*>(&t[0][ch + 2 * h]), cL = *reinterpret_cast<const v2i_t*>(&t[1][ch + 2 * h]),
                         cH = *reinterpret_cast<const v2i_t*>(&t[2][ch + 2 * h]);
-            v[2 * h] = conv_tail_k(acc[2 * h], cB[0], cL[0], cH[0], rs);
-            v[2 * h + 1] = conv_tail_k(acc[2 * h + 1], cB[1], cL[1], cH[1], rs);
+            if constexpr (kPcs) {
+                v[2 * h] = conv_tail_kp(acc[2 * h], cB[0], cL[0], cH[0]);
+                v[2 * h + 1] = conv_tail_kp(acc[2 * h + 1], cB[1], cL[1], cH[1]);
+            } else {
+                v[2 * h] = conv_tail_k(acc[2 * h], cB[0], cL[0], cH[0], rs);
+                v[2 * h + 1] = conv_tail_k(acc[2 * h + 1], cB[1], cL[1], cH[1], rs);
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
     }
+}
+
+// The constants of one channel for tail4<..., true>: B / hi (tail_consts) and this channel's shift rs_k[i] in lo (pack_lo_rs).
+template <bool kPcs>
+__device__ __forceinline__ void stage_bt(int (&t)[3][1024], int i, int qb, const TailParams& tp, const int* rs_k) {
+    const int rs = rs_k[i];
+    const TailK k = tail_consts_rs(qb, tp, rs);
+    t[0][i] = k.B; t[1][i] = pack_lo_rs(k.lo, rs); t[2][i] = k.hi;
 }
 
 // C: conv3's input channels (64 / 128).  C2: the fused next conv1's output channels (64 / 128; 0: no next conv -- the kernel is
@@ -96,7 +119,7 @@ __device__ __forceinline__ void tail4(int (&v)[4], int a0, int a1, int a2, int a
 // workgroup multiplies its 128 pixels of the block input with the slice's 128 rows of wp right before conv3's slice, runs the
 // projection's own integer tail, and passes the bytes through the wave's rows of the LDS tile into the registers the shortcut would
 // have been loaded into: same integers, CP instead of K3 bytes per pixel read, nothing written.
-template <int C, int C2, bool kRes16, int CP = 0>
+template <int C, int C2, bool kRes16, int CP = 0, bool kPcs = false>
 __global__ __launch_bounds__(kConvBlock) __attribute__((amdgpu_waves_per_eu(FQ_BT_WAVES))) void block_tail_i8_kernel(
     const int8_t* __restrict__ x, const int8_t* __restrict__ w3, const float* __restrict__ qbias3,
     const int8_t* __restrict__ w1, const float* __restrict__ qbias1, int8_t* __restrict__ q1, const BtParams p) {
@@ -126,19 +149,32 @@ __global__ __launch_bounds__(kConvBlock) __attribute__((amdgpu_waves_per_eu(FQ_B
     const int m0 = blockIdx.x * kTP;
     const int KT = p.K3 >> 7;
 
-    for (int i = tid; i < p.K3; i += kConvBlock) {
-        const TailK k = tail_consts((int)qbias3[i], p.t3);                           // (biases are integer valued by contract)
-        sT3[0][i] = k.B; sT3[1][i] = k.lo; sT3[2][i] = k.hi;
-    }
-    if constexpr (kProj) {
+    if constexpr (kPcs) {
+        for (int i = tid; i < p.K3; i += kConvBlock) stage_bt<true>(sT3, i, (int)qbias3[i], p.t3, p.rs3_k);
+        if constexpr (kProj) {
+            for (int i = tid; i < p.K3; i += kConvBlock) stage_bt<true>(sTP, i, (int)p.qbiasp[i], p.tp, p.rsp_k);
+        }
+    } else {
         for (int i = tid; i < p.K3; i += kConvBlock) {
-            const TailK k = tail_consts((int)p.qbiasp[i], p.tp);
-            sTP[0][i] = k.B; sTP[1][i] = k.lo; sTP[2][i] = k.hi;
+            const TailK k = tail_consts((int)qbias3[i], p.t3);                           // (biases are integer valued by contract)
+            sT3[0][i] = k.B; sT3[1][i] = k.lo; sT3[2][i] = k.hi;
+        }
+        if constexpr (kProj) {
+            for (int i = tid; i < p.K3; i += kConvBlock) {
+                const TailK k = tail_consts((int)p.qbiasp[i], p.tp);
+                sTP[0][i] = k.B; sTP[1][i] = k.lo; sTP[2][i] = k.hi;
+            }
         }
     }
     if (kNext && tid < C2) {
-        const TailK k = tail_consts((int)qbias1[tid], p.t1);
-        sT1[0][tid] = k.B; sT1[1][tid] = k.lo; sT1[2][tid] = k.hi;
+        if constexpr (kPcs) {
+            const int rs = p.rs1_k[tid];
+            const TailK k = tail_consts_rs((int)qbias1[tid], p.t1, rs);
+            sT1[0][tid] = k.B; sT1[1][tid] = pack_lo_rs(k.lo, rs); sT1[2][tid] = k.hi;
+        } else {
+            const TailK k = tail_consts((int)qbias1[tid], p.t1);
+            sT1[0][tid] = k.B; sT1[1][tid] = k.lo; sT1[2][tid] = k.hi;
+        }
     }
 
     // ---- x: this lane's pixel, 16 bytes per sub-step, for the whole tile's life
@@ -293,7 +329,7 @@ __global__ __launch_bounds__(kConvBlock) __attribute__((amdgpu_waves_per_eu(FQ_B
                     for (int g = 0; g < 4; ++g) {
                         int v[4];
                         const int byte = (2 * hs + a) * 32 + 8 * g + 4 * half;          // first of this lane's four channels
-                        tail4<TG>(v, acc[a][4 * g], acc[a][4 * g + 1], acc[a][4 * g + 2], acc[a][4 * g + 3], sTP, k0 + byte, p.tp.rs);
+                        tail4<TG, 1024, kPcs>(v, acc[a][4 * g], acc[a][4 * g + 1], acc[a][4 * g + 2], acc[a][4 * g + 3], sTP, k0 + byte, p.tp.rs);
                         *reinterpret_cast<unsigned*>(my_row + (((byte >> 4) ^ my_swz) * 16) + (byte & 15)) = pack4(v[0], v[1], v[2], v[3]);
                         __builtin_amdgcn_sched_barrier(0);
                     }
@@ -342,7 +378,7 @@ __global__ __launch_bounds__(kConvBlock) __attribute__((amdgpu_waves_per_eu(FQ_B
                 for (int g = 0; g < 4; ++g) {
                     int v[4];
                     const int byte = (PT * hs + a) * 32 + 8 * g + 4 * half;          // channel of v[0] inside the slice
-                    tail4<TG>(v, acc[a][4 * g], acc[a][4 * g + 1], acc[a][4 * g + 2], acc[a][4 * g + 3], sT3, k0 + byte, p.t3.rs);
+                    tail4<TG, 1024, kPcs>(v, acc[a][4 * g], acc[a][4 * g + 1], acc[a][4 * g + 2], acc[a][4 * g + 3], sT3, k0 + byte, p.t3.rs);
                     *reinterpret_cast<unsigned*>(my_row + (((byte >> 4) ^ my_swz) * 16) + (byte & 15)) = pack4(v[0], v[1], v[2], v[3]);
                     __builtin_amdgcn_sched_barrier(0);        // four values at a time: left alone the scheduler runs all 32 tails abreast
                 }
@@ -406,7 +442,7 @@ __global__ __launch_bounds__(kConvBlock) __attribute__((amdgpu_waves_per_eu(FQ_B
             for (int g = 0; g < 4; ++g) {
                 int v[4];
                 const int byte = a * 32 + 8 * g + 4 * half;
-                tail4<4>(v, acc1[a][4 * g], acc1[a][4 * g + 1], acc1[a][4 * g + 2], acc1[a][4 * g + 3], sT1, byte, p.t1.rs);
+                tail4<4, kNext ? C2 : 4, kPcs>(v, acc1[a][4 * g], acc1[a][4 * g + 1], acc1[a][4 * g + 2], acc1[a][4 * g + 3], sT1, byte, p.t1.rs);
                 *reinterpret_cast<unsigned*>(my_row + (((byte >> 4) ^ my_swz) * 16) + (byte & 15)) = pack4(v[0], v[1], v[2], v[3]);
             }
         }
@@ -433,7 +469,12 @@ TailParams tail_params(int rs, int relu) {
 template <int C, int C2>
 void launch_bt(dim3 grid, hipStream_t st, const int8_t* x, const int8_t* w3, const float* qb3, const int8_t* w1, const float* qb1,
                int8_t* q1, const BtParams& p) {
-    if (p.res_bytes == 2)
+    if (p.rs3_k) {
+        if (p.res_bytes == 2)
+            hipLaunchKernelGGL((block_tail_i8_kernel<C, C2, true, 0, true>), grid, dim3(kConvBlock), 0, st, x, w3, qb3, w1, qb1, q1, p);
+        else
+            hipLaunchKernelGGL((block_tail_i8_kernel<C, C2, false, 0, true>), grid, dim3(kConvBlock), 0, st, x, w3, qb3, w1, qb1, q1, p);
+    } else if (p.res_bytes == 2)
         hipLaunchKernelGGL((block_tail_i8_kernel<C, C2, true>), grid, dim3(kConvBlock), 0, st, x, w3, qb3, w1, qb1, q1, p);
     else
         hipLaunchKernelGGL((block_tail_i8_kernel<C, C2, false>), grid, dim3(kConvBlock), 0, st, x, w3, qb3, w1, qb1, q1, p);
@@ -442,8 +483,14 @@ void launch_bt(dim3 grid, hipStream_t st, const int8_t* x, const int8_t* w3, con
 template <int C, int C2, int CP>
 void launch_bt_proj(dim3 grid, hipStream_t st, const int8_t* x, const int8_t* w3, const float* qb3, const int8_t* w1, const float* qb1,
                     int8_t* q1, const BtParams& p) {
-    hipLaunchKernelGGL((block_tail_i8_kernel<C, C2, false, CP>), grid, dim3(kConvBlock), 0, st, x, w3, qb3, w1, qb1, q1, p);
+    if (p.rs3_k)
+        hipLaunchKernelGGL((block_tail_i8_kernel<C, C2, false, CP, true>), grid, dim3(kConvBlock), 0, st, x, w3, qb3, w1, qb1, q1, p);
+    else
+        hipLaunchKernelGGL((block_tail_i8_kernel<C, C2, false, CP>), grid, dim3(kConvBlock), 0, st, x, w3, qb3, w1, qb1, q1, p);
 }
+
+// the shift bounds of a per-channel entry point: every shift in [1, 16] (the integer tail; these kernels have no fp32 tail)
+bool pcs_bounds_ok(int lo, int hi) { return lo >= 1 && hi <= 16 && lo <= hi; }
 
 }  // namespace
 }  // namespace fq
@@ -458,10 +505,10 @@ extern "C" int fq_block_tail_i8_supported(int C, int K3, int C2, int rs3, int rs
     return (res_bytes == 1 || res_bytes == 2) ? 1 : 0;
 }
 
-extern "C" int fq_block_tail_i8(const int8_t* x_nhwc, const int8_t* w3_krsc, const float* qbias3, int rs3, int ob3, const void* res,
-                                int res_bytes, int g_res, int16_t* wide, int g_wide, int8_t* narrow, int ib, int relu,
-                                const int8_t* w1_krsc, const float* qbias1, int rs1, int relu1, int8_t* q1_nhwc, long M, int C,
-                                int K3, int C2, fq_stream_t stream) {
+static int block_tail_dispatch(const int8_t* x_nhwc, const int8_t* w3_krsc, const float* qbias3, int rs3, int ob3, const void* res,
+                               int res_bytes, int g_res, int16_t* wide, int g_wide, int8_t* narrow, int ib, int relu,
+                               const int8_t* w1_krsc, const float* qbias1, int rs1, int relu1, int8_t* q1_nhwc, long M, int C,
+                               int K3, int C2, fq_stream_t stream, const int32_t* rs3_k, const int32_t* rs1_k) {
     if (!res || (res_bytes != 1 && res_bytes != 2)) return FQ_ERR_INVALID_ARG;
     if (M < 0 || !fq_block_tail_i8_supported(C, K3, C2, rs3, rs1, ob3, g_res, res_bytes, ib)) return FQ_ERR_UNSUPPORTED;
     if (M == 0) return FQ_OK;
@@ -477,6 +524,9 @@ extern "C" int fq_block_tail_i8(const int8_t* x_nhwc, const int8_t* w3_krsc, con
     p.t1 = tail_params(C2 ? rs1 : 1, relu1);
     p.res = res; p.res_bytes = res_bytes; p.wide = wide; p.narrow = narrow;
     p.xp = nullptr; p.wp = nullptr; p.qbiasp = nullptr; p.tp = tail_params(1, 0); p.xp_bytes = 0; p.sp = 1; p.Ho = p.Wo = p.Hp = p.Wp = 1;
+    p.rs3_k = rs3_k; p.rs1_k = rs1_k; p.rsp_k = nullptr;
+    if (rs3_k && ((reinterpret_cast<uintptr_t>(rs3_k) | reinterpret_cast<uintptr_t>(rs1_k)) & 3u)) return FQ_ERR_INVALID_ARG;
+    if (rs3_k && C2 && !rs1_k) return FQ_ERR_INVALID_ARG;
     const int rc = make_add_params(ob3, g_res, g_wide, wide != nullptr, ib, relu, &p.ap);
     if (rc != FQ_OK) return rc;
     // the integer tail of conv3 is only the reference's fp32 chain while |acc| + 2^15 < 2^31: C * 127 * 128 is far below
@@ -498,6 +548,31 @@ extern "C" int fq_block_tail_i8(const int8_t* x_nhwc, const int8_t* w3_krsc, con
     return FQ_OK;
 }
 
+extern "C" int fq_block_tail_i8(const int8_t* x_nhwc, const int8_t* w3_krsc, const float* qbias3, int rs3, int ob3, const void* res,
+                                int res_bytes, int g_res, int16_t* wide, int g_wide, int8_t* narrow, int ib, int relu,
+                                const int8_t* w1_krsc, const float* qbias1, int rs1, int relu1, int8_t* q1_nhwc, long M, int C,
+                                int K3, int C2, fq_stream_t stream) {
+    return block_tail_dispatch(x_nhwc, w3_krsc, qbias3, rs3, ob3, res, res_bytes, g_res, wide, g_wide, narrow, ib, relu, w1_krsc, qbias1,
+                               rs1, relu1, q1_nhwc, M, C, K3, C2, stream, nullptr, nullptr);
+}
+
+extern "C" int fq_block_tail_i8_pcs_supported(int C, int K3, int C2, int rs3_min, int rs3_max, int rs1_min, int rs1_max, int ob3,
+                                              int g_res, int res_bytes, int ib) {
+    if (!pcs_bounds_ok(rs3_min, rs3_max) || (C2 && !pcs_bounds_ok(rs1_min, rs1_max))) return 0;
+    return fq_block_tail_i8_supported(C, K3, C2, rs3_min, C2 ? rs1_min : 1, ob3, g_res, res_bytes, ib);
+}
+
+extern "C" int fq_block_tail_i8_pcs(const int8_t* x_nhwc, const int8_t* w3_krsc, const float* qbias3, const int32_t* rs3_k, int rs3_min,
+                                    int rs3_max, int ob3, const void* res, int res_bytes, int g_res, int16_t* wide, int g_wide,
+                                    int8_t* narrow, int ib, int relu, const int8_t* w1_krsc, const float* qbias1, const int32_t* rs1_k,
+                                    int rs1_min, int rs1_max, int relu1, int8_t* q1_nhwc, long M, int C, int K3, int C2,
+                                    fq_stream_t stream) {
+    if (!fq_block_tail_i8_pcs_supported(C, K3, C2, rs3_min, rs3_max, rs1_min, rs1_max, ob3, g_res, res_bytes, ib)) return FQ_ERR_UNSUPPORTED;
+    if (M > 0 && !rs3_k) return FQ_ERR_INVALID_ARG;
+    return block_tail_dispatch(x_nhwc, w3_krsc, qbias3, rs3_min, ob3, res, res_bytes, g_res, wide, g_wide, narrow, ib, relu, w1_krsc,
+                               qbias1, C2 ? rs1_min : 1, relu1, q1_nhwc, M, C, K3, C2, stream, M > 0 ? rs3_k : nullptr, rs1_k);
+}
+
 // The first block of a stage: conv3 + NewAdd + (the next block's conv1) with the PROJECTION shortcut -- a 1x1 convolution of the
 // block's input, stride 1 or 2, its own RightShift + BiasAdd + Sp, no ReLU -- computed in the same kernel instead of being read.
 extern "C" int fq_block_tail_proj_i8_supported(int C, int K3, int C2, int CP, int rs3, int rs1, int rsp, int stride_p) {
@@ -507,11 +582,12 @@ extern "C" int fq_block_tail_proj_i8_supported(int C, int K3, int C2, int CP, in
     return (stride_p == 1 || stride_p == 2) ? 1 : 0;
 }
 
-extern "C" int fq_block_tail_proj_i8(const int8_t* x_nhwc, const int8_t* w3_krsc, const float* qbias3, int rs3, int ob3,
-                                     const int8_t* xp_nhwc, const int8_t* wp_krsc, const float* qbiasp, int rsp, int obp, int stride_p,
-                                     int Hp, int Wp, int16_t* wide, int g_wide, int8_t* narrow, int ib, int relu,
-                                     const int8_t* w1_krsc, const float* qbias1, int rs1, int relu1, int8_t* q1_nhwc, int N, int H,
-                                     int W, int C, int K3, int C2, int CP, fq_stream_t stream) {
+static int block_tail_proj_dispatch(const int8_t* x_nhwc, const int8_t* w3_krsc, const float* qbias3, int rs3, int ob3,
+                                    const int8_t* xp_nhwc, const int8_t* wp_krsc, const float* qbiasp, int rsp, int obp, int stride_p,
+                                    int Hp, int Wp, int16_t* wide, int g_wide, int8_t* narrow, int ib, int relu,
+                                    const int8_t* w1_krsc, const float* qbias1, int rs1, int relu1, int8_t* q1_nhwc, int N, int H,
+                                    int W, int C, int K3, int C2, int CP, fq_stream_t stream, const int32_t* rs3_k, const int32_t* rsp_k,
+                                    const int32_t* rs1_k) {
     if (N < 0 || H <= 0 || W <= 0 || Hp <= 0 || Wp <= 0) return FQ_ERR_INVALID_ARG;
     if (!fq_block_tail_proj_i8_supported(C, K3, C2, CP, rs3, rs1, rsp, stride_p)) return FQ_ERR_UNSUPPORTED;
     if ((Hp - 1) / stride_p + 1 != H || (Wp - 1) / stride_p + 1 != W) return FQ_ERR_INVALID_ARG;   // a 1x1 convolution without padding
@@ -532,6 +608,10 @@ extern "C" int fq_block_tail_proj_i8(const int8_t* x_nhwc, const int8_t* w3_krsc
     p.res = nullptr; p.res_bytes = 1; p.wide = wide; p.narrow = narrow;
     p.xp = xp_nhwc; p.wp = wp_krsc; p.qbiasp = qbiasp; p.tp = tail_params(rsp, 0); p.xp_bytes = (unsigned)(Mp * CP);
     p.sp = stride_p; p.Ho = H; p.Wo = W; p.Hp = Hp; p.Wp = Wp;
+    p.rs3_k = rs3_k; p.rsp_k = rsp_k; p.rs1_k = rs1_k;
+    if (rs3_k && (!rsp_k || (C2 && !rs1_k) ||
+                  ((reinterpret_cast<uintptr_t>(rs3_k) | reinterpret_cast<uintptr_t>(rsp_k) | reinterpret_cast<uintptr_t>(rs1_k)) & 3u)))
+        return FQ_ERR_INVALID_ARG;
     const int rc = make_add_params(ob3, obp, g_wide, wide != nullptr, ib, relu, &p.ap);
     if (rc != FQ_OK) return rc;
     const dim3 grid((unsigned)((M + kTP - 1) / kTP));
@@ -541,4 +621,35 @@ extern "C" int fq_block_tail_proj_i8(const int8_t* x_nhwc, const int8_t* w3_krsc
     note_conv_variant(12, 128);
     FQ_LAUNCH_CHECK();
     return FQ_OK;
+}
+
+extern "C" int fq_block_tail_proj_i8(const int8_t* x_nhwc, const int8_t* w3_krsc, const float* qbias3, int rs3, int ob3,
+                                     const int8_t* xp_nhwc, const int8_t* wp_krsc, const float* qbiasp, int rsp, int obp, int stride_p,
+                                     int Hp, int Wp, int16_t* wide, int g_wide, int8_t* narrow, int ib, int relu,
+                                     const int8_t* w1_krsc, const float* qbias1, int rs1, int relu1, int8_t* q1_nhwc, int N, int H,
+                                     int W, int C, int K3, int C2, int CP, fq_stream_t stream) {
+    return block_tail_proj_dispatch(x_nhwc, w3_krsc, qbias3, rs3, ob3, xp_nhwc, wp_krsc, qbiasp, rsp, obp, stride_p, Hp, Wp, wide, g_wide,
+                                    narrow, ib, relu, w1_krsc, qbias1, rs1, relu1, q1_nhwc, N, H, W, C, K3, C2, CP, stream, nullptr,
+                                    nullptr, nullptr);
+}
+
+extern "C" int fq_block_tail_proj_i8_pcs_supported(int C, int K3, int C2, int CP, int rs3_min, int rs3_max, int rs1_min, int rs1_max,
+                                                   int rsp_min, int rsp_max, int stride_p) {
+    if (!pcs_bounds_ok(rs3_min, rs3_max) || !pcs_bounds_ok(rsp_min, rsp_max) || (C2 && !pcs_bounds_ok(rs1_min, rs1_max))) return 0;
+    return fq_block_tail_proj_i8_supported(C, K3, C2, CP, rs3_min, C2 ? rs1_min : 1, rsp_min, stride_p);
+}
+
+extern "C" int fq_block_tail_proj_i8_pcs(const int8_t* x_nhwc, const int8_t* w3_krsc, const float* qbias3, const int32_t* rs3_k,
+                                         int rs3_min, int rs3_max, int ob3, const int8_t* xp_nhwc, const int8_t* wp_krsc,
+                                         const float* qbiasp, const int32_t* rsp_k, int rsp_min, int rsp_max, int obp, int stride_p,
+                                         int Hp, int Wp, int16_t* wide, int g_wide, int8_t* narrow, int ib, int relu,
+                                         const int8_t* w1_krsc, const float* qbias1, const int32_t* rs1_k, int rs1_min, int rs1_max,
+                                         int relu1, int8_t* q1_nhwc, int N, int H, int W, int C, int K3, int C2, int CP,
+                                         fq_stream_t stream) {
+    if (!fq_block_tail_proj_i8_pcs_supported(C, K3, C2, CP, rs3_min, rs3_max, rs1_min, rs1_max, rsp_min, rsp_max, stride_p))
+        return FQ_ERR_UNSUPPORTED;
+    if (N > 0 && (!rs3_k || !rsp_k)) return FQ_ERR_INVALID_ARG;
+    return block_tail_proj_dispatch(x_nhwc, w3_krsc, qbias3, rs3_min, ob3, xp_nhwc, wp_krsc, qbiasp, rsp_min, obp, stride_p, Hp, Wp, wide,
+                                    g_wide, narrow, ib, relu, w1_krsc, qbias1, C2 ? rs1_min : 1, relu1, q1_nhwc, N, H, W, C, K3, C2, CP,
+                                    stream, rs3_k, rsp_k, rs1_k);
 }

@@ -427,6 +427,7 @@ bool launch_conv1x1_stream(hipStream_t st, const int8_t* x, const int8_t* w, con
     static const bool on = [] { const char* e = getenv("FQ_CONV_STREAM"); return e && e[0] == '1'; }();
     if (!on || y || p.R != 1 || p.S != 1 || p.pad_h || p.pad_w || p.stride_h != p.stride_w || p.stride_h > 2) return false;
     if (p.rs == 0 || p.Kpad != p.K || (!q && !p.wide)) return false;           // integer tail, no channel padding
+    if (p.rs_k) return false;                              // (one shift per layer only: per-channel layers take the general kernels)
     if (!(p.C == 64 || p.C % 128 == 0) || p.K % 64) return false;
     const bool gather = p.stride_h != 1;
     if (gather && p.M >= (1 << 24)) return false;

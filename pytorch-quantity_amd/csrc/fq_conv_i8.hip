@@ -71,16 +71,21 @@ __device__ __forceinline__ bool conv_tile_of(const ConvParams& p, int& bx, int& 
 // with either sign of 0.5 (both truncate to 0), so the half is attached with a sign copy.
 // Returns the saturated integer (as a float) that DeQuantity then scales by 2^-ob; that integer is
 // also exactly what the NEXT layer's Quantity(ib = ob) would recover from the fp32 value.
-__device__ __forceinline__ float conv_tail_int(int acc, float qb, const ConvParams& p) {
-    const float v = (float)acc * p.inv_rs;
+__device__ __forceinline__ float conv_tail_int(int acc, float qb, const ConvParams& p, float inv_rs) {
+    const float v = (float)acc * inv_rs;
     const float w = v + __builtin_copysignf(0.5f, v);
     int r = (int)w;                                       // truncates toward zero, saturates
     r = min(max(r, p.ilo), p.ihi);
     return __builtin_amdgcn_fmed3f((float)r + qb, p.lo, p.hi);
 }
+__device__ __forceinline__ float conv_tail_int(int acc, float qb, const ConvParams& p) {
+    return conv_tail_int(acc, qb, p, p.inv_rs);
+}
 __device__ __forceinline__ float conv_tail(int acc, float qb, const ConvParams& p) {
     return conv_tail_int(acc, qb, p) * p.inv_ob;
 }
+// 2^-rs of a channel of a per-channel-shift layer (|rs| <= 120: exact)
+__device__ __forceinline__ float inv_shift(int rs) { return ldexpf(1.0f, -rs); }
 // The same tail in integer arithmetic: conv_tail_i (fq_int_tail.h), selected when the host proved it equivalent.
 
 // Position of a 16-byte chunk on the reduction axis: tap (r, s) and 16-channel group cc.
@@ -136,8 +141,10 @@ __device__ __forceinline__ void load_residual(ResRegs<TK>& r, const ConvParams& 
 template <int TK, int kOut, bool kIntTail, bool kStageAliased = true>
 __device__ __forceinline__ void conv_epilogue(v16i (&acc)[TK / 32], const ConvParams& p, float* __restrict__ y,
                                               int8_t* __restrict__ q, int8_t* sO, const float* sBias, const int* sBiasI,
-                                              const int (&sLH)[2][TK], int m0,
+                                              const int (&sLH)[2][TK], const int* sRs, int m0,
                                               int k0, int n_img, int pq, bool m_ok, ResRegs<TK>& res, int tid_base = 0) {
+    // (sRs: kOutPcs only -- the shift of each of the TK channels)
+    constexpr bool kPcs = (kOut & kOutPcs) != 0;
     constexpr int MT = TK / 32;
     // (tid_base: a 512-thread workgroup runs this once per 256-thread half, each on its own 128-pixel tile and its own sO)
     const int tid = (int)threadIdx.x - tid_base, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
@@ -153,7 +160,14 @@ __device__ __forceinline__ void conv_epilogue(v16i (&acc)[TK / 32], const ConvPa
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int kl = a * 32 + (r & 3) + 8 * (r >> 2);          // compile-time constant
-                if (kl < kmax)
+                if constexpr (kPcs) {
+                    if (kl < kmax) {
+                        const int rs = sRs[kl + 4 * half];
+                        out[(unsigned)(kl * PQ)] = kIntTail ? (float)conv_tail_k(acc[a][r], sBiasI[kl + 4 * half], sLH[0][kl + 4 * half],
+                                                                                 sLH[1][kl + 4 * half], rs) * p.inv_ob
+                                                            : conv_tail_int(acc[a][r], sBias[kl + 4 * half], p, inv_shift(rs)) * p.inv_ob;
+                    }
+                } else if (kl < kmax)
                     out[(unsigned)(kl * PQ)] = kIntTail ? (float)conv_tail_k(acc[a][r], sBiasI[kl + 4 * half], sLH[0][kl + 4 * half],
                                                                              sLH[1][kl + 4 * half], p.rs) * p.inv_ob
                                                         : conv_tail(acc[a][r], sBias[kl + 4 * half], p);
@@ -193,8 +207,20 @@ __device__ __forceinline__ void conv_epilogue(v16i (&acc)[TK / 32], const ConvPa
                     const int kl = a * 32 + 8 * g + 4 * half;
                     const v4i cB = *reinterpret_cast<const v4i*>(&sBiasI[kl]), cL = *reinterpret_cast<const v4i*>(&sLH[0][kl]),
                               cH = *reinterpret_cast<const v4i*>(&sLH[1][kl]);
+                    if constexpr (kPcs) {
+                        const v4i cR = *reinterpret_cast<const v4i*>(&sRs[kl]);
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = conv_tail_k(acc[a][4 * g + e], cB[e], cL[e], cH[e], p.rs);
+                        for (int e = 0; e < 4; ++e) v[e] = conv_tail_k(acc[a][4 * g + e], cB[e], cL[e], cH[e], cR[e]);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = conv_tail_k(acc[a][4 * g + e], cB[e], cL[e], cH[e], p.rs);
+                    }
+                } else if constexpr (kPcs) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int kl = a * 32 + e + 8 * g + 4 * half;
+                        v[e] = (int)conv_tail_int(acc[a][4 * g + e], sBias[kl], p, inv_shift(sRs[kl]));
+                    }
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = (int)conv_tail_int(acc[a][4 * g + e], sBias[a * 32 + e + 8 * g + 4 * half], p);
@@ -275,6 +301,7 @@ __global__ __launch_bounds__(kConvBlock) __attribute__((amdgpu_waves_per_eu(TK =
     __shared__ float sBias[TK];
     __shared__ __attribute__((aligned(16))) int sBiasI[TK];     // (integer tail: the rounding constant with the bias in it, tail_consts)
     __shared__ __attribute__((aligned(16))) int sLH[2][TK];     //  ... and the merged clamp's bounds
+    __shared__ __attribute__((aligned(16))) int sRs[(kOut & kOutPcs) ? TK : 4];     //  ... and, kOutPcs, each channel's shift
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5;
@@ -286,7 +313,7 @@ __global__ __launch_bounds__(kConvBlock) __attribute__((amdgpu_waves_per_eu(TK =
     if (tid < TK) {                                       // visible after the first barrier
         const float b = (k0 + tid < p.K) ? qbias[k0 + tid] : 0.0f;
         sBias[tid] = b;
-        const TailK tk = tail_consts((int)b, p);           // (integer valued by contract)
+        const TailK tk = stage_tail<kOut>((int)b, p, sRs, tid, k0 + tid);     // (integer valued by contract)
         sBiasI[tid] = tk.B; sLH[0][tid] = tk.lo; sLH[1][tid] = tk.hi;
     }
 
@@ -458,8 +485,8 @@ __global__ __launch_bounds__(kConvBlock) __attribute__((amdgpu_waves_per_eu(TK =
     }
 
     static_assert(kTP * (TK + 16) <= 2 * TK * BKB, "the int8 output tile is staged in the weight buffers");
-    if (p.rs) conv_epilogue<TK, kOut, true>(acc, p, y, q, &sA[0][0], sBias, sBiasI, sLH, m0, k0, n_img, pq, m_ok, res);
-    else conv_epilogue<TK, kOut, false>(acc, p, y, q, &sA[0][0], sBias, sBiasI, sLH, m0, k0, n_img, pq, m_ok, res);
+    if (p.rs) conv_epilogue<TK, kOut, true>(acc, p, y, q, &sA[0][0], sBias, sBiasI, sLH, (kOut & kOutPcs) ? sRs : nullptr, m0, k0, n_img, pq, m_ok, res);
+    else conv_epilogue<TK, kOut, false>(acc, p, y, q, &sA[0][0], sBias, sBiasI, sLH, (kOut & kOutPcs) ? sRs : nullptr, m0, k0, n_img, pq, m_ok, res);
 }
 
 // ---- C % 128 == 0, K % TK == 0: both operands by LDS-DMA ----------------------------------------------
@@ -502,6 +529,7 @@ __global__ __launch_bounds__(kConvBlock) void conv2d_i8_dma_kernel(const int8_t*
     __shared__ float sBias[TK];
     __shared__ __attribute__((aligned(16))) int sBiasI[TK];     // (integer tail: the rounding constant with the bias in it, tail_consts)
     __shared__ __attribute__((aligned(16))) int sLH[2][TK];     //  ... and the merged clamp's bounds
+    __shared__ __attribute__((aligned(16))) int sRs[(kOut & kOutPcs) ? TK : 4];     //  ... and, kOutPcs, each channel's shift
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave-uniform: LDS-DMA bases live in SGPRs (M0)
@@ -519,7 +547,7 @@ __global__ __launch_bounds__(kConvBlock) void conv2d_i8_dma_kernel(const int8_t*
     if (tid < TK) {                                       // visible after the first barrier
         const float b = qbias[k0 + tid];
         sBias[tid] = b;
-        const TailK tk = tail_consts((int)b, p);
+        const TailK tk = stage_tail<kOut>((int)b, p, sRs, tid, k0 + tid);
         sBiasI[tid] = tk.B; sLH[0][tid] = tk.lo; sLH[1][tid] = tk.hi;
     }
 
@@ -684,8 +712,8 @@ __global__ __launch_bounds__(kConvBlock) void conv2d_i8_dma_kernel(const int8_t*
 
     static_assert(kTP * (TK + 16) <= STAGES * TK * BKB, "the int8 output tile is staged in the weight buffers");
     ResRegs<TK> res;
-    if (p.rs) conv_epilogue<TK, kOut, true>(acc, p, y, q, &sA[0][0], sBias, sBiasI, sLH, m0, k0, n_img, pq, m_ok, res);
-    else conv_epilogue<TK, kOut, false>(acc, p, y, q, &sA[0][0], sBias, sBiasI, sLH, m0, k0, n_img, pq, m_ok, res);
+    if (p.rs) conv_epilogue<TK, kOut, true>(acc, p, y, q, &sA[0][0], sBias, sBiasI, sLH, (kOut & kOutPcs) ? sRs : nullptr, m0, k0, n_img, pq, m_ok, res);
+    else conv_epilogue<TK, kOut, false>(acc, p, y, q, &sA[0][0], sBias, sBiasI, sLH, (kOut & kOutPcs) ? sRs : nullptr, m0, k0, n_img, pq, m_ok, res);
     TR(4);
 }
 
@@ -726,6 +754,7 @@ __global__ __launch_bounds__(kConvBlock) void conv3x3_i8_halo_kernel(const int8_
     float* const sBias = reinterpret_cast<float*>(smem + ST * TK * BKB);
     int* const sBiasI = reinterpret_cast<int*>(smem + ST * TK * BKB + TK * 4);
     __shared__ __attribute__((aligned(16))) int sLH[2][TK];     // the merged clamp's bounds of the integer tail (tail_consts)
+    __shared__ __attribute__((aligned(16))) int sRs[(kOut & kOutPcs) ? TK : 4];     //  ... and, kOutPcs, each channel's shift
     int8_t* const sZero = smem + ST * TK * BKB + TK * 8;
     int8_t* const sSlab = sZero + BKB;
 
@@ -740,7 +769,7 @@ __global__ __launch_bounds__(kConvBlock) void conv3x3_i8_halo_kernel(const int8_
     if (tid < TK) {
         const float b = qbias[k0 + tid];
         sBias[tid] = b;
-        const TailK tk = tail_consts((int)b, p);
+        const TailK tk = stage_tail<kOut>((int)b, p, sRs, tid, k0 + tid);
         sBiasI[tid] = tk.B; sLH[0][tid] = tk.lo; sLH[1][tid] = tk.hi;
     }
     if (tid < BKB / 4) reinterpret_cast<int*>(sZero)[tid] = 0;
@@ -883,8 +912,8 @@ __global__ __launch_bounds__(kConvBlock) void conv3x3_i8_halo_kernel(const int8_
     for (int u = 0; u < NP; ++u) {
         if (u) __syncthreads();                               // the epilogue stages its int8 tile in sA: one half after the other
         ResRegs<TK> res;
-        if (p.rs) conv_epilogue<TK, kOut, true>(acc[u], p, y, q, sA, sBias, sBiasI, sLH, m0 + kTP * u, k0, n_img[u], pq[u], m_ok[u], res);
-        else conv_epilogue<TK, kOut, false>(acc[u], p, y, q, sA, sBias, sBiasI, sLH, m0 + kTP * u, k0, n_img[u], pq[u], m_ok[u], res);
+        if (p.rs) conv_epilogue<TK, kOut, true>(acc[u], p, y, q, sA, sBias, sBiasI, sLH, (kOut & kOutPcs) ? sRs : nullptr, m0 + kTP * u, k0, n_img[u], pq[u], m_ok[u], res);
+        else conv_epilogue<TK, kOut, false>(acc[u], p, y, q, sA, sBias, sBiasI, sLH, (kOut & kOutPcs) ? sRs : nullptr, m0 + kTP * u, k0, n_img[u], pq[u], m_ok[u], res);
     }
 }
 
@@ -911,6 +940,7 @@ __global__ __launch_bounds__(2 * kConvBlock) void conv3x3_i8_halo8_kernel(const 
     float* const sBias = reinterpret_cast<float*>(smem + ST * TK * BKB);
     int* const sBiasI = reinterpret_cast<int*>(smem + ST * TK * BKB + TK * 4);
     __shared__ __attribute__((aligned(16))) int sLH[2][TK];     // the merged clamp's bounds of the integer tail (tail_consts)
+    __shared__ __attribute__((aligned(16))) int sRs[(kOut & kOutPcs) ? TK : 4];     //  ... and, kOutPcs, each channel's shift
     int8_t* const sZero = smem + ST * TK * BKB + TK * 8;
     int8_t* const sSlab = sZero + BKB;
 
@@ -926,7 +956,7 @@ __global__ __launch_bounds__(2 * kConvBlock) void conv3x3_i8_halo8_kernel(const 
     if (tid < TK) {
         const float b = qbias[k0 + tid];
         sBias[tid] = b;
-        const TailK tk = tail_consts((int)b, p);
+        const TailK tk = stage_tail<kOut>((int)b, p, sRs, tid, k0 + tid);
         sBiasI[tid] = tk.B; sLH[0][tid] = tk.lo; sLH[1][tid] = tk.hi;
     }
     if (tid < BKB / 4) reinterpret_cast<int*>(sZero)[tid] = 0;
@@ -1052,8 +1082,8 @@ __global__ __launch_bounds__(2 * kConvBlock) void conv3x3_i8_halo8_kernel(const 
     static_assert(kTP * (TK + 16) <= 2 * TK * BKB, "the first half's int8 tile is staged in the weight buffers");
     int8_t* const sO = u ? sSlab : sA;
     ResRegs<TK> res;
-    if (p.rs) conv_epilogue<TK, kOut, true>(acc, p, y, q, sO, sBias, sBiasI, sLH, m0 + kTP * u, k0, n_img, pq, m_ok, res, u * kConvBlock);
-    else conv_epilogue<TK, kOut, false>(acc, p, y, q, sO, sBias, sBiasI, sLH, m0 + kTP * u, k0, n_img, pq, m_ok, res, u * kConvBlock);
+    if (p.rs) conv_epilogue<TK, kOut, true>(acc, p, y, q, sO, sBias, sBiasI, sLH, (kOut & kOutPcs) ? sRs : nullptr, m0 + kTP * u, k0, n_img, pq, m_ok, res, u * kConvBlock);
+    else conv_epilogue<TK, kOut, false>(acc, p, y, q, sO, sBias, sBiasI, sLH, (kOut & kOutPcs) ? sRs : nullptr, m0 + kTP * u, k0, n_img, pq, m_ok, res, u * kConvBlock);
 }
 
 // ---- 3 x 3, stride 1, padding 1, C == 64, K <= 64 (the first stage of a ResNet): weights stationary, persistent -------
@@ -1080,6 +1110,7 @@ __global__ __launch_bounds__(kConvBlock) void conv3x3_i8_c64_kernel(const int8_t
     float* const sBias = reinterpret_cast<float*>(smem + 9 * TK * RB);
     int* const sBiasI = reinterpret_cast<int*>(smem + 9 * TK * RB + TK * 4);
     __shared__ __attribute__((aligned(16))) int sLH[2][TK];     // the merged clamp's bounds of the integer tail (tail_consts)
+    __shared__ __attribute__((aligned(16))) int sRs[(kOut & kOutPcs) ? TK : 4];     //  ... and, kOutPcs, each channel's shift
     int8_t* const sZero = smem + 9 * TK * RB + TK * 8;
     int8_t* const sO = sZero + RB;
     int8_t* const sSlab = sO + kTP * (TK + 16);
@@ -1092,7 +1123,7 @@ __global__ __launch_bounds__(kConvBlock) void conv3x3_i8_c64_kernel(const int8_t
     if (tid < TK) {
         const float b = tid < p.K ? qbias[tid] : 0.0f;
         sBias[tid] = b;
-        const TailK tk = tail_consts((int)b, p);
+        const TailK tk = stage_tail<kOut>((int)b, p, sRs, tid, tid);
         sBiasI[tid] = tk.B; sLH[0][tid] = tk.lo; sLH[1][tid] = tk.hi;
     }
     if (tid < RB / 4) reinterpret_cast<int*>(sZero)[tid] = 0;
@@ -1192,8 +1223,8 @@ __global__ __launch_bounds__(kConvBlock) void conv3x3_i8_c64_kernel(const int8_t
             __builtin_amdgcn_sched_barrier(0);
         }
         ResRegs<TK> res;
-        if (p.rs) conv_epilogue<TK, kOut, true, false>(acc, p, y, q, sO, sBias, sBiasI, sLH, m0, 0, n_img, pq, m_ok, res);
-        else conv_epilogue<TK, kOut, false, false>(acc, p, y, q, sO, sBias, sBiasI, sLH, m0, 0, n_img, pq, m_ok, res);
+        if (p.rs) conv_epilogue<TK, kOut, true, false>(acc, p, y, q, sO, sBias, sBiasI, sLH, (kOut & kOutPcs) ? sRs : nullptr, m0, 0, n_img, pq, m_ok, res);
+        else conv_epilogue<TK, kOut, false, false>(acc, p, y, q, sO, sBias, sBiasI, sLH, (kOut & kOutPcs) ? sRs : nullptr, m0, 0, n_img, pq, m_ok, res);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the next slab has landed (mine) ...
         __syncthreads();                                      // ... and everybody's; everybody is done with this tile's slab and staging
         buf ^= 1;
@@ -1449,14 +1480,16 @@ template <int TK, int STAGES>
 static void launch_conv_dma_stages(dim3 grid, hipStream_t st, const int8_t* x, const int8_t* w, const float* qbias, float* y,
                                    int8_t* q, const ConvParams& p0) {
     const ConvParams p = xcd_order(grid, p0);
-    if (p.res)
-        hipLaunchKernelGGL((conv2d_i8_dma_kernel<TK, kOutI8 | kOutAdd, STAGES>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p);
-    else if (y && q)
-        hipLaunchKernelGGL((conv2d_i8_dma_kernel<TK, kOutF32 | kOutI8, STAGES>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p);
-    else if (q)
-        hipLaunchKernelGGL((conv2d_i8_dma_kernel<TK, kOutI8, STAGES>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p);
-    else
-        hipLaunchKernelGGL((conv2d_i8_dma_kernel<TK, kOutF32, STAGES>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p);
+#define FQ_DMA(OUT)                                                                                                      \
+    do {                                                                                                                 \
+        if (p.rs_k) hipLaunchKernelGGL((conv2d_i8_dma_kernel<TK, (OUT) | kOutPcs, STAGES>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p); \
+        else hipLaunchKernelGGL((conv2d_i8_dma_kernel<TK, OUT, STAGES>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p); \
+    } while (0)
+    if (p.res) FQ_DMA(kOutI8 | kOutAdd);
+    else if (y && q) FQ_DMA(kOutF32 | kOutI8);
+    else if (q) FQ_DMA(kOutI8);
+    else FQ_DMA(kOutF32);
+#undef FQ_DMA
 }
 
 template <int TK>
@@ -1483,21 +1516,24 @@ static void launch_conv_tile(dim3 grid, hipStream_t st, const int8_t* x, const i
     //  slower everywhere inside the network at 256 images: 86 -> 97 us on the 28 x 28 tail, 63.6 -> 74.5 on the 14 x 14 ones,
     //  38.8 -> 41.6 at 7 x 7; 333 -> 374 us on the 56 x 56 tail from HBM.  The burst of 32 KB per workgroup ahead of the other
     //  resident workgroups' operand requests delays THEIR matrix work by more than it saves this one.)
-    if (p.res)
-        hipLaunchKernelGGL((conv2d_i8_kernel<TK, kPath, kOutI8 | kOutAdd>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p);
-    else if (y && q)
-        hipLaunchKernelGGL((conv2d_i8_kernel<TK, kPath, kOutF32 | kOutI8>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p);
-    else if (q)
-        hipLaunchKernelGGL((conv2d_i8_kernel<TK, kPath, kOutI8>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p);
-    else
-        hipLaunchKernelGGL((conv2d_i8_kernel<TK, kPath, kOutF32>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p);
+#define FQ_TILE(OUT)                                                                                                     \
+    do {                                                                                                                 \
+        if (p.rs_k) hipLaunchKernelGGL((conv2d_i8_kernel<TK, kPath, (OUT) | kOutPcs>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p); \
+        else hipLaunchKernelGGL((conv2d_i8_kernel<TK, kPath, OUT>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p); \
+    } while (0)
+    if (p.res) FQ_TILE(kOutI8 | kOutAdd);
+    else if (y && q) FQ_TILE(kOutF32 | kOutI8);
+    else if (q) FQ_TILE(kOutI8);
+    else FQ_TILE(kOutF32);
+#undef FQ_TILE
 }
 
 // Dynamic LDS a kernel of the halo family may ask for and still run two workgroups per CU (160 KB): half the CU's LDS minus what
 // the kernel declares STATICALLY beside its dynamic carve-out -- sLH[2][TK] ints, the merged clamp bounds of the integer tail --
 // and the allocation granule.  (The budget used to ignore the static part; no shape fell into the gap, but one layout change
 // could have halved the occupancy silently.)
-static constexpr size_t two_per_cu_lds(int tk) { return (size_t)80 * 1024 - 64 - (size_t)8 * tk; }
+// (pcs: a kOutPcs kernel also declares sRs[TK], each channel's shift)
+static constexpr size_t two_per_cu_lds(int tk, bool pcs = false) { return (size_t)80 * 1024 - 64 - (size_t)(pcs ? 12 : 8) * tk; }
 
 // the halo form of the 3 x 3 layers; false when the layer is not of that shape
 template <int TK>
@@ -1508,6 +1544,7 @@ static bool launch_conv_halo(hipStream_t st, const int8_t* x, const int8_t* w, c
         p0.dil_w != 1 || (p0.C & 127) || (p0.K % TK) || p0.res)
         return false;
     static const int st_env = [] { const char* e = getenv("FQ_HALO_STAGES"); return e ? atoi(e) : 0; }();
+    const bool pcs = p0.rs_k != nullptr;
     static const int np_env = [] { const char* e = getenv("FQ_HALO_NP"); return e ? atoi(e) : 0; }();
     // 256-pixel tiles on eight waves (conv3x3_i8_halo8_kernel): FQ_HALO8=0 keeps the 128-pixel form
     static const int eight = [] { const char* e = getenv("FQ_HALO8"); return e ? atoi(e) : 1; }();
@@ -1518,7 +1555,7 @@ static bool launch_conv_halo(hipStream_t st, const int8_t* x, const int8_t* w, c
         const size_t fixed8 = (size_t)TK * 8 + 128 + (size_t)hp8.slab_rows * 128;
         const int stages8 = st_env ? st_env : 2;
         const size_t lds8 = (size_t)stages8 * TK * 128 + fixed8;
-        if (lds8 <= two_per_cu_lds(TK) && (stages8 == 2 || stages8 == 3)) {
+        if (lds8 <= two_per_cu_lds(TK, pcs) && (stages8 == 2 || stages8 == 3)) {
             dim3 grid8((unsigned)(((long)p0.M + 255) / 256), (unsigned)(p0.K / TK));
             const ConvParams p8 = xcd_order(grid8, p0);
 #define FQ_HALO8_K(OUT, STG)                                                                                             \
@@ -1528,11 +1565,13 @@ static bool launch_conv_halo(hipStream_t st, const int8_t* x, const int8_t* w, c
         if (!ensure_dynamic_lds(reinterpret_cast<const void*>(k), 80 * 1024, lds_ok)) return false;                      \
         hipLaunchKernelGGL(k, grid8, dim3(2 * kConvBlock), lds8, st, x, w, qbias, y, q, p8, hp8);                        \
     } while (0)
-#define FQ_HALO8(OUT) do { if (stages8 == 3) FQ_HALO8_K(OUT, 3); else FQ_HALO8_K(OUT, 2); } while (0)
+#define FQ_HALO8_S(OUT) do { if (stages8 == 3) FQ_HALO8_K(OUT, 3); else FQ_HALO8_K(OUT, 2); } while (0)
+#define FQ_HALO8(OUT) do { if (pcs) FQ_HALO8_S((OUT) | kOutPcs); else FQ_HALO8_S(OUT); } while (0)
             if (y && q) FQ_HALO8(kOutF32 | kOutI8);
             else if (q) FQ_HALO8(kOutI8);
             else FQ_HALO8(kOutF32);
 #undef FQ_HALO8
+#undef FQ_HALO8_S
 #undef FQ_HALO8_K
             note_conv_variant(kVarHalo8, TK);
             return true;
@@ -1545,9 +1584,9 @@ static bool launch_conv_halo(hipStream_t st, const int8_t* x, const int8_t* w, c
     hp.slab_rows = (128 * np + 2 + 2 * p0.W + 7) & ~7;
     hp.total_pixels = p0.N * p0.H * p0.W;
     const size_t fixed = (size_t)TK * 8 + 128 + (size_t)hp.slab_rows * 128;
-    const int stages = st_env ? st_env : ((size_t)3 * TK * 128 + fixed <= two_per_cu_lds(TK) ? 3 : 2);
+    const int stages = st_env ? st_env : ((size_t)3 * TK * 128 + fixed <= two_per_cu_lds(TK, pcs) ? 3 : 2);
     const size_t lds = (size_t)stages * TK * 128 + fixed;
-    if (lds > two_per_cu_lds(TK) || (stages != 2 && stages != 3) || (np != 1 && np != 2)) return false;   // two workgroups per CU
+    if (lds > two_per_cu_lds(TK, pcs) || (stages != 2 && stages != 3) || (np != 1 && np != 2)) return false;   // two workgroups per CU
     dim3 grid((unsigned)(((long)p0.M + 128 * np - 1) / (128 * np)), (unsigned)(p0.K / TK));
     const ConvParams p = xcd_order(grid, p0);
 #define FQ_HALO_K(OUT, STG, NPX)                                                                                         \
@@ -1557,15 +1596,17 @@ static bool launch_conv_halo(hipStream_t st, const int8_t* x, const int8_t* w, c
         if (!ensure_dynamic_lds(reinterpret_cast<const void*>(k), 80 * 1024, lds_ok)) return false;                      \
         hipLaunchKernelGGL(k, grid, dim3(kConvBlock), lds, st, x, w, qbias, y, q, p, hp);                                \
     } while (0)
-#define FQ_HALO(OUT)                                                                                                     \
+#define FQ_HALO_S(OUT)                                                                                                   \
     do {                                                                                                                 \
         if (np == 2) { if (stages == 3) FQ_HALO_K(OUT, 3, 2); else FQ_HALO_K(OUT, 2, 2); }                               \
         else { if (stages == 3) FQ_HALO_K(OUT, 3, 1); else FQ_HALO_K(OUT, 2, 1); }                                      \
     } while (0)
+#define FQ_HALO(OUT) do { if (pcs) FQ_HALO_S((OUT) | kOutPcs); else FQ_HALO_S(OUT); } while (0)
     if (y && q) FQ_HALO(kOutF32 | kOutI8);
     else if (q) FQ_HALO(kOutI8);
     else FQ_HALO(kOutF32);
 #undef FQ_HALO
+#undef FQ_HALO_S
 #undef FQ_HALO_K
     note_conv_variant(kVarHalo, TK);
     return true;
@@ -1584,23 +1625,26 @@ static bool launch_conv_c64(hipStream_t st, const int8_t* x, const int8_t* w, co
     static const bool xcd_order = [] { const char* e = getenv("FQ_C64_XCD"); return !(e && e[0] == '0'); }();
     cp.xcd_chunk = xcd_order ? (cp.tiles + 7) / 8 : 0;
     const size_t lds = (size_t)9 * 64 * 64 + 64 * 8 + 64 + (size_t)kTP * 80 + (size_t)2 * cp.slab_rows * 64;
-    if (lds > two_per_cu_lds(64)) return false;            // two workgroups per CU
+    const bool pcs = p0.rs_k != nullptr;
+    if (lds > two_per_cu_lds(64, pcs)) return false;       // two workgroups per CU
     ConvParams p = p0;
     p.xcd_kt = 0; p.tiles_m = cp.tiles;
     static const int per_cu = [] { const char* e = getenv("FQ_C64_WG_PER_CU"); return e ? atoi(e) : 2; }();
     unsigned grid = (unsigned)(kCUs * per_cu);
     if ((long)grid > cp.tiles) grid = (unsigned)cp.tiles;
-#define FQ_C64(OUT)                                                                                                      \
+#define FQ_C64_S(OUT)                                                                                                    \
     do {                                                                                                                 \
         auto k = conv3x3_i8_c64_kernel<OUT>;                                                                             \
         static bool lds_ok[kMaxDevices] = {};                                                                            \
         if (!ensure_dynamic_lds(reinterpret_cast<const void*>(k), 80 * 1024, lds_ok)) return false;                      \
         hipLaunchKernelGGL(k, dim3(grid), dim3(kConvBlock), lds, st, x, w, qbias, y, q, p, cp);                          \
     } while (0)
+#define FQ_C64(OUT) do { if (pcs) FQ_C64_S((OUT) | kOutPcs); else FQ_C64_S(OUT); } while (0)
     if (y && q) FQ_C64(kOutF32 | kOutI8);
     else if (q) FQ_C64(kOutI8);
     else FQ_C64(kOutF32);
 #undef FQ_C64
+#undef FQ_C64_S
     note_conv_variant(kVarC64Halo, 64);
     return true;
 }
@@ -1618,6 +1662,7 @@ struct FusedAdd {                        // residual operand and outputs of a fu
 // matrix is one lane's 16 bytes per sub-step), eight sub-steps of loads in flight per wave, and the four waves of the workgroup
 // take every fourth group of eight sub-steps; their int32 partial tiles meet in LDS (exact: integer sums in any order).
 constexpr int kLinWaves = 4;
+template <bool kPcs>
 __global__ __launch_bounds__(64 * kLinWaves) void linear_i8_wave_kernel(const int8_t* __restrict__ x, const int8_t* __restrict__ w,
                                                                         const float* __restrict__ qbias, float* __restrict__ y,
                                                                         const ConvParams p) {
@@ -1667,7 +1712,15 @@ __global__ __launch_bounds__(64 * kLinWaves) void linear_i8_wave_kernel(const in
             // (a bias of ANY magnitude, as fq.h promises: tail_consts brings it into the range beyond which the output is a bound
             //  whatever the accumulator holds; the unclamped six-instruction form would wrap on a bias near INT_MAX)
             float out;
-            if (p.rs) {
+            if constexpr (kPcs) {
+                const int rs = p.rs_k[k];
+                if (p.rs) {
+                    const TailK tk = tail_consts_rs((int)b, p, rs);
+                    out = (float)conv_tail_k(acc[i], tk.B, tk.lo, tk.hi, rs) * p.inv_ob;
+                } else {
+                    out = conv_tail_int(acc[i], b, p, inv_shift(rs)) * p.inv_ob;
+                }
+            } else if (p.rs) {
                 const TailK tk = tail_consts((int)b, p);               // (v_cvt_i32_f32 saturates)
                 out = (float)conv_tail_k(acc[i], tk.B, tk.lo, tk.hi, p.rs) * p.inv_ob;
             } else {
@@ -1680,8 +1733,11 @@ __global__ __launch_bounds__(64 * kLinWaves) void linear_i8_wave_kernel(const in
 
 static int conv2d_i8_dispatch(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, float* y_nchw, int8_t* q_nhwc,
                               int Kpad, int relu, const FusedAdd& fa, int N, int H, int W, int C, int K, int R, int S, int stride_h, int stride_w,
-                              int pad_h, int pad_w, int dil_h, int dil_w, int rs, int ob, int bitwidth, fq_stream_t stream) {
+                              int pad_h, int pad_w, int dil_h, int dil_w, int rs, int ob, int bitwidth, fq_stream_t stream,
+                              const int32_t* rs_k = nullptr, int rs_max = 0) {
+    // (rs_k: one shift per output channel, in [rs, rs_max] -- the caller's bounds; rs_k == nullptr: rs is the layer's shift)
     if (!valid_bitwidth(bitwidth) || rs < -120 || rs > 120 || ob < -120 || ob > 120) return FQ_ERR_INVALID_ARG;
+    if (rs_k && (rs_max < rs || rs_max > 120 || (reinterpret_cast<uintptr_t>(rs_k) & 15u))) return FQ_ERR_INVALID_ARG;
     if (N < 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || R <= 0 || S <= 0 || stride_h <= 0 || stride_w <= 0 ||
         pad_h < 0 || pad_w < 0 || dil_h <= 0 || dil_w <= 0)
         return FQ_ERR_INVALID_ARG;
@@ -1712,9 +1768,12 @@ static int conv2d_i8_dispatch(const int8_t* x_nhwc, const int8_t* w_krsc, const 
     // integer tail where it is provably the same function (see conv_tail_i)
     // (... and with the bias folded into the rounding constant -- tail_consts: |qb| <= shi - ilo after its clamp, shifted by rs)
     const long qmax = bitwidth == 8 ? 255 : 65535;
-    const bool int_tail = rs >= 1 && rs <= 16 && (long)R * S * C * 16384 + 65536 + (qmax << rs) < 0x7fffffffL;
+    // (per channel: every shift in [1, 16] and the bound at the largest one; the padding channels take the smallest)
+    const int rs_hi = rs_k ? rs_max : rs;
+    const bool int_tail = rs >= 1 && rs_hi <= 16 && (long)R * S * C * 16384 + 65536 + (qmax << rs_hi) < 0x7fffffffL;
     p.rs = int_tail ? rs : 0;
     p.half_rs = int_tail ? 1 << (rs - 1) : 0;
+    p.rs_k = rs_k;
     p.slo = (int)p.lo; p.shi = (int)p.hi;
     p.Kpad = (q_nhwc || fa.res) ? Kpad : 0;
     p.res = fa.res; p.res_bytes = fa.res_bytes; p.wide = fa.wide; p.ap = fa.ap;
@@ -1738,8 +1797,9 @@ static int conv2d_i8_dispatch(const int8_t* x_nhwc, const int8_t* w_krsc, const 
     static const bool thin = [] { const char* e = getenv("FQ_LINEAR_WAVE"); return !(e && e[0] == '0'); }();
     // (pad 0, dilation 1: with padding and a stride >= 3 the one output pixel would sample the zero border, not x)
     if (thin && H == 1 && W == 1 && R == 1 && S == 1 && P == 1 && Q == 1 && pad_h == 0 && pad_w == 0 && dil_h == 1 && dil_w == 1 && y_nchw && !q_nhwc && !fa.res && (M + 31) / 32 <= 65535) {
-        hipLaunchKernelGGL(linear_i8_wave_kernel, dim3((unsigned)((K + 31) / 32), (unsigned)((M + 31) / 32)), dim3(64 * kLinWaves), 0, st, x_nhwc, w_krsc,
-                           qbias, y_nchw, p);
+        const dim3 lgrid((unsigned)((K + 31) / 32), (unsigned)((M + 31) / 32));
+        if (rs_k) hipLaunchKernelGGL(linear_i8_wave_kernel<true>, lgrid, dim3(64 * kLinWaves), 0, st, x_nhwc, w_krsc, qbias, y_nchw, p);
+        else hipLaunchKernelGGL(linear_i8_wave_kernel<false>, lgrid, dim3(64 * kLinWaves), 0, st, x_nhwc, w_krsc, qbias, y_nchw, p);
         note_conv_variant(kVarLinearWave, 32);
         FQ_LAUNCH_CHECK();
         return FQ_OK;
@@ -1811,6 +1871,37 @@ extern "C" int fq_conv2d_i8_add_resident(const int8_t* x_nhwc, const int8_t* w_k
     if (rc != FQ_OK) return rc;
     return conv2d_i8_dispatch(x_nhwc, w_krsc, qbias, nullptr, narrow, Kpad, 0, fa, N, H, W, C, K, R, S, stride_h, stride_w, pad_h,
                               pad_w, dil_h, dil_w, rs, ob, 8, stream);
+}
+
+extern "C" int fq_conv2d_i8_pcs(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, const int32_t* rs_k, int rs_min,
+                                int rs_max, float* y_nchw, int N, int H, int W, int C, int K, int R, int S, int stride_h, int stride_w,
+                                int pad_h, int pad_w, int dil_h, int dil_w, int ob, int bitwidth, fq_stream_t stream) {
+    if ((!y_nchw || !rs_k) && N > 0) return FQ_ERR_INVALID_ARG;
+    return conv2d_i8_dispatch(x_nhwc, w_krsc, qbias, y_nchw, nullptr, 0, 0, FusedAdd{}, N, H, W, C, K, R, S, stride_h, stride_w, pad_h,
+                              pad_w, dil_h, dil_w, rs_min, ob, bitwidth, stream, rs_k, rs_max);
+}
+
+extern "C" int fq_conv2d_i8_resident_pcs(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, const int32_t* rs_k,
+                                         int rs_min, int rs_max, float* y_nchw, int8_t* q_nhwc, int Kpad, int relu, int N, int H, int W,
+                                         int C, int K, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                                         int dil_w, int ob, fq_stream_t stream) {
+    if (!rs_k && N > 0) return FQ_ERR_INVALID_ARG;
+    return conv2d_i8_dispatch(x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, Kpad, relu, FusedAdd{}, N, H, W, C, K, R, S, stride_h, stride_w, pad_h,
+                              pad_w, dil_h, dil_w, rs_min, ob, 8, stream, rs_k, rs_max);
+}
+
+extern "C" int fq_conv2d_i8_add_resident_pcs(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, const int32_t* rs_k,
+                                             int rs_min, int rs_max, const void* res, int res_bytes, int g_res, int16_t* wide,
+                                             int g_wide, int8_t* narrow, int ib, int relu, int Kpad, int N, int H, int W, int C, int K,
+                                             int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int ob,
+                                             fq_stream_t stream) {
+    if (!res || (res_bytes != 1 && res_bytes != 2) || (!rs_k && N > 0)) return FQ_ERR_INVALID_ARG;
+    FusedAdd fa;
+    fa.res = res; fa.res_bytes = res_bytes; fa.wide = wide;
+    const int rc = make_add_params(ob, g_res, g_wide, wide != nullptr, ib, relu, &fa.ap);
+    if (rc != FQ_OK) return rc;
+    return conv2d_i8_dispatch(x_nhwc, w_krsc, qbias, nullptr, narrow, Kpad, 0, fa, N, H, W, C, K, R, S, stride_h, stride_w, pad_h,
+                              pad_w, dil_h, dil_w, rs_min, ob, 8, stream, rs_k, rs_max);
 }
 
 #ifdef FQ_CONV_TRACE

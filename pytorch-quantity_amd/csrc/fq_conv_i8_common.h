@@ -34,6 +34,9 @@ struct ConvParams {
     AddResParams ap;
     // XCD-aware workgroup order (0 = plain 2-D grid): see conv_tile_of()
     int xcd_kt, tiles_m;
+    // per-channel shift (kOutPcs): rs_k[k] for output channel k < K replaces rs / half_rs / inv_rs; rs is then only nonzero or
+    // zero (integer or fp32 tail) and the shift of the padding channels k >= K, whose outputs are 0 either way
+    const int* rs_k;
 };
 
 // Activation loads are buffer loads: an out-of-image tap (zero padding) or a chunk past the end of the
@@ -81,6 +84,20 @@ __device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >>
 // resident hand-off to the next integer layer: 1 byte per element instead of 4 written + 4 read + 1).
 constexpr int kOutF32 = 1, kOutI8 = 2, kOutAdd = 4;      // kOutAdd: with kOutI8, NewAdd fused into the store
 constexpr int kOutResEarly = 8;                          // with kOutAdd (register-staged kernel): the residual is requested behind the first K-step's operand loads
+constexpr int kOutPcs = 16;                              // the shift is one per output channel (ConvParams::rs_k), staged in LDS beside B / lo / hi
+
+// The integer tail's constants of output channel k (tail_consts); a kOutPcs kernel also stages the channel's shift in sRs[t].
+// Rows k >= K carry zero weights and a zero bias and take the shift p.rs.  With the fp32 tail (p.rs == 0) only the shift is used.
+template <int kOut>
+__device__ __forceinline__ TailK stage_tail(int qb, const ConvParams& p, int* sRs, int t, int k) {
+    if constexpr ((kOut & kOutPcs) != 0) {
+        const int rs = k < p.K ? p.rs_k[k] : p.rs;
+        sRs[t] = rs;
+        return p.rs ? tail_consts_rs(qb, p, rs) : TailK{0, 0, 0};
+    } else {
+        return tail_consts(qb, p);
+    }
+}
 
 // fq_conv1x1_i8.hip: true when the streaming kernel took the launch (p is complete except xcd_kt / tiles_m)
 bool launch_conv1x1_stream(hipStream_t st, const int8_t* x, const int8_t* w, const float* qbias, float* y, int8_t* q,

@@ -64,6 +64,33 @@ __device__ __forceinline__ TailK tail_consts(int qb, const P& p) {
 __device__ __forceinline__ int conv_tail_k(int acc, int B, int lo, int hi, int rs) {
     return med3_i32((acc + B + (acc >> 31)) >> rs, lo, hi);
 }
+// tail_consts for a layer whose shift is one per output channel (fq_conv2d_i8_pcs): this channel's rs, 1 <= rs <= 16, in place
+// of p.rs / p.half_rs.  conv_tail_k then takes the same rs from a register -- v_ashrrev_i32 shifts by a VGPR as cheaply.
+template <typename P>
+__device__ __forceinline__ TailK tail_consts_rs(int qb, const P& p, int rs) {
+    TailK k;
+    const int qlo = p.slo - p.ihi, qhi = p.shi - p.ilo;
+    qb = qb < qlo ? qlo : (qb > qhi ? qhi : qb);
+    k.B = (1 << (rs - 1)) + (qb << rs);
+    const int a = p.ilo + qb, b = p.ihi + qb;
+    k.lo = a < p.slo ? p.slo : (a > p.shi ? p.shi : a);
+    k.hi = b < p.slo ? p.slo : (b > p.shi ? p.shi : b);
+    return k;
+}
+
+// Per-channel shift where no LDS row is left for it (fq_block_tail_i8): the shift rides in the low byte of the merged clamp's lower
+// bound, Lr = (lo << 8) | rs (lo is an Sp bound, |lo| <= 128), so the three per-channel constants stay three.  v_ashrrev_i32 reads
+// the low five bits of its count: the "& 31" costs nothing, recovering lo is one shift.
+__device__ __forceinline__ int pack_lo_rs(int lo, int rs) { return (int)((unsigned)lo << 8) | rs; }
+__device__ __forceinline__ int conv_tail_kp(int acc, int B, int Lr, int hi) {
+    return med3_i32((acc + B + (acc >> 31)) >> (Lr & 31), Lr >> 8, hi);
+}
+// conv_tail_i with this channel's shift, 1 <= rs <= 16 (fq_conv2d_i8_stem_pcs)
+template <typename P>
+__device__ __forceinline__ int conv_tail_i_rs(int acc, int qb, const P& p, int rs) {
+    const int r = (acc + (1 << (rs - 1)) + (acc >> 31)) >> rs;
+    return med3_i32(med3_i32(r, p.ilo, p.ihi) + qb, p.slo, p.shi);
+}
 
 // bytes 0 of four registers -> one dword
 __device__ __forceinline__ unsigned pack4(int b0, int b1, int b2, int b3) {

@@ -190,6 +190,40 @@ __global__ __launch_bounds__(kOpsBlock) void recon_epilogue_vec_kernel(const flo
     }
 }
 
+// Per-channel form (a layer whose shift is one per output channel, fq_recon_epilogue_pcs_f32): the RightShift of channel c is
+// by rs_k[c]; everything else as above.
+__global__ __launch_bounds__(kOpsBlock) void recon_epilogue_pcs_kernel(const float* __restrict__ acc, const float* __restrict__ qbias,
+                                                                       const int* __restrict__ rs_k, float* __restrict__ y, size_t planes,
+                                                                       size_t C, size_t inner, int ilo, int ihi, float lo, float hi,
+                                                                       float oinv) {
+    size_t i = (size_t)blockIdx.x * kOpsBlock + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * kOpsBlock;
+    const size_t n = planes * inner;
+    for (; i < n; i += stride) {
+        const size_t c = (i / inner) % C;
+        const RightShiftOp rs{ldexpf(1.0f, -rs_k[c]), ilo, ihi};
+        y[i] = clamp_nan(rs(acc[i]) + qbias[c], lo, hi) * oinv;
+    }
+}
+__global__ __launch_bounds__(kOpsBlock) void recon_epilogue_pcs_vec_kernel(const float4* __restrict__ acc, const float* __restrict__ qbias,
+                                                                           const int* __restrict__ rs_k, float4* __restrict__ y, size_t nvec,
+                                                                           size_t C, size_t inner4, int ilo, int ihi, float lo, float hi,
+                                                                           float oinv) {
+    size_t i = (size_t)blockIdx.x * kOpsBlock + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * kOpsBlock;
+    for (; i < nvec; i += stride) {
+        const size_t c = (i / inner4) % C;
+        const float bq = qbias[c];
+        const RightShiftOp rs{ldexpf(1.0f, -rs_k[c]), ilo, ihi};
+        float4 a = acc[i];
+        a.x = clamp_nan(rs(a.x) + bq, lo, hi) * oinv;
+        a.y = clamp_nan(rs(a.y) + bq, lo, hi) * oinv;
+        a.z = clamp_nan(rs(a.z) + bq, lo, hi) * oinv;
+        a.w = clamp_nan(rs(a.w) + bq, lo, hi) * oinv;
+        y[i] = a;
+    }
+}
+
 // ---- conv bias add / residual add of the float model with a calibration statistic taken on the way out --------------
 // A float Conv2d on this stack is a MIOpen convolution followed by a separate broadcast add of the bias (8 B per
 // element); the calibration then reads the result once more for the abs-max (pass 1) or the histogram (pass 2), 4 B.
@@ -458,6 +492,30 @@ extern "C" int fq_recon_epilogue_f32(const float* acc, const float* qbias, float
     } else {
         hipLaunchKernelGGL(recon_epilogue_kernel, dim3(grid_for(n)), dim3(kOpsBlock), 0, st, acc, qbias, y,
                            outer * C, C, inner, rso, r.lo, r.hi, oscale);
+    }
+    FQ_LAUNCH_CHECK();
+    return FQ_OK;
+}
+
+extern "C" int fq_recon_epilogue_pcs_f32(const float* acc, const float* qbias, const int32_t* rs_k, int rs_min, int rs_max, float* y,
+                                         size_t outer, size_t C, size_t inner, int ob, int bitwidth, fq_stream_t stream) {
+    if (!valid_bitwidth(bitwidth) || rs_min < -120 || rs_max > 120 || rs_min > rs_max || ob < -120 || ob > 120)
+        return FQ_ERR_INVALID_ARG;
+    const size_t n = outer * C * inner;
+    if (n == 0) return FQ_OK;
+    if (!acc || !qbias || !rs_k || !y) return FQ_ERR_INVALID_ARG;
+    const Range r = range_of(bitwidth);
+    const float oscale = ldexpf(1.0f, -ob);
+    hipStream_t st = as_stream(stream);
+    const bool aligned = ((reinterpret_cast<uintptr_t>(acc) | reinterpret_cast<uintptr_t>(y)) & 15u) == 0;
+    if (aligned && (inner & 3u) == 0) {
+        const size_t nvec = n >> 2;
+        hipLaunchKernelGGL(recon_epilogue_pcs_vec_kernel, dim3(grid_for(nvec)), dim3(kOpsBlock), 0, st,
+                           reinterpret_cast<const float4*>(acc), qbias, rs_k, reinterpret_cast<float4*>(y), nvec, C, inner >> 2,
+                           (int)r.lo, (int)r.hi, r.lo, r.hi, oscale);
+    } else {
+        hipLaunchKernelGGL(recon_epilogue_pcs_kernel, dim3(grid_for(n)), dim3(kOpsBlock), 0, st, acc, qbias, rs_k, y, outer * C, C,
+                           inner, (int)r.lo, (int)r.hi, r.lo, r.hi, oscale);
     }
     FQ_LAUNCH_CHECK();
     return FQ_OK;

@@ -41,16 +41,18 @@ struct StemParams {
     unsigned xcd_chunk;      // tiles per XCD (ceil(ntiles / 8)), 0: tiles dealt round robin (FQ_STEM_XCD=0)
     float scale;             // 2^ib
     int rs, half_rs, ilo, ihi, slo, shi;
+    const int* rs_k;         // kPcs: the shift of each output channel (fq_conv2d_i8_stem_pcs); channels >= K take rs
 };
 
 // kC = input channels (compile time: the quantise and fetch loops touch exactly kC planes).  The waves-per-SIMD target
 // keeps the accumulators out of the AGPRs (no v_accvgpr_read per output in the tail).
-template <int kC>
+template <int kC, bool kPcs = false>
 __global__ __launch_bounds__(kStemBlock) __attribute__((amdgpu_waves_per_eu(4))) void stem_conv_i8_kernel(const StemParams p) {
     __shared__ __attribute__((aligned(16))) int8_t sW[kStemMaxR * kStemK * 32];
     __shared__ __attribute__((aligned(16))) unsigned sPatch[kStemPatchWords];
     __shared__ __attribute__((aligned(16))) int8_t sOut[4][32 * kStemOS];
     __shared__ int sBiasI[kStemK];
+    __shared__ int sRs[kPcs ? kStemK : 1];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
 
@@ -60,6 +62,9 @@ __global__ __launch_bounds__(kStemBlock) __attribute__((amdgpu_waves_per_eu(4)))
         v4i* dst = reinterpret_cast<v4i*>(sW);
         for (int i = tid; i < p.R * kStemK * 2; i += kStemBlock) dst[i] = src[i];
         if (tid < kStemK) sBiasI[tid] = tid < p.K ? (int)p.qbias[tid] : 0;
+        if constexpr (kPcs) {
+            if (tid < kStemK) sRs[tid] = tid < p.K ? p.rs_k[tid] : p.rs;
+        }
         for (int i = tid; i < kStemPatchWords; i += kStemBlock) sPatch[i] = 0u;    // the over-read margin stays zero
     }
 
@@ -167,7 +172,8 @@ __global__ __launch_bounds__(kStemBlock) __attribute__((amdgpu_waves_per_eu(4)))
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int kl = a * 32 + 8 * g + 4 * half + e;
-                    v[e] = conv_tail_i(acc[a][4 * g + e], sBiasI[kl], p);
+                    if constexpr (kPcs) v[e] = conv_tail_i_rs(acc[a][4 * g + e], sBiasI[kl], p, sRs[kl]);
+                    else v[e] = conv_tail_i(acc[a][4 * g + e], sBiasI[kl], p);
                 }
                 *reinterpret_cast<unsigned*>(&so[a * 32 + 8 * g + 4 * half]) = pack4(v[0], v[1], v[2], v[3]);
             }
@@ -191,9 +197,9 @@ __global__ __launch_bounds__(kStemBlock) __attribute__((amdgpu_waves_per_eu(4)))
 }  // namespace fq
 
 // fp32 NCHW image -> int8 NHWC activations of the stem convolution (see include/fq.h)
-extern "C" int fq_conv2d_i8_stem(const float* x_nchw, const int8_t* w_stem, const float* qbias, int8_t* q_nhwc, int Kpad, int relu,
-                                 int N, int C, int H, int W, int K, int R, int S, int stride_h, int stride_w, int pad_h,
-                                 int pad_w, int ib, int rs, int ob, fq_stream_t stream) {
+static int stem_dispatch(const float* x_nchw, const int8_t* w_stem, const float* qbias, int8_t* q_nhwc, int Kpad, int relu,
+                         int N, int C, int H, int W, int K, int R, int S, int stride_h, int stride_w, int pad_h,
+                         int pad_w, int ib, int rs, int ob, fq_stream_t stream, const int32_t* rs_k) {
     using namespace fq;
     (void)ob;                                             // the output integers stand for q * 2^-ob; nothing to scale here
     if (N < 0 || C < 1 || C > 4 || H < 1 || W < 1 || K < 1 || K > kStemK || R < 1 || R > kStemMaxR || S < 1 || S > 8)
@@ -228,6 +234,7 @@ extern "C" int fq_conv2d_i8_stem(const float* x_nchw, const int8_t* w_stem, cons
     p.xcd_chunk = xcd_order ? (unsigned)((ntiles + 7) / 8) : 0u;
     p.scale = ldexpf(1.0f, ib);
     p.rs = rs; p.half_rs = 1 << (rs - 1);
+    p.rs_k = rs_k;
     p.ilo = -128; p.ihi = 127;
     p.slo = relu ? 0 : -128; p.shi = 127;
     static const int per_cu = [] { const char* e = getenv("FQ_STEM_WG_PER_CU"); return e ? atoi(e) : 0; }();
@@ -235,13 +242,39 @@ extern "C" int fq_conv2d_i8_stem(const float* x_nchw, const int8_t* w_stem, cons
     if (grid > ntiles) grid = ntiles;
     const dim3 g((unsigned)grid), b(kStemBlock);
     hipStream_t st = as_stream(stream);
-    switch (C) {
-        case 1: hipLaunchKernelGGL(stem_conv_i8_kernel<1>, g, b, 0, st, p); break;
-        case 2: hipLaunchKernelGGL(stem_conv_i8_kernel<2>, g, b, 0, st, p); break;
-        case 3: hipLaunchKernelGGL(stem_conv_i8_kernel<3>, g, b, 0, st, p); break;
-        default: hipLaunchKernelGGL(stem_conv_i8_kernel<4>, g, b, 0, st, p); break;
+    if (rs_k) {
+        switch (C) {
+            case 1: hipLaunchKernelGGL((stem_conv_i8_kernel<1, true>), g, b, 0, st, p); break;
+            case 2: hipLaunchKernelGGL((stem_conv_i8_kernel<2, true>), g, b, 0, st, p); break;
+            case 3: hipLaunchKernelGGL((stem_conv_i8_kernel<3, true>), g, b, 0, st, p); break;
+            default: hipLaunchKernelGGL((stem_conv_i8_kernel<4, true>), g, b, 0, st, p); break;
+        }
+    } else {
+        switch (C) {
+            case 1: hipLaunchKernelGGL(stem_conv_i8_kernel<1>, g, b, 0, st, p); break;
+            case 2: hipLaunchKernelGGL(stem_conv_i8_kernel<2>, g, b, 0, st, p); break;
+            case 3: hipLaunchKernelGGL(stem_conv_i8_kernel<3>, g, b, 0, st, p); break;
+            default: hipLaunchKernelGGL(stem_conv_i8_kernel<4>, g, b, 0, st, p); break;
+        }
     }
     note_conv_variant(kVarStem, 64);
     FQ_LAUNCH_CHECK();
     return FQ_OK;
+}
+
+extern "C" int fq_conv2d_i8_stem(const float* x_nchw, const int8_t* w_stem, const float* qbias, int8_t* q_nhwc, int Kpad, int relu,
+                                 int N, int C, int H, int W, int K, int R, int S, int stride_h, int stride_w, int pad_h,
+                                 int pad_w, int ib, int rs, int ob, fq_stream_t stream) {
+    return stem_dispatch(x_nchw, w_stem, qbias, q_nhwc, Kpad, relu, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, ib, rs, ob,
+                         stream, nullptr);
+}
+
+// the same with one shift per output channel: rs_k device int32[K], rs_min <= rs_k[k] <= rs_max, both in [1, 16]
+extern "C" int fq_conv2d_i8_stem_pcs(const float* x_nchw, const int8_t* w_stem, const float* qbias, const int32_t* rs_k, int rs_min,
+                                     int rs_max, int8_t* q_nhwc, int Kpad, int relu, int N, int C, int H, int W, int K, int R, int S,
+                                     int stride_h, int stride_w, int pad_h, int pad_w, int ib, int ob, fq_stream_t stream) {
+    if (rs_min < 1 || rs_max > 16 || rs_min > rs_max) return FQ_ERR_INVALID_ARG;
+    if (N > 0 && (!rs_k || (reinterpret_cast<uintptr_t>(rs_k) & 3u))) return FQ_ERR_INVALID_ARG;
+    return stem_dispatch(x_nchw, w_stem, qbias, q_nhwc, Kpad, relu, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, ib, rs_min, ob,
+                         stream, N > 0 ? rs_k : nullptr);
 }

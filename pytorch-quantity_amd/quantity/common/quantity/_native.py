@@ -114,6 +114,14 @@ def lib():
     L.fq_conv2d_i8.argtypes = [vp, vp, vp, vp] + [ci] * 16 + [vp]
     L.fq_conv2d_i8_resident.restype = ci
     L.fq_conv2d_i8_resident.argtypes = [vp, vp, vp, vp, vp] + [ci] * 17 + [vp]
+    L.fq_conv2d_i8_pcs.restype = ci
+    L.fq_conv2d_i8_pcs.argtypes = [vp, vp, vp, vp, ci, ci, vp] + [ci] * 15 + [vp]
+    L.fq_conv2d_i8_resident_pcs.restype = ci
+    L.fq_conv2d_i8_resident_pcs.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp] + [ci] * 16 + [vp]
+    L.fq_conv2d_i8_add_resident_pcs.restype = ci
+    L.fq_conv2d_i8_add_resident_pcs.argtypes = [vp, vp, vp, vp, ci, ci, vp, ci, ci, vp, ci, vp] + [ci] * 17 + [vp]
+    L.fq_recon_epilogue_pcs_f32.restype = ci
+    L.fq_recon_epilogue_pcs_f32.argtypes = [vp, vp, vp, ci, ci, vp, sz, sz, sz, ci, ci, vp]
     L.fq_bias_add_absmax_f32.restype = ci
     L.fq_bias_add_absmax_f32.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp]
     L.fq_add_absmax_f32.restype = ci
@@ -183,6 +191,18 @@ def lib():
     L.fq_block_tail_proj_i8_supported.restype = ci
     L.fq_block_tail_proj_i8_supported.argtypes = [ci] * 8
     L.fq_block_tail_proj_i8.restype = ci
+    L.fq_block_tail_i8_pcs_supported.restype = ci
+    L.fq_block_tail_i8_pcs_supported.argtypes = [ci] * 11
+    L.fq_block_tail_i8_pcs.restype = ci
+    L.fq_block_tail_i8_pcs.argtypes = ([vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, vp, ci, vp, ci, ci, vp, vp, vp, ci, ci, ci, vp,
+                                        ctypes.c_long, ci, ci, ci, vp])
+    L.fq_block_tail_proj_i8_pcs_supported.restype = ci
+    L.fq_block_tail_proj_i8_pcs_supported.argtypes = [ci] * 11
+    L.fq_block_tail_proj_i8_pcs.restype = ci
+    L.fq_block_tail_proj_i8_pcs.argtypes = ([vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, ci, ci,
+                                             vp, vp, vp, ci, ci, ci, vp] + [ci] * 7 + [vp])
+    L.fq_conv2d_i8_stem_pcs.restype = ci
+    L.fq_conv2d_i8_stem_pcs.argtypes = [vp, vp, vp, vp, ci, ci, vp] + [ci] * 15 + [vp]
     L.fq_block_tail_proj_i8.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, ci, vp, ci, ci, vp, vp, ci, ci, vp] + [ci] * 7 + [vp]
     L.fq_add_resident.restype = ci
     L.fq_add_resident.argtypes = [vp, ci, ci, vp, ci, ci, vp, ci, vp, ci, ci, sz, vp]
@@ -887,8 +907,47 @@ def add_sat(a, b, bitwidth=8, out=None):
     return y
 
 
+class ShiftVec(object):
+    """The right shift of a layer with per-channel weight bits, in place of an int `rs`: rs_k[c] = wb[c] + ib - ob as a
+    device int32[K] tensor, plus its bounds lo <= rs_k[c] <= hi, known on the host (the kernels choose their tail from them)."""
+    __slots__ = ("t", "lo", "hi")
+
+    def __init__(self, t, lo, hi):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and int(lo) <= int(hi)
+        self.t, self.lo, self.hi = t, int(lo), int(hi)
+
+
+_CONST_SHIFTS = {}
+
+
+def _shift_of(rs, K, device):
+    """rs as a ShiftVec of K entries: a per-tensor shift (an int) becomes a constant vector, made once per (value, K, device) and
+    kept, so that a per-tensor layer can share a kernel with per-channel neighbours (and a captured graph finds it made)."""
+    if isinstance(rs, ShiftVec):
+        return rs
+    key = (int(rs), int(K), str(device))
+    t = _CONST_SHIFTS.get(key)
+    if t is None:
+        t = torch.full((int(K),), int(rs), dtype=torch.int32, device=device)
+        _CONST_SHIFTS[key] = t
+    return ShiftVec(t, int(rs), int(rs))
+
+
+def _bounds(rs):
+    return (rs.lo, rs.hi) if isinstance(rs, ShiftVec) else (int(rs), int(rs))
+
+
+def _shift_vec(rs, K, device, what):
+    if rs.t.numel() != K or rs.t.device != device:
+        raise FqError("%s: the per-channel shift must be an int32 tensor of %d entries on %s" % (what, K, device))
+    if rs.t.data_ptr() & 15:
+        raise FqError("%s: the per-channel shift must be 16-byte aligned" % what)
+    return rs.t.data_ptr()
+
+
 def recon_epilogue(acc, qbias, rs, ob, bitwidth=8, out=None):
-    """acc: [N, C, ...] fp32 (conv/linear accumulator), qbias: fp32[C] integer valued."""
+    """acc: [N, C, ...] fp32 (conv/linear accumulator), qbias: fp32[C] integer valued.  rs: int, or a ShiftVec of C shifts
+    (fq_recon_epilogue_pcs_f32)."""
     _need_cuda(acc, torch.float32, "fq_recon_epilogue_f32")
     _need_cuda(qbias, torch.float32, "fq_recon_epilogue_f32")
     ac = acc.contiguous()
@@ -897,6 +956,11 @@ def recon_epilogue(acc, qbias, rs, ob, bitwidth=8, out=None):
     outer = ac.shape[0]
     inner = ac.numel() // (outer * C) if ac.numel() else 0
     y = _out_like(ac, out)
+    if isinstance(rs, ShiftVec):
+        rk = _shift_vec(rs, C, ac.device, "fq_recon_epilogue_pcs_f32")
+        _check(lib().fq_recon_epilogue_pcs_f32(ac.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi, y.data_ptr(), outer,
+                                               C, inner, int(ob), int(bitwidth), _stream(ac)), "fq_recon_epilogue_pcs_f32")
+        return y
     _check(lib().fq_recon_epilogue_f32(ac.data_ptr(), qbias.contiguous().data_ptr(), y.data_ptr(), outer, C, inner,
                                        int(rs), int(ob), int(bitwidth), _stream(ac)), "fq_recon_epilogue_f32")
     return y
@@ -983,9 +1047,15 @@ def conv2d_i8(xq, wq, qbias, stride, padding, dilation, rs, ob, bitwidth=8):
     P = (H + 2 * padding[0] - dilation[0] * (R - 1) - 1) // stride[0] + 1
     Q = (W + 2 * padding[1] - dilation[1] * (S - 1) - 1) // stride[1] + 1
     y = torch.empty(N, K, P, Q, dtype=torch.float32, device=xq.device)
-    _check(lib().fq_conv2d_i8(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), y.data_ptr(), N, H, W, C, K, R, S,
-                              stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], int(rs), int(ob),
-                              int(bitwidth), _stream(xq)), "fq_conv2d_i8")
+    if isinstance(rs, ShiftVec):
+        rk = _shift_vec(rs, K, xq.device, "fq_conv2d_i8_pcs")
+        _check(lib().fq_conv2d_i8_pcs(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi, y.data_ptr(), N,
+                                      H, W, C, K, R, S, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
+                                      int(ob), int(bitwidth), _stream(xq)), "fq_conv2d_i8_pcs")
+    else:
+        _check(lib().fq_conv2d_i8(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), y.data_ptr(), N, H, W, C, K, R, S,
+                                  stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], int(rs), int(ob),
+                                  int(bitwidth), _stream(xq)), "fq_conv2d_i8")
     _note_variant()
     return y.view(N, K) if linear else y
 
@@ -1004,6 +1074,14 @@ def conv2d_i8_resident(xq, wq, qbias, stride, padding, dilation, rs, ob, want_f3
     kpad = pad16(K)
     y = torch.empty(N, K, P, Q, dtype=torch.float32, device=xq.device) if want_f32 else None
     q = torch.empty(N, P, Q, kpad, dtype=torch.int8, device=xq.device) if want_i8 else None
+    if isinstance(rs, ShiftVec):
+        rk = _shift_vec(rs, K, xq.device, "fq_conv2d_i8_resident_pcs")
+        _check(lib().fq_conv2d_i8_resident_pcs(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi,
+                                               y.data_ptr() if want_f32 else None, q.data_ptr() if want_i8 else None, kpad,
+                                               1 if relu else 0, N, H, W, C, K, R, S, stride[0], stride[1], padding[0], padding[1],
+                                               dilation[0], dilation[1], int(ob), _stream(xq)), "fq_conv2d_i8_resident_pcs")
+        _note_variant()
+        return y, q
     _check(lib().fq_conv2d_i8_resident(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(),
                                        y.data_ptr() if want_f32 else None, q.data_ptr() if want_i8 else None, kpad,
                                        1 if relu else 0, N, H, W, C, K, R, S, stride[0], stride[1], padding[0], padding[1],
@@ -1017,7 +1095,8 @@ STEM_MAX_K, STEM_MAX_R, STEM_MAX_S, STEM_MAX_C = 64, 8, 8, 4
 
 def stem_supported(C, K, R, S, stride, dilation, rs):
     """True when fq_conv2d_i8_stem takes this layer (include/fq.h); otherwise the unfold path computes the same integers."""
-    if C > STEM_MAX_C or K > STEM_MAX_K or R > STEM_MAX_R or S > STEM_MAX_S or tuple(dilation) != (1, 1) or not 1 <= rs <= 16:
+    lo, hi = _bounds(rs)              # (a per-channel shift: fq_conv2d_i8_stem_pcs, every shift in [1, 16])
+    if C > STEM_MAX_C or K > STEM_MAX_K or R > STEM_MAX_R or S > STEM_MAX_S or tuple(dilation) != (1, 1) or not (1 <= lo and hi <= 16):
         return False
     pr, pc = 7 * stride[0] + R, 15 * stride[1] + S
     pcs = max(15 * stride[1] + 8, pc) | 1
@@ -1044,6 +1123,13 @@ def conv2d_i8_stem(x, w_stem, qbias, K, S, stride, padding, ib, rs, ob, relu):
     Q = (W + 2 * padding[1] - S) // stride[1] + 1
     kpad = pad16(K)
     q = torch.empty(N, P, Q, kpad, dtype=torch.int8, device=x.device)
+    if isinstance(rs, ShiftVec):
+        rk = _shift_vec(rs, K, x.device, "fq_conv2d_i8_stem_pcs")
+        _check(lib().fq_conv2d_i8_stem_pcs(x.data_ptr(), w_stem.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi, q.data_ptr(),
+                                           kpad, 1 if relu else 0, N, C, H, W, K, R, S, stride[0], stride[1], padding[0], padding[1],
+                                           int(ib), int(ob), _stream(x)), "fq_conv2d_i8_stem_pcs")
+        _note_variant()
+        return q
     _check(lib().fq_conv2d_i8_stem(x.data_ptr(), w_stem.data_ptr(), qbias.contiguous().data_ptr(), q.data_ptr(), kpad,
                                    1 if relu else 0, N, C, H, W, K, R, S, stride[0], stride[1], padding[0], padding[1],
                                    int(ib), int(rs), int(ob), _stream(x)), "fq_conv2d_i8_stem")
@@ -1071,6 +1157,16 @@ def conv2d_i8_add_resident(xq, wq, qbias, stride, padding, dilation, rs, ob, res
     assert tuple(res.shape) == (N, P, Q, kpad), (tuple(res.shape), (N, P, Q, kpad))
     wide = torch.empty(N, P, Q, kpad, dtype=torch.int16, device=xq.device) if want_wide else None
     narrow = torch.empty(N, P, Q, kpad, dtype=torch.int8, device=xq.device) if want_narrow else None
+    if isinstance(rs, ShiftVec):
+        rk = _shift_vec(rs, K, xq.device, "fq_conv2d_i8_add_resident_pcs")
+        _check(lib().fq_conv2d_i8_add_resident_pcs(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi,
+                                                   res.data_ptr(), _INT_BYTES[res.dtype], int(g_res),
+                                                   wide.data_ptr() if want_wide else None, int(g_wide),
+                                                   narrow.data_ptr() if want_narrow else None, int(ib), 1 if relu else 0, kpad, N, H,
+                                                   W, C, K, R, S, stride[0], stride[1], padding[0], padding[1], dilation[0],
+                                                   dilation[1], int(ob), _stream(xq)), "fq_conv2d_i8_add_resident_pcs")
+        _note_variant()
+        return wide, narrow
     _check(lib().fq_conv2d_i8_add_resident(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), res.data_ptr(),
                                            _INT_BYTES[res.dtype], int(g_res), wide.data_ptr() if want_wide else None, int(g_wide),
                                            narrow.data_ptr() if want_narrow else None, int(ib), 1 if relu else 0, kpad, N, H, W, C,
@@ -1081,7 +1177,12 @@ def conv2d_i8_add_resident(xq, wq, qbias, stride, padding, dilation, rs, ob, res
 
 
 def block_tail_supported(C, K3, C2, rs3, rs1, ob3, g_res, res_bytes, ib):
-    """Does fq_block_tail_i8 take this chain?  (shapes, integer tails, and grids for which NewAdd's packed-int16 form holds)"""
+    """Does fq_block_tail_i8 take this chain?  (shapes, integer tails, and grids for which NewAdd's packed-int16 form holds)
+    With a per-channel shift (ShiftVec) anywhere: fq_block_tail_i8_pcs_supported on the bounds."""
+    if isinstance(rs3, ShiftVec) or isinstance(rs1, ShiftVec):
+        (a, b), (c, d) = _bounds(rs3), _bounds(rs1)
+        return bool(lib().fq_block_tail_i8_pcs_supported(int(C), int(K3), int(C2), a, b, c, d, int(ob3), int(g_res), int(res_bytes),
+                                                         int(ib)))
     return bool(lib().fq_block_tail_i8_supported(int(C), int(K3), int(C2), int(rs3), int(rs1), int(ob3), int(g_res), int(res_bytes),
                                                  int(ib)))
 
@@ -1110,6 +1211,20 @@ def block_tail_i8(xq, w3q, qbias3, rs3, ob3, res, g_res, want_wide, g_wide, want
     wide = torch.empty(N, H, W, K3, dtype=torch.int16, device=xq.device) if want_wide else None
     narrow = torch.empty(N, H, W, K3, dtype=torch.int8, device=xq.device) if want_narrow else None
     q1 = torch.empty(N, H, W, C2, dtype=torch.int8, device=xq.device) if C2 else None
+    if isinstance(rs3, ShiftVec) or isinstance(rs1, ShiftVec):
+        # per-channel: both shifts as vectors (a per-tensor neighbour as a constant one)
+        v3 = _shift_of(rs3, K3, xq.device)
+        r3 = _shift_vec(v3, K3, xq.device, "fq_block_tail_i8_pcs")
+        v1 = _shift_of(rs1, C2, xq.device) if C2 else None
+        r1 = _shift_vec(v1, C2, xq.device, "fq_block_tail_i8_pcs") if C2 else None
+        _check(lib().fq_block_tail_i8_pcs(xq.data_ptr(), w3q.data_ptr(), qbias3.contiguous().data_ptr(), r3, v3.lo, v3.hi, int(ob3),
+                                          res.data_ptr(), _INT_BYTES[res.dtype], int(g_res), wide.data_ptr() if want_wide else None,
+                                          int(g_wide), narrow.data_ptr() if want_narrow else None, int(ib), 1 if relu else 0,
+                                          w1q.data_ptr() if C2 else None, qbias1.contiguous().data_ptr() if C2 else None, r1,
+                                          v1.lo if C2 else 1, v1.hi if C2 else 1, 1 if relu1 else 0, q1.data_ptr() if C2 else None,
+                                          N * H * W, C, K3, C2, _stream(xq)), "fq_block_tail_i8_pcs")
+        _note_variant()
+        return wide, narrow, q1
     _check(lib().fq_block_tail_i8(xq.data_ptr(), w3q.data_ptr(), qbias3.contiguous().data_ptr(), int(rs3), int(ob3), res.data_ptr(),
                                   _INT_BYTES[res.dtype], int(g_res), wide.data_ptr() if want_wide else None, int(g_wide),
                                   narrow.data_ptr() if want_narrow else None, int(ib), 1 if relu else 0,
@@ -1123,6 +1238,9 @@ def block_tail_i8(xq, w3q, qbias3, rs3, ob3, res, g_res, want_wide, g_wide, want
 def block_tail_proj_supported(C, K3, C2, CP, rs3, rs1, rsp, stride_p):
     """Does fq_block_tail_proj_i8 take this chain (the tail of a stage's first block with its projection shortcut computed in the
     kernel)?"""
+    if isinstance(rs3, ShiftVec) or isinstance(rs1, ShiftVec) or isinstance(rsp, ShiftVec):
+        (a, b), (c, d), (e, f) = _bounds(rs3), _bounds(rs1), _bounds(rsp)          # (as block_tail_supported)
+        return bool(lib().fq_block_tail_proj_i8_pcs_supported(int(C), int(K3), int(C2), int(CP), a, b, c, d, e, f, int(stride_p)))
     return bool(lib().fq_block_tail_proj_i8_supported(int(C), int(K3), int(C2), int(CP), int(rs3), int(rs1), int(rsp), int(stride_p)))
 
 
@@ -1150,6 +1268,21 @@ def block_tail_proj_i8(xq, w3q, qbias3, rs3, ob3, xpq, wpq, qbiasp, rsp, obp, st
     wide = torch.empty(N, H, W, K3, dtype=torch.int16, device=xq.device) if want_wide else None
     narrow = torch.empty(N, H, W, K3, dtype=torch.int8, device=xq.device) if want_narrow else None
     q1 = torch.empty(N, H, W, C2, dtype=torch.int8, device=xq.device) if C2 else None
+    if isinstance(rs3, ShiftVec) or isinstance(rs1, ShiftVec) or isinstance(rsp, ShiftVec):
+        v3, vp_ = _shift_of(rs3, K3, xq.device), _shift_of(rsp, K3, xq.device)
+        v1 = _shift_of(rs1, C2, xq.device) if C2 else None
+        r3 = _shift_vec(v3, K3, xq.device, "fq_block_tail_proj_i8_pcs")
+        rp = _shift_vec(vp_, K3, xq.device, "fq_block_tail_proj_i8_pcs")
+        r1 = _shift_vec(v1, C2, xq.device, "fq_block_tail_proj_i8_pcs") if C2 else None
+        _check(lib().fq_block_tail_proj_i8_pcs(xq.data_ptr(), w3q.data_ptr(), qbias3.contiguous().data_ptr(), r3, v3.lo, v3.hi, int(ob3),
+                                               xpq.data_ptr(), wpq.data_ptr(), qbiasp.contiguous().data_ptr(), rp, vp_.lo, vp_.hi,
+                                               int(obp), int(stride_p), Hp, Wp, wide.data_ptr() if want_wide else None, int(g_wide),
+                                               narrow.data_ptr() if want_narrow else None, int(ib), 1 if relu else 0,
+                                               w1q.data_ptr() if C2 else None, qbias1.contiguous().data_ptr() if C2 else None, r1,
+                                               v1.lo if C2 else 1, v1.hi if C2 else 1, 1 if relu1 else 0, q1.data_ptr() if C2 else None,
+                                               N, H, W, C, K3, C2, CP, _stream(xq)), "fq_block_tail_proj_i8_pcs")
+        _note_variant()
+        return wide, narrow, q1
     _check(lib().fq_block_tail_proj_i8(xq.data_ptr(), w3q.data_ptr(), qbias3.contiguous().data_ptr(), int(rs3), int(ob3),
                                        xpq.data_ptr(), wpq.data_ptr(), qbiasp.contiguous().data_ptr(), int(rsp), int(obp),
                                        int(stride_p), Hp, Wp, wide.data_ptr() if want_wide else None, int(g_wide),

@@ -47,6 +47,11 @@ class RightShift(nn.Module):
 
     def forward(self, x):
         _check_width(self.Bit_width)
+        if isinstance(self.rs, list):
+            # a layer with per-channel weight bits: channel c (dimension 1) shifted by rs[c] -- the per-channel epilogue with a
+            # zero bias and DeQuantity(0), whose clamp is the same saturation
+            rs = _native.ShiftVec(torch.tensor(self.rs, dtype=torch.int32, device=x.device), min(self.rs), max(self.rs))
+            return _native.recon_epilogue(x, torch.zeros(len(self.rs), device=x.device), rs, 0, self.Bit_width)
         return _native.rightshift(x, self.rs, self.Bit_width)
 
 
@@ -95,13 +100,27 @@ class BiasAdd(nn.Module):
 
 def _quantize_params(layer, weight_bit, bias_bit, out_count, weight_16bit_range=False):
     """Integer-valued fp32 weights / bias of a conv or linear layer (reference :135-163, :208-236).
-    One-time parameter preparation, done with torch ops on whatever device the layer lives on."""
+    One-time parameter preparation, done with torch ops on whatever device the layer lives on.
+    weight_bit: one int, or a list of one bit per output channel (per-channel weight bits)."""
     assert layer.weight is not None, "The layer weight can`t be None"
     w = layer.weight.data
     b = layer.bias.data if layer.bias is not None else torch.zeros(out_count, device=w.device, dtype=w.dtype)
     w_width = 8 if (QUANTIZE_BIT == 8 or not weight_16bit_range) else 16
     b_width = 8 if QUANTIZE_BIT == 8 else 16
-    return _round_clamp(w, weight_bit, w_width), _round_clamp(b, bias_bit, b_width)
+    return _per_channel(_round_clamp, w, weight_bit, w_width), _round_clamp(b, bias_bit, b_width)
+
+
+def _per_channel(fn, t, bit, width):
+    """fn(t, bit, width) with `bit` an int, or a list of one bit per row of t (dimension 0): the rows that share a bit go
+    through fn together, so each row gets exactly the arithmetic of a per-tensor call with its bit."""
+    if not isinstance(bit, (list, tuple)):
+        return fn(t, bit, width)
+    assert len(bit) == t.shape[0], (len(bit), tuple(t.shape))
+    out = torch.empty_like(t)
+    for b in sorted(set(int(v) for v in bit)):
+        rows = torch.tensor([i for i, v in enumerate(bit) if int(v) == b], dtype=torch.long, device=t.device)
+        out[rows] = fn(t.index_select(0, rows).contiguous(), b, width)
+    return out
 
 
 def _round_clamp(t, bit, width):
@@ -204,7 +223,16 @@ class _IntegerSimLayer(nn.Module):
         self.bias_bit = quantize_infor["bias_bit"]
         self.input_bit = quantize_infor["input_bit"]
         self.output_bit = quantize_infor["output_bit"]
-        self.rs_bit = self.weight_bit + self.input_bit - self.output_bit
+        if isinstance(self.weight_bit, (list, tuple)):
+            # per-channel weight bits: rs[c] = wb[c] + ib - ob, one shift per output channel (kernels: the _pcs entry points)
+            self.weight_bit = [int(b) for b in self.weight_bit]
+            assert len(self.weight_bit) == out_count, (len(self.weight_bit), out_count)
+            self.rs_bit = [b + self.input_bit - self.output_bit for b in self.weight_bit]
+            self.rs_min, self.rs_max = min(self.rs_bit), max(self.rs_bit)
+            self.register_buffer("rs_vec", torch.tensor(self.rs_bit, dtype=torch.int32, device=layer.weight.device),
+                                 persistent=False)
+        else:
+            self.rs_bit = self.weight_bit + self.input_bit - self.output_bit
         self.Quan = Quantity(self.input_bit)
         self.RightShift = RightShift(QUANTIZE_BIT, self.rs_bit)
         self.BiasAdd = BiasAdd()
@@ -222,8 +250,14 @@ class _IntegerSimLayer(nn.Module):
         # (non-persistent: state_dict keys stay the reference's)
         self.register_buffer("quantized_bias", qb, persistent=False)
 
+    def _rs(self):
+        """The shift as the kernels take it: rs_bit, or for per-channel weight bits the device vector with its bounds."""
+        if isinstance(self.rs_bit, list):
+            return _native.ShiftVec(self.rs_vec, self.rs_min, self.rs_max)
+        return self.rs_bit
+
     def _tail(self, acc):
-        return _native.recon_epilogue(acc, self.quantized_bias, self.rs_bit, self.output_bit,
+        return _native.recon_epilogue(acc, self.quantized_bias, self._rs(), self.output_bit,
                                       8 if QUANTIZE_BIT == 8 else 16, out=acc)
 
 
@@ -247,12 +281,12 @@ class NewConv2d(_IntegerSimLayer):
             fold = self._stem_fold(conv)
             if (fold and plan is not None and plan.emit_int and not plan.emit_f32 and not plan.defer and self.use_stem_kernel
                     and _native.stem_supported(conv.in_channels, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1],
-                                               conv.stride, conv.dilation, self.rs_bit)):
+                                               conv.stride, conv.dilation, self._rs())):
                 # the whole layer in one kernel: fp32 image in, int8 NHWC out (no unfolded copy of the image)
                 x = as_f32(input)
                 q = _native.conv2d_i8_stem(x if x.is_contiguous() else x.contiguous(), self._stem_weight(conv),
                                            self.quantized_bias, conv.out_channels, conv.kernel_size[1], conv.stride,
-                                           conv.padding, self.input_bit, self.rs_bit, self.output_bit, plan.relu)
+                                           conv.padding, self.input_bit, self._rs(), self.output_bit, plan.relu)
                 return QHandle((q.shape[0], conv.out_channels, q.shape[1], q.shape[2]), q, self.output_bit, q,
                                self.output_bit, plan.relu)
             if fold:
@@ -266,11 +300,11 @@ class NewConv2d(_IntegerSimLayer):
                     xq = _xq_cache.get(as_f32(input), self.input_bit, wq.shape[-1])
                 geom = (conv.stride, conv.padding, conv.dilation)
             if plan is None:
-                return _native.conv2d_i8(xq, wq, self.quantized_bias, geom[0], geom[1], geom[2], self.rs_bit,
+                return _native.conv2d_i8(xq, wq, self.quantized_bias, geom[0], geom[1], geom[2], self._rs(),
                                          self.output_bit, 8)
             if plan.defer:
                 return DeferredConv(self, xq, wq, geom)   # the resident NewAdd that consumes it runs it
-            y, q = _native.conv2d_i8_resident(xq, wq, self.quantized_bias, geom[0], geom[1], geom[2], self.rs_bit,
+            y, q = _native.conv2d_i8_resident(xq, wq, self.quantized_bias, geom[0], geom[1], geom[2], self._rs(),
                                               self.output_bit, plan.emit_f32, plan.emit_int, plan.relu)
             handle = None
             if q is not None:
@@ -312,7 +346,7 @@ class NewLinear(_IntegerSimLayer):
         if self._int8_ok(lin) and input.dim() == 2:
             wq = self._packed_weight(lin)
             xq = _native.quantize_i8_nhwc(input, self.input_bit, wq.shape[-1])
-            return _native.conv2d_i8(xq, wq, self.quantized_bias, (1, 1), (0, 0), (1, 1), self.rs_bit,
+            return _native.conv2d_i8(xq, wq, self.quantized_bias, (1, 1), (0, 0), (1, 1), self._rs(),
                                      self.output_bit, 8)
         q = self.Quan(input)
         acc = lin(q)
@@ -388,13 +422,13 @@ def _newadd_fused_conv_add(self, plan, x, y):
     one = tuple(tuple(int(v) for v in g) for g in d.geom) == ((1, 1), (0, 0), (1, 1)) and tuple(d.wq.shape[1:3]) == (1, 1)
     if (nxt is None and one and tuple(h.exact.shape[:3]) == tuple(d.xq.shape[:3]) and _block_tail_on()
             and d.xq.shape[-1] <= _BT_ALONE_MAX_C and L.Conv.out_channels == d.wq.shape[0]
-            and _native.block_tail_supported(d.xq.shape[-1], L.Conv.out_channels, 0, L.rs_bit, 0, L.output_bit, h.grid, h.exact.element_size(),
+            and _native.block_tail_supported(d.xq.shape[-1], L.Conv.out_channels, 0, L._rs(), 0, L.output_bit, h.grid, h.exact.element_size(),
                                              plan.narrow_bit if want_narrow else plan.grid - 1)):
         # conv3 + NewAdd alone on the same kernel (no next convolution to fuse) for the 64-channel stage, whose tensors come from
         # HBM: its barrier-free, wave-local epilogue streams them 1.5-1.6 x faster than the general kernel's when nothing is
         # cache resident (scripts/block_tail_probe.py), 6 % faster inside the network.  Deeper stages live in the Infinity
         # Cache at these sizes and the general kernel's 3 workgroups per CU win there.
-        wide, narrow, _ = _native.block_tail_i8(d.xq, d.wq, L.quantized_bias, L.rs_bit, L.output_bit, h.exact, h.grid, want_wide,
+        wide, narrow, _ = _native.block_tail_i8(d.xq, d.wq, L.quantized_bias, L._rs(), L.output_bit, h.exact, h.grid, want_wide,
                                                 plan.grid, want_narrow, plan.narrow_bit if want_narrow else 0, plan.relu)
         ref = wide if wide is not None else narrow
         return QHandle((ref.shape[0], L.Conv.out_channels, ref.shape[1], ref.shape[2]), wide, plan.grid, narrow, plan.narrow_bit,
@@ -405,17 +439,17 @@ def _newadd_fused_conv_add(self, plan, x, y):
         np_ = nxt.__dict__.get("_resident")
         w1 = nxt._packed_weight(nxt.Conv)
         if (np_ is not None and w1.shape[-1] == L.Conv.out_channels
-                and _native.block_tail_supported(d.xq.shape[-1], L.Conv.out_channels, nxt.Conv.out_channels, L.rs_bit, nxt.rs_bit,
+                and _native.block_tail_supported(d.xq.shape[-1], L.Conv.out_channels, nxt.Conv.out_channels, L._rs(), nxt._rs(),
                                                  L.output_bit, h.grid, h.exact.element_size(), plan.narrow_bit)):
-            wide, narrow, q1 = _native.block_tail_i8(d.xq, d.wq, L.quantized_bias, L.rs_bit, L.output_bit, h.exact, h.grid, True,
+            wide, narrow, q1 = _native.block_tail_i8(d.xq, d.wq, L.quantized_bias, L._rs(), L.output_bit, h.exact, h.grid, True,
                                                      plan.grid, plan.narrow_to_hbm, plan.narrow_bit, plan.relu, w1,
-                                                     nxt.quantized_bias, nxt.rs_bit, np_.relu)
+                                                     nxt.quantized_bias, nxt._rs(), np_.relu)
             out = QHandle((wide.shape[0], L.Conv.out_channels, wide.shape[1], wide.shape[2]), wide, plan.grid, narrow,
                           plan.narrow_bit, plan.relu)
             out.next_out = (nxt, QHandle((q1.shape[0], nxt.Conv.out_channels, q1.shape[1], q1.shape[2]), q1, nxt.output_bit, q1,
                                          nxt.output_bit, np_.relu))
             return out
-    wide, narrow = _native.conv2d_i8_add_resident(d.xq, d.wq, L.quantized_bias, d.geom[0], d.geom[1], d.geom[2], L.rs_bit,
+    wide, narrow = _native.conv2d_i8_add_resident(d.xq, d.wq, L.quantized_bias, d.geom[0], d.geom[1], d.geom[2], L._rs(),
                                                   L.output_bit, h.exact, h.grid, want_wide, plan.grid, want_narrow,
                                                   plan.narrow_bit if want_narrow else 0, plan.relu)
     ref = wide if wide is not None else narrow
@@ -449,20 +483,20 @@ def _newadd_fused_conv_proj_add(self, plan, x, y):
     if w1 is not None and w1.shape[-1] != L.Conv.out_channels:
         return None
     if not _native.block_tail_proj_supported(d.xq.shape[-1], L.Conv.out_channels, nxt.Conv.out_channels if nxt is not None else 0,
-                                             dp.xq.shape[-1], L.rs_bit, nxt.rs_bit if nxt is not None else 0, P.rs_bit, sp[0]):
+                                             dp.xq.shape[-1], L._rs(), nxt._rs() if nxt is not None else 0, P._rs(), sp[0]):
         return None
     if nxt is not None:
-        wide, narrow, q1 = _native.block_tail_proj_i8(d.xq, d.wq, L.quantized_bias, L.rs_bit, L.output_bit, dp.xq, dp.wq,
-                                                      P.quantized_bias, P.rs_bit, P.output_bit, sp[0], True, plan.grid,
+        wide, narrow, q1 = _native.block_tail_proj_i8(d.xq, d.wq, L.quantized_bias, L._rs(), L.output_bit, dp.xq, dp.wq,
+                                                      P.quantized_bias, P._rs(), P.output_bit, sp[0], True, plan.grid,
                                                       plan.narrow_to_hbm, plan.narrow_bit, plan.relu, w1, nxt.quantized_bias,
-                                                      nxt.rs_bit, np_.relu)
+                                                      nxt._rs(), np_.relu)
         out = QHandle((wide.shape[0], L.Conv.out_channels, wide.shape[1], wide.shape[2]), wide, plan.grid, narrow, plan.narrow_bit,
                       plan.relu)
         out.next_out = (nxt, QHandle((q1.shape[0], nxt.Conv.out_channels, q1.shape[1], q1.shape[2]), q1, nxt.output_bit, q1,
                                      nxt.output_bit, np_.relu))
         return out
-    wide, narrow, _ = _native.block_tail_proj_i8(d.xq, d.wq, L.quantized_bias, L.rs_bit, L.output_bit, dp.xq, dp.wq, P.quantized_bias,
-                                                 P.rs_bit, P.output_bit, sp[0], want_wide, plan.grid, want_narrow,
+    wide, narrow, _ = _native.block_tail_proj_i8(d.xq, d.wq, L.quantized_bias, L._rs(), L.output_bit, dp.xq, dp.wq, P.quantized_bias,
+                                                 P._rs(), P.output_bit, sp[0], want_wide, plan.grid, want_narrow,
                                                  plan.narrow_bit if want_narrow else 0, plan.relu)
     ref = wide if wide is not None else narrow
     return QHandle((ref.shape[0], L.Conv.out_channels, ref.shape[1], ref.shape[2]), wide, plan.grid, narrow, plan.narrow_bit,
@@ -526,7 +560,7 @@ class _FakeQuantLayer(nn.Module):
             b = layer.bias.data
         self.weight = layer.weight          # originals, as in the reference
         self.bias = layer.bias
-        w_q = _fake_quant_param(w, self.weight_qdp.bit, self.weight_qdp.bitwidth)
+        w_q = _per_channel(_fake_quant_param, w, self.weight_qdp.bit, self.weight_qdp.bitwidth)     # (a list: per-channel bits)
         b_q = _fake_quant_param(b, self.bias_qdp.bit, self.bias_qdp.bitwidth)
         layer.weight = nn.Parameter(w_q)
         layer.bias = nn.Parameter(b_q)

@@ -71,7 +71,7 @@ class DeferredConv(object):
         if self._handle is None:
             L = self.layer
             _, q = _native.conv2d_i8_resident(self.xq, self.wq, L.quantized_bias, self.geom[0], self.geom[1], self.geom[2],
-                                              L.rs_bit, L.output_bit, False, True, False)
+                                              L._rs(), L.output_bit, False, True, False)
             self._handle = QHandle((q.shape[0], L.Conv.out_channels, q.shape[1], q.shape[2]), q, L.output_bit, q, L.output_bit,
                                    False)
         return self._handle
@@ -512,7 +512,7 @@ def enable(model, example_input, verify=True):
                     and tuple(conv3.Conv.padding) == (0, 0) and c.input_bit == plan.narrow_bit
                     and conv3.Conv.out_channels == k.in_channels
                     and _native.block_tail_supported(conv3.Conv.in_channels, conv3.Conv.out_channels, k.out_channels,
-                                                     conv3.rs_bit, c.rs_bit, conv3.output_bit, other[1], other[0],
+                                                     conv3._rs(), c._rs(), conv3.output_bit, other[1], other[0],
                                                      plan.narrow_bit)):
                 nxt = c
                 break
@@ -541,8 +541,8 @@ def enable(model, example_input, verify=True):
                 or tuple(k3.kernel_size) != (1, 1) or tuple(k3.stride) != (1, 1) or tuple(k3.padding) != (0, 0)
                 or kp.out_channels != k3.out_channels or (kp.out_channels % 16) or (kp.in_channels % 16)
                 or not _native.block_tail_proj_supported(k3.in_channels, k3.out_channels, nxt.Conv.out_channels if nxt is not None else 0,
-                                                         kp.in_channels, conv3.rs_bit, nxt.rs_bit if nxt is not None else 0,
-                                                         proj.rs_bit, kp.stride[0])):
+                                                         kp.in_channels, conv3._rs(), nxt._rs() if nxt is not None else 0,
+                                                         proj._rs(), kp.stride[0])):
             continue
         pp.defer = True
         plan.fuse_proj = True

@@ -35,9 +35,9 @@ import torch
 import torch.nn as nn
 import yaml
 
-from common.quantity import DistributionCollector, Quantizer, walk_dirs, merge_bn, tid  # noqa: F401
+from common.quantity import DistributionCollector, Quantizer, BitReader, walk_dirs, merge_bn, tid  # noqa: F401
 from common.quantity import _native, _float_conv
-from .rewriter import BiasReWriter
+from .rewriter import BiasReWriter, rescale_rows
 from ._jsonio import dump_int_array
 
 __all__ = ["Quantity"]
@@ -1089,6 +1089,87 @@ class Quantity(_FusedForward, _FileInputs):
                 for line in table_lines:
                     fh.write(line + "\n")
         self.rewrite_weight()
+
+    def weight_quantize_per_channel(self):
+        """EXTENSION (no reference counterpart): weight bits per output channel.  For every parameter as weight_quantize sees
+        it (dilation handling included): m[c] = max |W[c, ...]| and wb0[c] = 7 - ceil(log2 m[c]) (the per-tensor expression,
+        per channel; an all-zero channel takes the tensor's bit), capped at MAX_SHIFT - in + out per channel.  Writes
+        WORK_DIR/weight_channel.table ("<name>.weight b0 ... b(K-1)", "<name>.bias <output bit>", in weight.table's order),
+        weight_channel/<name>.json at wb0 and new_weight_channel/<name>.json rescaled to the capped bits (rank 0 only).
+        Needs feat.table (activation_quantize first); the per-tensor files are not touched.
+        Returns {layer: [capped bit per output channel]}."""
+        settings = self.config["SETTINGS"]
+        out = self.config["OUTPUT"]
+        rank, _ = _dist_state()
+        feat_bits, infeat_bits = BitReader(feat_table=out["FEAT_BIT_TABLE"]).get_feat_info()
+
+        names, tensors = [], []
+        for name, param in self.model.named_parameters():
+            if not name.endswith("weight") and not name.endswith("bias"):
+                print("[WARNING]", " not supported param: {}".format(name))
+                continue
+            if name.endswith("bias"):
+                names.append(name)
+                tensors.append(None)
+                continue
+            owner = self.model
+            for part in name.split(".")[:-1]:
+                owner = getattr(owner, part)
+            t = param.detach()
+            if isinstance(owner, nn.Conv2d) and owner.dilation != (1, 1) and not settings["SUPPORT_DILATION"]:
+                t = self.dilation_to_zero_padding(t, owner.dilation)
+            names.append(name)
+            tensors.append(t.float().contiguous())
+
+        weights = [(n, t) for n, t in zip(names, tensors) if t is not None]
+        row_max = self._weight_row_max([t for _n, t in weights])
+        collector = self.collector_cls([n for n, _t in weights], interval_num=settings["INTERVAL_NUM"],
+                                       statistic=settings["STATISTIC"], worker_num=settings["WORKER_NUM"])
+        rewriter = BiasReWriter(None, None, None, None, None, None, max_shift_limit=settings["MAX_SHIFT"])
+        bits0, q0 = OrderedDict(), {}
+        for (name, t), m in zip(weights, row_max):
+            layer = name[:-len(".weight")]
+            tensor_bit = int(8 - 1 - math.ceil(math.log(float(m.max()), 2)))
+            wb0 = [int(8 - 1 - math.ceil(math.log(float(v), 2))) if v > 0 else tensor_bit for v in m]
+            q = np.empty(tuple(t.shape), dtype=np.int32)
+            for b in sorted(set(wb0)):
+                rows = [c for c, v in enumerate(wb0) if v == b]
+                q[rows] = collector.quantize_param(t, b)[rows]              # clip(rint(w * 2^b)), the per-tensor kernel
+            bits0[layer], q0[layer] = wb0, q
+        capped = rewriter.max_shift_limit_weight_per_channel(feat_bits, infeat_bits, bits0)
+
+        if rank != 0:
+            return capped
+        wdir, ndir = os.path.join(out["WORK_DIR"], "weight_channel"), os.path.join(out["WORK_DIR"], "new_weight_channel")
+        for d in (wdir, ndir):
+            os.makedirs(d, exist_ok=True)
+        lines = []
+        for name in names:
+            layer = name.rsplit(".", 1)[0]
+            if name.endswith("bias"):
+                assert layer in feat_bits, "{} not in {}".format(layer, out["FEAT_BIT_TABLE"])
+                lines.append("{} {}".format(name, feat_bits[layer]))
+                continue
+            lines.append(name + " " + " ".join(str(b) for b in capped[layer]))
+            dump_int_array(q0[layer], os.path.join(wdir, name + ".json"))
+            dump_int_array(rescale_rows(q0[layer], bits0[layer], capped[layer]), os.path.join(ndir, name + ".json"))
+        with open(os.path.join(out["WORK_DIR"], "weight_channel.table"), "w") as fh:
+            for line in lines:
+                fh.write(line + "\n")
+        return capped
+
+    def _weight_row_max(self, tensors):
+        """max |W[c, ...]| of every output channel of every tensor, fp32 ndarrays: fq_absmax_chan with [K, rest] seen as one
+        image of K channels."""
+        dev = torch.device("cuda", torch.cuda.current_device())
+        views = [t.to(dev, torch.float32).reshape(1, t.shape[0], -1) for t in tensors]
+        counts = [int(t.shape[0]) for t in tensors]
+        row0s = [int(v) for v in np.cumsum([0] + counts)[:-1]]
+        mx = torch.zeros(sum(counts), dtype=torch.float32, device=dev)
+        for i in range(0, len(views), 1024):                               # FQ_MAX_SEGS per call
+            _native.absmax_chan(views[i:i + 1024], row0s[i:i + 1024], mx)
+        mx = mx.cpu().numpy()
+        return [mx[r0:r0 + k] for r0, k in zip(row0s, counts)]
 
     def dilation_to_zero_padding(self, tensor, dilation):
         """A k x k kernel with dilation 2 as the equivalent dense (2k-1) x (2k-1) kernel."""

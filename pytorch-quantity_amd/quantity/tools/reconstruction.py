@@ -8,6 +8,7 @@ pickled class paths common.quantity.new_quantity_op.* stay loadable).  The dead
 Run_model_quantizer helper of the reference (:18-89, imports modules that do not exist) is not
 reproduced.
 """
+import os
 from collections import OrderedDict
 
 import torch
@@ -73,6 +74,19 @@ class Reconstruction(object):
             if name in info and kind in cared:
                 info[name]["layer"] = module
                 info[name]["layer_type"] = kind
+        return info
+
+    def get_quantity_information_per_channel(self, table=None):
+        """get_quantity_information() for per-channel weight bits: the same dict, except that weight_bit is a list of one
+        bit per output channel, read from `table` (default: WORK_DIR/weight_channel.table, written by
+        Quantity.weight_quantize_per_channel).  bias_bit stays the layer's output bit.  ReconModel / ReconTest take it as is."""
+        if table is None:
+            table = os.path.join(self.config["OUTPUT"]["WORK_DIR"], "weight_channel.table")
+        channel_bits, _bias_bits = BitReader(weight_table=table).get_weight_channel_info()
+        info = self.get_quantity_information()
+        for name, bits in channel_bits.items():
+            assert name in info and info[name]["weight_bit"] is not None, "{} is not a layer with weights".format(name)
+            info[name]["weight_bit"] = list(bits)
         return info
 
     def _rebuild(self, all_quantize_infor, new_model_path, make_conv, make_linear, label):

@@ -17,7 +17,7 @@ import numpy as np
 from common.quantity import BitReader, walk_dirs
 from ._jsonio import dump_int_array
 
-__all__ = ["BiasReWriter"]
+__all__ = ["BiasReWriter", "rescale_rows"]
 
 
 def _wrap_int8(values_f32):
@@ -31,6 +31,16 @@ def _rescale_file(src, dst, old_bit, new_bit):
         q = np.array(json.load(fh), dtype=np.float32)
     q = q / 2 ** old_bit * 2 ** new_bit
     dump_int_array(_wrap_int8(np.around(q)), dst)
+
+
+def rescale_rows(q, old_bits, new_bits):
+    """Per-channel form of the rescale above: row c of the integer array q (output channel c) goes from old_bits[c] to
+    new_bits[c] with the same fp32 expression and int8 wrap as _rescale_file."""
+    q = np.asarray(q, dtype=np.float32)
+    out = np.empty(q.shape, dtype=np.int8)
+    for c in range(q.shape[0]):
+        out[c] = _wrap_int8(np.around(q[c] / 2 ** int(old_bits[c]) * 2 ** int(new_bits[c])))
+    return out
 
 
 def _retable(path, suffix_len, known, new_bits):
@@ -99,6 +109,21 @@ class BiasReWriter(object):
         if not changed:
             print("Nothing needs to change.")
         return changed, capped
+
+    def max_shift_limit_weight_per_channel(self, feat_bits, infeat_bits, weight_bits):
+        """max_shift_limit_weight with one bit per output channel: {layer: [bit per channel]} ->
+        {layer: [min(bit, MAX_SHIFT - in + out) per channel]} (unchanged without a MAX_SHIFT)."""
+        capped = {}
+        for layer, wbits in weight_bits.items():
+            assert layer in feat_bits, "{} not in {}".format(layer, feat_bits)
+            assert layer in infeat_bits, "{} not in {}".format(layer, infeat_bits)
+            assert len(set(infeat_bits[layer])) == 1, infeat_bits[layer]
+            if self._max_shift_limit is None:
+                capped[layer] = [int(b) for b in wbits]
+                continue
+            cap = self._max_shift_limit - int(infeat_bits[layer][0]) + int(feat_bits[layer])
+            capped[layer] = [min(int(b), cap) for b in wbits]
+        return capped
 
     def rewrite_weight_dir(self, old_weight_bits, new_weight_bits):
         paths = walk_dirs(self._weight_dir, file_type=".json")
