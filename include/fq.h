@@ -60,8 +60,8 @@ int fq_last_hip_error(void);      /* thread-local hipError_t of the last FQ_ERR_
  * this thread launched -- low byte: 1 conv3x3_i8_c64 (stationary 64-channel 3x3), 2 conv1x1_i8_stream, 3 conv3x3_i8_halo8
  * (256-pixel tiles, eight waves), 4 conv3x3_i8_halo, 5 / 6 conv2d_i8_dma with a ring of 2 / 3, 7 / 8 / 9 conv2d_i8_kernel
  * (C % 128 / C = 64 / general path), 10 stem_conv_i8, 11 block_tail_i8 (fq_block_tail_i8), 12 the same with the projection
- * shortcut computed in the kernel (fq_block_tail_proj_i8), 13 linear_i8_wave (a linear layer, one wave per 32 x 32 tile), 0 nothing
- * launched; bits 8-15: output-channel
+ * shortcut computed in the kernel (fq_block_tail_proj_i8), 13 linear_i8_wave (a linear layer, one wave per 32 x 32 tile), 14 dwconv_i8
+ * (fq_dwconv2d_i8_resident, a depthwise layer), 0 nothing launched; bits 8-15: output-channel
  * tile (64 / 128).  Lets a test assert that the dispatch it checked against a golden is the dispatch a benchmark timed. */
 int fq_conv2d_i8_last_variant(void);
 
@@ -519,6 +519,29 @@ int fq_block_tail_proj_i8_pcs(const int8_t* x_nhwc, const int8_t* w3_krsc, const
 int fq_conv2d_i8_stem_pcs(const float* x_nchw, const int8_t* w_stem, const float* qbias, const int32_t* rs_k, int rs_min, int rs_max,
                           int8_t* q_nhwc, int Kpad, int relu, int N, int C, int H, int W, int K, int R, int S, int stride_h,
                           int stride_w, int pad_h, int pad_w, int ib, int ob, fq_stream_t stream);
+
+/* Depthwise convolution (nn.Conv2d with groups == in_channels == out_channels) on a resident activation: what
+ * NewConv2d.forward computes for such a layer after Quantity, one channel at a time,
+ *   acc[n][c][p][q] = sum_{r,s} w[c][r][s] * x[n][p*stride_h - pad_h + r][q*stride_w - pad_w + s][c]          (int32, exact)
+ *   q_nhwc          = clamp(RightShift(acc, rs) + qbias[c])     (= fq_conv2d_i8_resident's q_nhwc; ReLU fused when relu != 0)
+ * x_nhwc int8 [N][H][W][Cpad], q_nhwc int8 [N][P][Q][Cpad], the SAME Cpad, Cpad % 16 == 0 (FQ_ERR_UNSUPPORTED otherwise), both
+ *   16-byte aligned; channels [C, Cpad) of q_nhwc are written as zeros whatever those channels of x hold.
+ * w_rsc int8 [R][S][Cpad]: tap major, channels contiguous, channels [C, Cpad) zero.  qbias fp32 [C], integer valued, of any
+ *   magnitude (saturation as in fq_conv2d_i8).  ob: the output grid, as in fq_conv2d_i8_resident (the integers do not depend on it).
+ * Only int8 NHWC is written; a caller that needs fp32 NCHW follows with fq_dequant_nhwc_to_nchw(q_nhwc, 1, ob, ...).
+ * fq_dwconv2d_i8_supported: 1 for C >= 1, R == S in {3, 5}, stride_h == stride_w in {1, 2}, dilation 1 and every shift in
+ *   [1, 16] (the integer tail of fq_int_tail.h only; |acc| <= 25 * 128 * 128 < 2^19 by construction).  The entry points also
+ *   need pad_h < R, pad_w < S, N*H*W*Cpad < 2^31 and N*P*Q*Cpad < 2^30, and return FQ_ERR_UNSUPPORTED otherwise: callers keep
+ *   the fp32 grouped convolution + fq_recon_epilogue there, which compute the same integers.  _pcs: one shift per channel,
+ *   rs_k device int32[C], 16-byte aligned, rs_min <= rs_k[c] <= rs_max; a constant vector gives the bytes of the per-tensor
+ *   entry point.  fq_conv2d_i8_last_variant: 14. */
+int fq_dwconv2d_i8_supported(int C, int R, int S, int stride_h, int stride_w, int dil_h, int dil_w, int rs_min, int rs_max);
+int fq_dwconv2d_i8_resident(const int8_t* x_nhwc, const int8_t* w_rsc, const float* qbias, int8_t* q_nhwc, int Cpad, int relu,
+                            int N, int H, int W, int C, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                            int dil_w, int rs, int ob, fq_stream_t stream);
+int fq_dwconv2d_i8_resident_pcs(const int8_t* x_nhwc, const int8_t* w_rsc, const float* qbias, const int32_t* rs_k, int rs_min,
+                                int rs_max, int8_t* q_nhwc, int Cpad, int relu, int N, int H, int W, int C, int R, int S,
+                                int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int ob, fq_stream_t stream);
 
 /* The tail of a bottleneck block and the head of the next one in ONE kernel (round 4):
  *   NewConv2d.forward of conv3 (1x1, C -> K3; new_quantity_op.py:124-133)  ->  NewAdd.forward with the shortcut (:166-174)

@@ -204,6 +204,12 @@ def lib():
     L.fq_conv2d_i8_stem_pcs.restype = ci
     L.fq_conv2d_i8_stem_pcs.argtypes = [vp, vp, vp, vp, ci, ci, vp] + [ci] * 15 + [vp]
     L.fq_block_tail_proj_i8.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, ci, vp, ci, ci, vp, vp, ci, ci, vp] + [ci] * 7 + [vp]
+    L.fq_dwconv2d_i8_supported.restype = ci
+    L.fq_dwconv2d_i8_supported.argtypes = [ci] * 9
+    L.fq_dwconv2d_i8_resident.restype = ci
+    L.fq_dwconv2d_i8_resident.argtypes = [vp, vp, vp, vp] + [ci] * 16 + [vp]
+    L.fq_dwconv2d_i8_resident_pcs.restype = ci
+    L.fq_dwconv2d_i8_resident_pcs.argtypes = [vp, vp, vp, vp, ci, ci, vp] + [ci] * 15 + [vp]
     L.fq_add_resident.restype = ci
     L.fq_add_resident.argtypes = [vp, ci, ci, vp, ci, ci, vp, ci, vp, ci, ci, sz, vp]
     L.fq_dequant_nhwc_to_nchw.restype = ci
@@ -1021,7 +1027,7 @@ def pack_weight_krsc(w, cpad=None):
 # Which integer-convolution kernels ran (fq_conv2d_i8_last_variant): set conv_variant_log = {} and every call below counts its
 # kernel there by name -- tests and bench.py assert with it that the dispatch they checked is the dispatch they time.
 CONV_VARIANTS = {0: "none", 1: "c64_halo", 2: "stream", 3: "halo8", 4: "halo", 5: "dma2", 6: "dma3", 7: "tile_c128", 8: "tile_c64",
-                 9: "tile_general", 10: "stem", 11: "block_tail", 12: "block_tail_proj", 13: "linear_wave"}
+                 9: "tile_general", 10: "stem", 11: "block_tail", 12: "block_tail_proj", 13: "linear_wave", 14: "depthwise"}
 conv_variant_log = None
 
 
@@ -1133,6 +1139,53 @@ def conv2d_i8_stem(x, w_stem, qbias, K, S, stride, padding, ib, rs, ob, relu):
     _check(lib().fq_conv2d_i8_stem(x.data_ptr(), w_stem.data_ptr(), qbias.contiguous().data_ptr(), q.data_ptr(), kpad,
                                    1 if relu else 0, N, C, H, W, K, R, S, stride[0], stride[1], padding[0], padding[1],
                                    int(ib), int(rs), int(ob), _stream(x)), "fq_conv2d_i8_stem")
+    _note_variant()
+    return q
+
+
+def dwconv_supported(C, R, S, stride, dilation, rs):
+    """True when fq_dwconv2d_i8_resident takes a depthwise layer of this geometry and shift (include/fq.h): 3x3 / 5x5, stride 1 / 2
+    on both axes, dilation 1, every shift in [1, 16].  Pure host arithmetic (no GPU needed); rs: an int or a ShiftVec."""
+    lo, hi = _bounds(rs)
+    return bool(lib().fq_dwconv2d_i8_supported(int(C), int(R), int(S), int(stride[0]), int(stride[1]), int(dilation[0]),
+                                               int(dilation[1]), lo, hi))
+
+
+def pack_weight_dw(w, cpad=None):
+    """Integer-valued fp32 depthwise weights [C, 1, R, S] -> int8 [R, S, Cpad] for fq_dwconv2d_i8_resident (tap major, channels
+    contiguous, padding channels zero)."""
+    C, one, R, S = w.shape
+    assert one == 1, "depthwise weights are [C, 1, R, S]"
+    cpad = pad16(C) if cpad is None else int(cpad)
+    out = torch.zeros(R, S, cpad, dtype=torch.int8, device=w.device)
+    out[..., :C] = w[:, 0].permute(1, 2, 0).to(torch.int8)
+    return out.contiguous()
+
+
+def dwconv2d_i8_resident(xq, wq, qbias, stride, padding, rs, ob, relu):
+    """fq_dwconv2d_i8_resident: xq int8 [N,H,W,Cpad], wq int8 [R,S,Cpad] (pack_weight_dw), qbias fp32 [C]; returns q int8
+    [N,P,Q,Cpad], the integers before DeQuantity(ob) with the ReLU folded in.  rs: an int, or a ShiftVec (the _pcs entry point)."""
+    _need_cuda(xq, torch.int8, "fq_dwconv2d_i8_resident")
+    _need_cuda(wq, torch.int8, "fq_dwconv2d_i8_resident")
+    _need_cuda(qbias, torch.float32, "fq_dwconv2d_i8_resident")
+    N, H, W, cpad = xq.shape
+    R, S, Cw = wq.shape
+    C = qbias.numel()
+    assert cpad == Cw and xq.is_contiguous() and wq.is_contiguous() and C <= cpad
+    P = (H + 2 * padding[0] - R) // stride[0] + 1
+    Q = (W + 2 * padding[1] - S) // stride[1] + 1
+    if P <= 0 or Q <= 0:
+        raise FqError("fq_dwconv2d_i8_resident: the kernel does not fit the padded image")
+    q = torch.empty(N, P, Q, cpad, dtype=torch.int8, device=xq.device)
+    if isinstance(rs, ShiftVec):
+        rk = _shift_vec(rs, C, xq.device, "fq_dwconv2d_i8_resident_pcs")
+        _check(lib().fq_dwconv2d_i8_resident_pcs(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi,
+                                                 q.data_ptr(), cpad, 1 if relu else 0, N, H, W, C, R, S, stride[0], stride[1],
+                                                 padding[0], padding[1], 1, 1, int(ob), _stream(xq)), "fq_dwconv2d_i8_resident_pcs")
+    else:
+        _check(lib().fq_dwconv2d_i8_resident(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), q.data_ptr(), cpad,
+                                             1 if relu else 0, N, H, W, C, R, S, stride[0], stride[1], padding[0], padding[1], 1, 1,
+                                             int(rs), int(ob), _stream(xq)), "fq_dwconv2d_i8_resident")
     _note_variant()
     return q
 

@@ -177,6 +177,10 @@ class _IntegerSimLayer(nn.Module):
 
     use_int8_mfma = True
     use_stem_kernel = True        # False: the stem goes through fq_quantize_i8_unfold_w + the general kernel (same integers)
+    # True: a depthwise nn.Conv2d (groups == in_channels == out_channels) runs on fq_dwconv2d_i8_resident instead of the
+    # reference-shaped form below (Quantity -> grouped fp32 convolution -> tail).  Same fp32 tensor, bit for bit.  Off by default;
+    # settable per instance; resident.enable(..., depthwise=True) plans such layers as integer producers / consumers.
+    use_depthwise_i8 = False
 
     def _int8_ok(self, layer):
         if not self.use_int8_mfma or QUANTIZE_BIT != 8:
@@ -184,6 +188,30 @@ class _IntegerSimLayer(nn.Module):
         if isinstance(layer, nn.Conv2d):
             return layer.groups == 1 and layer.padding_mode == "zeros" and not isinstance(layer.padding, str)
         return isinstance(layer, nn.Linear)
+
+    def _depthwise_ok(self, layer, switch=None):
+        """True when `layer` is a depthwise convolution that fq_dwconv2d_i8_resident takes: the switch (use_depthwise_i8, or the
+        caller's `switch`), QUANTIZE_BIT == 8, groups == in_channels == out_channels, zero padding given as numbers, and the
+        kernel's own limits on geometry and shift (_native.dwconv_supported, padding below the kernel size)."""
+        if not (self.use_depthwise_i8 if switch is None else switch) or QUANTIZE_BIT != 8:
+            return False
+        if not isinstance(layer, nn.Conv2d) or layer.padding_mode != "zeros" or isinstance(layer.padding, str):
+            return False
+        if not (layer.groups == layer.in_channels == layer.out_channels) or layer.groups < 1:
+            return False
+        k = layer.kernel_size
+        if layer.padding[0] >= k[0] or layer.padding[1] >= k[1]:
+            return False
+        return _native.dwconv_supported(layer.out_channels, k[0], k[1], layer.stride, layer.dilation, self._rs())
+
+    def _dw_weight(self, layer):
+        """Weights packed for fq_dwconv2d_i8_resident, cached like _packed_weight."""
+        w = layer.weight
+        cached = getattr(self, "_w_dw", None)
+        if cached is None or cached[0] != (w.data_ptr(), w._version, str(w.device)):
+            object.__setattr__(self, "_w_dw", ((w.data_ptr(), w._version, str(w.device)), _native.pack_weight_dw(w.detach())))
+            cached = self._w_dw
+        return cached[1]
 
     @staticmethod
     def _stem_fold(layer):
@@ -216,6 +244,7 @@ class _IntegerSimLayer(nn.Module):
         state = self.__dict__.copy()
         state.pop("_w_i8", None)                  # derived data: rebuilt on first forward after loading
         state.pop("_w_stem", None)
+        state.pop("_w_dw", None)
         return state
 
     def _setup(self, layer, quantize_infor, out_count, wide_weights):
@@ -275,6 +304,9 @@ class NewConv2d(_IntegerSimLayer):
         ready = getattr(input, "next_out", None) if type(input) is QHandle else None
         if ready is not None and ready[0] is self:        # the NewAdd that produced `input` ran this convolution in its kernel
             return ready[1]
+        dw_plan = self.__dict__.get("_resident")
+        if (dw_plan is not None and dw_plan.depthwise) or self._depthwise_ok(conv):
+            return self._forward_depthwise(conv, input, dw_plan)
         if self._int8_ok(conv):
             wq = self._packed_weight(conv)
             plan = self.__dict__.get("_resident")         # set by common.quantity.resident.enable()
@@ -320,6 +352,25 @@ class NewConv2d(_IntegerSimLayer):
         q = self.Quan(as_f32(input))
         acc = conv(q)               # integer-valued fp32 in, exact below 2^24 per partial sum
         return self._tail(acc)
+
+    def _forward_depthwise(self, conv, input, plan):
+        """A depthwise layer on fq_dwconv2d_i8_resident: int8 NHWC in (the producer's bytes, or Quantity + repack of an fp32
+        tensor), int8 NHWC out; fp32 NCHW, where somebody needs it, through the de-quantising transpose."""
+        wq = self._dw_weight(conv)
+        xq = self._resident_input(input, wq.shape[-1])
+        if xq is None:
+            xq = _xq_cache.get(as_f32(input), self.input_bit, wq.shape[-1])
+        relu = plan is not None and plan.relu
+        q = _native.dwconv2d_i8_resident(xq, wq, self.quantized_bias, conv.stride, conv.padding, self._rs(), self.output_bit, relu)
+        handle = QHandle((q.shape[0], conv.out_channels, q.shape[1], q.shape[2]), q, self.output_bit, q, self.output_bit, relu)
+        if plan is not None and not plan.emit_f32:
+            return handle
+        y = handle.to_f32()
+        if plan is not None and plan.emit_int:
+            carry(y, handle)
+        if relu:
+            y._fq_relu_done = True
+        return y
 
     def _resident_input(self, input, cpad):
         """int8 NHWC operand already in HBM (left by the producer), or None."""

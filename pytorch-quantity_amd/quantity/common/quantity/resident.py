@@ -121,7 +121,7 @@ def as_f32(x):
 class Plan(object):
     """What one producer emits.  Plain data (pickles with the module)."""
     __slots__ = ("relu", "emit_f32", "emit_int", "narrow_bit", "want_wide", "grid", "resident_add", "defer", "fuse_arg",
-                 "fuse_next", "narrow_to_hbm", "fuse_proj")
+                 "fuse_next", "narrow_to_hbm", "fuse_proj", "depthwise")
 
     def __init__(self):
         self.relu = False            # the nn.ReLU that consumes this output is fused
@@ -136,6 +136,7 @@ class Plan(object):
         self.fuse_next = None        # NewAdd: the 1x1 NewConv2d consuming this sum that runs inside the add's kernel too
         self.narrow_to_hbm = True    # NewAdd with fuse_next: somebody besides that convolution reads the int8 re-quantisation
         self.fuse_proj = False       # NewAdd with fuse_arg: the OTHER operand is a deferred 1x1 projection that the kernel computes too
+        self.depthwise = False       # NewConv2d: a depthwise layer taken by enable(depthwise=True); runs on fq_dwconv2d_i8_resident
 
     def __getstate__(self):
         return {k: getattr(self, k) for k in self.__slots__}
@@ -336,13 +337,16 @@ def is_enabled(model):
     return bool(model.__dict__.get("_fq_resident_enabled"))
 
 
-def enable(model, example_input, verify=True):
+def enable(model, example_input, verify=True, depthwise=False):
     """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
     on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
     nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
     `example_input` is any valid input batch; the plan does not depend on its size.  With `verify`
     (default) the planned model is run once on `example_input` and must reproduce the traced forward
-    bit for bit, otherwise the plan is removed and FqError raised."""
+    bit for bit, otherwise the plan is removed and FqError raised.
+    `depthwise=True` also plans depthwise NewConv2d layers (groups == in_channels == out_channels, 3x3 / 5x5, stride 1 / 2,
+    shift in [1, 16]: NewConv2d._depthwise_ok) as integer producers and consumers, served by fq_dwconv2d_i8_resident; without
+    it they stay fp32 producers, as every other grouped convolution does.  The summary then counts them as `resident_depthwise`."""
     from .new_quantity_op import NewConv2d, NewLinear, NewAdd, QUANTIZE_BIT
     _clear(model)
     if QUANTIZE_BIT != 8:
@@ -376,11 +380,16 @@ def enable(model, example_input, verify=True):
                 return after, v.consumers[0][0]
         return v, None
 
+    def is_dw(m):
+        """A depthwise layer that this plan runs on fq_dwconv2d_i8_resident (called once, like every producer of the plan)."""
+        return (bool(depthwise) and isinstance(m, NewConv2d) and tracer.calls.get(m, 0) == 1
+                and m._depthwise_ok(m.Conv, True))
+
     def conv_can_emit(m):
-        return isinstance(m, NewConv2d) and tracer.calls.get(m, 0) == 1 and m._int8_ok(m.Conv)
+        return isinstance(m, NewConv2d) and tracer.calls.get(m, 0) == 1 and (m._int8_ok(m.Conv) or is_dw(m))
 
     def conv_can_read(m):
-        return isinstance(m, NewConv2d) and m._int8_ok(m.Conv) and not m._stem_fold(m.Conv)
+        return isinstance(m, NewConv2d) and ((m._int8_ok(m.Conv) and not m._stem_fold(m.Conv)) or is_dw(m))
 
     # pass 1 (execution order): integer format of every produced value
     fmt = {}                         # id(effective _Value) -> (bytes, grid)
@@ -425,6 +434,8 @@ def enable(model, example_input, verify=True):
     # pass 2: what every producer has to emit
     summary = {"resident_convs": 0, "resident_adds": 0, "resident_pools": 0, "fused_relus": 0, "fp32_outputs": 0,
                "int_only_outputs": 0}
+    if depthwise:
+        summary["resident_depthwise"] = 0
     for v in tracer.produced:
         m = v.producer
         e, relu_mod = eff_of[id(v)]
@@ -465,6 +476,9 @@ def enable(model, example_input, verify=True):
                 plan.want_wide = True                       # fp32 leaves through the exact int16 sum
         plan.emit_int = int_consumers > 0
         plan.emit_f32 = need_f32 or not plan.emit_int
+        if v.kind == "contraction" and is_dw(m):
+            plan.depthwise = True
+            summary["resident_depthwise"] += 1
         m.__dict__["_resident"] = plan
         if plan.relu:
             relu_mod.__dict__["forward"] = _ReluPassThrough(relu_mod)
@@ -481,8 +495,8 @@ def enable(model, example_input, verify=True):
             v = ops[pos]
             conv = v.producer
             plan = conv.__dict__.get("_resident") if isinstance(conv, NewConv2d) else None
-            if (v.kind == "contraction" and plan is not None and not plan.relu and not plan.emit_f32 and not v.foreign
-                    and v.consumers == [(add_mod, pos)] and ops[1 - pos] is not v
+            if (v.kind == "contraction" and plan is not None and not plan.depthwise and not plan.relu and not plan.emit_f32
+                    and not v.foreign and v.consumers == [(add_mod, pos)] and ops[1 - pos] is not v
                     and not add_mod.__dict__["_resident"].emit_f32):
                 plan.defer = True
                 add_mod.__dict__["_resident"].fuse_arg = pos
