@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """GPU probe: randomised parity sweep of fq_conv2d_i8 / _resident / _add_resident against the CPU oracle
-(oracle/fq_oracle.c: exact integer conv + the reference's fp32 tail).  usage: conv_fuzz.py [cases] [seed]"""
+(oracle/fq_oracle.c: exact integer conv + the reference's fp32 tail).  usage: conv_fuzz.py [cases] [seed] [conv|halo|stream]
+(no third argument: every sweep; `conv`: only the general sweep -- with FQ_CONV_TK=128, and FQ_CONV_STAGES=2 beside it, the 128-row
+tile kernels and the ring of two on shapes whose K ends inside a tile, which only chip-filling launches select by themselves)"""
 import os, sys
 import numpy as np
 import torch
@@ -12,9 +14,11 @@ orc.build()
 
 
 def run(cases, seed, verbose=True):
-    """Returns the list of mismatching cases (empty = parity)."""
+    """Returns the list of mismatching cases (empty = parity).  run.compared: how many of the `cases` draws were compared (a draw
+    whose output plane is empty is dropped)."""
     rng = np.random.default_rng(seed)
     failures = []
+    run.compared = 0
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
     for it in range(cases):
         kind = rng.integers(0, 5)
@@ -32,6 +36,7 @@ def run(cases, seed, verbose=True):
         st = int(rng.choice([1, 1, 2])); pd = int(rng.integers(0, (min(R, S) + 1) // 2 + 1)); dl = int(rng.choice([1, 1, 1, 2]))
         if (H + 2 * pd - dl * (R - 1) - 1) // st + 1 <= 0 or (W + 2 * pd - dl * (S - 1) - 1) // st + 1 <= 0:
             continue
+        run.compared += 1
         x = rng.integers(-128, 128, size=(N, C, H, W)).astype(np.int32)
         w = rng.integers(-128, 128, size=(K, C, R, S)).astype(np.int32)
         qb = rng.integers(-128, 128, size=K).astype(np.float32)
@@ -227,6 +232,15 @@ if __name__ == "__main__":
         print("stream_fuzz: %d cases, %d mismatches (FQ_CONV_STREAM=%s FQ_STREAM_GROUPS=%s)"
               % (n, len(stream_fails), os.environ.get("FQ_CONV_STREAM", ""), os.environ.get("FQ_STREAM_GROUPS", "")))
         sys.exit(1 if stream_fails else 0)
+    if len(sys.argv) > 3 and sys.argv[3] == "conv":            # only the general sweep (run with FQ_CONV_TK / FQ_CONV_STAGES / FQ_CONV_DMA)
+        nat.conv_variant_log = ran = {}
+        fails = run(n, seed)
+        nat.conv_variant_log = None
+        print("conv_fuzz: %d cases, %d mismatches (FQ_CONV_TK=%s FQ_CONV_STAGES=%s)"
+              % (n, len(fails), os.environ.get("FQ_CONV_TK", ""), os.environ.get("FQ_CONV_STAGES", "")))
+        print("compared: %d" % run.compared)
+        print("kernels: " + " ".join("%s=%d" % kv for kv in sorted(ran.items())))
+        sys.exit(1 if fails else 0)
     fails = run(n, seed)
     print("conv_fuzz: %d cases, %d mismatches" % (n, len(fails)))
     n_stem = max(20, n // 4)

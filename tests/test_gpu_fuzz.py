@@ -52,6 +52,33 @@ def test_eight_wave_halo_kernel_matches_the_oracle(stages):
     assert r.returncode == 0 and "60 cases, 0 mismatches" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
 
 
+@pytest.mark.parametrize("stages", ["", "2"])
+def test_128_row_tile_kernels_match_the_oracle_on_small_shapes(stages):
+    """By themselves only launches that fill the chip take the 128-row output tiles and the ring of two (tests/
+    test_gpu_conv_i8_large.py: K = 160, 200 and multiples of 128).  FQ_CONV_TK=128 (scripts/README.md; read once per process, hence
+    the child process) puts every shape of the general sweep on them: K from 1 to 320 ending anywhere inside a 128-row tile, ragged
+    channels, strides, dilation, all output forms and the fused add, against the CPU oracle -- with the default ring depth (three on
+    these small grids) and with FQ_CONV_STAGES=2."""
+    import subprocess
+    import sys
+    env = dict(os.environ, FQ_CONV_TK="128")
+    if stages:
+        env["FQ_CONV_STAGES"] = stages
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "conv_fuzz.py"), "120", "505", "conv"], env=env,
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "120 cases, 0 mismatches" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+    # "120 cases" counts draws, and a draw with an empty output plane is dropped.  Only dilation 2 (one draw in four) on a plane
+    # smaller than the dilated filter can be one, so at least three quarters were compared, each by two launches or more
+    compared = int(r.stdout.split("compared: ")[1].split()[0])
+    assert 90 <= compared <= 120, r.stdout[-2000:]
+    # ... and the sweep did run on the forms it is here for
+    ran = dict(kv.split("=") for kv in r.stdout.split("kernels: ")[1].split("\n")[0].split())
+    assert sum(int(v) for v in ran.values()) >= 2 * compared, (compared, ran)
+    for name in ("tile_general/128", "tile_c64/128", "tile_c128/128", "dma2/128" if stages else "dma3/128"):
+        assert int(ran.get(name, 0)) > 0, ran
+    assert not any(k in ran for k in ("tile_general/64", "tile_c64/64", "tile_c128/64", "dma2/64", "dma3/64")), ran
+
+
 def test_random_histograms_kl_sweep_matches_the_oracle_bit_for_bit():
     """scripts/kl_fuzz.py: 96 random histograms of eight families; thresholds and KL curves (same include/fq_log.h on
     both sides) must agree bit for bit."""

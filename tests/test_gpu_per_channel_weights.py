@@ -4,8 +4,9 @@ the per-channel epilogue, NewConv2d / NewLinear / ReconModel / ReconTest with li
 
 Kernel-level expected values: the oracle's integer convolution with recon_epilogue applied one channel slice at a time.  For
 the shapes that only a large launch selects (halo8, dma2, 128-row tiles) the oracle would take minutes on the CPU; there the
-expected value is the PER-TENSOR entry point (itself checked against the oracle by test_gpu_conv_i8.py) run once per distinct
-shift, channel by channel.  pytest -m gpu"""
+expected value is the PER-TENSOR entry point run once per distinct shift, channel by channel.  That entry point, and the _pcs
+one with it, is compared at these very shapes with an exact float64 convolution by test_gpu_conv_i8_large.py (whose case-list
+test checks that every such row of SHAPES is in its table); test_gpu_conv_i8.py covers the small launches.  pytest -m gpu"""
 import copy
 import os
 import zlib

@@ -395,6 +395,65 @@ def test_r50_reconmodel_at_the_batch_the_bench_times_equals_the_reference(g4r50)
         np.testing.assert_array_equal(dual(big).cpu().numpy(), want)
 
 
+@pytest.mark.timeout(1200)
+def test_r50_reconmodel_on_256_distinct_images_equals_the_same_net_two_images_at_a_time(g4r50):
+    """The test above feeds the golden pair tiled 128 times: a kernel of the chip-filling dispatch that fetched image n +- 2k, or
+    a tile of another image of the same parity, would read identical bytes and pass.  Here the batch is the golden pair followed
+    by 254 seeded images, no two equal.  Rows 0-1 of the 256-image forward must be the reference's CPU logits, and ALL rows must
+    equal the same net run two images at a time -- forwards on the small dispatches that the golden pair and the oracle-checked
+    cases of test_gpu_conv_i8.py anchor -- with fp32 module boundaries, resident, and as one captured graph."""
+    from common.quantity import _native, resident
+    tables, g4 = g4r50
+    x = cases.fixed_input(tuple(tables["input"]["shape"]), seed=tables["input"]["seed"])
+    assert x.shape[0] == 2
+    big = torch.cat([x, cases.fixed_input((254,) + tuple(x.shape[1:]), seed=tables["input"]["seed"] + 256)]).contiguous()
+    assert len({hashlib.sha256(img.numpy().tobytes()).digest() for img in big}) == 256           # pairwise different
+    big = big.cuda()
+
+    def pairs(fn):
+        return np.concatenate([fn(big[i:i + 2]).cpu().numpy() for i in range(0, 256, 2)])
+
+    def same_rows(got, want, what):
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        assert bad.size == 0, "%s: %d of %d images differ, first image %d, images with odd / even index among them: %d / %d" % (
+            what, bad.size, got.shape[0], bad[0], int((bad % 2 == 1).sum()), int((bad % 2 == 0).sum()))
+
+    with product_workdir(input_shape="1,3,224,224", device="gpu") as tmp:
+        rec, wd = _r50_rec(tables, tmp)
+        net = rec.ReconModel(rec.get_quantity_information(), os.path.join(wd, "recon.pth")).cuda()
+        with torch.no_grad():
+            full = net(big).cpu().numpy()                                                       # the reference's module boundaries
+            by_two = pairs(net)
+        np.testing.assert_array_equal(by_two[:2], g4["logits_recon"])
+        assert len({r.tobytes() for r in by_two}) == 256                                        # (a swapped image would show)
+        same_rows(full, by_two, "fp32 module boundaries")
+        resident.enable(net, big)
+        _native.conv_variant_log = log = {}
+        try:
+            with torch.no_grad():
+                full = net(big).cpu().numpy()
+        finally:
+            _native.conv_variant_log = None
+        # the dispatch of the forward bench.py times, as in the test above
+        assert sum(log.values()) == 48 and log.get("block_tail/128") == 5 and log.get("block_tail_proj/128") == 1, log
+        assert log.get("c64_halo/64") == 3 and sum(v for k, v in log.items() if k.startswith("halo8")) >= 7, log
+        assert sum(v for k, v in log.items() if k.startswith("dma")) >= 3, log
+        _native.conv_variant_log = small = {}
+        try:
+            with torch.no_grad():
+                res_by_two = pairs(net)
+        finally:
+            _native.conv_variant_log = None
+        assert not any(k.startswith("halo8") for k in small), small
+        np.testing.assert_array_equal(res_by_two[:2], g4["logits_recon"])
+        same_rows(res_by_two, by_two, "resident, two images at a time, against fp32 module boundaries")
+        np.testing.assert_array_equal(full[:2], g4["logits_recon"])
+        same_rows(full, res_by_two, "resident at 256 images")
+        graphed = resident.capture(net, big)
+        same_rows(graphed(big).cpu().numpy(), res_by_two, "captured graph at 256 images")
+        same_rows(graphed(torch.flip(big, dims=[0])).cpu().numpy(), res_by_two[::-1], "captured graph, images in reverse order")
+
+
 def test_r50_recontest_logits_match_the_reference(g4r50):
     """Fake-quant ResNet-50: float convolutions followed by QuanDequan.  The convolutions are this library's fp32 MFMA
     kernels (fq_conv1x1_f32 / fq_conv_kxk_f32 / fq_conv_stem_f32: a fixed k-ordered fma chain), the reference's are oneDNN's

@@ -26,13 +26,15 @@ def _dev(a):
 
 
 RES_CASES = [
-    # N, C, H, W, K, R, S, stride, pad
-    (2, 16, 8, 8, 64, 3, 3, 1, 1),             # TK = 64, general path
-    (3, 32, 9, 7, 40, 3, 3, 2, 1),             # K = 40 -> Kpad 48, ragged pixel tile
-    (2, 128, 7, 7, 200, 3, 3, 1, 1),           # two k tiles, second partial, Kpad 208
-    (1, 256, 6, 6, 512, 1, 1, 2, 0),           # C % 128 fast path, TK = 64 (few workgroups)
-    (40, 128, 14, 14, 256, 1, 1, 1, 0),        # C % 128 fast path, TK = 128
-    (2, 3, 20, 20, 10, 3, 3, 1, 1),            # K = 10 -> Kpad 16
+    # N, C, H, W, K, R, S, stride, pad, the kernel conv2d_i8_dispatch picks (asserted from the variant log below).  Every row is a
+    # launch of a few workgroups and therefore runs 64-row tiles: 128-row tiles need ceil(M / 128) * ceil(K / 128) >= 256, which
+    # tests/test_gpu_conv_i8_large.py reaches
+    (2, 16, 8, 8, 64, 3, 3, 1, 1, "tile_general/64"),
+    (3, 32, 9, 7, 40, 3, 3, 2, 1, "tile_general/64"),       # K = 40 -> Kpad 48, ragged pixel tile
+    (2, 128, 7, 7, 200, 3, 3, 1, 1, "tile_general/64"),     # four k tiles, the last partial, Kpad 208 (K % 64 != 0: no fast path)
+    (1, 256, 6, 6, 512, 1, 1, 2, 0, "tile_c128/64"),        # C % 128 fast path
+    (40, 128, 14, 14, 256, 1, 1, 1, 0, "tile_c128/64"),     # C % 128 fast path, 62 pixel tiles x 4 k tiles (62 x 2 < 256: not TK = 128)
+    (2, 3, 20, 20, 10, 3, 3, 1, 1, "tile_general/64"),      # K = 10 -> Kpad 16
 ]
 
 
@@ -41,8 +43,8 @@ RES_CASES = [
 def test_conv_resident_outputs(nat, oracle, case, relu):
     """q is what the NEXT layer's Quantity(ib = ob) recovers from the reference's fp32 output (after the
     ReLU when fused); y is the fp32 output itself; both-outputs mode gives the same two arrays."""
-    N, C, H, W, K, R, S, st, pd = case
-    rng = np.random.default_rng(sum(case) + int(relu))
+    N, C, H, W, K, R, S, st, pd, variant = case
+    rng = np.random.default_rng(sum(case[:9]) + int(relu))
     xq = rng.integers(-128, 128, size=(N, C, H, W)).astype(np.int32)
     wq = rng.integers(-128, 128, size=(K, C, R, S)).astype(np.int32)
     qb = rng.integers(-128, 128, size=K).astype(np.float32)
@@ -59,7 +61,12 @@ def test_conv_resident_outputs(nat, oracle, case, relu):
             ref = np.maximum(ref, np.float32(0))
         ref_q = oracle.quantity(ref, ob).astype(np.int8).transpose(0, 2, 3, 1)
         for want_f32, want_i8 in ((False, True), (True, True), (True, False)):
-            y, q = nat.conv2d_i8_resident(x_dev, w_dev, b_dev, (st, st), (pd, pd), (1, 1), rs, ob, want_f32, want_i8, relu)
+            nat.conv_variant_log = log = {}
+            try:
+                y, q = nat.conv2d_i8_resident(x_dev, w_dev, b_dev, (st, st), (pd, pd), (1, 1), rs, ob, want_f32, want_i8, relu)
+            finally:
+                nat.conv_variant_log = None
+            assert log == {variant: 1}, log
             if want_f32:
                 np.testing.assert_array_equal(y.cpu().numpy(), ref)
             else:
