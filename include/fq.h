@@ -543,6 +543,28 @@ int fq_dwconv2d_i8_resident_pcs(const int8_t* x_nhwc, const int8_t* w_rsc, const
                                 int rs_max, int8_t* q_nhwc, int Cpad, int relu, int N, int H, int W, int C, int R, int S,
                                 int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int ob, fq_stream_t stream);
 
+/* Channel concatenation (the Concat marker layer, torch.cat along dim 1) and nearest upsampling (nn.UpsamplingNearest2d with an
+ * integer factor) of resident int8 NHWC activations that share ONE grid: moving the integers is concatenating the values, and
+ * nearest upsampling and ReLU commute with the scale 2^-g.  nsrc is 1 or 2.
+ *   out[n][h][w][c] = src0[n][h / up0][w / up0][c]            for c < C0
+ *                   = src1[n][h / up1][w / up1][c - C0]       for C0 <= c < C0 + C1
+ *                   = 0                                       for C0 + C1 <= c < Cpad_out, whatever the sources' padding channels hold
+ *   relu != 0: max(., 0) on every byte afterwards.
+ * Source i: int8 [N][H / up_i][W / up_i][Cpad_i], 16-byte aligned, Cpad_i % 16 == 0, 1 <= C_i <= Cpad_i, up_i in {1, 2, 4} on both
+ *   axes with H % up_i == 0 and W % up_i == 0 (powers of two: torch's floor(dst * (1 / s)) is dst / s exactly).
+ * out: int8 [N][H][W][Cpad_out], 16-byte aligned, Cpad_out == pad16(C0 + C1) -- not the sum of the sources' paddings; it must not
+ *   overlap a source.  Only aligned loads are issued and no byte outside [q_i, q_i + N (H / up_i) (W / up_i) Cpad_i) is read.
+ * nsrc == 1 with up > 1 is the stand-alone nearest upsampling; nsrc == 1 with relu alone a ReLU on the integers.
+ * Return codes: FQ_ERR_INVALID_ARG for nsrc < 1, a null or misaligned pointer, C_i < 1, up_i < 1, Cpad_i < C_i, a wrong Cpad_out and
+ *   the call with nothing to do (nsrc == 1, up == 1, relu == 0); FQ_ERR_UNSUPPORTED for every other geometry (nsrc > 2, another
+ *   factor, H or W no multiple of it, Cpad_i % 16 != 0, C0 + C1 > 65536, or N*H*W*Cpad_out >= 2^31 - 1 or a source of that many
+ *   bytes: 32-bit element offsets, as fq_dwconv2d_i8_resident bounds its input): callers keep the fp32 form there.
+ * fq_concat_i8_nhwc_supported: 1 when the channel counts and factors alone are taken (host arithmetic, no GPU needed). */
+typedef struct fq_cat_src { const int8_t* q; int C; int Cpad; int up; } fq_cat_src;
+int fq_concat_i8_nhwc_supported(const int* C, const int* up, int nsrc);
+int fq_concat_i8_nhwc(const fq_cat_src* srcs, int nsrc, int8_t* out, int Cpad_out, int relu, int N, int H, int W,
+                      fq_stream_t stream);
+
 /* The tail of a bottleneck block and the head of the next one in ONE kernel (round 4):
  *   NewConv2d.forward of conv3 (1x1, C -> K3; new_quantity_op.py:124-133)  ->  NewAdd.forward with the shortcut (:166-174)
  *   -> nn.ReLU -> the next block's conv1: NewConv2d.forward again (1x1, K3 -> C2, Quantity(ib) on the sum, its own tail and

@@ -40,6 +40,10 @@ class _ChainSeg(ctypes.Structure):
                 ("row_y", ctypes.c_int32 * CHAIN_MAX), ("row_sum", ctypes.c_int32 * CHAIN_MAX)]
 
 
+class _CatSrc(ctypes.Structure):
+    _fields_ = [("q", ctypes.c_void_p), ("C", ctypes.c_int32), ("Cpad", ctypes.c_int32), ("up", ctypes.c_int32)]
+
+
 class _ChanSeg(ctypes.Structure):
     _fields_ = [("ptr", ctypes.c_void_p), ("N", ctypes.c_int32), ("C", ctypes.c_int32), ("HW", ctypes.c_int64),
                 ("row0", ctypes.c_int32), ("reserved", ctypes.c_int32)]
@@ -210,6 +214,10 @@ def lib():
     L.fq_dwconv2d_i8_resident.argtypes = [vp, vp, vp, vp] + [ci] * 16 + [vp]
     L.fq_dwconv2d_i8_resident_pcs.restype = ci
     L.fq_dwconv2d_i8_resident_pcs.argtypes = [vp, vp, vp, vp, ci, ci, vp] + [ci] * 15 + [vp]
+    L.fq_concat_i8_nhwc_supported.restype = ci
+    L.fq_concat_i8_nhwc_supported.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci), ci]
+    L.fq_concat_i8_nhwc.restype = ci
+    L.fq_concat_i8_nhwc.argtypes = [ctypes.POINTER(_CatSrc), ci, vp, ci, ci, ci, ci, ci, vp]
     L.fq_add_resident.restype = ci
     L.fq_add_resident.argtypes = [vp, ci, ci, vp, ci, ci, vp, ci, vp, ci, ci, sz, vp]
     L.fq_dequant_nhwc_to_nchw.restype = ci
@@ -1389,6 +1397,47 @@ def maxpool_i8_nhwc(x, kernel, stride, padding):
     _check(lib().fq_maxpool_i8_nhwc(x.data_ptr(), y.data_ptr(), N, H, W, cpad, kernel[0], kernel[1], stride[0], stride[1],
                                     padding[0], padding[1], _stream(x)), "fq_maxpool_i8_nhwc")
     return y
+
+
+def concat_supported(Cs, ups):
+    """True when fq_concat_i8_nhwc takes sources of these channel counts and nearest-upsampling factors (include/fq.h): one or
+    two sources, every C >= 1, every factor 1, 2 or 4.  Pure host arithmetic (no GPU needed)."""
+    n = len(Cs)
+    if n != len(ups) or n < 1:
+        return False
+    ci = ctypes.c_int * n
+    return bool(lib().fq_concat_i8_nhwc_supported(ci(*[int(c) for c in Cs]), ci(*[int(u) for u in ups]), n))
+
+
+def concat_i8_nhwc(srcs, relu, out=None):
+    """fq_concat_i8_nhwc.  srcs = [(q, C, up), ...]: one or two int8 [N, H / up, W / up, Cpad] tensors on ONE grid with C real
+    channels each, `up` the nearest-upsampling factor of that operand.  Returns int8 [N, H, W, pad16(sum C)]: the operands one
+    behind the other along the channels, the padding channels zero, max(., 0) applied when relu.  `out`: write there instead
+    (that shape, dense, 16-byte aligned).  Launches on the current stream and does not synchronise."""
+    n = len(srcs)
+    arr = (_CatSrc * max(n, 1))()
+    plane, total = None, 0
+    for i, (q, C, up) in enumerate(srcs):
+        _need_cuda(q, torch.int8, "fq_concat_i8_nhwc")
+        assert q.dim() == 4 and q.is_contiguous()
+        here = (int(q.shape[0]), int(q.shape[1]) * int(up), int(q.shape[2]) * int(up))
+        if plane is None:
+            plane = here
+        elif here != plane:
+            raise FqError("fq_concat_i8_nhwc: the operands give different output planes (%s, %s)" % (plane, here))
+        arr[i].q, arr[i].C, arr[i].Cpad, arr[i].up = q.data_ptr(), int(C), int(q.shape[3]), int(up)
+        total += int(C)
+    if plane is None:
+        raise FqError("fq_concat_i8_nhwc: no operand")
+    N, H, W = plane
+    cpad = pad16(total)
+    if out is None:
+        out = torch.empty(N, H, W, cpad, dtype=torch.int8, device=srcs[0][0].device)
+    else:
+        _need_cuda(out, torch.int8, "fq_concat_i8_nhwc")
+        assert tuple(out.shape) == (N, H, W, cpad) and out.is_contiguous()
+    _check(lib().fq_concat_i8_nhwc(arr, n, out.data_ptr(), cpad, 1 if relu else 0, N, H, W, _stream(out)), "fq_concat_i8_nhwc")
+    return out
 
 
 def avgpool_global_nhwc(q, g, channels):

@@ -80,6 +80,26 @@ class DeferredConv(object):
         return self.materialise().to_f32()
 
 
+class DeferredUpsample(object):
+    """A nearest upsampling whose only consumer is a resident Concat (enable(concat=True)): nothing has been launched, the
+    Concat reads the small tensor with the factor as its operand's `up` (fq_concat_i8_nhwc), so the s*s times larger tensor is
+    neither written nor read back.  Anything else that touches it materialises the upsampled activation."""
+    __slots__ = ("handle", "s", "_out")
+
+    def __init__(self, handle, s):
+        self.handle, self.s, self._out = handle, int(s), None
+
+    def materialise(self):
+        if self._out is None:
+            h = self.handle
+            y = _native.concat_i8_nhwc([(h.exact, h.shape[1], self.s)], False)
+            self._out = QHandle((h.shape[0], h.shape[1], y.shape[1], y.shape[2]), y, h.grid, y, h.grid, h.relu_done)
+        return self._out
+
+    def to_f32(self):
+        return self.materialise().to_f32()
+
+
 def block_tail_enabled():
     """FQ_BLOCK_TAIL=0: keep conv3 + add and the next conv1 as two launches (A/B timing)."""
     import os
@@ -106,7 +126,7 @@ def resident_of(x):
     """The integer form of an activation, if it has one (a handle, or an fp32 tensor carrying one that is still current)."""
     if type(x) is QHandle:
         return x
-    if type(x) is DeferredConv:
+    if type(x) in (DeferredConv, DeferredUpsample):
         return x.materialise()
     h = getattr(x, "_fq_resident", None)
     if h is not None and getattr(x, "_fq_resident_version", None) != x._version:
@@ -115,13 +135,13 @@ def resident_of(x):
 
 
 def as_f32(x):
-    return x.to_f32() if type(x) in (QHandle, DeferredConv) else x
+    return x.to_f32() if type(x) in (QHandle, DeferredConv, DeferredUpsample) else x
 
 
 class Plan(object):
     """What one producer emits.  Plain data (pickles with the module)."""
     __slots__ = ("relu", "emit_f32", "emit_int", "narrow_bit", "want_wide", "grid", "resident_add", "defer", "fuse_arg",
-                 "fuse_next", "narrow_to_hbm", "fuse_proj", "depthwise")
+                 "fuse_next", "narrow_to_hbm", "fuse_proj", "depthwise", "up")
 
     def __init__(self):
         self.relu = False            # the nn.ReLU that consumes this output is fused
@@ -137,6 +157,7 @@ class Plan(object):
         self.narrow_to_hbm = True    # NewAdd with fuse_next: somebody besides that convolution reads the int8 re-quantisation
         self.fuse_proj = False       # NewAdd with fuse_arg: the OTHER operand is a deferred 1x1 projection that the kernel computes too
         self.depthwise = False       # NewConv2d: a depthwise layer taken by enable(depthwise=True); runs on fq_dwconv2d_i8_resident
+        self.up = None               # nearest upsampling taken by enable(concat=True): its factor (with `defer`: the Concat applies it)
 
     def __getstate__(self):
         return {k: getattr(self, k) for k in self.__slots__}
@@ -224,13 +245,91 @@ class _AvgPoolResident(object):
         return type(m).forward(m, as_f32(x))
 
 
+def _upsample_factor(m):
+    """2 or 4 for an nn.Upsample / nn.UpsamplingNearest2d that fq_concat_i8_nhwc can stand for: mode "nearest", no `size`, one
+    integer scale factor for both axes; None for anything else."""
+    if not isinstance(m, nn.Upsample) or m.mode != "nearest" or m.size is not None or m.scale_factor is None:
+        return None
+    sf = m.scale_factor
+    if isinstance(sf, (tuple, list)):
+        if len(sf) != 2 or sf[0] != sf[1]:
+            return None
+        sf = sf[0]
+    return int(sf) if float(sf) in (2.0, 4.0) else None
+
+
+def _emit(plan, out):
+    """A finished integer activation as its consumers want it: the handle, or the fp32 tensor (carrying the handle)."""
+    if not plan.emit_f32:
+        return out
+    t = out.to_f32()
+    if plan.emit_int:
+        carry(t, out)
+    if out.relu_done:
+        t._fq_relu_done = True
+    return t
+
+
+class _UpsampleResident(object):
+    """Instance-level forward of a nearest upsampling between integer layers: repeating the int8 NHWC integers is repeating the
+    values.  With plan.defer nothing runs here: the resident Concat that consumes it reads the small tensor (DeferredUpsample)."""
+
+    def __init__(self, module):
+        self.module = module
+
+    def __call__(self, x):
+        m = self.module
+        plan = m.__dict__.get("_resident")
+        h = resident_of(x)
+        if (plan is None or plan.up is None or plan.up != _upsample_factor(m) or h is None or h.exact is None
+                or h.exact.dtype != torch.int8 or h.exact.dim() != 4 or h.grid != plan.narrow_bit):
+            return type(m).forward(m, as_f32(x))
+        if plan.defer and not plan.relu:
+            return DeferredUpsample(h, plan.up)
+        y = _native.concat_i8_nhwc([(h.exact, h.shape[1], plan.up)], plan.relu)
+        return _emit(plan, QHandle((h.shape[0], h.shape[1], y.shape[1], y.shape[2]), y, h.grid, y, h.grid, plan.relu or h.relu_done))
+
+
+class _ConcatResident(object):
+    """Instance-level forward of a Concat marker whose operands are int8 NHWC on one grid: concatenating the integers is
+    concatenating the values (fq_concat_i8_nhwc, the nn.ReLU behind it fused).  An operand that arrives as a DeferredUpsample is
+    upsampled by the same kernel."""
+
+    def __init__(self, module):
+        self.module = module
+
+    def __call__(self, x, y, dim=1):
+        m = self.module
+        plan = m.__dict__.get("_resident")
+        ops = []
+        for t in (x, y):
+            if type(t) is DeferredUpsample and t._out is None:
+                ops.append((t.handle, t.s))
+            else:
+                ops.append((resident_of(t), 1))
+        ok = plan is not None and dim == 1
+        for h, _up in ops:
+            ok = ok and h is not None and h.exact is not None and h.exact.dtype == torch.int8 and h.exact.dim() == 4 \
+                and h.grid == plan.narrow_bit
+        if ok:
+            planes = [(h.exact.shape[0], h.exact.shape[1] * up, h.exact.shape[2] * up) for h, up in ops]
+            ok = planes[0] == planes[1] and _native.concat_supported([h.shape[1] for h, _up in ops], [up for _h, up in ops])
+        if not ok:
+            return type(m).forward(m, as_f32(x), as_f32(y), dim)
+        q = _native.concat_i8_nhwc([(h.exact, h.shape[1], up) for h, up in ops], plan.relu)
+        g = plan.narrow_bit
+        return _emit(plan, QHandle((q.shape[0], sum(h.shape[1] for h, _up in ops), q.shape[1], q.shape[2]), q, g, q, g,
+                                   plan.relu or all(h.relu_done for h, _up in ops)))
+
+
 # ---- tracing -------------------------------------------------------------------------------------
 
 class _Value(object):
-    __slots__ = ("producer", "kind", "src", "consumers", "foreign", "order")
+    __slots__ = ("producer", "kind", "src", "consumers", "foreign", "order", "shape")
 
     def __init__(self, producer, kind, src, order):
         self.producer, self.kind, self.src, self.order = producer, kind, src, order
+        self.shape = None            # shape of the traced tensor (set when the value is recorded)
         self.consumers = []          # (module, argument position)
         self.foreign = False         # touched by code outside NewConv2d / NewLinear / NewAdd / nn.ReLU
 
@@ -261,6 +360,7 @@ class _Tracer(TorchFunctionMode):
         self.produced = []           # _Value of every NewConv2d / NewAdd output, in execution order
         self.relu_values = []        # _Value of every nn.ReLU output whose input is traced
         self.avgpool_shapes = {}     # nn.AvgPool2d module -> shape of its (traced) input
+        self.concat_ok = {}          # Concat module -> every call so far joined two 4-D tensors along dim 1
 
     def __torch_function__(self, func, types, args=(), kwargs=None):
         kwargs = kwargs or {}
@@ -286,6 +386,16 @@ class _Tracer(TorchFunctionMode):
                 if isinstance(module, nn.AvgPool2d) and pos == 0:
                     self.avgpool_shapes[module] = tuple(a.shape)       # (depth > 0 here: not a foreign touch)
 
+    def pre_concat(self, module, args, kwargs):
+        """Pre-hook of a Concat marker (with_kwargs: `dim`, and the operands themselves, may be given by name)."""
+        named = [kwargs[k] for k in ("x", "y") if k in kwargs]
+        self.pre(module, tuple(args[:2]) + tuple(named))
+        dim = args[2] if len(args) > 2 else kwargs.get("dim", 1)
+        pair = (tuple(args[:2]) + tuple(named))[:2]
+        ok = (isinstance(dim, int) and dim == 1 and len(pair) == 2
+              and all(isinstance(t, torch.Tensor) and t.dim() == 4 for t in pair))
+        self.concat_ok[module] = ok and self.concat_ok.get(module, True)
+
     def post(self, module, args, output):
         self.depth -= 1
         if not isinstance(output, torch.Tensor):
@@ -305,9 +415,19 @@ class _Tracer(TorchFunctionMode):
             self.produced.append(v)
         elif isinstance(module, nn.AvgPool2d):
             return                                          # its output is an ordinary fp32 tensor
+        elif isinstance(module, nn.Upsample):               # (hooked only with enable(concat=True))
+            src = self.values.get(id(args[0])) if args and isinstance(args[0], torch.Tensor) else None
+            if src is None:
+                return
+            v = _Value(module, "upsample", src, self.order)
+            self.produced.append(v)
+        elif type(module).__name__ == "Concat":             # (likewise)
+            v = _Value(module, "concat", None, self.order)
+            self.produced.append(v)
         else:
             v = _Value(module, "add" if type(module).__name__ == "NewAdd" else "contraction", None, self.order)
             self.produced.append(v)
+        v.shape = tuple(output.shape)
         self.values[id(output)] = v
         self.keep.append(output)
 
@@ -322,7 +442,7 @@ def _clear(model):
     for m in model.modules():
         m.__dict__.pop("_resident", None)
         fwd = m.__dict__.get("forward")
-        if isinstance(fwd, (_ReluPassThrough, _MaxPoolResident, _AvgPoolResident)):
+        if isinstance(fwd, (_ReluPassThrough, _MaxPoolResident, _AvgPoolResident, _ConcatResident, _UpsampleResident)):
             del m.__dict__["forward"]
     model.__dict__.pop("_fq_resident_enabled", None)
 
@@ -337,7 +457,7 @@ def is_enabled(model):
     return bool(model.__dict__.get("_fq_resident_enabled"))
 
 
-def enable(model, example_input, verify=True, depthwise=False):
+def enable(model, example_input, verify=True, depthwise=False, concat=False):
     """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
     on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
     nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
@@ -346,8 +466,17 @@ def enable(model, example_input, verify=True, depthwise=False):
     bit for bit, otherwise the plan is removed and FqError raised.
     `depthwise=True` also plans depthwise NewConv2d layers (groups == in_channels == out_channels, 3x3 / 5x5, stride 1 / 2,
     shift in [1, 16]: NewConv2d._depthwise_ok) as integer producers and consumers, served by fq_dwconv2d_i8_resident; without
-    it they stay fp32 producers, as every other grouped convolution does.  The summary then counts them as `resident_depthwise`."""
+    it they stay fp32 producers, as every other grouped convolution does.  The summary then counts them as `resident_depthwise`.
+    `concat=True` also plans the Concat marker layer and nearest upsampling (nn.UpsamplingNearest2d, nn.Upsample(mode="nearest"))
+    by an integer scale_factor of 2 or 4, both served by fq_concat_i8_nhwc: a Concat whose two operands are int8 activations on
+    ONE grid -- what the calibrator's merge group gives them -- joins the integers, with the nn.ReLU behind it fused; an upsampling
+    whose only consumer is such a Concat is not launched at all, the Concat reads the small tensor (DeferredUpsample).  Without
+    the argument both are foreign code and their operands leave as fp32, as before.  Left in fp32 form (out of scope): a Concat
+    with a NewAdd sum (int16) as an operand or with operands on different grids, any dim but 1, more than two operands, nested
+    Concats are not flattened, the `size=` form and other factors of an upsampling; a bare torch.cat stays foreign, as a bare `+`
+    does.  The summary then gains `resident_concats`, `resident_upsamples` and `fused_upsamples`."""
     from .new_quantity_op import NewConv2d, NewLinear, NewAdd, QUANTIZE_BIT
+    from .fabu_layer import Concat
     _clear(model)
     if QUANTIZE_BIT != 8:
         raise _native.FqError("resident activations are defined for QUANTIZE_BIT = 8")
@@ -356,6 +485,12 @@ def enable(model, example_input, verify=True, depthwise=False):
     hooks = []
     for m in model.modules():
         if isinstance(m, planned_types):
+            hooks.append(m.register_forward_pre_hook(tracer.pre))
+            hooks.append(m.register_forward_hook(tracer.post))
+        elif concat and isinstance(m, Concat):
+            hooks.append(m.register_forward_pre_hook(tracer.pre_concat, with_kwargs=True))
+            hooks.append(m.register_forward_hook(tracer.post))
+        elif concat and _upsample_factor(m) is not None:      # any other nn.Upsample stays foreign code
             hooks.append(m.register_forward_pre_hook(tracer.pre))
             hooks.append(m.register_forward_hook(tracer.post))
     was_training = model.training
@@ -394,12 +529,13 @@ def enable(model, example_input, verify=True, depthwise=False):
     # pass 1 (execution order): integer format of every produced value
     fmt = {}                         # id(effective _Value) -> (bytes, grid)
     eff_of = {}                      # id(produced _Value) -> (effective _Value, relu module)
-    operands = {}                    # NewAdd module -> [value at arg 0, value at arg 1]
+    operands = {}                    # NewAdd / Concat module -> [value at arg 0, value at arg 1]
     for v in tracer.values.values():
         for (m, pos) in v.consumers:
-            if isinstance(m, NewAdd) and pos < 2:
+            if isinstance(m, (NewAdd, Concat)) and pos < 2:
                 operands.setdefault(m, [None, None])[pos] = v
     add_resident, pool_resident = set(), set()
+    cat_resident = set()             # Concat and nearest-upsampling modules that run on fq_concat_i8_nhwc
 
     def avg_can_read(m):
         shape = tracer.avgpool_shapes.get(m)
@@ -418,6 +554,25 @@ def enable(model, example_input, verify=True, depthwise=False):
             if f is not None and f[0] == 1 and tracer.calls.get(m, 0) == 1 and _maxpool_supported(m):
                 pool_resident.add(m)
                 fmt[id(e)] = f
+        elif v.kind == "upsample":
+            f = fmt.get(id(v.src))
+            s = _upsample_factor(m)
+            if (f is not None and f[0] == 1 and tracer.calls.get(m, 0) == 1 and s is not None and len(v.shape) == 4
+                    and _native.concat_supported([v.shape[1]], [s])):
+                cat_resident.add(m)
+                fmt[id(e)] = f
+        elif v.kind == "concat":
+            ops = operands.get(m)
+            if (tracer.calls.get(m, 0) != 1 or not tracer.concat_ok.get(m) or ops is None or ops[0] is None or ops[1] is None):
+                continue
+            fx, fy = fmt.get(id(ops[0])), fmt.get(id(ops[1]))
+            # int8 operands on one grid only: a NewAdd sum (2, .) or two grids keep the fp32 form
+            if fx is None or fy is None or fx[0] != 1 or fx != fy or ops[0].shape is None or ops[1].shape is None:
+                continue
+            if not _native.concat_supported([ops[0].shape[1], ops[1].shape[1]], [1, 1]):
+                continue
+            cat_resident.add(m)
+            fmt[id(e)] = fx
         else:
             ops = operands.get(m)
             if tracer.calls.get(m, 0) != 1 or ops is None or ops[0] is None or ops[1] is None:
@@ -436,6 +591,8 @@ def enable(model, example_input, verify=True, depthwise=False):
                "int_only_outputs": 0}
     if depthwise:
         summary["resident_depthwise"] = 0
+    if concat:
+        summary["resident_concats"] = summary["resident_upsamples"] = 0
     for v in tracer.produced:
         m = v.producer
         e, relu_mod = eff_of[id(v)]
@@ -452,11 +609,11 @@ def enable(model, example_input, verify=True, depthwise=False):
             elif (isinstance(c, NewAdd) and c in add_resident) or avg_can_read(c):
                 int_consumers += 1
                 plan.want_wide = True                       # these read the exact value
-            elif c in pool_resident and v.kind != "add":
-                int_consumers += 1                          # int8 max-pool of an int8 activation
+            elif (c in pool_resident or c in cat_resident) and v.kind != "add":
+                int_consumers += 1                          # int8 max-pool / Concat / nearest upsampling of an int8 activation
             else:
                 need_f32 = True
-        if v.kind in ("contraction", "maxpool"):
+        if v.kind in ("contraction", "maxpool", "concat", "upsample"):
             grid = m.output_bit if v.kind == "contraction" else fmt[id(e)][1]
             ok = [b for b in narrow_bits if b == grid]
             if len(ok) != len(narrow_bits):
@@ -485,7 +642,13 @@ def enable(model, example_input, verify=True, depthwise=False):
             summary["fused_relus"] += 1
         if v.kind == "maxpool":
             m.__dict__["forward"] = _MaxPoolResident(m)
-        summary[{"contraction": "resident_convs", "add": "resident_adds", "maxpool": "resident_pools"}[v.kind]] += 1
+        elif v.kind == "concat":
+            m.__dict__["forward"] = _ConcatResident(m)
+        elif v.kind == "upsample":
+            plan.up = _upsample_factor(m)
+            m.__dict__["forward"] = _UpsampleResident(m)
+        summary[{"contraction": "resident_convs", "add": "resident_adds", "maxpool": "resident_pools",
+                 "concat": "resident_concats", "upsample": "resident_upsamples"}[v.kind]] += 1
         summary["fp32_outputs" if plan.emit_f32 else "int_only_outputs"] += 1
     # a convolution whose value goes to one resident add and nowhere else is run BY that add
     summary["fused_conv_adds"] = 0
@@ -561,6 +724,24 @@ def enable(model, example_input, verify=True, depthwise=False):
         pp.defer = True
         plan.fuse_proj = True
         summary["fused_projections"] += 1
+    # a nearest upsampling whose value goes to one resident Concat and nowhere else is applied BY that Concat (its operand's `up`)
+    if concat:
+        summary["fused_upsamples"] = 0
+        for v in tracer.produced:
+            m = v.producer
+            plan = m.__dict__.get("_resident")
+            if v.kind != "upsample" or plan is None or plan.up is None or plan.relu or plan.emit_f32 or v.foreign:
+                continue
+            if len(v.consumers) != 1 or v.consumers[0][0] not in cat_resident or not isinstance(v.consumers[0][0], Concat):
+                continue
+            cat_mod, pos = v.consumers[0]
+            ops = operands[cat_mod]
+            ups = [1, 1]
+            ups[pos] = plan.up
+            if ops[pos] is not v or ops[1 - pos] is v or not _native.concat_supported([ops[0].shape[1], ops[1].shape[1]], ups):
+                continue
+            plan.defer = True
+            summary["fused_upsamples"] += 1
     for m in tracer.avgpool_shapes:
         if avg_can_read(m):
             m.__dict__["forward"] = _AvgPoolResident(m)
