@@ -373,6 +373,33 @@ int fq_conv3x3_wino_qd_f32(const float* x, const float* u, const float* bias, fl
 int fq_conv_stem_qd_f32(const float* x, const float* wp, const float* bias, float* y, int N, int Cin, int H, int W,
                         int Cout, int R, int S, int stride, int pad, int bit, int bitwidth, fq_stream_t stream);
 
+/* The depthwise float convolutions of the calibration forward (nn.Conv2d with groups == in_channels == out_channels: the
+ * thirteen 3x3 layers of model/mobilenet/MobileNet_fabu.py), same epilogue contract as fq_conv1x1_f32 (bias may be NULL;
+ * relu_out may be NULL; with relu_out given y may be NULL and its statistic is still taken; exactly one of {max_inout,
+ * hist_row + interval} or neither):
+ *   y[n][c][oh][ow] = bias[c] + sum_{r,s} w[c][r][s] * x[n][c][oh*stride - pad + r][ow*stride - pad + s]
+ * x: fp32 [N][C][H][W] contiguous; y / relu_out: fp32 [N][C][Ho][Wo], Ho = (H + 2 pad - R)/stride + 1; both below 2^30 elements.
+ * w_crs: the module's own weight, fp32 [C][1][R][S] contiguous -- no packing step.  Pointers need only their type's alignment
+ *   (a y that is a view at an odd float offset is stored with narrower stores where a 16-byte one would be misaligned).
+ * Taken (fq_dwconv_f32_supported, host arithmetic only): R == S in {3, 5}, stride 1 or 2 on both axes, dilation 1, zero
+ *   padding 0 <= pad < R on both axes, H + 2 pad >= R and W + 2 pad >= R, any N, C, H, W.  FQ_ERR_UNSUPPORTED for everything
+ *   else: callers keep the library convolution there.  FQ_ERR_INVALID_ARG for a null or misaligned pointer, N, C, H, W < 1
+ *   (or R, S, stride < 1, pad < 0), both statistics at once, a histogram without its interval, or a bit / bitwidth outside
+ *   fq_conv1x1_qd_f32's range.
+ * Numerics (part of the contract: the plain, abs-max, histogram and QuanDequan forms must see the same bits).  Per output:
+ *   acc = 0, then acc = fmaf(w[r][s], x, acc) with r outer and s inner, then acc + bias[c].  A tap outside the image
+ *   contributes the operand +0.0f -- never a value loaded from a neighbouring row or plane, never a masked product (an Inf or
+ *   NaN next to the padding stays where the reference has it).  No split, no workspace, no atomics on floats other than the
+ *   abs-max publish.  The value does not depend on N or on which tile or lane computed it: image i of a batch gets the bits
+ *   of the same image alone.  Exact zeros are not counted by the histogram; the abs-max ignores NaN.
+ * fq_dwconv_qd_f32: TestConv.forward of such a layer in one kernel, fq_quandequan_f32(bit, bitwidth) of the value
+ *   fq_dwconv_f32 would have stored. */
+int fq_dwconv_f32_supported(int C, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int H, int W);
+int fq_dwconv_f32(const float* x, const float* w_crs, const float* bias, float* y, float* relu_out, int N, int C, int H, int W,
+                  int R, int S, int stride, int pad, float* max_inout, const float* interval, int64_t* hist_row, fq_stream_t stream);
+int fq_dwconv_qd_f32(const float* x, const float* w_crs, const float* bias, float* y, int N, int C, int H, int W,
+                     int R, int S, int stride, int pad, int bit, int bitwidth, fq_stream_t stream);
+
 /* The last 1x1 convolution of a residual block together with the `Eltwise` that consumes it and the ReLU behind that
  * (fabu_layer.py:5-11 called from the model the reference runs at pytorch_quantizer.py:288-296), calibration pass 1, in ONE
  * kernel:  v = conv1x1(x) + bias  (abs-max folded into *max_y; stored to y unless y is NULL),  s = v + res  (abs-max folded

@@ -1,7 +1,8 @@
 """The float convolutions this package runs on its own fp32 MFMA kernels instead of torch's (no reference counterpart: the
 reference calls torch's Conv2d.forward -- pytorch_quantizer.py:288-296 inside the calibration forward, new_quantity_op.py:283-292
 inside TestConv): 1x1 layers on fq_conv1x1_f32, R x S layers with zero padding (the 3x3 ones) on fq_conv_kxk_f32, the 7x7
-stride-2 stem on fq_conv_stem_f32 (csrc/) -- every convolution of a ResNet, so that the calibration forward is deterministic
+stride-2 stem on fq_conv_stem_f32 (csrc/) -- every convolution of a ResNet -- and, opt-in (FQ_OWN_DWCONV=1), the depthwise 3x3 /
+5x5 layers of a separable network on fq_dwconv_f32, so that the calibration forward is deterministic
 and never enters the convolution library (whose first-use solver search costs seconds in a fresh process).  Which call qualifies, the
 weights in the kernels' layout (cached on the module), the once-per-process check of every module against an independent
 implementation of the same fp32 mathematics, and the plain (no statistic) forward.  Shared by tools.Quantity (which adds the
@@ -17,8 +18,8 @@ import torch
 
 from . import _native
 
-__all__ = ["enabled", "kind", "weight", "runner", "verified", "plain", "call", "call_qd", "call_linear_qd", "state", "is_verified",
-           "is_off", "forget", "kernel_key", "own_convs", "TOL"]
+__all__ = ["enabled", "depthwise_enabled", "kind", "weight", "runner", "dw_reference", "verified", "plain", "call", "call_qd",
+           "call_linear_qd", "state", "is_verified", "is_off", "forget", "kernel_key", "own_convs", "TOL"]
 
 TOL = 1e-5                                      # |own - torch| <= TOL * (|W| * |x| + |b|): summation order only
 # module -> {"verified": the set of kernels (kernel_key) that agreed with torch on this module, "off": one disagreed (the module
@@ -69,16 +70,37 @@ def enabled():
     return os.environ.get("FQ_OWN_CONV1X1", "1") != "0"
 
 
-def kind(m, x, wino=True):
+def depthwise_enabled():
+    """FQ_OWN_DWCONV=1 (read at call time; default off): depthwise layers run on fq_dwconv_f32 instead of the library's grouped
+    convolution."""
+    return os.environ.get("FQ_OWN_DWCONV", "0") == "1"
+
+
+def _dw_ok(m, h, w):
+    """Does fq_dwconv_f32 take the nn.Conv2d m on an h x w plane?  Host arithmetic on the module alone (what
+    fq_dwconv_f32_supported answers for the same numbers, plus what the C ABI cannot see: the bias, the padding mode)."""
+    k, s, p, d = m.kernel_size, m.stride, m.padding, m.dilation
+    return (m.groups > 0 and m.groups == m.in_channels == m.out_channels and m.bias is not None
+            and tuple(k) in ((3, 3), (5, 5)) and tuple(s) in ((1, 1), (2, 2)) and tuple(d) == (1, 1)
+            and not isinstance(p, str) and m.padding_mode == "zeros" and p[0] == p[1] and 0 <= p[0] < k[0]
+            and h + 2 * p[0] >= k[0] and w + 2 * p[1] >= k[1])
+
+
+def kind(m, x, wino=True, depthwise=None):
     """"c1" (fq_conv1x1_f32), "kxk" (fq_conv_kxk_f32), "wino" (fq_conv3x3_wino_f32: the Winograd form of the stride-1 3x3
-    layers; wino=False or FQ_CONV_WINO=0 keeps them on "kxk"), "stem" (fq_conv_stem_f32) or None: which own kernel takes this call
-    of the nn.Conv2d m.  Every kind has the plain, the statistic and the QuanDequan form, so TestConv's two ways through a layer
-    (fused with QuanDequan, or not when somebody watches the module) see the same sums."""
+    layers; wino=False or FQ_CONV_WINO=0 keeps them on "kxk"), "stem" (fq_conv_stem_f32), "dw" (fq_dwconv_f32: a depthwise 3x3 /
+    5x5 layer, only with depthwise=True; None reads FQ_OWN_DWCONV) or None: which own kernel takes this call of the nn.Conv2d m.
+    Every kind has the plain, the statistic and the QuanDequan form, so TestConv's two ways through a layer (fused with
+    QuanDequan, or not when somebody watches the module) see the same sums."""
     if (not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or m.weight.dtype != torch.float32 or m.bias is None
-            or is_off(m) or m.groups != 1 or m.dilation != (1, 1) or m.stride[0] != m.stride[1] or x.dim() != 4
+            or is_off(m) or m.dilation != (1, 1) or m.stride[0] != m.stride[1] or x.dim() != 4
             or not x.is_contiguous() or isinstance(m.padding, str) or m.padding[0] != m.padding[1] or m.padding_mode != "zeros"
             or x.numel() >= 2 ** 30 or x.shape[0] * m.out_channels * x.shape[2] * x.shape[3] >= 2 ** 30):
         return None
+    if m.groups != 1:
+        if not (depthwise_enabled() if depthwise is None else depthwise):
+            return None
+        return "dw" if _dw_ok(m, x.shape[2], x.shape[3]) else None
     if m.kernel_size == (1, 1) and m.padding == (0, 0) and m.out_channels % 4 == 0:
         return "c1"
     if (x.shape[2] + 2 * m.padding[0] >= m.kernel_size[0] and x.shape[3] + 2 * m.padding[1] >= m.kernel_size[1]
@@ -99,8 +121,11 @@ def kind(m, x, wino=True):
 
 def weight(m, k):
     """The weights in the layout the kernel reads (Wt [Cin][Cout] / the packed stem matrix / the transformed Winograd
-    weights), one entry per kind, rebuilt when the parameter was written to or replaced."""
+    weights), one entry per kind, rebuilt when the parameter was written to or replaced.  "dw": the parameter itself
+    ([C][1][R][S] is the layout fq_dwconv_f32 reads)."""
     w = m.weight
+    if k == "dw":
+        return w.detach() if w.is_contiguous() else w.detach().contiguous()
     tag = (w._version, w.data_ptr(), w.device, _native.conv_sb_enabled())
     by_kind = state(m).setdefault("wt", {})
     cached = by_kind.get(k)
@@ -124,7 +149,22 @@ def runner(m, k, x):
         return lambda **kw: _native.conv_kxk_f32(x, wq, m.bias, m.kernel_size, s, m.padding[0], **kw)
     if k == "wino":
         return lambda **kw: _native.conv_wino_f32(x, wq, m.bias, m.out_channels, **kw)
+    if k == "dw":
+        return lambda **kw: _native.dwconv_f32(x, wq, m.bias, m.kernel_size, s, m.padding[0], **kw)
     return lambda **kw: _native.conv_stem_f32(x, wq, m.bias, m.out_channels, m.kernel_size, s, m.padding[0], **kw)
+
+
+def dw_reference(x, w, bias, kernel, stride, padding):
+    """(reference, bound) of a depthwise convolution WITHOUT the convolution library, on CPU or CUDA tensors: unfold, then the
+    R * S products of each channel summed -- the same fp32 mathematics as fq_dwconv_f32 in another order; bound is the same
+    expression with absolute values, [n, C, L] both (L = Ho * Wo)."""
+    n, c = x.shape[0], x.shape[1]
+    rs = kernel[0] * kernel[1]
+    cols = torch.nn.functional.unfold(x, kernel, padding=padding, stride=stride).view(n, c, rs, -1)
+    wv = w.reshape(1, c, rs, 1)
+    ref = (cols * wv).sum(2) + bias.view(1, -1, 1)
+    bound = (cols.abs() * wv.abs()).sum(2) + bias.abs().view(1, -1, 1)
+    return ref, bound
 
 
 def verified(m, run, x, k=None):
@@ -155,6 +195,11 @@ def verified(m, run, x, k=None):
     ok = scratch[0] == torch.linalg.vector_norm(own.reshape(-1), float("inf"))
     for lo, hi in groups:
         xh = x[lo:hi]
+        if m.groups != 1:                                       # depthwise: no GEMM to lean on, the products summed per channel
+            ref, bound = dw_reference(xh, m.weight, m.bias, m.kernel_size, m.stride, m.padding)
+            ok = ok & ((own[lo:hi].reshape(hi - lo, m.out_channels, -1) - ref).abs() <= TOL * bound).all()
+            del ref, bound
+            continue
         if m.kernel_size == (1, 1):
             s = m.stride[0]
             cols = (xh if s == 1 else xh[:, :, ::s, ::s]).reshape(hi - lo, x.shape[1], -1)
