@@ -658,6 +658,30 @@ int fq_maxpool_i8_nhwc(const int8_t* x, int8_t* y, int N, int H, int W, int Cpad
 int fq_avgpool_global_nhwc(const void* q_nhwc, int q_bytes, int g, float* y, int N, int C, int HW, int Cpad,
                            fq_stream_t stream);
 
+/* Windowed nn.AvgPool2d (ceil_mode False, no divisor_override) on a resident int8 NHWC activation, re-quantised for the
+ * convolution behind it.  The reference's chain is DeQuantity(g) -> nn.AvgPool2d -> optional nn.ReLU -> Quantity(b); the source is
+ * int8 on the grid g, so every partial sum of torch's fp32 accumulation is exact and the chain equals, per output element and channel,
+ *   S = sum of x[n][ih][iw][c] over window ∩ image          (int32; taps outside the image add nothing)
+ *   D = kh * kw                                              if count_include_pad (floor mode: the padded window is never cut)
+ *       (#window rows inside the image) * (#window columns inside)          otherwise
+ *   f = (float)S / (float)D                                  one IEEE round-to-nearest fp32 division
+ *   t = f * 2^shift                                          shift = b - g, exact
+ *   r = rint(t)                                              round half to even (torch.round)
+ *   y = clamp(relu ? max(r, 0) : r, -128, 127)
+ * The DOUBLE rounding is part of the rule: f is rounded to fp32 first and t to an integer after that; rounding the exact rational
+ * S * 2^shift / D once is a different function and is wrong here.
+ * x: int8 [N][H][W][Cpad]; y: int8 [N][P][Q][Cpad], P = (H + 2*ph - kh)/sh + 1 (floor), Q alike; Cpad % 16 == 0, 1 <= C <= Cpad,
+ *   both 16-byte aligned; y[..][c] = 0 for c in [C, Cpad) whatever the source's padding channels hold (the contract of
+ *   fq_dwconv2d_i8_resident and fq_concat_i8_nhwc).  Only aligned 16-byte loads inside [x, x + N*H*W*Cpad) are issued.
+ * Return codes: FQ_ERR_INVALID_ARG for a null or misaligned pointer with N > 0, a non-positive size, kernel or stride, negative
+ *   padding, C > Cpad, Cpad % 16 != 0, 2*ph > kh or 2*pw > kw (torch's own constraint, as fq_maxpool_i8_nhwc has it), P < 1 or
+ *   Q < 1; FQ_ERR_UNSUPPORTED -- callers keep the fp32 form -- for kh*kw > 64 (|S| <= 8192: a lane accumulates in packed int16),
+ *   |shift| > 8, or an input or output of 2^31 - 1 bytes or more (32-bit byte offsets).  N == 0 is FQ_OK.
+ * fq_avgpool_i8_nhwc_supported: 1 when window, stride, padding and shift alone are taken (host arithmetic, no GPU needed). */
+int fq_avgpool_i8_nhwc_supported(int kh, int kw, int sh, int sw, int ph, int pw, int shift);
+int fq_avgpool_i8_nhwc(const int8_t* x, int8_t* y, int N, int H, int W, int C, int Cpad, int kh, int kw, int sh, int sw,
+                       int ph, int pw, int count_include_pad, int shift, int relu, fq_stream_t stream);
+
 /* ---- input files ------------------------------------------------------------------------------- */
 
 /* HOST helper for PRE_PROCESS.IMG = 2 (pytorch_quantizer.py:276-280: np.load of one CHW fp32 image per calibration item):

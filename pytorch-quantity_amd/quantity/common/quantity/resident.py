@@ -149,7 +149,7 @@ class Plan(object):
         self.emit_int = False        # some consumer reads the integer form
         self.narrow_bit = None       # NewAdd: Quantity bit of the conv consumers (None: no narrow output)
         self.want_wide = False       # NewAdd: exact int16 sum needed (next add, or fp32 via dequant)
-        self.grid = None             # NewAdd: grid of the exact sum
+        self.grid = None             # NewAdd: grid of the exact sum; windowed nn.AvgPool2d (enable(avgpool=True)): grid of its source
         self.resident_add = False    # NewAdd: operands arrive as integers
         self.defer = False           # NewConv2d: only consumer is a resident NewAdd, which runs this conv itself
         self.fuse_arg = None         # NewAdd: operand position (0 / 1) that arrives as a DeferredConv
@@ -243,6 +243,38 @@ class _AvgPoolResident(object):
                 and h.exact.shape[1] * h.exact.shape[2] * 32768 < (1 << 24)):
             return _native.avgpool_global_nhwc(h.exact, h.grid, h.shape[1])
         return type(m).forward(m, as_f32(x))
+
+
+class _AvgPoolWindowResident(object):
+    """Instance-level forward of a windowed nn.AvgPool2d between an int8 activation and the convolution(s) behind it
+    (enable(avgpool=True)): DeQuantity -> pool -> ReLU -> the consumers' Quantity in one kernel (fq_avgpool_i8_nhwc).  The result
+    has no exact integer form: the handle carries the narrow payload only, and anything but a NewConv2d at that bit that touches it
+    raises (QHandle.to_f32)."""
+
+    def __init__(self, module):
+        self.module = module
+
+    def __call__(self, x):
+        m = self.module
+        plan = m.__dict__.get("_resident")
+        h = resident_of(x)
+        if (plan is None or plan.narrow_bit is None or plan.grid is None or h is None or h.exact is None
+                or h.exact.dtype != torch.int8 or h.exact.dim() != 4 or h.grid != plan.grid or not _avgpool_window_ok(m)):
+            return type(m).forward(m, as_f32(x))
+        k, st, pd = _avgpool_geometry(m)
+        hh, ww = int(h.exact.shape[1]), int(h.exact.shape[2])
+        if (not _native.avgpool_supported(k, st, pd, plan.narrow_bit - h.grid) or hh + 2 * pd[0] < k[0] or ww + 2 * pd[1] < k[1]):
+            return type(m).forward(m, as_f32(x))
+        y = _native.avgpool_i8_nhwc(h.exact, h.shape[1], k, st, pd, m.count_include_pad, plan.narrow_bit - h.grid, plan.relu)
+        return QHandle((y.shape[0], h.shape[1], y.shape[1], y.shape[2]), None, None, y, plan.narrow_bit, plan.relu or h.relu_done)
+
+
+def _avgpool_geometry(m):
+    return _pair(m.kernel_size), _pair(m.stride if m.stride is not None else m.kernel_size), _pair(m.padding)
+
+
+def _avgpool_window_ok(m):
+    return not m.ceil_mode and getattr(m, "divisor_override", None) is None
 
 
 def _upsample_factor(m):
@@ -349,9 +381,10 @@ def _iter_tensors(obj):
 
 class _Tracer(TorchFunctionMode):
 
-    def __init__(self, planned_types):
+    def __init__(self, planned_types, avgpool=False):
         super(_Tracer, self).__init__()
         self.planned_types = planned_types
+        self.avgpool = bool(avgpool)     # enable(avgpool=True): an nn.AvgPool2d output is a traced value
         self.values = {}             # id(tensor) -> _Value
         self.keep = []               # keeps traced tensors alive so ids are not reused
         self.depth = 0
@@ -414,7 +447,13 @@ class _Tracer(TorchFunctionMode):
             v = _Value(module, "maxpool", src, self.order)
             self.produced.append(v)
         elif isinstance(module, nn.AvgPool2d):
-            return                                          # its output is an ordinary fp32 tensor
+            if not self.avgpool:
+                return                                      # its output is an ordinary fp32 tensor
+            src = self.values.get(id(args[0])) if args and isinstance(args[0], torch.Tensor) else None
+            if src is None or src.shape is None or len(src.shape) != 4:     # (the recorded shape: a tensor method here would be a foreign touch)
+                return
+            v = _Value(module, "avgpool", src, self.order)
+            self.produced.append(v)
         elif isinstance(module, nn.Upsample):               # (hooked only with enable(concat=True))
             src = self.values.get(id(args[0])) if args and isinstance(args[0], torch.Tensor) else None
             if src is None:
@@ -442,7 +481,8 @@ def _clear(model):
     for m in model.modules():
         m.__dict__.pop("_resident", None)
         fwd = m.__dict__.get("forward")
-        if isinstance(fwd, (_ReluPassThrough, _MaxPoolResident, _AvgPoolResident, _ConcatResident, _UpsampleResident)):
+        if isinstance(fwd, (_ReluPassThrough, _MaxPoolResident, _AvgPoolResident, _ConcatResident, _UpsampleResident,
+                            _AvgPoolWindowResident)):
             del m.__dict__["forward"]
     model.__dict__.pop("_fq_resident_enabled", None)
 
@@ -457,7 +497,7 @@ def is_enabled(model):
     return bool(model.__dict__.get("_fq_resident_enabled"))
 
 
-def enable(model, example_input, verify=True, depthwise=False, concat=False):
+def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False):
     """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
     on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
     nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
@@ -474,14 +514,21 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False):
     the argument both are foreign code and their operands leave as fp32, as before.  Left in fp32 form (out of scope): a Concat
     with a NewAdd sum (int16) as an operand or with operands on different grids, any dim but 1, more than two operands, nested
     Concats are not flattened, the `size=` form and other factors of an upsampling; a bare torch.cat stays foreign, as a bare `+`
-    does.  The summary then gains `resident_concats`, `resident_upsamples` and `fused_upsamples`."""
+    does.  The summary then gains `resident_concats`, `resident_upsamples` and `fused_upsamples`.
+    `avgpool=True` also plans a windowed nn.AvgPool2d (the pool branch of an Inception block, the 2x2 pool of a transition) that
+    reads an int8 activation and is read by NewConv2d layers only, all at one input bit: DeQuantity -> pool -> the nn.ReLU behind
+    it -> the consumers' Quantity run as one kernel on the integers (fq_avgpool_i8_nhwc), so the pool's source no longer has to
+    leave as fp32 for it.  Its value has no exact integer form and is handed to those convolutions only.  Left in fp32 form (out
+    of scope): a NewAdd sum (int16) as the source, consumers that are not all convolutions at one bit, ceil_mode,
+    divisor_override, windows above 64 taps, |bit - grid| > 8, a pool called twice; F.avg_pool2d and nn.AdaptiveAvgPool2d stay
+    foreign.  The whole-plane pool in front of the head is served as before.  The summary then gains `resident_avgpools`."""
     from .new_quantity_op import NewConv2d, NewLinear, NewAdd, QUANTIZE_BIT
     from .fabu_layer import Concat
     _clear(model)
     if QUANTIZE_BIT != 8:
         raise _native.FqError("resident activations are defined for QUANTIZE_BIT = 8")
     planned_types = (NewConv2d, NewLinear, NewAdd, nn.ReLU, nn.MaxPool2d, nn.AvgPool2d)
-    tracer = _Tracer(planned_types)
+    tracer = _Tracer(planned_types, avgpool)
     hooks = []
     for m in model.modules():
         if isinstance(m, planned_types):
@@ -536,6 +583,7 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False):
                 operands.setdefault(m, [None, None])[pos] = v
     add_resident, pool_resident = set(), set()
     cat_resident = set()             # Concat and nearest-upsampling modules that run on fq_concat_i8_nhwc
+    avg_resident = {}                # windowed nn.AvgPool2d that runs on fq_avgpool_i8_nhwc -> (source grid g, consumer bit b)
 
     def avg_can_read(m):
         shape = tracer.avgpool_shapes.get(m)
@@ -561,6 +609,21 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False):
                     and _native.concat_supported([v.shape[1]], [s])):
                 cat_resident.add(m)
                 fmt[id(e)] = f
+        elif v.kind == "avgpool":
+            # int8 source on a grid g, NewConv2d consumers at one bit b; the value itself gets NO entry in fmt (it has no exact
+            # integer form), so no Concat, add, max-pool, upsampling or second pool takes it as an operand
+            f = fmt.get(id(v.src))
+            if (avg_can_read(m) or f is None or f[0] != 1 or tracer.calls.get(m, 0) != 1 or not _avgpool_window_ok(m)
+                    or e.foreign or not e.consumers or not all(conv_can_read(c) for (c, _pos) in e.consumers)):
+                continue
+            bits = set(c.input_bit for (c, _pos) in e.consumers)
+            if len(bits) != 1:
+                continue
+            b = bits.pop()
+            k, st, pd = _avgpool_geometry(m)
+            if min(st) < 1 or not _native.avgpool_supported(k, st, pd, b - f[1]):
+                continue
+            avg_resident[m] = (f[1], b)
         elif v.kind == "concat":
             ops = operands.get(m)
             if (tracer.calls.get(m, 0) != 1 or not tracer.concat_ok.get(m) or ops is None or ops[0] is None or ops[1] is None):
@@ -593,9 +656,25 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False):
         summary["resident_depthwise"] = 0
     if concat:
         summary["resident_concats"] = summary["resident_upsamples"] = 0
+    if avgpool:
+        summary["resident_avgpools"] = 0
     for v in tracer.produced:
         m = v.producer
         e, relu_mod = eff_of[id(v)]
+        if v.kind == "avgpool":
+            if m in avg_resident:
+                plan = Plan()
+                plan.relu = relu_mod is not None
+                plan.emit_int, plan.emit_f32 = True, False
+                plan.grid, plan.narrow_bit = avg_resident[m]
+                m.__dict__["_resident"] = plan
+                m.__dict__["forward"] = _AvgPoolWindowResident(m)
+                if plan.relu:
+                    relu_mod.__dict__["forward"] = _ReluPassThrough(relu_mod)
+                    summary["fused_relus"] += 1
+                summary["resident_avgpools"] += 1
+                summary["int_only_outputs"] += 1
+            continue
         if id(e) not in fmt:
             continue                                        # plain fp32 producer
         plan = Plan()
@@ -609,8 +688,8 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False):
             elif (isinstance(c, NewAdd) and c in add_resident) or avg_can_read(c):
                 int_consumers += 1
                 plan.want_wide = True                       # these read the exact value
-            elif (c in pool_resident or c in cat_resident) and v.kind != "add":
-                int_consumers += 1                          # int8 max-pool / Concat / nearest upsampling of an int8 activation
+            elif (c in pool_resident or c in cat_resident or c in avg_resident) and v.kind != "add":
+                int_consumers += 1                          # int8 max-pool / Concat / nearest upsampling / windowed average pool of an int8 activation
             else:
                 need_f32 = True
         if v.kind in ("contraction", "maxpool", "concat", "upsample"):
