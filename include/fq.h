@@ -61,7 +61,8 @@ int fq_last_hip_error(void);      /* thread-local hipError_t of the last FQ_ERR_
  * (256-pixel tiles, eight waves), 4 conv3x3_i8_halo, 5 / 6 conv2d_i8_dma with a ring of 2 / 3, 7 / 8 / 9 conv2d_i8_kernel
  * (C % 128 / C = 64 / general path), 10 stem_conv_i8, 11 block_tail_i8 (fq_block_tail_i8), 12 the same with the projection
  * shortcut computed in the kernel (fq_block_tail_proj_i8), 13 linear_i8_wave (a linear layer, one wave per 32 x 32 tile), 14 dwconv_i8
- * (fq_dwconv2d_i8_resident, a depthwise layer), 0 nothing launched; bits 8-15: output-channel
+ * (fq_dwconv2d_i8_resident, a depthwise layer), 15 gconv_i8 (fq_gconv2d_i8_resident, a grouped layer), 0 nothing launched; bits
+ * 8-15: output-channel
  * tile (64 / 128).  Lets a test assert that the dispatch it checked against a golden is the dispatch a benchmark timed. */
 int fq_conv2d_i8_last_variant(void);
 
@@ -569,6 +570,38 @@ int fq_dwconv2d_i8_resident(const int8_t* x_nhwc, const int8_t* w_rsc, const flo
 int fq_dwconv2d_i8_resident_pcs(const int8_t* x_nhwc, const int8_t* w_rsc, const float* qbias, const int32_t* rs_k, int rs_min,
                                 int rs_max, int8_t* q_nhwc, int Cpad, int relu, int N, int H, int W, int C, int R, int S,
                                 int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int ob, fq_stream_t stream);
+
+/* Grouped convolution (nn.Conv2d with 1 < groups < channels: the 3x3 of a ResNeXt / RegNet block, the grouped 1x1 of a
+ * ShuffleNet) on a resident activation.  G = groups, Cgi = C / G input and Cgo = K / G output channels per group:
+ *   acc[n][k][p][q] = sum_{r,s} sum_{j < Cgi} w[k][j][r][s] * x[n][p*stride_h - pad_h + r][q*stride_w - pad_w + s][(k / Cgo)*Cgi + j]
+ *                     (int32, exact)
+ *   q_nhwc          = clamp(RightShift(acc, rs) + qbias[k])     (= fq_conv2d_i8_resident's q_nhwc; ReLU fused when relu != 0)
+ * x_nhwc int8 [N][H][W][Cpad], Cpad = pad16(C); q_nhwc int8 [N][P][Q][Kpad], Kpad = pad16(K); both 16-byte aligned.  Channels
+ *   [K, Kpad) of q_nhwc are written as zeros whatever x holds; channels [C, Cpad) of x are never read.
+ * w_pack int8, Kpad * R * S * Cgi bytes, 16-byte aligned, in units of 16 bytes.  Unit ((kq * R*S + r*S + s) * (Cgi / 4) + j4),
+ *   kq < Kpad / 4, j4 < Cgi / 4, holds 4 output x 4 input channels of one tap: byte 4 * i + c of the unit is
+ *   w[4 * kq + i][4 * j4 + c][r][s] (w the layer's [K][Cgi][R][S] weights; i, c < 4), and zero for 4 * kq + i >= K.
+ * qbias fp32 [K], integer valued, of any magnitude (saturation as in fq_conv2d_i8).  ob: the output grid, as in
+ *   fq_conv2d_i8_resident (the integers do not depend on it).  Only int8 NHWC is written; a caller that needs fp32 NCHW follows
+ *   with fq_dequant_nhwc_to_nchw(q_nhwc, 1, ob, ...).
+ * fq_gconv2d_i8_supported (host arithmetic only): 1 for groups >= 2, C % groups == 0, K % groups == 0, Cgi and Cgo multiples
+ *   of 4 in [4, 64], R == S in {1, 3}, stride_h == stride_w in {1, 2}, dilation 1 and every shift in [1, 16] (the integer tail of
+ *   fq_int_tail.h only; |acc| <= 9 * 64 * 128 * 128 < 2^24 by construction, which is also why the fp32 grouped convolution of the
+ *   default form is exact on the same operands).  The entry points also need pad_h < R, pad_w < S, N*H*W*Cpad < 2^31,
+ *   N*P*Q*Kpad < 2^30 and Kpad <= 32768, and return FQ_ERR_UNSUPPORTED otherwise (depthwise and dense layers included): callers
+ *   keep the fp32 grouped convolution + fq_recon_epilogue there, which compute the same integers.  FQ_ERR_INVALID_ARG: a null or
+ *   misaligned pointer, a non-positive size, Cpad != pad16(C) or Kpad != pad16(K), C or K not divisible by groups.  N == 0 is FQ_OK.
+ * _pcs: one shift per output channel, rs_k device int32[K], 16-byte aligned, rs_min <= rs_k[k] <= rs_max; a constant vector gives
+ *   the bytes of the per-tensor entry point.  fq_conv2d_i8_last_variant: 15. */
+int fq_gconv2d_i8_supported(int C, int K, int groups, int R, int S, int stride_h, int stride_w, int dil_h, int dil_w, int rs_min,
+                            int rs_max);
+int fq_gconv2d_i8_resident(const int8_t* x_nhwc, const int8_t* w_pack, const float* qbias, int8_t* q_nhwc, int Cpad, int Kpad,
+                           int relu, int N, int H, int W, int C, int K, int groups, int R, int S, int stride_h, int stride_w,
+                           int pad_h, int pad_w, int dil_h, int dil_w, int rs, int ob, fq_stream_t stream);
+int fq_gconv2d_i8_resident_pcs(const int8_t* x_nhwc, const int8_t* w_pack, const float* qbias, const int32_t* rs_k, int rs_min,
+                               int rs_max, int8_t* q_nhwc, int Cpad, int Kpad, int relu, int N, int H, int W, int C, int K,
+                               int groups, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                               int ob, fq_stream_t stream);
 
 /* Channel concatenation (the Concat marker layer, torch.cat along dim 1) and nearest upsampling (nn.UpsamplingNearest2d with an
  * integer factor) of resident int8 NHWC activations that share ONE grid: moving the integers is concatenating the values, and

@@ -214,6 +214,12 @@ def lib():
     L.fq_dwconv2d_i8_resident.argtypes = [vp, vp, vp, vp] + [ci] * 16 + [vp]
     L.fq_dwconv2d_i8_resident_pcs.restype = ci
     L.fq_dwconv2d_i8_resident_pcs.argtypes = [vp, vp, vp, vp, ci, ci, vp] + [ci] * 15 + [vp]
+    L.fq_gconv2d_i8_supported.restype = ci
+    L.fq_gconv2d_i8_supported.argtypes = [ci] * 11
+    L.fq_gconv2d_i8_resident.restype = ci
+    L.fq_gconv2d_i8_resident.argtypes = [vp, vp, vp, vp] + [ci] * 19 + [vp]
+    L.fq_gconv2d_i8_resident_pcs.restype = ci
+    L.fq_gconv2d_i8_resident_pcs.argtypes = [vp, vp, vp, vp, ci, ci, vp] + [ci] * 18 + [vp]
     L.fq_dwconv_f32_supported.restype = ci
     L.fq_dwconv_f32_supported.argtypes = [ci] * 11
     L.fq_dwconv_f32.restype = ci
@@ -1090,7 +1096,8 @@ def pack_weight_krsc(w, cpad=None):
 # Which integer-convolution kernels ran (fq_conv2d_i8_last_variant): set conv_variant_log = {} and every call below counts its
 # kernel there by name -- tests and bench.py assert with it that the dispatch they checked is the dispatch they time.
 CONV_VARIANTS = {0: "none", 1: "c64_halo", 2: "stream", 3: "halo8", 4: "halo", 5: "dma2", 6: "dma3", 7: "tile_c128", 8: "tile_c64",
-                 9: "tile_general", 10: "stem", 11: "block_tail", 12: "block_tail_proj", 13: "linear_wave", 14: "depthwise"}
+                 9: "tile_general", 10: "stem", 11: "block_tail", 12: "block_tail_proj", 13: "linear_wave", 14: "depthwise",
+                 15: "grouped"}
 conv_variant_log = None
 
 
@@ -1249,6 +1256,61 @@ def dwconv2d_i8_resident(xq, wq, qbias, stride, padding, rs, ob, relu):
         _check(lib().fq_dwconv2d_i8_resident(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), q.data_ptr(), cpad,
                                              1 if relu else 0, N, H, W, C, R, S, stride[0], stride[1], padding[0], padding[1], 1, 1,
                                              int(rs), int(ob), _stream(xq)), "fq_dwconv2d_i8_resident")
+    _note_variant()
+    return q
+
+
+def gconv_supported(C, K, groups, R, S, stride, dilation, rs):
+    """True when fq_gconv2d_i8_resident takes a grouped layer of this geometry and shift (include/fq.h): groups >= 2, 4 .. 64
+    input and output channels per group in multiples of 4, 1x1 / 3x3, stride 1 / 2 on both axes, dilation 1, every shift in
+    [1, 16].  Never true for a dense or a depthwise layer.  Pure host arithmetic (no GPU needed); rs: an int or a ShiftVec."""
+    lo, hi = _bounds(rs)
+    return bool(lib().fq_gconv2d_i8_supported(int(C), int(K), int(groups), int(R), int(S), int(stride[0]), int(stride[1]),
+                                              int(dilation[0]), int(dilation[1]), lo, hi))
+
+
+def pack_weight_grouped(w, groups, kpad=None):
+    """Integer-valued fp32 grouped weights [K, Cgi, R, S] -> int8 [Kpad / 4, R * S, Cgi / 4, 4, 4] for fq_gconv2d_i8_resident:
+    16-byte units of 4 output x 4 input channels of one tap, output quads outermost; output channels [K, Kpad) zero."""
+    K, cgi, R, S = w.shape
+    assert groups >= 2 and K % groups == 0 and K % 4 == 0 and cgi % 4 == 0, "grouped weights are [K, C / groups, R, S]"
+    kpad = pad16(K) if kpad is None else int(kpad)
+    full = torch.zeros(kpad, cgi, R, S, dtype=torch.int8, device=w.device)
+    full[:K] = w.to(torch.int8)
+    # [kq, i, j4, c, r, s] -> [kq, r, s, j4, i, c]
+    out = full.reshape(kpad // 4, 4, cgi // 4, 4, R, S).permute(0, 4, 5, 2, 1, 3)
+    return out.reshape(kpad // 4, R * S, cgi // 4, 4, 4).contiguous()
+
+
+def gconv2d_i8_resident(xq, wq, qbias, K, groups, stride, padding, rs, ob, relu):
+    """fq_gconv2d_i8_resident: xq int8 [N,H,W,Cpad], wq int8 (pack_weight_grouped), qbias fp32 [K]; returns q int8
+    [N,P,Q,Kpad], the integers before DeQuantity(ob) with the ReLU folded in.  The input channel count is groups * Cgi, Cgi
+    read off wq, as is the (square) kernel's size.  rs: an int, or a ShiftVec (the _pcs entry point)."""
+    _need_cuda(xq, torch.int8, "fq_gconv2d_i8_resident")
+    _need_cuda(wq, torch.int8, "fq_gconv2d_i8_resident")
+    _need_cuda(qbias, torch.float32, "fq_gconv2d_i8_resident")
+    N, H, W, cpad = xq.shape
+    kq, taps, ch = wq.shape[0], wq.shape[1], wq.shape[2]
+    K, groups = int(K), int(groups)
+    C = groups * ch * 4
+    kpad = pad16(K)
+    R = int(round(taps ** 0.5))
+    assert xq.is_contiguous() and wq.is_contiguous() and kq * 4 == kpad and qbias.numel() == K and R * R == taps
+    P = (H + 2 * padding[0] - R) // stride[0] + 1
+    Q = (W + 2 * padding[1] - R) // stride[1] + 1
+    if P <= 0 or Q <= 0:
+        raise FqError("fq_gconv2d_i8_resident: the kernel does not fit the padded image")
+    q = torch.empty(N, P, Q, kpad, dtype=torch.int8, device=xq.device)
+    if isinstance(rs, ShiftVec):
+        rk = _shift_vec(rs, K, xq.device, "fq_gconv2d_i8_resident_pcs")
+        _check(lib().fq_gconv2d_i8_resident_pcs(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi,
+                                                q.data_ptr(), cpad, kpad, 1 if relu else 0, N, H, W, C, K, groups, R, R,
+                                                stride[0], stride[1], padding[0], padding[1], 1, 1, int(ob), _stream(xq)),
+               "fq_gconv2d_i8_resident_pcs")
+    else:
+        _check(lib().fq_gconv2d_i8_resident(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), q.data_ptr(), cpad, kpad,
+                                            1 if relu else 0, N, H, W, C, K, groups, R, R, stride[0], stride[1], padding[0],
+                                            padding[1], 1, 1, int(rs), int(ob), _stream(xq)), "fq_gconv2d_i8_resident")
     _note_variant()
     return q
 

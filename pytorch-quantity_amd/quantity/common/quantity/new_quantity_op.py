@@ -181,6 +181,10 @@ class _IntegerSimLayer(nn.Module):
     # reference-shaped form below (Quantity -> grouped fp32 convolution -> tail).  Same fp32 tensor, bit for bit.  Off by default;
     # settable per instance; resident.enable(..., depthwise=True) plans such layers as integer producers / consumers.
     use_depthwise_i8 = False
+    # True: a grouped nn.Conv2d (1 < groups < channels, 4 .. 64 channels per group in multiples of 4, 1x1 / 3x3) runs on
+    # fq_gconv2d_i8_resident instead of the reference-shaped form below.  Same fp32 tensor, bit for bit.  Off by default;
+    # settable per instance; resident.enable(..., grouped=True) plans such layers as integer producers / consumers.
+    use_grouped_i8 = False
 
     def _int8_ok(self, layer):
         if not self.use_int8_mfma or QUANTIZE_BIT != 8:
@@ -203,6 +207,30 @@ class _IntegerSimLayer(nn.Module):
         if layer.padding[0] >= k[0] or layer.padding[1] >= k[1]:
             return False
         return _native.dwconv_supported(layer.out_channels, k[0], k[1], layer.stride, layer.dilation, self._rs())
+
+    def _grouped_ok(self, layer, switch=None):
+        """True when `layer` is a grouped convolution that fq_gconv2d_i8_resident takes: the switch (use_grouped_i8, or the
+        caller's `switch`), QUANTIZE_BIT == 8, zero padding given as numbers and below the kernel size, and the kernel's own
+        limits on groups, widths, geometry and shift (_native.gconv_supported).  Never true for a depthwise or dense layer."""
+        if not (self.use_grouped_i8 if switch is None else switch) or QUANTIZE_BIT != 8:
+            return False
+        if not isinstance(layer, nn.Conv2d) or layer.padding_mode != "zeros" or isinstance(layer.padding, str):
+            return False
+        k = layer.kernel_size
+        if layer.groups < 2 or layer.padding[0] >= k[0] or layer.padding[1] >= k[1]:
+            return False
+        return _native.gconv_supported(layer.in_channels, layer.out_channels, layer.groups, k[0], k[1], layer.stride,
+                                       layer.dilation, self._rs())
+
+    def _grouped_weight(self, layer):
+        """Weights packed for fq_gconv2d_i8_resident, cached like _packed_weight."""
+        w = layer.weight
+        cached = getattr(self, "_w_gc", None)
+        if cached is None or cached[0] != (w.data_ptr(), w._version, str(w.device)):
+            object.__setattr__(self, "_w_gc", ((w.data_ptr(), w._version, str(w.device)),
+                                               _native.pack_weight_grouped(w.detach(), layer.groups)))
+            cached = self._w_gc
+        return cached[1]
 
     def _dw_weight(self, layer):
         """Weights packed for fq_dwconv2d_i8_resident, cached like _packed_weight."""
@@ -245,6 +273,7 @@ class _IntegerSimLayer(nn.Module):
         state.pop("_w_i8", None)                  # derived data: rebuilt on first forward after loading
         state.pop("_w_stem", None)
         state.pop("_w_dw", None)
+        state.pop("_w_gc", None)
         return state
 
     def _setup(self, layer, quantize_infor, out_count, wide_weights):
@@ -307,6 +336,8 @@ class NewConv2d(_IntegerSimLayer):
         dw_plan = self.__dict__.get("_resident")
         if (dw_plan is not None and dw_plan.depthwise) or self._depthwise_ok(conv):
             return self._forward_depthwise(conv, input, dw_plan)
+        if (dw_plan is not None and dw_plan.grouped) or self._grouped_ok(conv):
+            return self._forward_grouped(conv, input, dw_plan)
         if self._int8_ok(conv):
             wq = self._packed_weight(conv)
             plan = self.__dict__.get("_resident")         # set by common.quantity.resident.enable()
@@ -362,6 +393,27 @@ class NewConv2d(_IntegerSimLayer):
             xq = _xq_cache.get(as_f32(input), self.input_bit, wq.shape[-1])
         relu = plan is not None and plan.relu
         q = _native.dwconv2d_i8_resident(xq, wq, self.quantized_bias, conv.stride, conv.padding, self._rs(), self.output_bit, relu)
+        handle = QHandle((q.shape[0], conv.out_channels, q.shape[1], q.shape[2]), q, self.output_bit, q, self.output_bit, relu)
+        if plan is not None and not plan.emit_f32:
+            return handle
+        y = handle.to_f32()
+        if plan is not None and plan.emit_int:
+            carry(y, handle)
+        if relu:
+            y._fq_relu_done = True
+        return y
+
+    def _forward_grouped(self, conv, input, plan):
+        """A grouped layer on fq_gconv2d_i8_resident: int8 NHWC in (the producer's bytes, or Quantity + repack of an fp32
+        tensor), int8 NHWC out; fp32 NCHW, where somebody needs it, through the de-quantising transpose."""
+        wq = self._grouped_weight(conv)
+        cpad = _native.pad16(conv.in_channels)
+        xq = self._resident_input(input, cpad)
+        if xq is None:
+            xq = _xq_cache.get(as_f32(input), self.input_bit, cpad)
+        relu = plan is not None and plan.relu
+        q = _native.gconv2d_i8_resident(xq, wq, self.quantized_bias, conv.out_channels, conv.groups, conv.stride, conv.padding,
+                                        self._rs(), self.output_bit, relu)
         handle = QHandle((q.shape[0], conv.out_channels, q.shape[1], q.shape[2]), q, self.output_bit, q, self.output_bit, relu)
         if plan is not None and not plan.emit_f32:
             return handle

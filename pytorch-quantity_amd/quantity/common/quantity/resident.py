@@ -141,7 +141,7 @@ def as_f32(x):
 class Plan(object):
     """What one producer emits.  Plain data (pickles with the module)."""
     __slots__ = ("relu", "emit_f32", "emit_int", "narrow_bit", "want_wide", "grid", "resident_add", "defer", "fuse_arg",
-                 "fuse_next", "narrow_to_hbm", "fuse_proj", "depthwise", "up")
+                 "fuse_next", "narrow_to_hbm", "fuse_proj", "depthwise", "up", "grouped")
 
     def __init__(self):
         self.relu = False            # the nn.ReLU that consumes this output is fused
@@ -158,6 +158,7 @@ class Plan(object):
         self.fuse_proj = False       # NewAdd with fuse_arg: the OTHER operand is a deferred 1x1 projection that the kernel computes too
         self.depthwise = False       # NewConv2d: a depthwise layer taken by enable(depthwise=True); runs on fq_dwconv2d_i8_resident
         self.up = None               # nearest upsampling taken by enable(concat=True): its factor (with `defer`: the Concat applies it)
+        self.grouped = False         # NewConv2d: a grouped layer taken by enable(grouped=True); runs on fq_gconv2d_i8_resident
 
     def __getstate__(self):
         return {k: getattr(self, k) for k in self.__slots__}
@@ -497,7 +498,7 @@ def is_enabled(model):
     return bool(model.__dict__.get("_fq_resident_enabled"))
 
 
-def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False):
+def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False, grouped=False):
     """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
     on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
     nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
@@ -521,7 +522,11 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
     leave as fp32 for it.  Its value has no exact integer form and is handed to those convolutions only.  Left in fp32 form (out
     of scope): a NewAdd sum (int16) as the source, consumers that are not all convolutions at one bit, ceil_mode,
     divisor_override, windows above 64 taps, |bit - grid| > 8, a pool called twice; F.avg_pool2d and nn.AdaptiveAvgPool2d stay
-    foreign.  The whole-plane pool in front of the head is served as before.  The summary then gains `resident_avgpools`."""
+    foreign.  The whole-plane pool in front of the head is served as before.  The summary then gains `resident_avgpools`.
+    `grouped=True` also plans grouped NewConv2d layers (1 < groups < channels, 4 .. 64 input and output channels per group in
+    multiples of 4, 1x1 / 3x3, stride 1 / 2, shift in [1, 16]: NewConv2d._grouped_ok) as integer producers and consumers, served
+    by fq_gconv2d_i8_resident.  Such a layer is never run inside a NewAdd's kernel; an add reads its integers like any other
+    operand.  Without the argument they stay fp32 producers.  The summary then counts them as `resident_grouped`."""
     from .new_quantity_op import NewConv2d, NewLinear, NewAdd, QUANTIZE_BIT
     from .fabu_layer import Concat
     _clear(model)
@@ -567,11 +572,16 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
         return (bool(depthwise) and isinstance(m, NewConv2d) and tracer.calls.get(m, 0) == 1
                 and m._depthwise_ok(m.Conv, True))
 
+    def is_gc(m):
+        """A grouped layer that this plan runs on fq_gconv2d_i8_resident (called once, like every producer of the plan)."""
+        return (bool(grouped) and isinstance(m, NewConv2d) and tracer.calls.get(m, 0) == 1
+                and m._grouped_ok(m.Conv, True))
+
     def conv_can_emit(m):
-        return isinstance(m, NewConv2d) and tracer.calls.get(m, 0) == 1 and (m._int8_ok(m.Conv) or is_dw(m))
+        return isinstance(m, NewConv2d) and tracer.calls.get(m, 0) == 1 and (m._int8_ok(m.Conv) or is_dw(m) or is_gc(m))
 
     def conv_can_read(m):
-        return isinstance(m, NewConv2d) and ((m._int8_ok(m.Conv) and not m._stem_fold(m.Conv)) or is_dw(m))
+        return isinstance(m, NewConv2d) and ((m._int8_ok(m.Conv) and not m._stem_fold(m.Conv)) or is_dw(m) or is_gc(m))
 
     # pass 1 (execution order): integer format of every produced value
     fmt = {}                         # id(effective _Value) -> (bytes, grid)
@@ -658,6 +668,8 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
         summary["resident_concats"] = summary["resident_upsamples"] = 0
     if avgpool:
         summary["resident_avgpools"] = 0
+    if grouped:
+        summary["resident_grouped"] = 0
     for v in tracer.produced:
         m = v.producer
         e, relu_mod = eff_of[id(v)]
@@ -715,6 +727,9 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
         if v.kind == "contraction" and is_dw(m):
             plan.depthwise = True
             summary["resident_depthwise"] += 1
+        if v.kind == "contraction" and is_gc(m):
+            plan.grouped = True
+            summary["resident_grouped"] += 1
         m.__dict__["_resident"] = plan
         if plan.relu:
             relu_mod.__dict__["forward"] = _ReluPassThrough(relu_mod)
@@ -737,7 +752,7 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
             v = ops[pos]
             conv = v.producer
             plan = conv.__dict__.get("_resident") if isinstance(conv, NewConv2d) else None
-            if (v.kind == "contraction" and plan is not None and not plan.depthwise and not plan.relu and not plan.emit_f32
+            if (v.kind == "contraction" and plan is not None and not plan.depthwise and not plan.grouped and not plan.relu and not plan.emit_f32
                     and not v.foreign and v.consumers == [(add_mod, pos)] and ops[1 - pos] is not v
                     and not add_mod.__dict__["_resident"].emit_f32):
                 plan.defer = True
@@ -762,7 +777,7 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
         for c in readers:
             cp = c.__dict__.get("_resident")
             k = c.Conv
-            if (cp is not None and not cp.defer and cp.emit_int and not cp.emit_f32 and tracer.calls.get(c, 0) == 1
+            if (cp is not None and not cp.defer and not cp.grouped and cp.emit_int and not cp.emit_f32 and tracer.calls.get(c, 0) == 1
                     and tuple(k.kernel_size) == (1, 1) and tuple(k.stride) == (1, 1) and tuple(k.padding) == (0, 0)
                     and tuple(conv3.Conv.kernel_size) == (1, 1) and tuple(conv3.Conv.stride) == (1, 1)
                     and tuple(conv3.Conv.padding) == (0, 0) and c.input_bit == plan.narrow_bit
@@ -788,7 +803,7 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
         v3, vp = ops[plan.fuse_arg], ops[1 - plan.fuse_arg]
         conv3, proj = v3.producer, vp.producer
         pp = proj.__dict__.get("_resident") if isinstance(proj, NewConv2d) else None
-        if (vp.kind != "contraction" or pp is None or pp.relu or pp.emit_f32 or pp.defer or vp.foreign
+        if (vp.kind != "contraction" or pp is None or pp.relu or pp.emit_f32 or pp.defer or pp.grouped or vp.foreign
                 or vp.consumers != [(add_mod, 1 - plan.fuse_arg)] or not conv_can_read(proj) or tracer.calls.get(proj, 0) != 1):
             continue
         k3, kp = conv3.Conv, proj.Conv
