@@ -21,7 +21,7 @@ import torch
 from torch import nn
 
 from . import _native, _float_conv
-from .resident import QHandle, DeferredConv, resident_of, as_f32, carry
+from .resident import QHandle, DeferredConv, resident_of, as_f32, block_tail_enabled, _emit
 
 QUANTIZE_BIT = 8
 
@@ -167,6 +167,46 @@ class _QuantizedInputCache(object):
 _xq_cache = _QuantizedInputCache()
 
 
+def _own_kernel_candidate(layer, switch):
+    """What _depthwise_ok and _grouped_ok ask before the kernel's own rule: the switch, QUANTIZE_BIT == 8, an nn.Conv2d with zero
+    padding given as numbers and smaller than the kernel size."""
+    if not switch or QUANTIZE_BIT != 8:
+        return False
+    if not isinstance(layer, nn.Conv2d) or layer.padding_mode != "zeros" or isinstance(layer.padding, str):
+        return False
+    return layer.padding[0] < layer.kernel_size[0] and layer.padding[1] < layer.kernel_size[1]
+
+
+# Weights as a kernel reads them, cached on the integer layer by _IntegerSimLayer._packed: attribute -> what packs it
+_WEIGHT_SLOTS = ("_w_i8", "_w_stem", "_w_dw", "_w_gc")
+
+
+def _pack_dense(layer):                     # _w_i8: fq_conv2d_i8 and its kin (a stem-like layer: its width folded into the channels)
+    fold = _IntegerSimLayer._stem_fold(layer)
+    return _native.pack_weight_unfold_w(layer.weight.detach(), fold) if fold else _native.pack_weight_krsc(layer.weight.detach())
+
+
+def _pack_stem(layer):                      # _w_stem: fq_conv2d_i8_stem (one kernel for the whole stem layer)
+    return _native.pack_weight_stem(layer.weight.detach())
+
+
+def _pack_depthwise(layer):                 # _w_dw: fq_dwconv2d_i8_resident
+    return _native.pack_weight_dw(layer.weight.detach())
+
+
+def _pack_grouped(layer):                   # _w_gc: fq_gconv2d_i8_resident
+    return _native.pack_weight_grouped(layer.weight.detach(), layer.groups)
+
+
+def _launch_depthwise(self, conv, xq, wq, relu):
+    return _native.dwconv2d_i8_resident(xq, wq, self.quantized_bias, conv.stride, conv.padding, self._rs(), self.output_bit, relu)
+
+
+def _launch_grouped(self, conv, xq, wq, relu):
+    return _native.gconv2d_i8_resident(xq, wq, self.quantized_bias, conv.out_channels, conv.groups, conv.stride, conv.padding,
+                                       self._rs(), self.output_bit, relu)
+
+
 class _IntegerSimLayer(nn.Module):
     """Shared body of NewConv2d / NewLinear: Quantity -> integer contraction -> fused tail.
 
@@ -197,49 +237,22 @@ class _IntegerSimLayer(nn.Module):
         """True when `layer` is a depthwise convolution that fq_dwconv2d_i8_resident takes: the switch (use_depthwise_i8, or the
         caller's `switch`), QUANTIZE_BIT == 8, groups == in_channels == out_channels, zero padding given as numbers, and the
         kernel's own limits on geometry and shift (_native.dwconv_supported, padding below the kernel size)."""
-        if not (self.use_depthwise_i8 if switch is None else switch) or QUANTIZE_BIT != 8:
-            return False
-        if not isinstance(layer, nn.Conv2d) or layer.padding_mode != "zeros" or isinstance(layer.padding, str):
+        if not _own_kernel_candidate(layer, self.use_depthwise_i8 if switch is None else switch):
             return False
         if not (layer.groups == layer.in_channels == layer.out_channels) or layer.groups < 1:
             return False
         k = layer.kernel_size
-        if layer.padding[0] >= k[0] or layer.padding[1] >= k[1]:
-            return False
         return _native.dwconv_supported(layer.out_channels, k[0], k[1], layer.stride, layer.dilation, self._rs())
 
     def _grouped_ok(self, layer, switch=None):
         """True when `layer` is a grouped convolution that fq_gconv2d_i8_resident takes: the switch (use_grouped_i8, or the
         caller's `switch`), QUANTIZE_BIT == 8, zero padding given as numbers and below the kernel size, and the kernel's own
         limits on groups, widths, geometry and shift (_native.gconv_supported).  Never true for a depthwise or dense layer."""
-        if not (self.use_grouped_i8 if switch is None else switch) or QUANTIZE_BIT != 8:
-            return False
-        if not isinstance(layer, nn.Conv2d) or layer.padding_mode != "zeros" or isinstance(layer.padding, str):
+        if not _own_kernel_candidate(layer, self.use_grouped_i8 if switch is None else switch) or layer.groups < 2:
             return False
         k = layer.kernel_size
-        if layer.groups < 2 or layer.padding[0] >= k[0] or layer.padding[1] >= k[1]:
-            return False
         return _native.gconv_supported(layer.in_channels, layer.out_channels, layer.groups, k[0], k[1], layer.stride,
                                        layer.dilation, self._rs())
-
-    def _grouped_weight(self, layer):
-        """Weights packed for fq_gconv2d_i8_resident, cached like _packed_weight."""
-        w = layer.weight
-        cached = getattr(self, "_w_gc", None)
-        if cached is None or cached[0] != (w.data_ptr(), w._version, str(w.device)):
-            object.__setattr__(self, "_w_gc", ((w.data_ptr(), w._version, str(w.device)),
-                                               _native.pack_weight_grouped(w.detach(), layer.groups)))
-            cached = self._w_gc
-        return cached[1]
-
-    def _dw_weight(self, layer):
-        """Weights packed for fq_dwconv2d_i8_resident, cached like _packed_weight."""
-        w = layer.weight
-        cached = getattr(self, "_w_dw", None)
-        if cached is None or cached[0] != (w.data_ptr(), w._version, str(w.device)):
-            object.__setattr__(self, "_w_dw", ((w.data_ptr(), w._version, str(w.device)), _native.pack_weight_dw(w.detach())))
-            cached = self._w_dw
-        return cached[1]
 
     @staticmethod
     def _stem_fold(layer):
@@ -249,31 +262,21 @@ class _IntegerSimLayer(nn.Module):
             return _native.pad16(layer.kernel_size[1] * layer.in_channels)
         return 0
 
-    def _packed_weight(self, layer):
+    def _packed(self, slot, layer, pack):
+        """pack(layer), the weights of `layer` as one kernel reads them, kept in the attribute `slot` (one of _WEIGHT_SLOTS)
+        for as long as layer.weight has the same storage, version and device."""
         w = layer.weight
-        cached = getattr(self, "_w_i8", None)
-        if cached is None or cached[0] != (w.data_ptr(), w._version, str(w.device)):
-            fold = self._stem_fold(layer)
-            packed = _native.pack_weight_unfold_w(w.detach(), fold) if fold else _native.pack_weight_krsc(w.detach())
-            object.__setattr__(self, "_w_i8", ((w.data_ptr(), w._version, str(w.device)), packed))
-            cached = self._w_i8
-        return cached[1]
-
-    def _stem_weight(self, layer):
-        """Weights packed for fq_conv2d_i8_stem (one kernel for the whole stem layer), cached like _packed_weight."""
-        w = layer.weight
-        cached = getattr(self, "_w_stem", None)
-        if cached is None or cached[0] != (w.data_ptr(), w._version, str(w.device)):
-            object.__setattr__(self, "_w_stem", ((w.data_ptr(), w._version, str(w.device)), _native.pack_weight_stem(w.detach())))
-            cached = self._w_stem
+        key = (w.data_ptr(), w._version, str(w.device))
+        cached = self.__dict__.get(slot)
+        if cached is None or cached[0] != key:
+            cached = (key, pack(layer))
+            object.__setattr__(self, slot, cached)
         return cached[1]
 
     def __getstate__(self):
         state = self.__dict__.copy()
-        state.pop("_w_i8", None)                  # derived data: rebuilt on first forward after loading
-        state.pop("_w_stem", None)
-        state.pop("_w_dw", None)
-        state.pop("_w_gc", None)
+        for slot in _WEIGHT_SLOTS:                # derived data: rebuilt on first forward after loading
+            state.pop(slot, None)
         return state
 
     def _setup(self, layer, quantize_infor, out_count, wide_weights):
@@ -333,25 +336,25 @@ class NewConv2d(_IntegerSimLayer):
         ready = getattr(input, "next_out", None) if type(input) is QHandle else None
         if ready is not None and ready[0] is self:        # the NewAdd that produced `input` ran this convolution in its kernel
             return ready[1]
-        dw_plan = self.__dict__.get("_resident")
-        if (dw_plan is not None and dw_plan.depthwise) or self._depthwise_ok(conv):
-            return self._forward_depthwise(conv, input, dw_plan)
-        if (dw_plan is not None and dw_plan.grouped) or self._grouped_ok(conv):
-            return self._forward_grouped(conv, input, dw_plan)
+        plan = self.__dict__.get("_resident")             # set by common.quantity.resident.enable()
+        if (plan is not None and plan.depthwise) or (self.use_depthwise_i8 and self._depthwise_ok(conv)):
+            wq = self._packed("_w_dw", conv, _pack_depthwise)
+            return self._forward_own_kernel(conv, input, plan, wq, wq.shape[-1], _launch_depthwise)
+        if (plan is not None and plan.grouped) or (self.use_grouped_i8 and self._grouped_ok(conv)):
+            return self._forward_own_kernel(conv, input, plan, self._packed("_w_gc", conv, _pack_grouped),
+                                            _native.pad16(conv.in_channels), _launch_grouped)
         if self._int8_ok(conv):
-            wq = self._packed_weight(conv)
-            plan = self.__dict__.get("_resident")         # set by common.quantity.resident.enable()
+            wq = self._packed("_w_i8", conv, _pack_dense)
             fold = self._stem_fold(conv)
             if (fold and plan is not None and plan.emit_int and not plan.emit_f32 and not plan.defer and self.use_stem_kernel
                     and _native.stem_supported(conv.in_channels, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1],
                                                conv.stride, conv.dilation, self._rs())):
                 # the whole layer in one kernel: fp32 image in, int8 NHWC out (no unfolded copy of the image)
                 x = as_f32(input)
-                q = _native.conv2d_i8_stem(x if x.is_contiguous() else x.contiguous(), self._stem_weight(conv),
+                q = _native.conv2d_i8_stem(x if x.is_contiguous() else x.contiguous(), self._packed("_w_stem", conv, _pack_stem),
                                            self.quantized_bias, conv.out_channels, conv.kernel_size[1], conv.stride,
                                            conv.padding, self.input_bit, self._rs(), self.output_bit, plan.relu)
-                return QHandle((q.shape[0], conv.out_channels, q.shape[1], q.shape[2]), q, self.output_bit, q,
-                               self.output_bit, plan.relu)
+                return QHandle.int8(q, conv.out_channels, self.output_bit, plan.relu)
             if fold:
                 input = as_f32(input)
                 xq = _native.quantize_i8_unfold_w(input, self.input_bit, conv.kernel_size[1], conv.stride[1],
@@ -369,60 +372,24 @@ class NewConv2d(_IntegerSimLayer):
                 return DeferredConv(self, xq, wq, geom)   # the resident NewAdd that consumes it runs it
             y, q = _native.conv2d_i8_resident(xq, wq, self.quantized_bias, geom[0], geom[1], geom[2], self._rs(),
                                               self.output_bit, plan.emit_f32, plan.emit_int, plan.relu)
-            handle = None
-            if q is not None:
-                handle = QHandle((q.shape[0], conv.out_channels, q.shape[1], q.shape[2]), q, self.output_bit, q,
-                                 self.output_bit, plan.relu)
-            if y is None:
-                return handle
-            if handle is not None:
-                carry(y, handle)
-            if plan.relu:
-                y._fq_relu_done = True
-            return y
+            if q is None:                                 # fp32 consumers only: the kernel wrote y and no integers
+                if plan.relu:
+                    y._fq_relu_done = True
+                return y
+            return _emit(plan, QHandle.int8(q, conv.out_channels, self.output_bit, plan.relu), y)     # (y: the kernel's own, or None)
         q = self.Quan(as_f32(input))
         acc = conv(q)               # integer-valued fp32 in, exact below 2^24 per partial sum
         return self._tail(acc)
 
-    def _forward_depthwise(self, conv, input, plan):
-        """A depthwise layer on fq_dwconv2d_i8_resident: int8 NHWC in (the producer's bytes, or Quantity + repack of an fp32
-        tensor), int8 NHWC out; fp32 NCHW, where somebody needs it, through the de-quantising transpose."""
-        wq = self._dw_weight(conv)
-        xq = self._resident_input(input, wq.shape[-1])
-        if xq is None:
-            xq = _xq_cache.get(as_f32(input), self.input_bit, wq.shape[-1])
-        relu = plan is not None and plan.relu
-        q = _native.dwconv2d_i8_resident(xq, wq, self.quantized_bias, conv.stride, conv.padding, self._rs(), self.output_bit, relu)
-        handle = QHandle((q.shape[0], conv.out_channels, q.shape[1], q.shape[2]), q, self.output_bit, q, self.output_bit, relu)
-        if plan is not None and not plan.emit_f32:
-            return handle
-        y = handle.to_f32()
-        if plan is not None and plan.emit_int:
-            carry(y, handle)
-        if relu:
-            y._fq_relu_done = True
-        return y
-
-    def _forward_grouped(self, conv, input, plan):
-        """A grouped layer on fq_gconv2d_i8_resident: int8 NHWC in (the producer's bytes, or Quantity + repack of an fp32
-        tensor), int8 NHWC out; fp32 NCHW, where somebody needs it, through the de-quantising transpose."""
-        wq = self._grouped_weight(conv)
-        cpad = _native.pad16(conv.in_channels)
+    def _forward_own_kernel(self, conv, input, plan, wq, cpad, launch):
+        """A depthwise or grouped layer on its own kernel (`launch`, over the weights wq): int8 NHWC with cpad channels in (the
+        producer's bytes, or Quantity + repack of an fp32 tensor), int8 NHWC out; fp32 NCHW, where somebody needs it, through
+        the de-quantising transpose."""
         xq = self._resident_input(input, cpad)
         if xq is None:
             xq = _xq_cache.get(as_f32(input), self.input_bit, cpad)
         relu = plan is not None and plan.relu
-        q = _native.gconv2d_i8_resident(xq, wq, self.quantized_bias, conv.out_channels, conv.groups, conv.stride, conv.padding,
-                                        self._rs(), self.output_bit, relu)
-        handle = QHandle((q.shape[0], conv.out_channels, q.shape[1], q.shape[2]), q, self.output_bit, q, self.output_bit, relu)
-        if plan is not None and not plan.emit_f32:
-            return handle
-        y = handle.to_f32()
-        if plan is not None and plan.emit_int:
-            carry(y, handle)
-        if relu:
-            y._fq_relu_done = True
-        return y
+        return _emit(plan, QHandle.int8(launch(self, conv, xq, wq, relu), conv.out_channels, self.output_bit, relu))
 
     def _resident_input(self, input, cpad):
         """int8 NHWC operand already in HBM (left by the producer), or None."""
@@ -447,7 +414,7 @@ class NewLinear(_IntegerSimLayer):
         lin = self.Linear
         input = as_f32(input)
         if self._int8_ok(lin) and input.dim() == 2:
-            wq = self._packed_weight(lin)
+            wq = self._packed("_w_i8", lin, _pack_dense)
             xq = _native.quantize_i8_nhwc(input, self.input_bit, wq.shape[-1])
             return _native.conv2d_i8(xq, wq, self.quantized_bias, (1, 1), (0, 0), (1, 1), self._rs(),
                                      self.output_bit, 8)
@@ -473,18 +440,10 @@ class NewAdd(nn.Module):
             hx, hy = resident_of(x), resident_of(y)
             if (hx is not None and hy is not None and hx.exact is not None and hy.exact is not None
                     and hx.exact.shape == hy.exact.shape and max(0, hx.grid, hy.grid) == plan.grid):
-                want_narrow = plan.emit_int and plan.narrow_bit is not None
-                wide, narrow = _native.add_resident(hx.exact, hx.grid, hy.exact, hy.grid, plan.want_wide or not want_narrow,
-                                                    plan.grid, want_narrow, plan.narrow_bit if want_narrow else 0, plan.relu)
-                handle = QHandle(hx.shape, wide, plan.grid, narrow, plan.narrow_bit, plan.relu)
-                if not plan.emit_f32:
-                    return handle
-                out = handle.to_f32()
-                if plan.emit_int:
-                    carry(out, handle)
-                if plan.relu:
-                    out._fq_relu_done = True
-                return out
+                want_wide, want_narrow = plan.sum_outputs()
+                wide, narrow = _native.add_resident(hx.exact, hx.grid, hy.exact, hy.grid, want_wide, plan.grid, want_narrow,
+                                                    plan.narrow_bit if want_narrow else 0, plan.relu)
+                return _emit(plan, QHandle(hx.shape, wide, plan.grid, narrow, plan.narrow_bit, plan.relu))
         out = _native.add_sat(as_f32(x), as_f32(y), self.Sp.bitwidth)
         if plan is not None and plan.relu:
             out = torch.relu_(out)                        # the ReLU module after this add passes through
@@ -493,10 +452,6 @@ class NewAdd(nn.Module):
 
 
 _BT_ALONE_MAX_C = int(os.environ.get("FQ_BT_ALONE_MAX_C", "64"))     # conv3 + NewAdd WITHOUT a next conv1 on fq_block_tail_i8 up to this width
-
-
-def _block_tail_on():
-    return os.environ.get("FQ_BLOCK_TAIL", "1") != "0"
 
 
 def _newadd_fused_conv_add(self, plan, x, y):
@@ -517,13 +472,11 @@ def _newadd_fused_conv_add(self, plan, x, y):
     L = d.layer
     if h is None or h.exact is None or max(0, L.output_bit, h.grid) != plan.grid or plan.emit_f32:
         return None
-    want_narrow = plan.emit_int and plan.narrow_bit is not None
-    want_wide = plan.want_wide or not want_narrow
+    want_wide, want_narrow = plan.sum_outputs()
     if h.exact.shape[0] != d.xq.shape[0] or h.exact.shape[-1] != _native.pad16(L.Conv.out_channels):
         return None
     nxt = plan.fuse_next
-    one = tuple(tuple(int(v) for v in g) for g in d.geom) == ((1, 1), (0, 0), (1, 1)) and tuple(d.wq.shape[1:3]) == (1, 1)
-    if (nxt is None and one and tuple(h.exact.shape[:3]) == tuple(d.xq.shape[:3]) and _block_tail_on()
+    if (nxt is None and d.pointwise() and tuple(h.exact.shape[:3]) == tuple(d.xq.shape[:3]) and block_tail_enabled()
             and d.xq.shape[-1] <= _BT_ALONE_MAX_C and L.Conv.out_channels == d.wq.shape[0]
             and _native.block_tail_supported(d.xq.shape[-1], L.Conv.out_channels, 0, L._rs(), 0, L.output_bit, h.grid, h.exact.element_size(),
                                              plan.narrow_bit if want_narrow else plan.grid - 1)):
@@ -533,77 +486,65 @@ def _newadd_fused_conv_add(self, plan, x, y):
         # Cache at these sizes and the general kernel's 3 workgroups per CU win there.
         wide, narrow, _ = _native.block_tail_i8(d.xq, d.wq, L.quantized_bias, L._rs(), L.output_bit, h.exact, h.grid, want_wide,
                                                 plan.grid, want_narrow, plan.narrow_bit if want_narrow else 0, plan.relu)
-        ref = wide if wide is not None else narrow
-        return QHandle((ref.shape[0], L.Conv.out_channels, ref.shape[1], ref.shape[2]), wide, plan.grid, narrow, plan.narrow_bit,
-                       plan.relu)
+        return QHandle.wide_narrow(L.Conv.out_channels, wide, plan.grid, narrow, plan.narrow_bit, plan.relu)
     if nxt is not None and want_narrow and want_wide and tuple(h.exact.shape[:3]) == tuple(d.xq.shape[:3]):
         # conv3 + NewAdd + the next block's conv1 in one kernel (fq_block_tail_i8): the re-quantised sum is that convolution's
         # operand, staged in LDS, and reaches HBM only if somebody else reads it too
         np_ = nxt.__dict__.get("_resident")
-        w1 = nxt._packed_weight(nxt.Conv)
+        w1 = nxt._packed("_w_i8", nxt.Conv, _pack_dense)
         if (np_ is not None and w1.shape[-1] == L.Conv.out_channels
                 and _native.block_tail_supported(d.xq.shape[-1], L.Conv.out_channels, nxt.Conv.out_channels, L._rs(), nxt._rs(),
                                                  L.output_bit, h.grid, h.exact.element_size(), plan.narrow_bit)):
             wide, narrow, q1 = _native.block_tail_i8(d.xq, d.wq, L.quantized_bias, L._rs(), L.output_bit, h.exact, h.grid, True,
                                                      plan.grid, plan.narrow_to_hbm, plan.narrow_bit, plan.relu, w1,
                                                      nxt.quantized_bias, nxt._rs(), np_.relu)
-            out = QHandle((wide.shape[0], L.Conv.out_channels, wide.shape[1], wide.shape[2]), wide, plan.grid, narrow,
-                          plan.narrow_bit, plan.relu)
-            out.next_out = (nxt, QHandle((q1.shape[0], nxt.Conv.out_channels, q1.shape[1], q1.shape[2]), q1, nxt.output_bit, q1,
-                                         nxt.output_bit, np_.relu))
+            out = QHandle.wide_narrow(L.Conv.out_channels, wide, plan.grid, narrow, plan.narrow_bit, plan.relu)
+            out.next_out = (nxt, QHandle.int8(q1, nxt.Conv.out_channels, nxt.output_bit, np_.relu))
             return out
     wide, narrow = _native.conv2d_i8_add_resident(d.xq, d.wq, L.quantized_bias, d.geom[0], d.geom[1], d.geom[2], L._rs(),
                                                   L.output_bit, h.exact, h.grid, want_wide, plan.grid, want_narrow,
                                                   plan.narrow_bit if want_narrow else 0, plan.relu)
-    ref = wide if wide is not None else narrow
-    return QHandle((ref.shape[0], L.Conv.out_channels, ref.shape[1], ref.shape[2]), wide, plan.grid, narrow, plan.narrow_bit,
-                   plan.relu)
+    return QHandle.wide_narrow(L.Conv.out_channels, wide, plan.grid, narrow, plan.narrow_bit, plan.relu)
 
 
 def _newadd_fused_conv_proj_add(self, plan, x, y):
     """The first block of a stage: conv3 -> add <- projection, (-> the next block's conv1), in ONE kernel (fq_block_tail_proj_i8)
     when both operands arrive as DeferredConvs and the plan says so; None otherwise."""
-    if not plan.fuse_proj or plan.fuse_arg is None or plan.emit_f32 or not _block_tail_on():
+    if not plan.fuse_proj or plan.fuse_arg is None or plan.emit_f32 or not block_tail_enabled():
         return None
     d, dp = (x, y) if plan.fuse_arg == 0 else (y, x)
     if d._handle is not None or dp._handle is not None:
         return None
     L, P = d.layer, dp.layer
-    one = lambda dd: tuple(tuple(int(v) for v in g) for g in dd.geom[1:]) == ((0, 0), (1, 1)) and tuple(dd.wq.shape[1:3]) == (1, 1)
-    sp = tuple(int(v) for v in dp.geom[0])
-    if (not one(d) or not one(dp) or tuple(int(v) for v in d.geom[0]) != (1, 1) or sp[0] != sp[1]
+    sp = int(dp.geom[0][0])                                # the projection's stride (square: pointwise(any_stride=True))
+    if (not d.pointwise() or not dp.pointwise(any_stride=True)
             or max(0, L.output_bit, P.output_bit) != plan.grid or d.xq.shape[0] != dp.xq.shape[0]
-            or (dp.xq.shape[1] - 1) // sp[0] + 1 != d.xq.shape[1] or (dp.xq.shape[2] - 1) // sp[0] + 1 != d.xq.shape[2]
+            or (dp.xq.shape[1] - 1) // sp + 1 != d.xq.shape[1] or (dp.xq.shape[2] - 1) // sp + 1 != d.xq.shape[2]
             or L.Conv.out_channels != d.wq.shape[0] or P.Conv.out_channels != dp.wq.shape[0] or d.wq.shape[0] != dp.wq.shape[0]):
         return None
-    want_narrow = plan.emit_int and plan.narrow_bit is not None
-    want_wide = plan.want_wide or not want_narrow
+    want_wide, want_narrow = plan.sum_outputs()
     nxt = plan.fuse_next
     np_ = nxt.__dict__.get("_resident") if nxt is not None else None
     if nxt is not None and (np_ is None or not want_narrow or not want_wide):
         return None
-    w1 = nxt._packed_weight(nxt.Conv) if nxt is not None else None
+    w1 = nxt._packed("_w_i8", nxt.Conv, _pack_dense) if nxt is not None else None
     if w1 is not None and w1.shape[-1] != L.Conv.out_channels:
         return None
     if not _native.block_tail_proj_supported(d.xq.shape[-1], L.Conv.out_channels, nxt.Conv.out_channels if nxt is not None else 0,
-                                             dp.xq.shape[-1], L._rs(), nxt._rs() if nxt is not None else 0, P._rs(), sp[0]):
+                                             dp.xq.shape[-1], L._rs(), nxt._rs() if nxt is not None else 0, P._rs(), sp):
         return None
     if nxt is not None:
         wide, narrow, q1 = _native.block_tail_proj_i8(d.xq, d.wq, L.quantized_bias, L._rs(), L.output_bit, dp.xq, dp.wq,
-                                                      P.quantized_bias, P._rs(), P.output_bit, sp[0], True, plan.grid,
+                                                      P.quantized_bias, P._rs(), P.output_bit, sp, True, plan.grid,
                                                       plan.narrow_to_hbm, plan.narrow_bit, plan.relu, w1, nxt.quantized_bias,
                                                       nxt._rs(), np_.relu)
-        out = QHandle((wide.shape[0], L.Conv.out_channels, wide.shape[1], wide.shape[2]), wide, plan.grid, narrow, plan.narrow_bit,
-                      plan.relu)
-        out.next_out = (nxt, QHandle((q1.shape[0], nxt.Conv.out_channels, q1.shape[1], q1.shape[2]), q1, nxt.output_bit, q1,
-                                     nxt.output_bit, np_.relu))
+        out = QHandle.wide_narrow(L.Conv.out_channels, wide, plan.grid, narrow, plan.narrow_bit, plan.relu)
+        out.next_out = (nxt, QHandle.int8(q1, nxt.Conv.out_channels, nxt.output_bit, np_.relu))
         return out
     wide, narrow, _ = _native.block_tail_proj_i8(d.xq, d.wq, L.quantized_bias, L._rs(), L.output_bit, dp.xq, dp.wq, P.quantized_bias,
-                                                 P._rs(), P.output_bit, sp[0], want_wide, plan.grid, want_narrow,
+                                                 P._rs(), P.output_bit, sp, want_wide, plan.grid, want_narrow,
                                                  plan.narrow_bit if want_narrow else 0, plan.relu)
-    ref = wide if wide is not None else narrow
-    return QHandle((ref.shape[0], L.Conv.out_channels, ref.shape[1], ref.shape[2]), wide, plan.grid, narrow, plan.narrow_bit,
-                   plan.relu)
+    return QHandle.wide_narrow(L.Conv.out_channels, wide, plan.grid, narrow, plan.narrow_bit, plan.relu)
 
 
 NewAdd._fused_conv_add = _newadd_fused_conv_add

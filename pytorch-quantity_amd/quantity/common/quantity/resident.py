@@ -20,6 +20,8 @@ The plan assumes a static dataflow (as a captured graph would).  Consumers stay 
 that unexpectedly receives fp32 quantises it as usual -- and a resident handle reaching code that
 is not part of the plan raises instead of computing garbage.
 """
+import os
+
 import torch
 from torch import nn
 from torch.overrides import TorchFunctionMode
@@ -45,6 +47,17 @@ class QHandle(object):
         # (consumer NewConv2d, its finished output handle): set by a NewAdd that ran that consumer inside its own kernel
         # (fq_block_tail_i8, Plan.fuse_next) -- the consumer hands it out instead of launching
         self.next_out = None
+
+    @classmethod
+    def int8(cls, q, channels, bit, relu_done):
+        """An int8 NHWC activation q = value * 2^bit: exact, and already what a convolution at that bit reads."""
+        return cls((q.shape[0], channels, q.shape[1], q.shape[2]), q, bit, q, bit, relu_done)
+
+    @classmethod
+    def wide_narrow(cls, channels, wide, grid, narrow, bit, relu_done):
+        """A sum: its exact integers on `grid` and / or its re-quantisation at `bit` (NHWC, at least one of the two)."""
+        ref = wide if wide is not None else narrow
+        return cls((ref.shape[0], channels, ref.shape[1], ref.shape[2]), wide, grid, narrow, bit, relu_done)
 
     def to_f32(self):
         """The fp32 NCHW tensor this handle stands for (DeQuantity + layout change, one kernel)."""
@@ -72,12 +85,14 @@ class DeferredConv(object):
             L = self.layer
             _, q = _native.conv2d_i8_resident(self.xq, self.wq, L.quantized_bias, self.geom[0], self.geom[1], self.geom[2],
                                               L._rs(), L.output_bit, False, True, False)
-            self._handle = QHandle((q.shape[0], L.Conv.out_channels, q.shape[1], q.shape[2]), q, L.output_bit, q, L.output_bit,
-                                   False)
+            self._handle = QHandle.int8(q, L.Conv.out_channels, L.output_bit, False)
         return self._handle
 
     def to_f32(self):
         return self.materialise().to_f32()
+
+    def pointwise(self, any_stride=False):
+        return _pointwise(self.wq.shape[1:3], self.geom[0], self.geom[1], any_stride) and _pair(self.geom[2]) == (1, 1)
 
 
 class DeferredUpsample(object):
@@ -93,7 +108,7 @@ class DeferredUpsample(object):
         if self._out is None:
             h = self.handle
             y = _native.concat_i8_nhwc([(h.exact, h.shape[1], self.s)], False)
-            self._out = QHandle((h.shape[0], h.shape[1], y.shape[1], y.shape[2]), y, h.grid, y, h.grid, h.relu_done)
+            self._out = QHandle.int8(y, h.shape[1], h.grid, h.relu_done)
         return self._out
 
     def to_f32(self):
@@ -101,14 +116,12 @@ class DeferredUpsample(object):
 
 
 def block_tail_enabled():
-    """FQ_BLOCK_TAIL=0: keep conv3 + add and the next conv1 as two launches (A/B timing)."""
-    import os
+    """FQ_BLOCK_TAIL=0: keep conv3 + add and the next conv1 as two launches (A/B timing).  Read at every call."""
     return os.environ.get("FQ_BLOCK_TAIL", "1") != "0"
 
 
 def block_tail_proj_enabled():
     """FQ_BLOCK_TAIL_PROJ=0: a stage's first block keeps its projection shortcut as a launch of its own (A/B timing)."""
-    import os
     return os.environ.get("FQ_BLOCK_TAIL_PROJ", "1") != "0"
 
 
@@ -168,15 +181,25 @@ class Plan(object):
         for k, v in state.items():
             setattr(self, k, v)
 
+    def sum_outputs(self):
+        """(want_wide, want_narrow) of a NewAdd's kernel: the re-quantisation where a convolution reads it, the exact sum where
+        somebody needs it or nothing else would be written."""
+        want_narrow = self.emit_int and self.narrow_bit is not None
+        return self.want_wide or not want_narrow, want_narrow
+
     def __repr__(self):
         return "Plan(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.__slots__)
 
 
-class _ReluPassThrough(object):
-    """Instance-level forward of an nn.ReLU whose producer already applied it."""
+class _InstanceForward(object):
+    """What enable() puts in a module's own `forward` attribute, in front of its class's method; disable() takes it out."""
 
     def __init__(self, module):
         self.module = module
+
+
+class _ReluPassThrough(_InstanceForward):
+    """Instance-level forward of an nn.ReLU whose producer already applied it."""
 
     def __call__(self, x):
         if type(x) is QHandle:
@@ -193,25 +216,31 @@ def _pair(v):
     return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
 
 
+def _pointwise(kernel, stride, padding, any_stride=False):
+    """A 1x1 convolution without padding at stride 1 -- or, with `any_stride` (a projection shortcut), at any square stride."""
+    st = _pair(stride)
+    return _pair(kernel) == (1, 1) and _pair(padding) == (0, 0) and (st[0] == st[1] if any_stride else st == (1, 1))
+
+
+def _pointwise_conv(k, any_stride=False):
+    return _pointwise(k.kernel_size, k.stride, k.padding, any_stride)
+
+
 def _maxpool_supported(m):
-    k, st, pd, dl = _pair(m.kernel_size), _pair(m.stride if m.stride is not None else m.kernel_size), _pair(m.padding), \
-        _pair(m.dilation)
-    return (dl == (1, 1) and not m.ceil_mode and not m.return_indices and 2 * pd[0] <= k[0] and 2 * pd[1] <= k[1]
+    k, st, pd = _pool_geometry(m)
+    return (_pair(m.dilation) == (1, 1) and not m.ceil_mode and not m.return_indices and 2 * pd[0] <= k[0] and 2 * pd[1] <= k[1]
             and min(st) >= 1)
 
 
 def _avgpool_is_global(m, h, w):
-    k = _pair(m.kernel_size)
-    return (k == (int(h), int(w)) and _pair(m.padding) == (0, 0) and not m.ceil_mode
-            and getattr(m, "divisor_override", None) is None)
+    """The pool covers the whole h x w plane, and a plane's sum of int16 values stays exact in fp32."""
+    return (_pair(m.kernel_size) == (int(h), int(w)) and _pair(m.padding) == (0, 0) and _avgpool_window_ok(m)
+            and h * w * 32768 < (1 << 24))
 
 
-class _MaxPoolResident(object):
+class _MaxPoolResident(_InstanceForward):
     """Instance-level forward of an nn.MaxPool2d between integer layers: pooling the int8 NHWC integers is
     pooling the values (max commutes with the monotone scale q -> q * 2^-g)."""
-
-    def __init__(self, module):
-        self.module = module
 
     def __call__(self, x):
         m = self.module
@@ -219,41 +248,27 @@ class _MaxPoolResident(object):
         h = resident_of(x)
         if plan is None or h is None or h.exact is None or h.exact.dtype != torch.int8 or not _maxpool_supported(m):
             return type(m).forward(m, as_f32(x))
-        k, st, pd = _pair(m.kernel_size), _pair(m.stride if m.stride is not None else m.kernel_size), _pair(m.padding)
-        y = _native.maxpool_i8_nhwc(h.exact, k, st, pd)
+        y = _native.maxpool_i8_nhwc(h.exact, *_pool_geometry(m))
         narrow = y if (h.narrow is h.exact or h.bit == h.grid) else None
-        out = QHandle((y.shape[0], h.shape[1], y.shape[1], y.shape[2]), y, h.grid, narrow, h.grid, h.relu_done)
-        if not plan.emit_f32:
-            return out
-        t = out.to_f32()
-        if plan.emit_int:
-            carry(t, out)
-        return t
+        return _emit(plan, QHandle.wide_narrow(h.shape[1], y, h.grid, narrow, h.grid, h.relu_done))
 
 
-class _AvgPoolResident(object):
+class _AvgPoolResident(_InstanceForward):
     """Instance-level forward of an nn.AvgPool2d that covers the whole plane of a resident activation."""
-
-    def __init__(self, module):
-        self.module = module
 
     def __call__(self, x):
         m = self.module
         h = resident_of(x)
-        if (h is not None and h.exact is not None and _avgpool_is_global(m, h.exact.shape[1], h.exact.shape[2])
-                and h.exact.shape[1] * h.exact.shape[2] * 32768 < (1 << 24)):
+        if h is not None and h.exact is not None and _avgpool_is_global(m, h.exact.shape[1], h.exact.shape[2]):
             return _native.avgpool_global_nhwc(h.exact, h.grid, h.shape[1])
         return type(m).forward(m, as_f32(x))
 
 
-class _AvgPoolWindowResident(object):
+class _AvgPoolWindowResident(_InstanceForward):
     """Instance-level forward of a windowed nn.AvgPool2d between an int8 activation and the convolution(s) behind it
     (enable(avgpool=True)): DeQuantity -> pool -> ReLU -> the consumers' Quantity in one kernel (fq_avgpool_i8_nhwc).  The result
     has no exact integer form: the handle carries the narrow payload only, and anything but a NewConv2d at that bit that touches it
     raises (QHandle.to_f32)."""
-
-    def __init__(self, module):
-        self.module = module
 
     def __call__(self, x):
         m = self.module
@@ -262,15 +277,15 @@ class _AvgPoolWindowResident(object):
         if (plan is None or plan.narrow_bit is None or plan.grid is None or h is None or h.exact is None
                 or h.exact.dtype != torch.int8 or h.exact.dim() != 4 or h.grid != plan.grid or not _avgpool_window_ok(m)):
             return type(m).forward(m, as_f32(x))
-        k, st, pd = _avgpool_geometry(m)
+        k, st, pd = _pool_geometry(m)
         hh, ww = int(h.exact.shape[1]), int(h.exact.shape[2])
         if (not _native.avgpool_supported(k, st, pd, plan.narrow_bit - h.grid) or hh + 2 * pd[0] < k[0] or ww + 2 * pd[1] < k[1]):
             return type(m).forward(m, as_f32(x))
         y = _native.avgpool_i8_nhwc(h.exact, h.shape[1], k, st, pd, m.count_include_pad, plan.narrow_bit - h.grid, plan.relu)
-        return QHandle((y.shape[0], h.shape[1], y.shape[1], y.shape[2]), None, None, y, plan.narrow_bit, plan.relu or h.relu_done)
+        return QHandle.wide_narrow(h.shape[1], None, None, y, plan.narrow_bit, plan.relu or h.relu_done)
 
 
-def _avgpool_geometry(m):
+def _pool_geometry(m):
     return _pair(m.kernel_size), _pair(m.stride if m.stride is not None else m.kernel_size), _pair(m.padding)
 
 
@@ -291,24 +306,25 @@ def _upsample_factor(m):
     return int(sf) if float(sf) in (2.0, 4.0) else None
 
 
-def _emit(plan, out):
-    """A finished integer activation as its consumers want it: the handle, or the fp32 tensor (carrying the handle)."""
-    if not plan.emit_f32:
+def _emit(plan, out, t=None):
+    """A finished integer activation as its consumers want it: the handle, or the fp32 tensor (carrying the handle where
+    somebody reads the integers too).  The only copy of this hand-off: every integer producer ends here.  plan None: a layer
+    switched per instance, outside a plan, hands out the plain fp32 tensor.  t: the fp32 tensor, where the producer's kernel
+    wrote it itself."""
+    if plan is not None and not plan.emit_f32:
         return out
-    t = out.to_f32()
-    if plan.emit_int:
+    if t is None:
+        t = out.to_f32()
+    if plan is not None and plan.emit_int:
         carry(t, out)
     if out.relu_done:
         t._fq_relu_done = True
     return t
 
 
-class _UpsampleResident(object):
+class _UpsampleResident(_InstanceForward):
     """Instance-level forward of a nearest upsampling between integer layers: repeating the int8 NHWC integers is repeating the
     values.  With plan.defer nothing runs here: the resident Concat that consumes it reads the small tensor (DeferredUpsample)."""
-
-    def __init__(self, module):
-        self.module = module
 
     def __call__(self, x):
         m = self.module
@@ -320,16 +336,13 @@ class _UpsampleResident(object):
         if plan.defer and not plan.relu:
             return DeferredUpsample(h, plan.up)
         y = _native.concat_i8_nhwc([(h.exact, h.shape[1], plan.up)], plan.relu)
-        return _emit(plan, QHandle((h.shape[0], h.shape[1], y.shape[1], y.shape[2]), y, h.grid, y, h.grid, plan.relu or h.relu_done))
+        return _emit(plan, QHandle.int8(y, h.shape[1], h.grid, plan.relu or h.relu_done))
 
 
-class _ConcatResident(object):
+class _ConcatResident(_InstanceForward):
     """Instance-level forward of a Concat marker whose operands are int8 NHWC on one grid: concatenating the integers is
     concatenating the values (fq_concat_i8_nhwc, the nn.ReLU behind it fused).  An operand that arrives as a DeferredUpsample is
     upsampled by the same kernel."""
-
-    def __init__(self, module):
-        self.module = module
 
     def __call__(self, x, y, dim=1):
         m = self.module
@@ -350,18 +363,17 @@ class _ConcatResident(object):
         if not ok:
             return type(m).forward(m, as_f32(x), as_f32(y), dim)
         q = _native.concat_i8_nhwc([(h.exact, h.shape[1], up) for h, up in ops], plan.relu)
-        g = plan.narrow_bit
-        return _emit(plan, QHandle((q.shape[0], sum(h.shape[1] for h, _up in ops), q.shape[1], q.shape[2]), q, g, q, g,
-                                   plan.relu or all(h.relu_done for h, _up in ops)))
+        return _emit(plan, QHandle.int8(q, sum(h.shape[1] for h, _up in ops), plan.narrow_bit,
+                                        plan.relu or all(h.relu_done for h, _up in ops)))
 
 
 # ---- tracing -------------------------------------------------------------------------------------
 
 class _Value(object):
-    __slots__ = ("producer", "kind", "src", "consumers", "foreign", "order", "shape")
+    __slots__ = ("producer", "kind", "src", "consumers", "foreign", "shape")
 
-    def __init__(self, producer, kind, src, order):
-        self.producer, self.kind, self.src, self.order = producer, kind, src, order
+    def __init__(self, producer, kind, src):
+        self.producer, self.kind, self.src = producer, kind, src
         self.shape = None            # shape of the traced tensor (set when the value is recorded)
         self.consumers = []          # (module, argument position)
         self.foreign = False         # touched by code outside NewConv2d / NewLinear / NewAdd / nn.ReLU
@@ -382,15 +394,13 @@ def _iter_tensors(obj):
 
 class _Tracer(TorchFunctionMode):
 
-    def __init__(self, planned_types, avgpool=False):
+    def __init__(self, avgpool=False):
         super(_Tracer, self).__init__()
-        self.planned_types = planned_types
         self.avgpool = bool(avgpool)     # enable(avgpool=True): an nn.AvgPool2d output is a traced value
         self.values = {}             # id(tensor) -> _Value
         self.keep = []               # keeps traced tensors alive so ids are not reused
         self.depth = 0
         self.calls = {}              # module -> number of forward calls
-        self.order = 0
         self.produced = []           # _Value of every NewConv2d / NewAdd output, in execution order
         self.relu_values = []        # _Value of every nn.ReLU output whose input is traced
         self.avgpool_shapes = {}     # nn.AvgPool2d module -> shape of its (traced) input
@@ -399,14 +409,7 @@ class _Tracer(TorchFunctionMode):
     def __torch_function__(self, func, types, args=(), kwargs=None):
         kwargs = kwargs or {}
         if self.depth == 0:
-            for t in _iter_tensors(args):
-                v = self.values.get(id(t))
-                if v is not None:
-                    v.foreign = True
-            for t in _iter_tensors(kwargs):
-                v = self.values.get(id(t))
-                if v is not None:
-                    v.foreign = True
+            self.mark_foreign((args, kwargs))
         return func(*args, **kwargs)
 
     # module hooks
@@ -430,43 +433,35 @@ class _Tracer(TorchFunctionMode):
               and all(isinstance(t, torch.Tensor) and t.dim() == 4 for t in pair))
         self.concat_ok[module] = ok and self.concat_ok.get(module, True)
 
+    @staticmethod
+    def _kind(module):
+        if isinstance(module, nn.ReLU):
+            return "relu"
+        if isinstance(module, nn.MaxPool2d):
+            return "maxpool"
+        if isinstance(module, nn.AvgPool2d):
+            return "avgpool"
+        if isinstance(module, nn.Upsample):                 # (hooked only with enable(concat=True))
+            return "upsample"
+        name = type(module).__name__
+        return {"Concat": "concat", "NewAdd": "add"}.get(name, "contraction")     # (Concat: likewise)
+
     def post(self, module, args, output):
         self.depth -= 1
         if not isinstance(output, torch.Tensor):
             return
-        self.order += 1
-        if isinstance(module, nn.ReLU):
-            src = self.values.get(id(args[0])) if args and isinstance(args[0], torch.Tensor) else None
-            if src is None:
-                return
-            v = _Value(module, "relu", src, self.order)
-            self.relu_values.append(v)
-        elif isinstance(module, nn.MaxPool2d):
-            src = self.values.get(id(args[0])) if args and isinstance(args[0], torch.Tensor) else None
-            if src is None:
-                return
-            v = _Value(module, "maxpool", src, self.order)
-            self.produced.append(v)
-        elif isinstance(module, nn.AvgPool2d):
-            if not self.avgpool:
+        kind = self._kind(module)
+        src = None
+        if kind in ("relu", "maxpool", "avgpool", "upsample"):     # a value of these kinds exists only behind a traced value
+            if kind == "avgpool" and not self.avgpool:
                 return                                      # its output is an ordinary fp32 tensor
             src = self.values.get(id(args[0])) if args and isinstance(args[0], torch.Tensor) else None
-            if src is None or src.shape is None or len(src.shape) != 4:     # (the recorded shape: a tensor method here would be a foreign touch)
-                return
-            v = _Value(module, "avgpool", src, self.order)
-            self.produced.append(v)
-        elif isinstance(module, nn.Upsample):               # (hooked only with enable(concat=True))
-            src = self.values.get(id(args[0])) if args and isinstance(args[0], torch.Tensor) else None
             if src is None:
                 return
-            v = _Value(module, "upsample", src, self.order)
-            self.produced.append(v)
-        elif type(module).__name__ == "Concat":             # (likewise)
-            v = _Value(module, "concat", None, self.order)
-            self.produced.append(v)
-        else:
-            v = _Value(module, "add" if type(module).__name__ == "NewAdd" else "contraction", None, self.order)
-            self.produced.append(v)
+            if kind == "avgpool" and (src.shape is None or len(src.shape) != 4):    # (the recorded shape: a tensor method here would be a foreign touch)
+                return
+        v = _Value(module, kind, src)
+        (self.relu_values if kind == "relu" else self.produced).append(v)
         v.shape = tuple(output.shape)
         self.values[id(output)] = v
         self.keep.append(output)
@@ -482,8 +477,7 @@ def _clear(model):
     for m in model.modules():
         m.__dict__.pop("_resident", None)
         fwd = m.__dict__.get("forward")
-        if isinstance(fwd, (_ReluPassThrough, _MaxPoolResident, _AvgPoolResident, _ConcatResident, _UpsampleResident,
-                            _AvgPoolWindowResident)):
+        if isinstance(fwd, _InstanceForward):
             del m.__dict__["forward"]
     model.__dict__.pop("_fq_resident_enabled", None)
 
@@ -498,52 +492,373 @@ def is_enabled(model):
     return bool(model.__dict__.get("_fq_resident_enabled"))
 
 
-def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False, grouped=False):
-    """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
-    on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
-    nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
-    `example_input` is any valid input batch; the plan does not depend on its size.  With `verify`
-    (default) the planned model is run once on `example_input` and must reproduce the traced forward
-    bit for bit, otherwise the plan is removed and FqError raised.
-    `depthwise=True` also plans depthwise NewConv2d layers (groups == in_channels == out_channels, 3x3 / 5x5, stride 1 / 2,
-    shift in [1, 16]: NewConv2d._depthwise_ok) as integer producers and consumers, served by fq_dwconv2d_i8_resident; without
-    it they stay fp32 producers, as every other grouped convolution does.  The summary then counts them as `resident_depthwise`.
-    `concat=True` also plans the Concat marker layer and nearest upsampling (nn.UpsamplingNearest2d, nn.Upsample(mode="nearest"))
-    by an integer scale_factor of 2 or 4, both served by fq_concat_i8_nhwc: a Concat whose two operands are int8 activations on
-    ONE grid -- what the calibrator's merge group gives them -- joins the integers, with the nn.ReLU behind it fused; an upsampling
-    whose only consumer is such a Concat is not launched at all, the Concat reads the small tensor (DeferredUpsample).  Without
-    the argument both are foreign code and their operands leave as fp32, as before.  Left in fp32 form (out of scope): a Concat
-    with a NewAdd sum (int16) as an operand or with operands on different grids, any dim but 1, more than two operands, nested
-    Concats are not flattened, the `size=` form and other factors of an upsampling; a bare torch.cat stays foreign, as a bare `+`
-    does.  The summary then gains `resident_concats`, `resident_upsamples` and `fused_upsamples`.
-    `avgpool=True` also plans a windowed nn.AvgPool2d (the pool branch of an Inception block, the 2x2 pool of a transition) that
-    reads an int8 activation and is read by NewConv2d layers only, all at one input bit: DeQuantity -> pool -> the nn.ReLU behind
-    it -> the consumers' Quantity run as one kernel on the integers (fq_avgpool_i8_nhwc), so the pool's source no longer has to
-    leave as fp32 for it.  Its value has no exact integer form and is handed to those convolutions only.  Left in fp32 form (out
-    of scope): a NewAdd sum (int16) as the source, consumers that are not all convolutions at one bit, ceil_mode,
-    divisor_override, windows above 64 taps, |bit - grid| > 8, a pool called twice; F.avg_pool2d and nn.AdaptiveAvgPool2d stay
-    foreign.  The whole-plane pool in front of the head is served as before.  The summary then gains `resident_avgpools`.
-    `grouped=True` also plans grouped NewConv2d layers (1 < groups < channels, 4 .. 64 input and output channels per group in
-    multiples of 4, 1x1 / 3x3, stride 1 / 2, shift in [1, 16]: NewConv2d._grouped_ok) as integer producers and consumers, served
-    by fq_gconv2d_i8_resident.  Such a layer is never run inside a NewAdd's kernel; an add reads its integers like any other
-    operand.  Without the argument they stay fp32 producers.  The summary then counts them as `resident_grouped`."""
-    from .new_quantity_op import NewConv2d, NewLinear, NewAdd, QUANTIZE_BIT
+_COUNTER = {"contraction": "resident_convs", "add": "resident_adds", "maxpool": "resident_pools", "concat": "resident_concats",
+            "upsample": "resident_upsamples"}
+_FORWARD = {"maxpool": _MaxPoolResident, "concat": _ConcatResident, "upsample": _UpsampleResident}
+
+
+class _Planning(object):
+    """The plan of one traced forward.  enable() calls the passes below in order; they decide on the trace alone and change
+    nothing on the model until install() writes the plans and the instance-level forwards to the modules."""
+
+    def __init__(self, tracer, depthwise, concat, avgpool, grouped):
+        from .new_quantity_op import NewConv2d, NewAdd
+        from .fabu_layer import Concat
+        self.conv_type, self.concat_type = NewConv2d, Concat
+        self.tracer = tracer
+        self.depthwise, self.grouped = bool(depthwise), bool(grouped)
+        self.relu_value = dict((id(c.src), c) for c in tracer.relu_values)
+        self.fmt = {}                    # id(effective _Value) -> (bytes, grid)
+        self.eff_of = {}                 # id(produced _Value) -> (effective _Value, relu module)
+        self.operands = {}               # NewAdd / Concat module -> [value at arg 0, value at arg 1]
+        for v in tracer.values.values():
+            for (m, pos) in v.consumers:
+                if isinstance(m, (NewAdd, Concat)) and pos < 2:
+                    self.operands.setdefault(m, [None, None])[pos] = v
+        self.add_resident = set()        # NewAdd modules whose operands arrive as integers
+        self.int8_resident = set()       # nn.MaxPool2d, Concat and nearest-upsampling modules that run on the int8 integers
+        self.avg_resident = {}           # windowed nn.AvgPool2d that runs on fq_avgpool_i8_nhwc -> (source grid g, consumer bit b)
+        self.plans = {}                  # producer module -> Plan
+        self.forwards = []               # (module, its instance-level forward)
+        self.summary = {"resident_convs": 0, "resident_adds": 0, "resident_pools": 0, "fused_relus": 0, "fp32_outputs": 0,
+                        "int_only_outputs": 0}
+        if depthwise:
+            self.summary["resident_depthwise"] = 0
+        if concat:
+            self.summary["resident_concats"] = self.summary["resident_upsamples"] = 0
+        if avgpool:
+            self.summary["resident_avgpools"] = 0
+        if grouped:
+            self.summary["resident_grouped"] = 0
+
+    # ---- what a value is and what a module can do
+
+    def once(self, m):
+        """Every producer of the plan is called exactly once per forward."""
+        return self.tracer.calls.get(m, 0) == 1
+
+    def effective(self, v):
+        """(value the consumers see, fused ReLU module or None)"""
+        if v.kind != "maxpool" and not v.foreign and len(v.consumers) == 1 and isinstance(v.consumers[0][0], nn.ReLU):
+            after = self.relu_value.get(id(v))
+            if after is not None:
+                return after, v.consumers[0][0]
+        return v, None
+
+    def is_dw(self, m):
+        """A depthwise layer that this plan runs on fq_dwconv2d_i8_resident: `depthwise=True` plans depthwise NewConv2d layers
+        (groups == in_channels == out_channels, 3x3 / 5x5, stride 1 / 2, shift in [1, 16]: NewConv2d._depthwise_ok) as integer
+        producers and consumers; without it they stay fp32 producers, as every other grouped convolution does.  The summary then
+        counts them as `resident_depthwise`."""
+        return self.depthwise and isinstance(m, self.conv_type) and self.once(m) and m._depthwise_ok(m.Conv, True)
+
+    def is_gc(self, m):
+        """A grouped layer that this plan runs on fq_gconv2d_i8_resident: `grouped=True` plans grouped NewConv2d layers
+        (1 < groups < channels, 4 .. 64 input and output channels per group in multiples of 4, 1x1 / 3x3, stride 1 / 2, shift in
+        [1, 16]: NewConv2d._grouped_ok) as integer producers and consumers.  Such a layer is never run inside a NewAdd's kernel;
+        an add reads its integers like any other operand.  Without the argument they stay fp32 producers.  The summary then counts
+        them as `resident_grouped`."""
+        return self.grouped and isinstance(m, self.conv_type) and self.once(m) and m._grouped_ok(m.Conv, True)
+
+    def conv_can_emit(self, m):
+        return isinstance(m, self.conv_type) and self.once(m) and (m._int8_ok(m.Conv) or self.is_dw(m) or self.is_gc(m))
+
+    def conv_can_read(self, m):
+        return isinstance(m, self.conv_type) and ((m._int8_ok(m.Conv) and not m._stem_fold(m.Conv)) or self.is_dw(m)
+                                                  or self.is_gc(m))
+
+    def avg_can_read(self, m):
+        """The whole-plane nn.AvgPool2d in front of the head, which reads the exact integers of its source (_AvgPoolResident)."""
+        shape = self.tracer.avgpool_shapes.get(m)
+        return isinstance(m, nn.AvgPool2d) and shape is not None and len(shape) == 4 and _avgpool_is_global(m, shape[2], shape[3])
+
+    def resident_adds(self):
+        """(module, its Plan, its two operand values, its own value) of every resident add, in execution order."""
+        return [(v.producer, self.plans[v.producer], self.operands[v.producer], v) for v in self.tracer.produced
+                if v.kind == "add" and v.producer in self.add_resident]
+
+    # ---- pass 1 (execution order): integer format of every produced value
+
+    def plan_formats(self):
+        for v in self.tracer.produced:
+            e, relu_mod = self.effective(v)
+            self.eff_of[id(v)] = (e, relu_mod)
+            m = v.producer
+            f = None
+            if v.kind == "contraction":
+                if self.conv_can_emit(m):
+                    f = (1, m.output_bit)
+            elif v.kind == "maxpool":
+                f = self._int8_source(v) if _maxpool_supported(m) else None
+            elif v.kind == "upsample":
+                s = _upsample_factor(m)
+                f = self._int8_source(v) if s is not None and len(v.shape) == 4 else None
+                if f is not None and not _native.concat_supported([v.shape[1]], [s]):
+                    f = None
+            elif v.kind == "avgpool":
+                self._plan_avgpool_window(v, e)             # (the value itself has no integer format)
+            elif v.kind == "concat":
+                f = self._concat_format(v)
+            else:
+                f = self._add_format(v)
+            if f is not None:
+                self.fmt[id(e)] = f
+                if v.kind != "contraction":
+                    (self.add_resident if v.kind == "add" else self.int8_resident).add(m)
+
+    def _int8_source(self, v):
+        """The format of the value that a max-pool / upsampling / average pool called once reads, if that is int8."""
+        f = self.fmt.get(id(v.src))
+        return f if f is not None and f[0] == 1 and self.once(v.producer) else None
+
+    def _plan_avgpool_window(self, v, e):
+        """`avgpool=True` plans a windowed nn.AvgPool2d (the pool branch of an Inception block, the 2x2 pool of a transition) that
+        reads an int8 activation on a grid g and is read by NewConv2d layers only, all at one input bit b: DeQuantity -> pool ->
+        the nn.ReLU behind it -> the consumers' Quantity run as one kernel on the integers (fq_avgpool_i8_nhwc), so the pool's
+        source no longer has to leave as fp32 for it.  Its value has no exact integer form and gets NO entry in fmt: no Concat,
+        add, max-pool, upsampling or second pool takes it as an operand, it is handed to those convolutions only.  Left in fp32
+        form (out of scope): a NewAdd sum (int16) as the source, consumers that are not all convolutions at one bit, ceil_mode,
+        divisor_override, windows above 64 taps, |bit - grid| > 8, a pool called twice; F.avg_pool2d and nn.AdaptiveAvgPool2d stay
+        foreign.  The whole-plane pool in front of the head is served as before.  The summary then gains `resident_avgpools`."""
+        m = v.producer
+        f = self._int8_source(v)
+        if (self.avg_can_read(m) or f is None or not _avgpool_window_ok(m) or e.foreign or not e.consumers
+                or not all(self.conv_can_read(c) for (c, _pos) in e.consumers)):
+            return
+        bits = set(c.input_bit for (c, _pos) in e.consumers)
+        if len(bits) != 1:
+            return
+        b = bits.pop()
+        k, st, pd = _pool_geometry(m)
+        if min(st) >= 1 and _native.avgpool_supported(k, st, pd, b - f[1]):
+            self.avg_resident[m] = (f[1], b)
+
+    def _integer_operands(self, m):
+        """(value, value, format, format) of the two operands of a NewAdd / Concat called once, if both are integers; or None."""
+        ops = self.operands.get(m)
+        if not self.once(m) or ops is None or ops[0] is None or ops[1] is None:
+            return None
+        fx, fy = self.fmt.get(id(ops[0])), self.fmt.get(id(ops[1]))
+        return (ops[0], ops[1], fx, fy) if fx is not None and fy is not None else None
+
+    def _concat_format(self, v):
+        """`concat=True` plans the Concat marker layer and nearest upsampling (nn.UpsamplingNearest2d, nn.Upsample(mode="nearest"))
+        by an integer scale_factor of 2 or 4, both served by fq_concat_i8_nhwc: a Concat whose two operands are int8 activations
+        on ONE grid -- what the calibrator's merge group gives them -- joins the integers, with the nn.ReLU behind it fused.
+        Without the argument both are foreign code and their operands leave as fp32.  Left in fp32 form (out of scope): a Concat
+        with a NewAdd sum (int16) as an operand or with operands on different grids, any dim but 1, more than two operands, nested
+        Concats are not flattened, the `size=` form and other factors of an upsampling; a bare torch.cat stays foreign, as a bare
+        `+` does.  The summary then gains `resident_concats`, `resident_upsamples` and `fused_upsamples` (defer_upsamples)."""
+        m = v.producer
+        ops = self._integer_operands(m) if self.tracer.concat_ok.get(m) else None
+        if ops is None:
+            return None
+        x, y, fx, fy = ops
+        if fx[0] != 1 or fx != fy or x.shape is None or y.shape is None:
+            return None
+        if not _native.concat_supported([x.shape[1], y.shape[1]], [1, 1]):
+            return None
+        return fx
+
+    def _add_format(self, v):
+        """A NewAdd of two integer operands: the exact sum as int16 on the finer of their grids, where that fits."""
+        ops = self._integer_operands(v.producer)
+        if ops is None:
+            return None
+        gx, gy = ops[2][1], ops[3][1]
+        g = max(0, gx, gy)
+        if g > MAX_WIDE_GRID or min(gx, gy) < -16:
+            return None
+        return (2, g)
+
+    # ---- pass 2: what every producer has to emit
+
+    def plan_outputs(self):
+        for v in self.tracer.produced:
+            e, relu_mod = self.eff_of[id(v)]
+            if v.kind == "avgpool":
+                if v.producer in self.avg_resident:
+                    plan = Plan()
+                    plan.emit_int, plan.emit_f32 = True, False
+                    plan.grid, plan.narrow_bit = self.avg_resident[v.producer]
+                    self._take(v.producer, plan, relu_mod, _AvgPoolWindowResident)
+                    self.summary["resident_avgpools"] += 1
+            elif id(e) in self.fmt:                         # (anything else stays a plain fp32 producer)
+                self._plan_output(v, e, relu_mod)
+
+    def _take(self, m, plan, relu_mod, forward=None):
+        """Module m emits what `plan` says, with the nn.ReLU behind it (if any) fused and, for a module that is no integer
+        layer itself, `forward` as its instance-level forward."""
+        plan.relu = relu_mod is not None
+        self.plans[m] = plan
+        if plan.relu:
+            self.forwards.append((relu_mod, _ReluPassThrough(relu_mod)))
+            self.summary["fused_relus"] += 1
+        if forward is not None:
+            self.forwards.append((m, forward(m)))
+        self.summary["fp32_outputs" if plan.emit_f32 else "int_only_outputs"] += 1
+
+    def _readers(self, v, e):
+        """Who reads the value: (somebody needs the fp32 tensor, readers of the exact integers, other readers of the int8 form,
+        [the input bit of every convolution that reads it])."""
+        need_f32, exact, int8, bits = e.foreign, 0, 0, []
+        for (c, _pos) in e.consumers:
+            if self.conv_can_read(c):
+                bits.append(c.input_bit)
+            elif c in self.add_resident or self.avg_can_read(c):
+                exact += 1
+            elif (c in self.int8_resident or c in self.avg_resident) and v.kind != "add":
+                int8 += 1                                   # int8 max-pool / Concat / nearest upsampling / windowed average pool
+            else:
+                need_f32 = True
+        return need_f32, exact, int8, bits
+
+    def _plan_output(self, v, e, relu_mod):
+        m = v.producer
+        plan = Plan()
+        need_f32, exact, int8, bits = self._readers(v, e)
+        plan.want_wide = exact > 0
+        if v.kind == "add":
+            plan.resident_add = True
+            plan.grid = self.fmt[id(e)][1]
+            plan.narrow_bit = bits[0] if bits else None
+        else:
+            plan.narrow_bit = self.fmt[id(e)][1]            # (a convolution's own output bit)
+        served = bits.count(plan.narrow_bit)
+        if served != len(bits):
+            need_f32 = True                                 # a consumer quantises at another bit: from fp32
+        if v.kind == "add" and need_f32:
+            plan.want_wide = True                           # fp32 leaves through the exact int16 sum
+        plan.emit_int = exact + int8 + served > 0
+        plan.emit_f32 = need_f32 or not plan.emit_int
+        if v.kind == "contraction" and self.is_dw(m):
+            plan.depthwise = True
+            self.summary["resident_depthwise"] += 1
+        if v.kind == "contraction" and self.is_gc(m):
+            plan.grouped = True
+            self.summary["resident_grouped"] += 1
+        if v.kind == "upsample":
+            plan.up = _upsample_factor(m)
+        self._take(m, plan, relu_mod, _FORWARD.get(v.kind))
+        self.summary[_COUNTER[v.kind]] += 1
+
+    # ---- fusion passes (in this order: fuse_projections reads the fuse_next that fuse_block_tails sets)
+
+    def defer_convs(self):
+        """A convolution whose value goes to one resident add and nowhere else is run BY that add (DeferredConv)."""
+        self.summary["fused_conv_adds"] = 0
+        for add_mod, add_plan, ops, _va in self.resident_adds():
+            for pos in (0, 1):
+                v = ops[pos]
+                plan = self.plans.get(v.producer) if isinstance(v.producer, self.conv_type) else None
+                if (v.kind == "contraction" and plan is not None and not plan.depthwise and not plan.grouped and not plan.relu
+                        and not plan.emit_f32 and not v.foreign and v.consumers == [(add_mod, pos)] and ops[1 - pos] is not v
+                        and not add_plan.emit_f32):
+                    plan.defer = True
+                    add_plan.fuse_arg = pos
+                    self.summary["fused_conv_adds"] += 1
+                    break
+
+    def fuse_block_tails(self):
+        """When the re-quantised sum of an add that runs its conv3 feeds a 1x1 convolution (the next bottleneck's conv1), that
+        convolution runs inside the same kernel (fq_block_tail_i8, Plan.fuse_next): its operand is staged in LDS and, if nobody
+        else reads it, never written."""
+        self.summary["fused_block_tails"] = 0
+        for _add_mod, plan, ops, va in self.resident_adds():
+            if plan.fuse_arg is None or plan.emit_f32 or not plan.want_wide or not block_tail_enabled():
+                continue
+            conv3 = ops[plan.fuse_arg].producer
+            other = self.fmt.get(id(ops[1 - plan.fuse_arg]))                     # (bytes, grid) of the shortcut
+            if other is None or not _pointwise_conv(conv3.Conv):
+                continue
+            readers = [c for (c, _pos) in self.eff_of[id(va)][0].consumers if self.conv_can_read(c)]
+            for c in readers:
+                cp = self.plans.get(c)
+                if (cp is not None and not cp.defer and not cp.grouped and cp.emit_int and not cp.emit_f32 and self.once(c)
+                        and _pointwise_conv(c.Conv) and c.input_bit == plan.narrow_bit
+                        and conv3.Conv.out_channels == c.Conv.in_channels
+                        and _native.block_tail_supported(conv3.Conv.in_channels, conv3.Conv.out_channels, c.Conv.out_channels,
+                                                         conv3._rs(), c._rs(), conv3.output_bit, other[1], other[0],
+                                                         plan.narrow_bit)):
+                    plan.fuse_next = c
+                    plan.narrow_to_hbm = len(readers) > 1
+                    self.summary["fused_block_tails"] += 1
+                    break
+
+    def fuse_projections(self):
+        """When the OTHER operand of such an add is a 1x1 projection of the block's input that nobody else reads (the first block
+        of a stage), the kernel computes that convolution as well (fq_block_tail_proj_i8, Plan.fuse_proj): its K3 bytes per pixel
+        are neither written nor read back."""
+        self.summary["fused_projections"] = 0
+        for add_mod, plan, ops, _va in self.resident_adds():
+            if plan.fuse_arg is None or plan.emit_f32 or not block_tail_enabled() or not block_tail_proj_enabled():
+                continue
+            conv3, vp = ops[plan.fuse_arg].producer, ops[1 - plan.fuse_arg]
+            proj = vp.producer
+            pp = self.plans.get(proj) if isinstance(proj, self.conv_type) else None
+            if (vp.kind != "contraction" or pp is None or pp.relu or pp.emit_f32 or pp.defer or pp.grouped or vp.foreign
+                    or vp.consumers != [(add_mod, 1 - plan.fuse_arg)] or not self.conv_can_read(proj) or not self.once(proj)):
+                continue
+            k3, kp = conv3.Conv, proj.Conv
+            nxt = plan.fuse_next
+            if (not _pointwise_conv(kp, any_stride=True) or not _pointwise_conv(k3)
+                    or kp.out_channels != k3.out_channels or (kp.out_channels % 16) or (kp.in_channels % 16)
+                    or not _native.block_tail_proj_supported(k3.in_channels, k3.out_channels,
+                                                             nxt.Conv.out_channels if nxt is not None else 0, kp.in_channels,
+                                                             conv3._rs(), nxt._rs() if nxt is not None else 0, proj._rs(),
+                                                             kp.stride[0])):
+                continue
+            pp.defer = True
+            plan.fuse_proj = True
+            self.summary["fused_projections"] += 1
+
+    def defer_upsamples(self):
+        """(`concat=True`) A nearest upsampling whose value goes to one resident Concat and nowhere else is not launched at all:
+        the Concat reads the small tensor with the factor as its operand's `up` (DeferredUpsample)."""
+        self.summary["fused_upsamples"] = 0
+        for v in self.tracer.produced:
+            plan = self.plans.get(v.producer)
+            if v.kind != "upsample" or plan is None or plan.up is None or plan.relu or plan.emit_f32 or v.foreign:
+                continue
+            if (len(v.consumers) != 1 or v.consumers[0][0] not in self.int8_resident
+                    or not isinstance(v.consumers[0][0], self.concat_type)):
+                continue
+            cat_mod, pos = v.consumers[0]
+            ops = self.operands[cat_mod]
+            ups = [1, 1]
+            ups[pos] = plan.up
+            if ops[pos] is not v or ops[1 - pos] is v or not _native.concat_supported([ops[0].shape[1], ops[1].shape[1]], ups):
+                continue
+            plan.defer = True
+            self.summary["fused_upsamples"] += 1
+
+    def hook_global_pools(self):
+        for m in self.tracer.avgpool_shapes:
+            if self.avg_can_read(m):
+                self.forwards.append((m, _AvgPoolResident(m)))
+                self.summary["resident_pools"] += 1
+
+    def install(self, model):
+        for m, plan in self.plans.items():
+            m.__dict__["_resident"] = plan
+        for m, forward in self.forwards:
+            m.__dict__["forward"] = forward
+        model.__dict__["_fq_resident_enabled"] = True
+
+
+def _trace(model, example_input, concat, avgpool):
+    """One forward of `model` in eval mode under the tracer: (tracer, the outputs of that forward)."""
+    from .new_quantity_op import NewConv2d, NewLinear, NewAdd
     from .fabu_layer import Concat
-    _clear(model)
-    if QUANTIZE_BIT != 8:
-        raise _native.FqError("resident activations are defined for QUANTIZE_BIT = 8")
     planned_types = (NewConv2d, NewLinear, NewAdd, nn.ReLU, nn.MaxPool2d, nn.AvgPool2d)
-    tracer = _Tracer(planned_types, avgpool)
+    tracer = _Tracer(avgpool)
     hooks = []
     for m in model.modules():
-        if isinstance(m, planned_types):
+        if isinstance(m, planned_types) or (concat and _upsample_factor(m) is not None):     # (any other nn.Upsample stays foreign code)
             hooks.append(m.register_forward_pre_hook(tracer.pre))
             hooks.append(m.register_forward_hook(tracer.post))
         elif concat and isinstance(m, Concat):
             hooks.append(m.register_forward_pre_hook(tracer.pre_concat, with_kwargs=True))
-            hooks.append(m.register_forward_hook(tracer.post))
-        elif concat and _upsample_factor(m) is not None:      # any other nn.Upsample stays foreign code
-            hooks.append(m.register_forward_pre_hook(tracer.pre))
             hooks.append(m.register_forward_hook(tracer.post))
     was_training = model.training
     model.eval()
@@ -556,291 +871,35 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
         for h in hooks:
             h.remove()
         model.train(was_training)
+    return tracer, traced_out
 
-    relu_value = dict((id(c.src), c) for c in tracer.relu_values)
 
-    def effective(v):
-        """(value the consumers see, fused ReLU module or None)"""
-        if v.kind != "maxpool" and not v.foreign and len(v.consumers) == 1 and isinstance(v.consumers[0][0], nn.ReLU):
-            after = relu_value.get(id(v))
-            if after is not None:
-                return after, v.consumers[0][0]
-        return v, None
-
-    def is_dw(m):
-        """A depthwise layer that this plan runs on fq_dwconv2d_i8_resident (called once, like every producer of the plan)."""
-        return (bool(depthwise) and isinstance(m, NewConv2d) and tracer.calls.get(m, 0) == 1
-                and m._depthwise_ok(m.Conv, True))
-
-    def is_gc(m):
-        """A grouped layer that this plan runs on fq_gconv2d_i8_resident (called once, like every producer of the plan)."""
-        return (bool(grouped) and isinstance(m, NewConv2d) and tracer.calls.get(m, 0) == 1
-                and m._grouped_ok(m.Conv, True))
-
-    def conv_can_emit(m):
-        return isinstance(m, NewConv2d) and tracer.calls.get(m, 0) == 1 and (m._int8_ok(m.Conv) or is_dw(m) or is_gc(m))
-
-    def conv_can_read(m):
-        return isinstance(m, NewConv2d) and ((m._int8_ok(m.Conv) and not m._stem_fold(m.Conv)) or is_dw(m) or is_gc(m))
-
-    # pass 1 (execution order): integer format of every produced value
-    fmt = {}                         # id(effective _Value) -> (bytes, grid)
-    eff_of = {}                      # id(produced _Value) -> (effective _Value, relu module)
-    operands = {}                    # NewAdd / Concat module -> [value at arg 0, value at arg 1]
-    for v in tracer.values.values():
-        for (m, pos) in v.consumers:
-            if isinstance(m, (NewAdd, Concat)) and pos < 2:
-                operands.setdefault(m, [None, None])[pos] = v
-    add_resident, pool_resident = set(), set()
-    cat_resident = set()             # Concat and nearest-upsampling modules that run on fq_concat_i8_nhwc
-    avg_resident = {}                # windowed nn.AvgPool2d that runs on fq_avgpool_i8_nhwc -> (source grid g, consumer bit b)
-
-    def avg_can_read(m):
-        shape = tracer.avgpool_shapes.get(m)
-        return (isinstance(m, nn.AvgPool2d) and shape is not None and len(shape) == 4
-                and _avgpool_is_global(m, shape[2], shape[3]) and shape[2] * shape[3] * 32768 < (1 << 24))
-
-    for v in tracer.produced:
-        e, relu_mod = effective(v)
-        eff_of[id(v)] = (e, relu_mod)
-        m = v.producer
-        if v.kind == "contraction":
-            if conv_can_emit(m):
-                fmt[id(e)] = (1, m.output_bit)
-        elif v.kind == "maxpool":
-            f = fmt.get(id(v.src))
-            if f is not None and f[0] == 1 and tracer.calls.get(m, 0) == 1 and _maxpool_supported(m):
-                pool_resident.add(m)
-                fmt[id(e)] = f
-        elif v.kind == "upsample":
-            f = fmt.get(id(v.src))
-            s = _upsample_factor(m)
-            if (f is not None and f[0] == 1 and tracer.calls.get(m, 0) == 1 and s is not None and len(v.shape) == 4
-                    and _native.concat_supported([v.shape[1]], [s])):
-                cat_resident.add(m)
-                fmt[id(e)] = f
-        elif v.kind == "avgpool":
-            # int8 source on a grid g, NewConv2d consumers at one bit b; the value itself gets NO entry in fmt (it has no exact
-            # integer form), so no Concat, add, max-pool, upsampling or second pool takes it as an operand
-            f = fmt.get(id(v.src))
-            if (avg_can_read(m) or f is None or f[0] != 1 or tracer.calls.get(m, 0) != 1 or not _avgpool_window_ok(m)
-                    or e.foreign or not e.consumers or not all(conv_can_read(c) for (c, _pos) in e.consumers)):
-                continue
-            bits = set(c.input_bit for (c, _pos) in e.consumers)
-            if len(bits) != 1:
-                continue
-            b = bits.pop()
-            k, st, pd = _avgpool_geometry(m)
-            if min(st) < 1 or not _native.avgpool_supported(k, st, pd, b - f[1]):
-                continue
-            avg_resident[m] = (f[1], b)
-        elif v.kind == "concat":
-            ops = operands.get(m)
-            if (tracer.calls.get(m, 0) != 1 or not tracer.concat_ok.get(m) or ops is None or ops[0] is None or ops[1] is None):
-                continue
-            fx, fy = fmt.get(id(ops[0])), fmt.get(id(ops[1]))
-            # int8 operands on one grid only: a NewAdd sum (2, .) or two grids keep the fp32 form
-            if fx is None or fy is None or fx[0] != 1 or fx != fy or ops[0].shape is None or ops[1].shape is None:
-                continue
-            if not _native.concat_supported([ops[0].shape[1], ops[1].shape[1]], [1, 1]):
-                continue
-            cat_resident.add(m)
-            fmt[id(e)] = fx
-        else:
-            ops = operands.get(m)
-            if tracer.calls.get(m, 0) != 1 or ops is None or ops[0] is None or ops[1] is None:
-                continue
-            fx, fy = fmt.get(id(ops[0])), fmt.get(id(ops[1]))
-            if fx is None or fy is None:
-                continue
-            g = max(0, fx[1], fy[1])
-            if g > MAX_WIDE_GRID or min(fx[1], fy[1]) < -16:
-                continue
-            add_resident.add(m)
-            fmt[id(e)] = (2, g)
-
-    # pass 2: what every producer has to emit
-    summary = {"resident_convs": 0, "resident_adds": 0, "resident_pools": 0, "fused_relus": 0, "fp32_outputs": 0,
-               "int_only_outputs": 0}
-    if depthwise:
-        summary["resident_depthwise"] = 0
+def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False, grouped=False):
+    """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
+    on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
+    nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
+    `example_input` is any valid input batch; the plan does not depend on its size.  With `verify`
+    (default) the planned model is run once on `example_input` and must reproduce the traced forward
+    bit for bit, otherwise the plan is removed and FqError raised.
+    Opt-in, each adding its own keys to the summary and leaving the plan as it was when off:
+    `depthwise=True` also plans depthwise NewConv2d layers (_Planning.is_dw), `grouped=True` grouped ones (_Planning.is_gc);
+    `concat=True` also plans the Concat marker layer and nearest upsampling by 2 or 4 (_Planning._concat_format, defer_upsamples);
+    `avgpool=True` also plans a windowed nn.AvgPool2d between an int8 activation and convolutions (_plan_avgpool_window)."""
+    from .new_quantity_op import QUANTIZE_BIT
+    _clear(model)
+    if QUANTIZE_BIT != 8:
+        raise _native.FqError("resident activations are defined for QUANTIZE_BIT = 8")
+    tracer, traced_out = _trace(model, example_input, concat, avgpool)
+    planning = _Planning(tracer, depthwise, concat, avgpool, grouped)
+    planning.plan_formats()
+    planning.plan_outputs()
+    planning.defer_convs()
+    planning.fuse_block_tails()
+    planning.fuse_projections()
     if concat:
-        summary["resident_concats"] = summary["resident_upsamples"] = 0
-    if avgpool:
-        summary["resident_avgpools"] = 0
-    if grouped:
-        summary["resident_grouped"] = 0
-    for v in tracer.produced:
-        m = v.producer
-        e, relu_mod = eff_of[id(v)]
-        if v.kind == "avgpool":
-            if m in avg_resident:
-                plan = Plan()
-                plan.relu = relu_mod is not None
-                plan.emit_int, plan.emit_f32 = True, False
-                plan.grid, plan.narrow_bit = avg_resident[m]
-                m.__dict__["_resident"] = plan
-                m.__dict__["forward"] = _AvgPoolWindowResident(m)
-                if plan.relu:
-                    relu_mod.__dict__["forward"] = _ReluPassThrough(relu_mod)
-                    summary["fused_relus"] += 1
-                summary["resident_avgpools"] += 1
-                summary["int_only_outputs"] += 1
-            continue
-        if id(e) not in fmt:
-            continue                                        # plain fp32 producer
-        plan = Plan()
-        plan.relu = relu_mod is not None
-        need_f32 = e.foreign
-        int_consumers = 0
-        narrow_bits = []
-        for (c, pos) in e.consumers:
-            if conv_can_read(c):
-                narrow_bits.append(c.input_bit)
-            elif (isinstance(c, NewAdd) and c in add_resident) or avg_can_read(c):
-                int_consumers += 1
-                plan.want_wide = True                       # these read the exact value
-            elif (c in pool_resident or c in cat_resident or c in avg_resident) and v.kind != "add":
-                int_consumers += 1                          # int8 max-pool / Concat / nearest upsampling / windowed average pool of an int8 activation
-            else:
-                need_f32 = True
-        if v.kind in ("contraction", "maxpool", "concat", "upsample"):
-            grid = m.output_bit if v.kind == "contraction" else fmt[id(e)][1]
-            ok = [b for b in narrow_bits if b == grid]
-            if len(ok) != len(narrow_bits):
-                need_f32 = True                             # a consumer quantises at another bit: from fp32
-            int_consumers += len(ok)
-            plan.narrow_bit = grid
-        else:
-            plan.resident_add = True
-            plan.grid = fmt[id(e)][1]
-            if narrow_bits:
-                plan.narrow_bit = narrow_bits[0]
-                ok = [b for b in narrow_bits if b == plan.narrow_bit]
-                if len(ok) != len(narrow_bits):
-                    need_f32 = True
-                int_consumers += len(ok)
-            if need_f32:
-                plan.want_wide = True                       # fp32 leaves through the exact int16 sum
-        plan.emit_int = int_consumers > 0
-        plan.emit_f32 = need_f32 or not plan.emit_int
-        if v.kind == "contraction" and is_dw(m):
-            plan.depthwise = True
-            summary["resident_depthwise"] += 1
-        if v.kind == "contraction" and is_gc(m):
-            plan.grouped = True
-            summary["resident_grouped"] += 1
-        m.__dict__["_resident"] = plan
-        if plan.relu:
-            relu_mod.__dict__["forward"] = _ReluPassThrough(relu_mod)
-            summary["fused_relus"] += 1
-        if v.kind == "maxpool":
-            m.__dict__["forward"] = _MaxPoolResident(m)
-        elif v.kind == "concat":
-            m.__dict__["forward"] = _ConcatResident(m)
-        elif v.kind == "upsample":
-            plan.up = _upsample_factor(m)
-            m.__dict__["forward"] = _UpsampleResident(m)
-        summary[{"contraction": "resident_convs", "add": "resident_adds", "maxpool": "resident_pools",
-                 "concat": "resident_concats", "upsample": "resident_upsamples"}[v.kind]] += 1
-        summary["fp32_outputs" if plan.emit_f32 else "int_only_outputs"] += 1
-    # a convolution whose value goes to one resident add and nowhere else is run BY that add
-    summary["fused_conv_adds"] = 0
-    for add_mod in add_resident:
-        ops = operands[add_mod]
-        for pos in (0, 1):
-            v = ops[pos]
-            conv = v.producer
-            plan = conv.__dict__.get("_resident") if isinstance(conv, NewConv2d) else None
-            if (v.kind == "contraction" and plan is not None and not plan.depthwise and not plan.grouped and not plan.relu and not plan.emit_f32
-                    and not v.foreign and v.consumers == [(add_mod, pos)] and ops[1 - pos] is not v
-                    and not add_mod.__dict__["_resident"].emit_f32):
-                plan.defer = True
-                add_mod.__dict__["_resident"].fuse_arg = pos
-                summary["fused_conv_adds"] += 1
-                break
-    # ... and when the re-quantised sum of such an add feeds a 1x1 convolution (the next bottleneck's conv1), that convolution
-    # runs inside the same kernel (fq_block_tail_i8): its operand is staged in LDS and, if nobody else reads it, never written
-    summary["fused_block_tails"] = 0
-    for v in tracer.produced:
-        add_mod = v.producer
-        plan = add_mod.__dict__.get("_resident")
-        if v.kind != "add" or plan is None or plan.fuse_arg is None or plan.emit_f32 or not plan.want_wide or not block_tail_enabled():
-            continue
-        e, _relu = eff_of[id(v)]
-        conv3 = operands[add_mod][plan.fuse_arg].producer
-        other = fmt.get(id(operands[add_mod][1 - plan.fuse_arg]))            # (bytes, grid) of the shortcut
-        if other is None:
-            continue
-        readers = [c for (c, _pos) in e.consumers if conv_can_read(c)]
-        nxt = None
-        for c in readers:
-            cp = c.__dict__.get("_resident")
-            k = c.Conv
-            if (cp is not None and not cp.defer and not cp.grouped and cp.emit_int and not cp.emit_f32 and tracer.calls.get(c, 0) == 1
-                    and tuple(k.kernel_size) == (1, 1) and tuple(k.stride) == (1, 1) and tuple(k.padding) == (0, 0)
-                    and tuple(conv3.Conv.kernel_size) == (1, 1) and tuple(conv3.Conv.stride) == (1, 1)
-                    and tuple(conv3.Conv.padding) == (0, 0) and c.input_bit == plan.narrow_bit
-                    and conv3.Conv.out_channels == k.in_channels
-                    and _native.block_tail_supported(conv3.Conv.in_channels, conv3.Conv.out_channels, k.out_channels,
-                                                     conv3._rs(), c._rs(), conv3.output_bit, other[1], other[0],
-                                                     plan.narrow_bit)):
-                nxt = c
-                break
-        if nxt is not None:
-            plan.fuse_next = nxt
-            plan.narrow_to_hbm = len(readers) > 1
-            summary["fused_block_tails"] += 1
-    # ... and when the OTHER operand of such an add is a 1x1 projection of the block's input that nobody else reads (the first
-    # block of a stage), the kernel computes that convolution as well (fq_block_tail_proj_i8): its K3 bytes per pixel are neither
-    # written nor read back
-    summary["fused_projections"] = 0
-    for add_mod in add_resident:
-        plan = add_mod.__dict__.get("_resident")
-        if plan is None or plan.fuse_arg is None or plan.emit_f32 or not block_tail_enabled() or not block_tail_proj_enabled():
-            continue
-        ops = operands[add_mod]
-        v3, vp = ops[plan.fuse_arg], ops[1 - plan.fuse_arg]
-        conv3, proj = v3.producer, vp.producer
-        pp = proj.__dict__.get("_resident") if isinstance(proj, NewConv2d) else None
-        if (vp.kind != "contraction" or pp is None or pp.relu or pp.emit_f32 or pp.defer or pp.grouped or vp.foreign
-                or vp.consumers != [(add_mod, 1 - plan.fuse_arg)] or not conv_can_read(proj) or tracer.calls.get(proj, 0) != 1):
-            continue
-        k3, kp = conv3.Conv, proj.Conv
-        nxt = plan.fuse_next
-        if (tuple(kp.kernel_size) != (1, 1) or tuple(kp.padding) != (0, 0) or kp.stride[0] != kp.stride[1]
-                or tuple(k3.kernel_size) != (1, 1) or tuple(k3.stride) != (1, 1) or tuple(k3.padding) != (0, 0)
-                or kp.out_channels != k3.out_channels or (kp.out_channels % 16) or (kp.in_channels % 16)
-                or not _native.block_tail_proj_supported(k3.in_channels, k3.out_channels, nxt.Conv.out_channels if nxt is not None else 0,
-                                                         kp.in_channels, conv3._rs(), nxt._rs() if nxt is not None else 0,
-                                                         proj._rs(), kp.stride[0])):
-            continue
-        pp.defer = True
-        plan.fuse_proj = True
-        summary["fused_projections"] += 1
-    # a nearest upsampling whose value goes to one resident Concat and nowhere else is applied BY that Concat (its operand's `up`)
-    if concat:
-        summary["fused_upsamples"] = 0
-        for v in tracer.produced:
-            m = v.producer
-            plan = m.__dict__.get("_resident")
-            if v.kind != "upsample" or plan is None or plan.up is None or plan.relu or plan.emit_f32 or v.foreign:
-                continue
-            if len(v.consumers) != 1 or v.consumers[0][0] not in cat_resident or not isinstance(v.consumers[0][0], Concat):
-                continue
-            cat_mod, pos = v.consumers[0]
-            ops = operands[cat_mod]
-            ups = [1, 1]
-            ups[pos] = plan.up
-            if ops[pos] is not v or ops[1 - pos] is v or not _native.concat_supported([ops[0].shape[1], ops[1].shape[1]], ups):
-                continue
-            plan.defer = True
-            summary["fused_upsamples"] += 1
-    for m in tracer.avgpool_shapes:
-        if avg_can_read(m):
-            m.__dict__["forward"] = _AvgPoolResident(m)
-            summary["resident_pools"] += 1
-    model.__dict__["_fq_resident_enabled"] = True
+        planning.defer_upsamples()
+    planning.hook_global_pools()
+    planning.install(model)
     if verify:
         with torch.no_grad():
             planned_out = model(example_input)
@@ -849,7 +908,7 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
             _clear(model)
             raise _native.FqError("resident plan does not reproduce the fp32-boundary forward on the example input; "
                                   "plan removed (please report the model)")
-    return summary
+    return planning.summary
 
 
 def describe(model):
