@@ -401,6 +401,42 @@ int fq_dwconv_f32(const float* x, const float* w_crs, const float* bias, float* 
 int fq_dwconv_qd_f32(const float* x, const float* w_crs, const float* bias, float* y, int N, int C, int H, int W,
                      int R, int S, int stride, int pad, int bit, int bitwidth, fq_stream_t stream);
 
+/* The grouped float convolutions of the calibration forward that are not depthwise (nn.Conv2d with 1 < groups and at least 4
+ * channels per group: the sixteen 3x3 layers of model/resnext/ResNeXt_fabu.py), same epilogue contract as fq_conv1x1_f32 (bias
+ * may be NULL; relu_out may be NULL; with relu_out given y may be NULL and its statistic is still taken; exactly one of
+ * {max_inout, hist_row + interval} or neither):
+ *   y[n][k][oh][ow] = bias[k] + sum_{r,s,c} w[k][c][r][s] * x[n][g*Cgi + c][oh*stride - pad + r][ow*stride - pad + s],
+ *   Cgi = C / groups, Cgo = K / groups, g = k / Cgo.
+ * x: fp32 [N][C][H][W] contiguous; y / relu_out: fp32 [N][K][Ho][Wo], Ho = (H + 2 pad - R)/stride + 1; both below 2^30 elements.
+ * w_kcrs: the module's own weight, fp32 [K][Cgi][R][S] contiguous -- no packing step.  Pointers need only their type's
+ *   alignment (a y that is a view at an odd float offset is stored with narrower stores where a 16-byte one would be misaligned).
+ * Taken (fq_gconv_f32_supported, host arithmetic only; the layers fq_gconv2d_i8_supported takes, so that the calibration and
+ *   the resident plan agree on what a grouped layer is): groups >= 2, C % groups == 0, K % groups == 0, Cgi and Cgo multiples
+ *   of 4 in [4, 64] (not necessarily equal; depthwise layers stay with fq_dwconv_f32), R == S in {1, 3}, stride 1 or 2 on both
+ *   axes, dilation 1, zero padding 0 <= pad < R on both axes, H + 2 pad >= R and W + 2 pad >= R.  FQ_ERR_UNSUPPORTED for
+ *   everything else (and for an x, y or w of 2^30 elements or more): callers keep the library convolution there.
+ *   FQ_ERR_INVALID_ARG for a null or misaligned pointer, N, C, H, W, K, groups < 1 (or R, S, stride < 1, pad < 0), both
+ *   statistics at once, a histogram without its interval, or a bit / bitwidth outside fq_conv1x1_qd_f32's range.
+ * Numerics (part of the contract: the plain, abs-max, histogram and QuanDequan forms must see the same bits).  Per output:
+ *   acc = +0.0f
+ *   for r: for s: for c in 0 .. Cgi-1:
+ *       acc = fmaf(w[k][c][r][s], x[n][g*Cgi + c][oh*stride - pad + r][ow*stride - pad + s], acc)
+ *   y = acc + bias[k]                                                      (bias == NULL: acc + 0.0f)
+ *   A tap outside the image is the operand +0.0f -- never a value loaded from a neighbouring row, plane or group, never a
+ *   masked product (an Inf or NaN next to the padding stays where the reference has it).  No K split, no workspace, no atomics
+ *   on floats other than the abs-max publish.  The value depends on neither N nor the tile, lane or code path that computed
+ *   it: image i of a batch gets the bits of the same image alone.  Exact zeros are not counted by the histogram (the fast or
+ *   the IEEE quotient is chosen from the interval as in fq_conv1x1_f32); the abs-max ignores NaN.
+ * fq_gconv_qd_f32: TestConv.forward of such a layer in one kernel, fq_quandequan_f32(bit, bitwidth) of the value
+ *   fq_gconv_f32 would have stored. */
+int fq_gconv_f32_supported(int C, int K, int groups, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                           int dil_w, int H, int W);
+int fq_gconv_f32(const float* x, const float* w_kcrs, const float* bias, float* y, float* relu_out, int N, int C, int H, int W,
+                 int K, int groups, int R, int S, int stride, int pad, float* max_inout, const float* interval, int64_t* hist_row,
+                 fq_stream_t stream);
+int fq_gconv_qd_f32(const float* x, const float* w_kcrs, const float* bias, float* y, int N, int C, int H, int W, int K, int groups,
+                    int R, int S, int stride, int pad, int bit, int bitwidth, fq_stream_t stream);
+
 /* The last 1x1 convolution of a residual block together with the `Eltwise` that consumes it and the ReLU behind that
  * (fabu_layer.py:5-11 called from the model the reference runs at pytorch_quantizer.py:288-296), calibration pass 1, in ONE
  * kernel:  v = conv1x1(x) + bias  (abs-max folded into *max_y; stored to y unless y is NULL),  s = v + res  (abs-max folded

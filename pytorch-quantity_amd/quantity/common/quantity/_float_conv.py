@@ -1,8 +1,9 @@
 """The float convolutions this package runs on its own fp32 MFMA kernels instead of torch's (no reference counterpart: the
 reference calls torch's Conv2d.forward -- pytorch_quantizer.py:288-296 inside the calibration forward, new_quantity_op.py:283-292
 inside TestConv): 1x1 layers on fq_conv1x1_f32, R x S layers with zero padding (the 3x3 ones) on fq_conv_kxk_f32, the 7x7
-stride-2 stem on fq_conv_stem_f32 (csrc/) -- every convolution of a ResNet -- and, opt-in (FQ_OWN_DWCONV=1), the depthwise 3x3 /
-5x5 layers of a separable network on fq_dwconv_f32, so that the calibration forward is deterministic
+stride-2 stem on fq_conv_stem_f32 (csrc/) -- every convolution of a ResNet -- and, opt-in, the depthwise 3x3 / 5x5 layers of a
+separable network on fq_dwconv_f32 (FQ_OWN_DWCONV=1) and the grouped 1x1 / 3x3 layers of a ResNeXt-shaped one on fq_gconv_f32
+(FQ_OWN_GCONV=1), so that the calibration forward is deterministic
 and never enters the convolution library (whose first-use solver search costs seconds in a fresh process).  Which call qualifies, the
 weights in the kernels' layout (cached on the module), the once-per-process check of every module against an independent
 implementation of the same fp32 mathematics, and the plain (no statistic) forward.  Shared by tools.Quantity (which adds the
@@ -18,7 +19,7 @@ import torch
 
 from . import _native
 
-__all__ = ["enabled", "depthwise_enabled", "kind", "weight", "runner", "dw_reference", "verified", "plain", "call", "call_qd",
+__all__ = ["enabled", "depthwise_enabled", "grouped_enabled", "kind", "weight", "runner", "dw_reference", "g_reference", "verified", "plain", "call", "call_qd",
            "call_linear_qd", "state", "is_verified", "is_off", "forget", "kernel_key", "own_convs", "TOL"]
 
 TOL = 1e-5                                      # |own - torch| <= TOL * (|W| * |x| + |b|): summation order only
@@ -86,10 +87,34 @@ def _dw_ok(m, h, w):
             and h + 2 * p[0] >= k[0] and w + 2 * p[1] >= k[1])
 
 
-def kind(m, x, wino=True, depthwise=None):
+def grouped_enabled():
+    """FQ_OWN_GCONV=1 (read at call time; default off): grouped layers that are not depthwise run on fq_gconv_f32 instead of the
+    library's grouped convolution."""
+    return os.environ.get("FQ_OWN_GCONV", "0") == "1"
+
+
+def _g_ok(m, h, w):
+    """Does fq_gconv_f32 take the nn.Conv2d m on an h x w plane?  Host arithmetic on the module alone (what
+    fq_gconv_f32_supported answers for the same numbers, plus what the C ABI cannot see: the bias, the padding mode)."""
+    k, s, p, d, g = m.kernel_size, m.stride, m.padding, m.dilation, m.groups
+    if g < 2 or m.in_channels % g or m.out_channels % g or m.bias is None:
+        return False
+    cgi, cgo = m.in_channels // g, m.out_channels // g
+    return (cgi % 4 == 0 and cgo % 4 == 0 and 4 <= cgi <= 64 and 4 <= cgo <= 64
+            and tuple(k) in ((1, 1), (3, 3)) and tuple(s) in ((1, 1), (2, 2)) and tuple(d) == (1, 1)
+            and not isinstance(p, str) and m.padding_mode == "zeros" and p[0] == p[1] and 0 <= p[0] < k[0]
+            and h + 2 * p[0] >= k[0] and w + 2 * p[1] >= k[1])
+
+
+def _is_depthwise(m):
+    return m.groups == m.in_channels
+
+
+def kind(m, x, wino=True, depthwise=None, grouped=None):
     """"c1" (fq_conv1x1_f32), "kxk" (fq_conv_kxk_f32), "wino" (fq_conv3x3_wino_f32: the Winograd form of the stride-1 3x3
     layers; wino=False or FQ_CONV_WINO=0 keeps them on "kxk"), "stem" (fq_conv_stem_f32), "dw" (fq_dwconv_f32: a depthwise 3x3 /
-    5x5 layer, only with depthwise=True; None reads FQ_OWN_DWCONV) or None: which own kernel takes this call of the nn.Conv2d m.
+    5x5 layer, only with depthwise=True; None reads FQ_OWN_DWCONV), "g" (fq_gconv_f32: a grouped 1x1 / 3x3 layer with 4 .. 64
+    channels per group, only with grouped=True; None reads FQ_OWN_GCONV) or None: which own kernel takes this call of the nn.Conv2d m.
     Every kind has the plain, the statistic and the QuanDequan form, so TestConv's two ways through a layer (fused with
     QuanDequan, or not when somebody watches the module) see the same sums."""
     if (not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or m.weight.dtype != torch.float32 or m.bias is None
@@ -98,6 +123,10 @@ def kind(m, x, wino=True, depthwise=None):
             or x.numel() >= 2 ** 30 or x.shape[0] * m.out_channels * x.shape[2] * x.shape[3] >= 2 ** 30):
         return None
     if m.groups != 1:
+        if not _is_depthwise(m):                                # (a depthwise layer is never "g": fewer than 4 channels per group)
+            if not (grouped_enabled() if grouped is None else grouped):
+                return None
+            return "g" if _g_ok(m, x.shape[2], x.shape[3]) else None
         if not (depthwise_enabled() if depthwise is None else depthwise):
             return None
         return "dw" if _dw_ok(m, x.shape[2], x.shape[3]) else None
@@ -121,10 +150,10 @@ def kind(m, x, wino=True, depthwise=None):
 
 def weight(m, k):
     """The weights in the layout the kernel reads (Wt [Cin][Cout] / the packed stem matrix / the transformed Winograd
-    weights), one entry per kind, rebuilt when the parameter was written to or replaced.  "dw": the parameter itself
-    ([C][1][R][S] is the layout fq_dwconv_f32 reads)."""
+    weights), one entry per kind, rebuilt when the parameter was written to or replaced.  "dw" and "g": the parameter itself
+    ([C][1][R][S] and [K][C / groups][R][S] are the layouts fq_dwconv_f32 and fq_gconv_f32 read)."""
     w = m.weight
-    if k == "dw":
+    if k == "dw" or k == "g":
         return w.detach() if w.is_contiguous() else w.detach().contiguous()
     tag = (w._version, w.data_ptr(), w.device, _native.conv_sb_enabled())
     by_kind = state(m).setdefault("wt", {})
@@ -151,6 +180,8 @@ def runner(m, k, x):
         return lambda **kw: _native.conv_wino_f32(x, wq, m.bias, m.out_channels, **kw)
     if k == "dw":
         return lambda **kw: _native.dwconv_f32(x, wq, m.bias, m.kernel_size, s, m.padding[0], **kw)
+    if k == "g":
+        return lambda **kw: _native.gconv_f32(x, wq, m.bias, m.groups, m.kernel_size, s, m.padding[0], **kw)
     return lambda **kw: _native.conv_stem_f32(x, wq, m.bias, m.out_channels, m.kernel_size, s, m.padding[0], **kw)
 
 
@@ -164,6 +195,20 @@ def dw_reference(x, w, bias, kernel, stride, padding):
     wv = w.reshape(1, c, rs, 1)
     ref = (cols * wv).sum(2) + bias.view(1, -1, 1)
     bound = (cols.abs() * wv.abs()).sum(2) + bias.abs().view(1, -1, 1)
+    return ref, bound
+
+
+def g_reference(x, w, bias, groups, kernel, stride, padding):
+    """(reference, bound) of a grouped convolution WITHOUT the convolution library, on CPU or CUDA tensors: unfold, the columns
+    seen as [n, G, Cgi * R * S, L], one batched matmul with the weight seen as [G, Cgo, Cgi * R * S], the bias -- the same fp32
+    mathematics as fq_gconv_f32 in another order; bound is the same expression with absolute values, [n, K, L] both
+    (L = Ho * Wo)."""
+    n, k = x.shape[0], w.shape[0]
+    cols = torch.nn.functional.unfold(x, kernel, padding=padding, stride=stride)
+    cols = cols.view(n, groups, cols.shape[1] // groups, -1)
+    wv = w.reshape(groups, k // groups, -1)
+    ref = torch.matmul(wv, cols).view(n, k, -1) + bias.view(1, -1, 1)
+    bound = torch.matmul(wv.abs(), cols.abs()).view(n, k, -1) + bias.abs().view(1, -1, 1)
     return ref, bound
 
 
@@ -183,9 +228,9 @@ def verified(m, run, x, k=None):
     #  full-size temporary of `own.abs().max()` were allocator growth in a fresh process, most of the 0.16 s these checks cost a
     #  one-shot calibration of ResNet-50; round 5)
     n_all = int(x.shape[0])
-    if m.kernel_size == (1, 1):                                 # 1x1: a GEMM (rocBLAS through torch.matmul), 16 + 16 images
+    if m.kernel_size == (1, 1) and m.groups == 1:               # 1x1: a GEMM (rocBLAS through torch.matmul), 16 + 16 images
         per = 16
-    else:                                                       # R x S (the stem included): im2col (unfold) + GEMM, 8 + 8 images
+    else:                                                       # R x S (the stem, depthwise and grouped layers included): im2col (unfold) + GEMM, 8 + 8 images
         per = max(1, min(8, (1 << 27) // max(x[0].numel() * m.kernel_size[0] * m.kernel_size[1], 1)))
     groups = [(0, n_all)] if n_all <= 2 * per else [(0, per), (n_all - per, n_all)]
     w2 = m.weight.view(m.out_channels, -1)
@@ -196,7 +241,10 @@ def verified(m, run, x, k=None):
     for lo, hi in groups:
         xh = x[lo:hi]
         if m.groups != 1:                                       # depthwise: no GEMM to lean on, the products summed per channel
-            ref, bound = dw_reference(xh, m.weight, m.bias, m.kernel_size, m.stride, m.padding)
+            if _is_depthwise(m):
+                ref, bound = dw_reference(xh, m.weight, m.bias, m.kernel_size, m.stride, m.padding)
+            else:                                               # grouped: one batched GEMM over the groups
+                ref, bound = g_reference(xh, m.weight, m.bias, m.groups, m.kernel_size, m.stride, m.padding)
             ok = ok & ((own[lo:hi].reshape(hi - lo, m.out_channels, -1) - ref).abs() <= TOL * bound).all()
             del ref, bound
             continue

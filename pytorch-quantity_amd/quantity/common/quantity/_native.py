@@ -226,6 +226,12 @@ def lib():
     L.fq_dwconv_f32.argtypes = [vp, vp, vp, vp, vp] + [ci] * 8 + [vp, vp, vp, vp]
     L.fq_dwconv_qd_f32.restype = ci
     L.fq_dwconv_qd_f32.argtypes = [vp, vp, vp, vp] + [ci] * 10 + [vp]
+    L.fq_gconv_f32_supported.restype = ci
+    L.fq_gconv_f32_supported.argtypes = [ci] * 13
+    L.fq_gconv_f32.restype = ci
+    L.fq_gconv_f32.argtypes = [vp, vp, vp, vp, vp] + [ci] * 10 + [vp, vp, vp, vp]
+    L.fq_gconv_qd_f32.restype = ci
+    L.fq_gconv_qd_f32.argtypes = [vp, vp, vp, vp] + [ci] * 12 + [vp]
     L.fq_concat_i8_nhwc_supported.restype = ci
     L.fq_concat_i8_nhwc_supported.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci), ci]
     L.fq_concat_i8_nhwc.restype = ci
@@ -779,6 +785,55 @@ def dwconv_f32(x, w, bias, kernel, stride, pad, max_dev=None, interval_dev=None,
     _check(lib().fq_dwconv_f32(x.data_ptr(), w.data_ptr(), bp, None if y is None else y.data_ptr(),
                                _relu_ptr(relu_out, relu_out if y is None else y), N, C, H, W, R, S, st, pd, mp, ivp, hp, _stream(x)),
            "fq_dwconv_f32")
+    return y
+
+
+def gconv_f32_supported(c, k, groups, kernel, stride, pad, dilation, h, w):
+    """fq_gconv_f32_supported: does fq_gconv_f32 take this grouped geometry (c -> k channels in `groups` groups)?  kernel, stride,
+    pad, dilation: (h, w) pairs."""
+    return bool(lib().fq_gconv_f32_supported(int(c), int(k), int(groups), int(kernel[0]), int(kernel[1]), int(stride[0]),
+                                             int(stride[1]), int(pad[0]), int(pad[1]), int(dilation[0]), int(dilation[1]), int(h),
+                                             int(w)))
+
+
+def gconv_f32(x, w, bias, groups, kernel, stride, pad, max_dev=None, interval_dev=None, hist_dev=None, row=None, relu_out=None,
+              out=None, qd=None):
+    """fq_gconv_f32: the float grouped convolution (1 < groups, 4 .. 64 channels per group, zero padding `pad`, dilation 1) of
+    x [N, C, H, W] with the module's own weight w [K, C / groups, R, S]; statistics / relu_out / out / qd as in conv1x1_f32.
+    Returns y."""
+    _need_cuda(x, torch.float32, "fq_gconv_f32")
+    _need_cuda(w, torch.float32, "fq_gconv_f32")
+    R, S, G = int(kernel[0]), int(kernel[1]), int(groups)
+    assert x.dim() == 4 and x.is_contiguous() and w.is_contiguous() and w.dim() == 4 and G >= 1 and x.shape[1] % G == 0
+    assert tuple(w.shape[1:]) == (x.shape[1] // G, R, S)
+    N, C, H, W = (int(v) for v in x.shape)
+    K, st, pd = int(w.shape[0]), int(stride), int(pad)
+    shape = (N, K, (H + 2 * pd - R) // st + 1, (W + 2 * pd - S) // st + 1)
+    if out is False:                                            # only the ReLU's output is wanted: y is not written
+        assert relu_out is not None and qd is None and tuple(relu_out.shape) == shape
+        y = None
+    else:
+        y = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else out
+        assert tuple(y.shape) == shape and y.is_contiguous() and y.dtype == torch.float32 and y.is_cuda
+    if bias is not None:
+        _need_cuda(bias, torch.float32, "fq_gconv_f32")
+        assert bias.is_contiguous() and bias.numel() == K
+    bp = None if bias is None else bias.data_ptr()
+    if qd is not None:
+        bit, bw = _qd_args(qd, max_dev, hist_dev, relu_out, "fq_gconv_qd_f32")
+        _check(lib().fq_gconv_qd_f32(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), N, C, H, W, K, G, R, S, st, pd, bit, bw,
+                                     _stream(x)), "fq_gconv_qd_f32")
+        return y
+    mp = ivp = hp = None
+    if hist_dev is not None:
+        ivp, hp = _hist_row_ptrs(interval_dev, hist_dev, row)
+    elif max_dev is not None:
+        _need_cuda(max_dev, torch.float32, "fq_gconv_f32")
+        assert max_dev.is_contiguous() and 0 <= row < max_dev.numel()
+        mp = max_dev.data_ptr() + 4 * int(row)
+    _check(lib().fq_gconv_f32(x.data_ptr(), w.data_ptr(), bp, None if y is None else y.data_ptr(),
+                              _relu_ptr(relu_out, relu_out if y is None else y), N, C, H, W, K, G, R, S, st, pd, mp, ivp, hp,
+                              _stream(x)), "fq_gconv_f32")
     return y
 
 

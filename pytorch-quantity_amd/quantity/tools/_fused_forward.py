@@ -57,7 +57,7 @@ class _FusedForward(object):
         """Instance-level forwards for the duration of a GPU calibration (undo: del module.forward; returns the patched modules):
         every hooked nn.Conv2d with a bias leaves its work to its forward hook -- the whole convolution with the statistic in
         the epilogue where common.quantity._float_conv takes the layer (1x1, R x S with zero padding, the 7x7/2 stem, depthwise
-        3x3 / 5x5 with own_depthwise), else
+        3x3 / 5x5 with own_depthwise, grouped 1x1 / 3x3 with own_grouped -- never deferred into an Eltwise), else
         convolution-without-bias here and fq_bias_add_absmax_f32 / fq_bias_add_hist_f32 in the hook; `Eltwise` likewise
         (fq_add_absmax_f32 / fq_add_hist_f32); nn.MaxPool2d / a global nn.AvgPool2d run on fq_maxpool2d_f32 /
         fq_avgpool_global_f32; an out-of-place nn.ReLU fed by one of the producers hands out the copy that producer wrote."""
@@ -74,7 +74,7 @@ class _FusedForward(object):
                         or torch.is_grad_enabled()):
                     return torch.nn.Conv2d.forward(m, x)
                 if ctl.own_plain:                    # per-channel calibration: the convolution only, statistics by its hooks
-                    own = _float_conv.kind(m, x, depthwise=self.own_depthwise) if self.own_conv1x1 else None
+                    own = _float_conv.kind(m, x, depthwise=self.own_depthwise, grouped=self.own_grouped) if self.own_conv1x1 else None
                     if own is None:
                         return torch.nn.Conv2d.forward(m, x)
                     y = _float_conv.plain(m, own, x, check=ctl.own_plain != "unchecked")
@@ -85,7 +85,7 @@ class _FusedForward(object):
                     return torch.nn.Conv2d.forward(m, x)
                 if ctl.fuse_stat == "hist" and m not in ctl.fuse_verified:
                     return torch.nn.Conv2d.forward(m, x)    # pass 2 fuses verified modules only
-                own = _float_conv.kind(m, x, depthwise=self.own_depthwise) if self.own_conv1x1 else None
+                own = _float_conv.kind(m, x, depthwise=self.own_depthwise, grouped=self.own_grouped) if self.own_conv1x1 else None
                 if own is None and m not in ctl.fuse_warm and not _flag(m, _FUSION_VERIFIED):
                     ctl.fuse_warm.add(m)                 # the first call of a shape may run a one-off MIOpen kernel:
                     return torch.nn.Conv2d.forward(m, x)    # plain forward now, verification on the next batch

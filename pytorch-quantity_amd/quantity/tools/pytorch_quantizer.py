@@ -117,6 +117,9 @@ class Quantity(_FusedForward, _FileInputs):
     # Opt-in (FQ_OWN_DWCONV=1): the depthwise 3x3 / 5x5 layers of a separable network run on fq_dwconv_f32 with the statistic in
     # its epilogue, like the dense layers above, instead of the library's grouped convolution + the bias-add producer
     own_depthwise = _float_conv.depthwise_enabled()
+    # Opt-in (FQ_OWN_GCONV=1): the grouped 1x1 / 3x3 layers of a ResNeXt-shaped network (4 .. 64 channels per group) run on
+    # fq_gconv_f32 in the same way
+    own_grouped = _float_conv.grouped_enabled()
     # A residual sum both of whose operands pass 2's cache keeps anyway (conv3's output; the shortcut = the previous block's ReLU
     # output or the projection) is not written by pass 1: the cache keeps the shortcut in the sum's place and pass 2 histograms
     # (conv3 output, conv3 output + shortcut) in one pass over the pair (fq_hist2048_pair_seg).  Same integers.
