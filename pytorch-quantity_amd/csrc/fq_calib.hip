@@ -36,7 +36,6 @@ constexpr int kWgPerCUAbsmax = 2;
 constexpr int kWgPerCUHist = 2;
 constexpr uint32_t kChunkVec = 4 * 256;   // 16-byte vectors per chunk: one workgroup step (4 loads in flight per lane) = 16 KB
 constexpr uint32_t kMinChunksPerWg = 4;   // at least 64 KB per workgroup, so zeroing + flushing 2048 bins stays amortised
-constexpr int kHistFastQuotientDefault = 1;   // exhaustive proof: profiles/r01_verify_fastdiv.log
 
 // 16-byte streaming load.  The statistics kernels read every activation exactly once and a calibration batch
 // (8.6 GB for ResNet-50 at batch 128) is far larger than the 256 MB Infinity Cache, so the lines are marked
@@ -781,15 +780,6 @@ static int for_each_chan_chunk(const fq_chan_seg* segs, int nseg, Launch&& launc
 // ---------------------------------------------------------------------------------------------
 // host side: tiling and chunked launches
 // ---------------------------------------------------------------------------------------------
-// FQ_HIST_IEEE_DIV=1 forces the IEEE divide sequence (A/B timing, paranoia).
-static int hist_fast_quotient_enabled() {
-    static const int v = [] {
-        const char* e = getenv("FQ_HIST_IEEE_DIV");
-        return (e && e[0] && e[0] != '0') ? 0 : kHistFastQuotientDefault;
-    }();
-    return v;
-}
-
 // FQ_WG_PER_CU overrides the workgroups per CU of both statistics kernels (tuning knob).
 static int wg_per_cu(int default_per_cu) {
     static const int env_per_cu = [] {
@@ -884,7 +874,7 @@ extern "C" int fq_hist2048_seg(const fq_seg* segs, int nseg, const float* interv
     hipStream_t st = as_stream(stream);
     return for_each_chunk(segs, nseg, kWgPerCUHist, [&](const SegTable& tab, uint32_t wgs) -> int {
         hipLaunchKernelGGL(hist2048_seg_kernel, dim3(wgs), dim3(kHistBlock), 0, st, tab, interval,
-                           reinterpret_cast<unsigned long long*>(hist), hist_fast_quotient_enabled());
+                           reinterpret_cast<unsigned long long*>(hist), hist_fast_quotient_allowed());
         FQ_LAUNCH_CHECK();
         return FQ_OK;
     });
@@ -901,9 +891,9 @@ extern "C" int fq_hist_seg_n(const fq_seg* segs, int nseg, const float* interval
     hipStream_t st = as_stream(stream);
     return for_each_chunk(segs, nseg, kWgPerCUHist, [&](const SegTable& tab, uint32_t wgs) -> int {
         unsigned long long* h = reinterpret_cast<unsigned long long*>(hist);
-        if (bins == 512) hipLaunchKernelGGL(hist_seg_n_kernel<512>, dim3(wgs), dim3(kHistBlock), 0, st, tab, interval, h, hist_fast_quotient_enabled());
-        else if (bins == 1024) hipLaunchKernelGGL(hist_seg_n_kernel<1024>, dim3(wgs), dim3(kHistBlock), 0, st, tab, interval, h, hist_fast_quotient_enabled());
-        else hipLaunchKernelGGL(hist_seg_n_kernel<4096>, dim3(wgs), dim3(kHistBlock), 0, st, tab, interval, h, hist_fast_quotient_enabled());
+        if (bins == 512) hipLaunchKernelGGL(hist_seg_n_kernel<512>, dim3(wgs), dim3(kHistBlock), 0, st, tab, interval, h, hist_fast_quotient_allowed());
+        else if (bins == 1024) hipLaunchKernelGGL(hist_seg_n_kernel<1024>, dim3(wgs), dim3(kHistBlock), 0, st, tab, interval, h, hist_fast_quotient_allowed());
+        else hipLaunchKernelGGL(hist_seg_n_kernel<4096>, dim3(wgs), dim3(kHistBlock), 0, st, tab, interval, h, hist_fast_quotient_allowed());
         FQ_LAUNCH_CHECK();
         return FQ_OK;
     });
@@ -915,7 +905,7 @@ static int launch_chain_tb(const ChainArgs<L>& a, uint64_t chunks, uint64_t per_
     static bool lds_ok[kMaxDevices] = {};
     if (lds > 64 * 1024 && !ensure_dynamic_lds(reinterpret_cast<const void*>(hist2048_chain_kernel<L, TB>), (int)lds, lds_ok)) return FQ_ERR_UNSUPPORTED;
     hipLaunchKernelGGL((hist2048_chain_kernel<L, TB>), dim3((uint32_t)((chunks + per_wg - 1) / per_wg)), dim3(TB), lds, st, a, interval,
-                       reinterpret_cast<unsigned long long*>(hist), hist_fast_quotient_enabled());
+                       reinterpret_cast<unsigned long long*>(hist), hist_fast_quotient_allowed());
     FQ_LAUNCH_CHECK();
     return FQ_OK;
 }
@@ -1033,7 +1023,7 @@ extern "C" int fq_hist2048_pair_seg(const fq_pair_seg* segs, int nseg, const flo
         tab.chunks_per_wg = (uint32_t)per_wg;
         tab.total_chunks = (uint32_t)chunks;
         hipLaunchKernelGGL(hist2048_pair_seg_kernel, dim3((uint32_t)((chunks + per_wg - 1) / per_wg)), dim3(kHistBlock), 0, st, tab, interval,
-                           reinterpret_cast<unsigned long long*>(hist), hist_fast_quotient_enabled());
+                           reinterpret_cast<unsigned long long*>(hist), hist_fast_quotient_allowed());
         FQ_LAUNCH_CHECK();
     }
     return FQ_OK;
@@ -1061,7 +1051,7 @@ extern "C" int fq_hist2048_chan(const fq_chan_seg* segs, int nseg, const float* 
     const bool own_ok = !(own_env && own_env[0] == '0');
     return for_each_chan_chunk(segs, nseg, [&](const ChanTable& tab, uint32_t wgs) -> int {
         hipLaunchKernelGGL(hist2048_chan_kernel, dim3(wgs), dim3(kHistBlock), 0, st, tab, interval,
-                           reinterpret_cast<unsigned long long*>(hist), hist_fast_quotient_enabled());
+                           reinterpret_cast<unsigned long long*>(hist), hist_fast_quotient_allowed());
         FQ_LAUNCH_CHECK();
         return FQ_OK;
     }, own_ok && (reinterpret_cast<uintptr_t>(hist) & 15u) == 0);

@@ -42,6 +42,10 @@ constexpr int kCUs = 256;          // MI355X
 
 inline bool valid_bitwidth(int bw) { return bw == 8 || bw == 16; }
 
+// May the histogram kernels bin with the fast quotient (exhaustive proof: profiles/r01_verify_fastdiv.log)?  FQ_HIST_IEEE_DIV=1
+// forces the IEEE divide sequence (A/B timing, paranoia); read once per process, at the first call (fq_host.cpp).
+int hist_fast_quotient_allowed();
+
 // More than 64 KB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize, and that attribute is PER DEVICE: a
 // process that drives a second GPU must opt in there too (a function-local "done once" flag, what round 3 had, made the launch
 // on the second device fail after the dispatch had already committed to the kernel).  One flag per kernel AND device; the

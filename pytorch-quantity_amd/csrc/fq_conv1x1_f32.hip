@@ -75,10 +75,6 @@ struct C1Args {
 #define FQ_C1_OFF(bit) false
 #endif
 
-struct NoStat {
-    __device__ __forceinline__ void add(float) {}
-};
-
 // the add form's pair of statistics: the convolution output's and the sum's running abs-max
 // (kMayStore = false: the form that never writes the two tensors themselves -- pass 2, where nothing is kept)
 template <typename SC, typename SS, bool kStores>
@@ -1039,7 +1035,7 @@ int conv_f32_launch(const float* x, const float* wt, const float* bias, float* y
 #endif
     hipStream_t st = as_stream(stream);
     static const int hist_per_cu = env_int("FQ_CONV1X1_HIST_WG_PER_CU", 0);   // 0: what the occupancy query says
-    static const int fast = [] { const char* e = getenv("FQ_HIST_IEEE_DIV"); return (e && e[0] && e[0] != '0') ? 0 : 1; }();
+    const int fast = hist_fast_quotient_allowed();
     const int mode = taps ? 2 : ((Cin % kBK) != 0 ? 1 : 0);
     // tile shape: 128 x 128; 64 x 128 for the 64-channel layers (a 128-row tile would be half empty) and for launches whose
     // 128 x 128 tiles would not even fill the 1 024 resident slots once (1024 -> 256 @14x14 at 256 images: 784 tiles leave
@@ -1126,13 +1122,13 @@ static int conv_add_launch(const float* x, const float* wt_in, const unsigned sh
     a.tiles_m = (unsigned)Cout / (narrow ? 64u : 128u);
     a.tiles = (unsigned)((cols + 127) / 128) * a.tiles_m;
     if (wsb) {
-        static const int fast_sb = [] { const char* e = getenv("FQ_HIST_IEEE_DIV"); return (e && e[0] && e[0] != '0') ? 0 : 1; }();
+        const int fast_sb = hist_fast_quotient_allowed();
         if (narrow) return launch_sb<1, 2>(a, nullptr, nullptr, nullptr, fast_sb, nullptr, interval_y, hist_y, interval_sum, hist_sum, max_y, max_sum, true, workspace, workspace_bytes, st);
         return launch_sb<2, 2>(a, nullptr, nullptr, nullptr, fast_sb, nullptr, interval_y, hist_y, interval_sum, hist_sum, max_y, max_sum, true, workspace, workspace_bytes, st);
     }
     plan_split(a, (unsigned)Cin / (unsigned)(narrow ? step_of<1>() : step_of<2>()), workspace, workspace_bytes);
     if (hist) {
-        static const int fast = [] { const char* e = getenv("FQ_HIST_IEEE_DIV"); return (e && e[0] && e[0] != '0') ? 0 : 1; }();
+        const int fast = hist_fast_quotient_allowed();
         static const int res12 = [] {
             int n = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv1x1_f32_add_hist_kernel<1, 2>, kT, 0) != hipSuccess || n < 1) n = 1;
@@ -1183,18 +1179,11 @@ extern "C" int fq_conv1x1_add_hist_f32(const float* x, const float* wt, const fl
 // TestConv.forward (new_quantity_op.py:283-292) / TestLinear.forward (:248-256 on the classifier seen as a 1x1 layer) in one
 // kernel: y = QuanDequan(conv(x) + bias, bit).  The value QuanDequan sees is the kernel's own fp32 sum -- the same one
 // fq_conv1x1_f32 / fq_conv_kxk_f32 would have stored -- so the result equals fq_quandequan_f32 of their output bit for bit.
-static bool qd_params(int bit, int bitwidth, QdStat* qd) {
-    if ((bitwidth != 8 && bitwidth != 16) || bit < -120 || bit > 120) return false;
-    qd->scale = ldexpf(1.0f, bit); qd->inv = ldexpf(1.0f, -bit);
-    qd->lo = bitwidth == 8 ? -128.0f : -32768.0f; qd->hi = bitwidth == 8 ? 127.0f : 32767.0f;
-    return true;
-}
-
 extern "C" int fq_conv1x1_qd_f32(const float* x, const float* wt, const float* bias, float* y, int N, int Cin, int Hin, int Win,
                                  int Cout, int stride, int bit, int bitwidth, void* workspace, size_t workspace_bytes,
                                  fq_stream_t stream) {
     QdStat qd;
-    if (!qd_params(bit, bitwidth, &qd)) return FQ_ERR_INVALID_ARG;
+    if (!qd_from_bit(bit, bitwidth, &qd)) return FQ_ERR_INVALID_ARG;
     return conv_f32_launch(x, wt, bias, y, nullptr, N, Cin, Hin, Win, Cout, 1, 1, stride, 0, nullptr, nullptr, nullptr, workspace,
                            workspace_bytes, stream, &qd);
 }
@@ -1203,7 +1192,7 @@ extern "C" int fq_conv_kxk_qd_f32(const float* x, const float* wt, const float* 
                                   int Cout, int R, int S, int stride, int pad, int bit, int bitwidth, void* workspace,
                                   size_t workspace_bytes, fq_stream_t stream) {
     QdStat qd;
-    if (!qd_params(bit, bitwidth, &qd)) return FQ_ERR_INVALID_ARG;
+    if (!qd_from_bit(bit, bitwidth, &qd)) return FQ_ERR_INVALID_ARG;
     return conv_f32_launch(x, wt, bias, y, nullptr, N, Cin, Hin, Win, Cout, R, S, stride, pad, nullptr, nullptr, nullptr, workspace,
                            workspace_bytes, stream, &qd);
 }
@@ -1235,7 +1224,7 @@ extern "C" int fq_conv1x1_sb_qd_f32(const float* x, const void* wsb, const float
                                     int Cout, int stride, int bit, int bitwidth, void* workspace, size_t workspace_bytes,
                                     fq_stream_t stream) {
     QdStat qd;
-    if (!wsb || !qd_params(bit, bitwidth, &qd)) return FQ_ERR_INVALID_ARG;
+    if (!wsb || !qd_from_bit(bit, bitwidth, &qd)) return FQ_ERR_INVALID_ARG;
     return conv_f32_launch(x, nullptr, bias, y, nullptr, N, Cin, Hin, Win, Cout, 1, 1, stride, 0, nullptr, nullptr, nullptr, workspace,
                            workspace_bytes, stream, &qd, static_cast<const unsigned short*>(wsb));
 }

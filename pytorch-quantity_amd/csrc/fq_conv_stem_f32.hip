@@ -56,10 +56,6 @@ struct StemArgs {
     unsigned x_bytes, y_bytes;
 };
 
-struct NoStat {
-    __device__ __forceinline__ void add(float) {}
-};
-
 template <int I>
 struct Buf {
     static constexpr int value = I;
@@ -336,8 +332,7 @@ static int stem_launch(const float* x, const float* wp, const float* bias, float
     a.x_bytes = (unsigned)(in_elems * 4);
     a.y_bytes = (unsigned)(out_elems * 4);
     a.stream_stores = out_elems * (relu_out && y ? 8 : 4) > ((size_t)256 << 20);
-    static const int fast = [] { const char* e = getenv("FQ_HIST_IEEE_DIV"); return (e && e[0] && e[0] != '0') ? 0 : 1; }();
-    const int rc = launch_stem<3, 7, 7>(a, max_inout, interval, hist_row, fast, qd, as_stream(stream));
+    const int rc = launch_stem<3, 7, 7>(a, max_inout, interval, hist_row, hist_fast_quotient_allowed(), qd, as_stream(stream));
     if (rc != FQ_OK) return rc;
     FQ_LAUNCH_CHECK();
     return FQ_OK;
@@ -352,9 +347,7 @@ extern "C" int fq_conv_stem_f32(const float* x, const float* wp, const float* bi
 // TestConv.forward of the stem in one kernel: y = QuanDequan(conv(x) + bias, bit) (fq_conv1x1_qd_f32's contract)
 extern "C" int fq_conv_stem_qd_f32(const float* x, const float* wp, const float* bias, float* y, int N, int Cin, int H, int W,
                                    int Cout, int R, int S, int stride, int pad, int bit, int bitwidth, fq_stream_t stream) {
-    if ((bitwidth != 8 && bitwidth != 16) || bit < -120 || bit > 120) return FQ_ERR_INVALID_ARG;
     QdStat qd;
-    qd.scale = ldexpf(1.0f, bit); qd.inv = ldexpf(1.0f, -bit);
-    qd.lo = bitwidth == 8 ? -128.0f : -32768.0f; qd.hi = bitwidth == 8 ? 127.0f : 32767.0f;
+    if (!qd_from_bit(bit, bitwidth, &qd)) return FQ_ERR_INVALID_ARG;
     return stem_launch(x, wp, bias, y, nullptr, N, Cin, H, W, Cout, R, S, stride, pad, nullptr, nullptr, nullptr, &qd, stream);
 }

@@ -93,10 +93,6 @@ struct WArgs {
     int stream_stores;
 };
 
-struct NoStat {
-    __device__ __forceinline__ void add(float) {}
-};
-
 __device__ __forceinline__ void stat_add_if(NoStat&, bool, float) {}
 __device__ __forceinline__ void stat_add_if(QdStat&, bool, float) {}
 __device__ __forceinline__ void stat_add_if(MaxStat& s, bool ok, float v) { s.add(ok ? v : 0.0f); }
@@ -484,9 +480,8 @@ static int wino_launch_geo(WArgs a, float* max_inout, const float* interval, int
         hipLaunchKernelGGL(wino_f32_qd_kernel<WT>, dim3(grid), dim3(G::kT), G::kLdsBytes, st, a, *qd);
     } else if (hist_row) {
         if (!ensure_dynamic_lds(reinterpret_cast<const void*>(wino_f32_hist_kernel<WT>), (int)G::kLdsBytes, done_hist)) return FQ_ERR_HIP;
-        static const int fast = [] { const char* e = getenv("FQ_HIST_IEEE_DIV"); return (e && e[0] && e[0] != '0') ? 0 : 1; }();
         hipLaunchKernelGGL(wino_f32_hist_kernel<WT>, dim3(grid), dim3(G::kT), G::kLdsBytes, st, a, interval,
-                           reinterpret_cast<unsigned long long*>(hist_row), fast);
+                           reinterpret_cast<unsigned long long*>(hist_row), hist_fast_quotient_allowed());
     } else if (max_inout) {
         if (!ensure_dynamic_lds(reinterpret_cast<const void*>(wino_f32_absmax_kernel<WT>), (int)G::kLdsBytes, done_max)) return FQ_ERR_HIP;
         hipLaunchKernelGGL(wino_f32_absmax_kernel<WT>, dim3(grid), dim3(G::kT), G::kLdsBytes, st, a, reinterpret_cast<unsigned int*>(max_inout));
@@ -533,9 +528,7 @@ extern "C" int fq_conv3x3_wino_f32(const float* x, const float* u, const float* 
 // fq_quandequan_f32 of its output bit for bit.
 extern "C" int fq_conv3x3_wino_qd_f32(const float* x, const float* u, const float* bias, float* y, int N, int Cin, int Hin, int Win,
                                       int Cout, int bit, int bitwidth, fq_stream_t stream) {
-    if ((bitwidth != 8 && bitwidth != 16) || bit < -120 || bit > 120 || !y) return FQ_ERR_INVALID_ARG;
     QdStat qd;
-    qd.scale = ldexpf(1.0f, bit); qd.inv = ldexpf(1.0f, -bit);
-    qd.lo = bitwidth == 8 ? -128.0f : -32768.0f; qd.hi = bitwidth == 8 ? 127.0f : 32767.0f;
+    if (!qd_from_bit(bit, bitwidth, &qd) || !y) return FQ_ERR_INVALID_ARG;
     return wino_launch(x, u, bias, y, nullptr, N, Cin, Hin, Win, Cout, nullptr, nullptr, nullptr, &qd, stream);
 }

@@ -17,7 +17,7 @@
 //   * the R x S weights and the bias of the tile's planes are staged next to the input and read into registers once per tile;
 //   * at most 2048 workgroups (1024 in the histogram form, which flushes 2048 bins per workgroup), each walking its tiles.
 // Row-band halos (2 or 4 rows of a 16- to 18-row band) are re-read by the neighbouring tile, which an XCD's run of
-// consecutive tiles (dwf_first_tile) keeps in one L2.
+// consecutive tiles (geom_first_tile) keeps in one L2.
 //
 // Numerics: one chain per output whatever N, the tile or the lane is -- every form of the kernel stores the same bits, and
 // image i of a batch gets the bits of the same image alone.  No split, no workspace, no float atomics but publish_max's.
@@ -41,11 +41,6 @@ struct DwfArgs {
     DwfGeom g;
 };
 
-struct DwfNoStat {
-    __device__ __forceinline__ void add(float) {}
-};
-struct DwfHistTag {};                  // the histogram form: HistStat<fast> or HistStat<slow>, chosen by the interval at run time
-
 template <int R, int STRIDE, typename Stat>
 __device__ __forceinline__ void dwf_tiles(const DwfArgs& a, Stat& stat, float* smem) {
     constexpr int RR = R * R, WS = RR + 1;                        // a slot's weights and its bias
@@ -57,7 +52,7 @@ __device__ __forceinline__ void dwf_tiles(const DwfArgs& a, Stat& stat, float* s
     const unsigned rd0 = lp.active ? dwf_read_index(g, lp) : 0u;
     const unsigned nw = (unsigned)g.PP * WS;
 
-    for (unsigned tile = dwf_first_tile(blockIdx.x, gridDim.x); tile < g.tiles; tile += gridDim.x) {
+    for (unsigned tile = geom_first_tile(blockIdx.x, gridDim.x); tile < g.tiles; tile += gridDim.x) {
         const DwfTilePos tp = dwf_tile_pos(g, tile);
         // stage: four loads in flight per lane, then their LDS stores
         for (unsigned e0 = tid; e0 < g.fill; e0 += 4u * kT) {
@@ -143,18 +138,10 @@ __device__ __forceinline__ void dwf_tiles(const DwfArgs& a, Stat& stat, float* s
     }
 }
 
-struct DwfStatArgs {
-    unsigned int* max_bits;
-    const float* interval;
-    unsigned long long* hist_row;
-    int allow_fast;
-    QdStat qd;
-};
-
 template <int R, int STRIDE, typename Stat>
-__global__ __launch_bounds__(kT) void dwconv_f32_kernel(const DwfArgs a, const DwfStatArgs sa) {
+__global__ __launch_bounds__(kT) void dwconv_f32_kernel(const DwfArgs a, const ProducerStatArgs sa) {
     __shared__ __attribute__((aligned(16))) float smem[kDwfLdsFloats + kDwfMaxPP * (R * R + 1)];
-    if constexpr (__is_same(Stat, DwfHistTag)) {
+    if constexpr (__is_same(Stat, HistTag)) {
         __shared__ unsigned int s_bins[FQ_BINS + kWave];
         for (int b = threadIdx.x; b < FQ_BINS + kWave; b += kT) s_bins[b] = 0u;
         __syncthreads();
@@ -176,13 +163,13 @@ __global__ __launch_bounds__(kT) void dwconv_f32_kernel(const DwfArgs a, const D
         QdStat st = sa.qd;
         dwf_tiles<R, STRIDE>(a, st, smem);
     } else {
-        DwfNoStat st;
+        NoStat st;
         dwf_tiles<R, STRIDE>(a, st, smem);
     }
 }
 
 template <typename Stat>
-void dwf_launch(int R, int stride, unsigned grid, hipStream_t st, const DwfArgs& a, const DwfStatArgs& sa) {
+void dwf_launch(int R, int stride, unsigned grid, hipStream_t st, const DwfArgs& a, const ProducerStatArgs& sa) {
     if (R == 3 && stride == 1) hipLaunchKernelGGL((dwconv_f32_kernel<3, 1, Stat>), dim3(grid), dim3(kT), 0, st, a, sa);
     else if (R == 3) hipLaunchKernelGGL((dwconv_f32_kernel<3, 2, Stat>), dim3(grid), dim3(kT), 0, st, a, sa);
     else if (stride == 1) hipLaunchKernelGGL((dwconv_f32_kernel<5, 1, Stat>), dim3(grid), dim3(kT), 0, st, a, sa);
@@ -197,13 +184,7 @@ bool dwf_supported(int C, int R, int S, int stride_h, int stride_w, int pad_h, i
 int dwf_dispatch(const float* x, const float* w, const float* bias, float* y, float* relu_out, int N, int C, int H, int W, int R, int S,
                  int stride, int pad, float* max_inout, const float* interval, int64_t* hist_row, const QdStat* qd, fq_stream_t stream) {
     if (N < 1 || C < 1 || H < 1 || W < 1 || R < 1 || S < 1 || stride < 1 || pad < 0) return FQ_ERR_INVALID_ARG;
-    if (max_inout && hist_row) return FQ_ERR_INVALID_ARG;
-    if (hist_row && !interval) return FQ_ERR_INVALID_ARG;
-    if (!x || !w || (!y && (!relu_out || qd))) return FQ_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(y) |
-         reinterpret_cast<uintptr_t>(relu_out) | reinterpret_cast<uintptr_t>(max_inout) | reinterpret_cast<uintptr_t>(interval)) & 3u)
-        return FQ_ERR_INVALID_ARG;
-    if (reinterpret_cast<uintptr_t>(hist_row) & 7u) return FQ_ERR_INVALID_ARG;
+    if (const int rc = producer_args_ok(x, w, bias, y, relu_out, max_inout, interval, hist_row, qd)) return rc;
     if (!dwf_supported(C, R, S, stride, stride, pad, pad, 1, 1, H, W)) return FQ_ERR_UNSUPPORTED;
     const long Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
     // 32-bit element offsets into x and y
@@ -211,19 +192,18 @@ int dwf_dispatch(const float* x, const float* w, const float* bias, float* y, fl
     DwfArgs a;
     a.x = x; a.w = w; a.bias = bias; a.y = y; a.relu = relu_out; a.C = (unsigned)C;
     if (!dwf_plan(a.g, N, C, H, W, R, stride, pad)) return FQ_ERR_UNSUPPORTED;
-    DwfStatArgs sa;
+    ProducerStatArgs sa;
     sa.max_bits = reinterpret_cast<unsigned int*>(max_inout);
     sa.interval = interval;
     sa.hist_row = reinterpret_cast<unsigned long long*>(hist_row);
-    static const int fast = [] { const char* e = getenv("FQ_HIST_IEEE_DIV"); return (e && e[0] && e[0] != '0') ? 0 : 1; }();
-    sa.allow_fast = fast;
+    sa.allow_fast = hist_fast_quotient_allowed();
     sa.qd = qd ? *qd : QdStat{1.0f, 1.0f, -128.0f, 127.0f};
     hipStream_t st = as_stream(stream);
     const unsigned grid = dwf_grid(a.g, hist_row != nullptr);
     if (qd) dwf_launch<QdStat>(R, stride, grid, st, a, sa);
-    else if (hist_row) dwf_launch<DwfHistTag>(R, stride, grid, st, a, sa);
+    else if (hist_row) dwf_launch<HistTag>(R, stride, grid, st, a, sa);
     else if (max_inout) dwf_launch<MaxStat>(R, stride, grid, st, a, sa);
-    else dwf_launch<DwfNoStat>(R, stride, grid, st, a, sa);
+    else dwf_launch<NoStat>(R, stride, grid, st, a, sa);
     FQ_LAUNCH_CHECK();
     return FQ_OK;
 }
@@ -247,9 +227,7 @@ extern "C" int fq_dwconv_f32(const float* x, const float* w_crs, const float* bi
 // TestConv.forward of a depthwise layer in one kernel: QuanDequan(bit) of the value fq_dwconv_f32 would have stored
 extern "C" int fq_dwconv_qd_f32(const float* x, const float* w_crs, const float* bias, float* y, int N, int C, int H, int W, int R,
                                 int S, int stride, int pad, int bit, int bitwidth, fq_stream_t stream) {
-    if ((bitwidth != 8 && bitwidth != 16) || bit < -120 || bit > 120) return FQ_ERR_INVALID_ARG;
     QdStat qd;
-    qd.scale = ldexpf(1.0f, bit); qd.inv = ldexpf(1.0f, -bit);
-    qd.lo = bitwidth == 8 ? -128.0f : -32768.0f; qd.hi = bitwidth == 8 ? 127.0f : 32767.0f;
+    if (!qd_from_bit(bit, bitwidth, &qd)) return FQ_ERR_INVALID_ARG;
     return dwf_dispatch(x, w_crs, bias, y, nullptr, N, C, H, W, R, S, stride, pad, nullptr, nullptr, nullptr, &qd, stream);
 }

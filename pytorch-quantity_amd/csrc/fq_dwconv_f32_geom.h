@@ -8,17 +8,12 @@
 // tile with the PP - 1 planes behind it (they are contiguous in NCHW: 18 planes of 7 x 7 per tile); a larger plane is cut
 // into RB row bands x CB column blocks and PP is 1.
 #pragma once
-
-#if defined(__HIPCC__)
-#define FQ_DWF_HD __host__ __device__ __forceinline__
-#else
-#define FQ_DWF_HD inline
-#endif
+#include "fq_f32_geom_common.h"
 
 namespace fq {
 
 constexpr int kDwfBlock = 256;             // threads per workgroup = output strips per tile
-constexpr int kDwfStrip = 4;               // output columns per lane: one 16-byte store
+constexpr int kDwfStrip = kGeomStrip;              // output columns per lane: one 16-byte store
 constexpr int kDwfMaxQW = 16;              // strips per tile row: 64 output columns
 constexpr int kDwfMaxPP = 32;              // plane slots per tile
 constexpr int kDwfLdsFloats = 5120;        // staged input of one tile (20 KB)
@@ -36,9 +31,6 @@ struct DwfGeom {
     unsigned m_slot, m_pitch;              // ceil(2^32 / slot), ceil(2^32 / IWP): e / d = mulhi(e, m) for e * d < 2^32
 };
 
-// input columns a strip reads: (4 - 1) * stride + R, rounded up to whole 16-byte LDS reads
-FQ_DWF_HD int dwf_strip_reads(int R, int stride) { return ((kDwfStrip - 1) * stride + R + 3) / 4; }
-
 // The plan: a function of the layer's shape alone (never of the statistic that rides on the launch).
 inline bool dwf_plan(DwfGeom& g, int N, int C, int H, int W, int R, int stride, int pad) {
     if (N < 1 || C < 1 || H < 1 || W < 1 || (R != 3 && R != 5) || (stride != 1 && stride != 2) || pad < 0 || pad >= R ||
@@ -50,7 +42,7 @@ inline bool dwf_plan(DwfGeom& g, int N, int C, int H, int W, int R, int stride, 
     const int strips = (g.Wo + kDwfStrip - 1) / kDwfStrip;
     g.QW = strips < kDwfMaxQW ? strips : kDwfMaxQW;
     g.CB = (strips + g.QW - 1) / g.QW;
-    g.IWP = (g.QW - 1) * kDwfStrip * stride + 4 * dwf_strip_reads(R, stride);
+    g.IWP = (g.QW - 1) * kDwfStrip * stride + 4 * geom_strip_reads(R, stride);
     int th = kDwfBlock / g.QW;
     const int th_lds = (kDwfLdsFloats / g.IWP - R) / stride + 1;          // ((TH - 1) stride + R) IWP <= kDwfLdsFloats
     if (th > th_lds) th = th_lds;
@@ -80,18 +72,9 @@ inline unsigned dwf_grid(const DwfGeom& g, bool hist) {
     return g.tiles < cap ? g.tiles : cap;
 }
 
-// Workgroup b of G runs on XCD b % 8, each with its own L2: an XCD takes a contiguous run of tiles, so the row bands
-// that share halo rows meet in one L2.  Then every workgroup steps by G.
-FQ_DWF_HD unsigned dwf_first_tile(unsigned b, unsigned G) {
-    const unsigned G8 = G & ~7u;
-    return b < G8 ? (b & 7u) * (G8 >> 3) + (b >> 3) : b;
-}
-
-FQ_DWF_HD unsigned dwf_mulhi(unsigned a, unsigned m) { return (unsigned)(((unsigned long long)a * m) >> 32); }
-
 // tile -> first plane, first output row, first output column (column block fastest, then row band, then plane group)
 struct DwfTilePos { unsigned plane0; int oh0, ow0; };
-FQ_DWF_HD DwfTilePos dwf_tile_pos(const DwfGeom& g, unsigned tile) {
+FQ_GEOM_HD DwfTilePos dwf_tile_pos(const DwfGeom& g, unsigned tile) {
     DwfTilePos t;
     const unsigned per = (unsigned)(g.RB * g.CB), grp = tile / per, rest = tile - grp * per;
     const unsigned rb = rest / (unsigned)g.CB, cb = rest - rb * (unsigned)g.CB;
@@ -103,7 +86,7 @@ FQ_DWF_HD DwfTilePos dwf_tile_pos(const DwfGeom& g, unsigned tile) {
 
 // lane -> (plane slot, output row of the tile, strip of that row); the same for every tile of a launch
 struct DwfLanePos { int pi, t, q; bool active; };
-FQ_DWF_HD DwfLanePos dwf_lane_pos(const DwfGeom& g, unsigned tid) {
+FQ_GEOM_HD DwfLanePos dwf_lane_pos(const DwfGeom& g, unsigned tid) {
     DwfLanePos l;
     const unsigned per = (unsigned)(g.TH * g.QW);
     l.pi = (int)(tid / per);
@@ -116,9 +99,9 @@ FQ_DWF_HD DwfLanePos dwf_lane_pos(const DwfGeom& g, unsigned tid) {
 
 // Staging: LDS float e of the tile <- input pixel (plane0 + pi, ih0 + r, iw0 + col), or +0.0f outside the image (and behind
 // the last plane).  Returns whether it is a load; *off is then its element offset into x.
-FQ_DWF_HD bool dwf_fill_src(const DwfGeom& g, const DwfTilePos& tp, unsigned e, unsigned* off) {
-    const unsigned pi = dwf_mulhi(e, g.m_slot), rem = e - pi * g.slot;
-    const unsigned r = dwf_mulhi(rem, g.m_pitch), col = rem - r * (unsigned)g.IWP;
+FQ_GEOM_HD bool dwf_fill_src(const DwfGeom& g, const DwfTilePos& tp, unsigned e, unsigned* off) {
+    const unsigned pi = geom_mulhi(e, g.m_slot), rem = e - pi * g.slot;
+    const unsigned r = geom_mulhi(rem, g.m_pitch), col = rem - r * (unsigned)g.IWP;
     const int ih = tp.oh0 * g.stride - g.pad + (int)r, iw = tp.ow0 * g.stride - g.pad + (int)col;
     const unsigned plane = tp.plane0 + pi;
     const bool ok = plane < g.planes && (unsigned)ih < (unsigned)g.H && (unsigned)iw < (unsigned)g.W;
@@ -127,17 +110,17 @@ FQ_DWF_HD bool dwf_fill_src(const DwfGeom& g, const DwfTilePos& tp, unsigned e, 
 }
 
 // first LDS float of the lane's strip in staged row 0 of its window (kernel row r adds r * IWP); 16-byte aligned
-FQ_DWF_HD unsigned dwf_read_index(const DwfGeom& g, const DwfLanePos& l) {
+FQ_GEOM_HD unsigned dwf_read_index(const DwfGeom& g, const DwfLanePos& l) {
     return (unsigned)l.pi * g.slot + (unsigned)(l.t * g.stride * g.IWP + l.q * kDwfStrip * g.stride);
 }
 
 // the lane's strip in y: how many of its 4 outputs exist (0: none), and the element offset of the first
-FQ_DWF_HD int dwf_out_count(const DwfGeom& g, const DwfTilePos& tp, const DwfLanePos& l) {
+FQ_GEOM_HD int dwf_out_count(const DwfGeom& g, const DwfTilePos& tp, const DwfLanePos& l) {
     const int oh = tp.oh0 + l.t, ow = tp.ow0 + l.q * kDwfStrip;
     if (!l.active || tp.plane0 + (unsigned)l.pi >= g.planes || oh >= g.Ho || ow >= g.Wo) return 0;
     return g.Wo - ow < kDwfStrip ? g.Wo - ow : kDwfStrip;
 }
-FQ_DWF_HD unsigned dwf_out_off(const DwfGeom& g, const DwfTilePos& tp, const DwfLanePos& l) {
+FQ_GEOM_HD unsigned dwf_out_off(const DwfGeom& g, const DwfTilePos& tp, const DwfLanePos& l) {
     return ((tp.plane0 + (unsigned)l.pi) * (unsigned)g.Ho + (unsigned)(tp.oh0 + l.t)) * (unsigned)g.Wo +
            (unsigned)(tp.ow0 + l.q * kDwfStrip);
 }

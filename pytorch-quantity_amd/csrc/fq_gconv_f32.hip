@@ -40,11 +40,6 @@ struct GfArgs {
     GfGeom g;
 };
 
-struct GfNoStat {
-    __device__ __forceinline__ void add(float) {}
-};
-struct GfHistTag {};                   // the histogram form: HistStat<fast> or HistStat<slow>, chosen by the interval at run time
-
 template <int R, int STRIDE, typename Stat>
 __device__ __forceinline__ void gf_tiles(const GfArgs& a, Stat& stat, float* smem) {
     constexpr int NRD = ((kGfStrip - 1) * STRIDE + R + 3) / 4;    // 16-byte LDS reads per strip and kernel row
@@ -59,7 +54,7 @@ __device__ __forceinline__ void gf_tiles(const GfArgs& a, Stat& stat, float* sme
     const int Cgi = g.Cgi, KC = g.KC;
     const unsigned slot = g.slot;
 
-    for (unsigned tile = gf_first_tile(blockIdx.x, gridDim.x); tile < g.tiles; tile += gridDim.x) {
+    for (unsigned tile = geom_first_tile(blockIdx.x, gridDim.x); tile < g.tiles; tile += gridDim.x) {
         const GfTilePos tp = gf_tile_pos(g, tile);
         // stage the input: four loads in flight per lane, then their LDS stores
         for (unsigned e0 = tid; e0 < g.fill; e0 += 4u * kT) {
@@ -171,18 +166,10 @@ __device__ __forceinline__ void gf_tiles(const GfArgs& a, Stat& stat, float* sme
     }
 }
 
-struct GfStatArgs {
-    unsigned int* max_bits;
-    const float* interval;
-    unsigned long long* hist_row;
-    int allow_fast;
-    QdStat qd;
-};
-
 template <int R, int STRIDE, typename Stat>
-__global__ __launch_bounds__(kT) void gconv_f32_kernel(const GfArgs a, const GfStatArgs sa) {
+__global__ __launch_bounds__(kT) void gconv_f32_kernel(const GfArgs a, const ProducerStatArgs sa) {
     __shared__ __attribute__((aligned(16))) float smem[kGfLdsFloats];
-    if constexpr (__is_same(Stat, GfHistTag)) {
+    if constexpr (__is_same(Stat, HistTag)) {
         __shared__ unsigned int s_bins[FQ_BINS + kWave];
         for (int b = threadIdx.x; b < FQ_BINS + kWave; b += kT) s_bins[b] = 0u;
         __syncthreads();
@@ -204,13 +191,13 @@ __global__ __launch_bounds__(kT) void gconv_f32_kernel(const GfArgs a, const GfS
         QdStat st = sa.qd;
         gf_tiles<R, STRIDE>(a, st, smem);
     } else {
-        GfNoStat st;
+        NoStat st;
         gf_tiles<R, STRIDE>(a, st, smem);
     }
 }
 
 template <typename Stat>
-void gf_launch(int R, int stride, unsigned grid, hipStream_t st, const GfArgs& a, const GfStatArgs& sa) {
+void gf_launch(int R, int stride, unsigned grid, hipStream_t st, const GfArgs& a, const ProducerStatArgs& sa) {
     if (R == 3 && stride == 1) hipLaunchKernelGGL((gconv_f32_kernel<3, 1, Stat>), dim3(grid), dim3(kT), 0, st, a, sa);
     else if (R == 3) hipLaunchKernelGGL((gconv_f32_kernel<3, 2, Stat>), dim3(grid), dim3(kT), 0, st, a, sa);
     else if (stride == 1) hipLaunchKernelGGL((gconv_f32_kernel<1, 1, Stat>), dim3(grid), dim3(kT), 0, st, a, sa);
@@ -221,13 +208,7 @@ int gf_dispatch(const float* x, const float* w, const float* bias, float* y, flo
                 int groups, int R, int S, int stride, int pad, float* max_inout, const float* interval, int64_t* hist_row,
                 const QdStat* qd, fq_stream_t stream) {
     if (N < 1 || C < 1 || H < 1 || W < 1 || K < 1 || groups < 1 || R < 1 || S < 1 || stride < 1 || pad < 0) return FQ_ERR_INVALID_ARG;
-    if (max_inout && hist_row) return FQ_ERR_INVALID_ARG;
-    if (hist_row && !interval) return FQ_ERR_INVALID_ARG;
-    if (!x || !w || (!y && (!relu_out || qd))) return FQ_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(y) |
-         reinterpret_cast<uintptr_t>(relu_out) | reinterpret_cast<uintptr_t>(max_inout) | reinterpret_cast<uintptr_t>(interval)) & 3u)
-        return FQ_ERR_INVALID_ARG;
-    if (reinterpret_cast<uintptr_t>(hist_row) & 7u) return FQ_ERR_INVALID_ARG;
+    if (const int rc = producer_args_ok(x, w, bias, y, relu_out, max_inout, interval, hist_row, qd)) return rc;
     if (!gf_supported(C, K, groups, R, S, stride, stride, pad, pad, 1, 1, H, W)) return FQ_ERR_UNSUPPORTED;
     const long Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
     // 32-bit element offsets into x, y and w
@@ -236,19 +217,18 @@ int gf_dispatch(const float* x, const float* w, const float* bias, float* y, flo
     GfArgs a;
     a.x = x; a.w = w; a.bias = bias; a.y = y; a.relu = relu_out;
     if (!gf_plan(a.g, N, C, H, W, K, groups, R, stride, pad)) return FQ_ERR_UNSUPPORTED;
-    GfStatArgs sa;
+    ProducerStatArgs sa;
     sa.max_bits = reinterpret_cast<unsigned int*>(max_inout);
     sa.interval = interval;
     sa.hist_row = reinterpret_cast<unsigned long long*>(hist_row);
-    static const int fast = [] { const char* e = getenv("FQ_HIST_IEEE_DIV"); return (e && e[0] && e[0] != '0') ? 0 : 1; }();
-    sa.allow_fast = fast;
+    sa.allow_fast = hist_fast_quotient_allowed();
     sa.qd = qd ? *qd : QdStat{1.0f, 1.0f, -128.0f, 127.0f};
     hipStream_t st = as_stream(stream);
     const unsigned grid = gf_grid(a.g, hist_row != nullptr);
     if (qd) gf_launch<QdStat>(R, stride, grid, st, a, sa);
-    else if (hist_row) gf_launch<GfHistTag>(R, stride, grid, st, a, sa);
+    else if (hist_row) gf_launch<HistTag>(R, stride, grid, st, a, sa);
     else if (max_inout) gf_launch<MaxStat>(R, stride, grid, st, a, sa);
-    else gf_launch<GfNoStat>(R, stride, grid, st, a, sa);
+    else gf_launch<NoStat>(R, stride, grid, st, a, sa);
     FQ_LAUNCH_CHECK();
     return FQ_OK;
 }
@@ -273,9 +253,7 @@ extern "C" int fq_gconv_f32(const float* x, const float* w_kcrs, const float* bi
 // TestConv.forward of a grouped layer in one kernel: QuanDequan(bit) of the value fq_gconv_f32 would have stored
 extern "C" int fq_gconv_qd_f32(const float* x, const float* w_kcrs, const float* bias, float* y, int N, int C, int H, int W, int K,
                                int groups, int R, int S, int stride, int pad, int bit, int bitwidth, fq_stream_t stream) {
-    if ((bitwidth != 8 && bitwidth != 16) || bit < -120 || bit > 120) return FQ_ERR_INVALID_ARG;
     QdStat qd;
-    qd.scale = ldexpf(1.0f, bit); qd.inv = ldexpf(1.0f, -bit);
-    qd.lo = bitwidth == 8 ? -128.0f : -32768.0f; qd.hi = bitwidth == 8 ? 127.0f : 32767.0f;
+    if (!qd_from_bit(bit, bitwidth, &qd)) return FQ_ERR_INVALID_ARG;
     return gf_dispatch(x, w_kcrs, bias, y, nullptr, N, C, H, W, K, groups, R, S, stride, pad, nullptr, nullptr, nullptr, &qd, stream);
 }

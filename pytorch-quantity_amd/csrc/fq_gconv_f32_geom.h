@@ -9,17 +9,12 @@
 // everything that is left the group's Cgi input windows (IH rows of pitch IWP each, zero halo included) one behind the other:
 // a group of few channels gets tall tiles, a group of many channels still gets its 4096 floats.
 #pragma once
-
-#if defined(__HIPCC__)
-#define FQ_GF_HD __host__ __device__ __forceinline__
-#else
-#define FQ_GF_HD inline
-#endif
+#include "fq_f32_geom_common.h"
 
 namespace fq {
 
 constexpr int kGfBlock = 256;              // threads per workgroup
-constexpr int kGfStrip = 4;                // output columns per lane: one 16-byte store per channel
+constexpr int kGfStrip = kGeomStrip;               // output columns per lane: one 16-byte store per channel
 constexpr int kGfKB = 4;                   // output channels per lane: one 16-byte weight read per (tap, c)
 constexpr int kGfMaxQW = 16;               // strips per tile row: 64 output columns
 constexpr int kGfMaxKC = 64;               // output channels per tile
@@ -43,9 +38,6 @@ struct GfGeom {
     unsigned b0, x0, in_floats;            // LDS float offsets of the bias (= wfill) and of the input; floats the input may take
     unsigned m_slot, m_pitch, m_ckr, m_rr; // ceil(2^32 / d) of slot, IWP, ckr, RR: e / d = mulhi(e, m) for e * d < 2^32
 };
-
-// input columns a strip reads: (4 - 1) * stride + R, rounded up to whole 16-byte LDS reads
-FQ_GF_HD int gf_strip_reads(int R, int stride) { return ((kGfStrip - 1) * stride + R + 3) / 4; }
 
 inline bool gf_supported(int C, int K, int groups, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
                          int dil_w, int H, int W) {
@@ -73,7 +65,7 @@ inline bool gf_plan(GfGeom& g, int N, int C, int H, int W, int K, int groups, in
     g.x0 = g.wfill + (unsigned)kGfMaxKC;
     g.in_floats = (unsigned)kGfLdsFloats - g.x0;                          // >= kGfMinInFloats
     const int slot_max = (int)g.in_floats / g.Cgi;                        // >= 64
-    const int strips = (g.Wo + kGfStrip - 1) / kGfStrip, nrd = gf_strip_reads(R, stride);
+    const int strips = (g.Wo + kGfStrip - 1) / kGfStrip, nrd = geom_strip_reads(R, stride);
     // every width of a column block: the blocks made evenly wide and the row bands evenly tall, then the widest one, unless a
     // narrower one keeps 15 % more lanes busy (a wide tile stores long row segments)
     int best = 0;
@@ -108,19 +100,10 @@ inline unsigned gf_grid(const GfGeom& g, bool hist) {
     return g.tiles < cap ? g.tiles : cap;
 }
 
-// Workgroup b of G runs on XCD b % 8, each with its own L2: an XCD takes a contiguous run of tiles, so the tiles that share
-// a group's input (its channel chunks, the row bands with their halo rows) meet in one L2.  Then every workgroup steps by G.
-FQ_GF_HD unsigned gf_first_tile(unsigned b, unsigned G) {
-    const unsigned G8 = G & ~7u;
-    return b < G8 ? (b & 7u) * (G8 >> 3) + (b >> 3) : b;
-}
-
-FQ_GF_HD unsigned gf_mulhi(unsigned a, unsigned m) { return (unsigned)(((unsigned long long)a * m) >> 32); }
-
 // tile -> image, group, first output channel of the chunk (within the group), first output row, first output column
 // (column block fastest, then row band, then channel chunk, then group, then image)
 struct GfTilePos { unsigned n, grp; int k0, oh0, ow0; };
-FQ_GF_HD GfTilePos gf_tile_pos(const GfGeom& g, unsigned tile) {
+FQ_GEOM_HD GfTilePos gf_tile_pos(const GfGeom& g, unsigned tile) {
     GfTilePos t;
     const unsigned sp = (unsigned)(g.RB * g.CB), per = (unsigned)g.KCN * sp;
     const unsigned u = tile / per, rest = tile - u * per;
@@ -136,7 +119,7 @@ FQ_GF_HD GfTilePos gf_tile_pos(const GfGeom& g, unsigned tile) {
 
 // lane -> (channel block of the chunk, output row of the tile, strip of that row); the same for every tile of a launch
 struct GfLanePos { int kb, t, q; bool active; };
-FQ_GF_HD GfLanePos gf_lane_pos(const GfGeom& g, unsigned tid) {
+FQ_GEOM_HD GfLanePos gf_lane_pos(const GfGeom& g, unsigned tid) {
     GfLanePos l;
     const unsigned per = (unsigned)(g.TH * g.QW);
     l.kb = (int)(tid / per);
@@ -149,9 +132,9 @@ FQ_GF_HD GfLanePos gf_lane_pos(const GfGeom& g, unsigned tid) {
 
 // Input staging: LDS float e (< fill) of the tile <- input pixel (n, grp * Cgi + c, ih0 + r, iw0 + col), or +0.0f outside the
 // image.  Returns whether it is a load; *off is then its element offset into x.
-FQ_GF_HD bool gf_fill_src(const GfGeom& g, const GfTilePos& tp, unsigned e, unsigned* off) {
-    const unsigned c = gf_mulhi(e, g.m_slot), rem = e - c * g.slot;
-    const unsigned r = gf_mulhi(rem, g.m_pitch), col = rem - r * (unsigned)g.IWP;
+FQ_GEOM_HD bool gf_fill_src(const GfGeom& g, const GfTilePos& tp, unsigned e, unsigned* off) {
+    const unsigned c = geom_mulhi(e, g.m_slot), rem = e - c * g.slot;
+    const unsigned r = geom_mulhi(rem, g.m_pitch), col = rem - r * (unsigned)g.IWP;
     const int ih = tp.oh0 * g.stride - g.pad + (int)r, iw = tp.ow0 * g.stride - g.pad + (int)col;
     const bool ok = (unsigned)ih < (unsigned)g.H && (unsigned)iw < (unsigned)g.W;
     const unsigned plane = tp.n * (unsigned)g.C + tp.grp * (unsigned)g.Cgi + c;
@@ -162,9 +145,9 @@ FQ_GF_HD bool gf_fill_src(const GfGeom& g, const GfTilePos& tp, unsigned e, unsi
 // Weight staging: element i (< wfill) of the chunk's run of w_kcrs -- (kk, c, tap), the module's own order -- goes to the LDS
 // weight float *dst = (tap * Cgi + c) * KC + kk.  Returns whether it is a load (a channel behind the group's last is +0.0f);
 // *off is then its element offset into w.
-FQ_GF_HD bool gf_w_src(const GfGeom& g, const GfTilePos& tp, unsigned i, unsigned* off, unsigned* dst) {
-    const unsigned kk = gf_mulhi(i, g.m_ckr), rem = i - kk * g.ckr;
-    const unsigned c = g.RR == 1 ? rem : gf_mulhi(rem, g.m_rr), tap = rem - c * (unsigned)g.RR;     // (2^32 / 1 has no 32-bit form)
+FQ_GEOM_HD bool gf_w_src(const GfGeom& g, const GfTilePos& tp, unsigned i, unsigned* off, unsigned* dst) {
+    const unsigned kk = geom_mulhi(i, g.m_ckr), rem = i - kk * g.ckr;
+    const unsigned c = g.RR == 1 ? rem : geom_mulhi(rem, g.m_rr), tap = rem - c * (unsigned)g.RR;     // (2^32 / 1 has no 32-bit form)
     *dst = (tap * (unsigned)g.Cgi + c) * (unsigned)g.KC + kk;
     const bool ok = tp.k0 + (int)kk < g.Cgo;
     *off = ok ? (tp.grp * (unsigned)g.Cgo + (unsigned)tp.k0) * g.ckr + i : 0u;
@@ -173,22 +156,22 @@ FQ_GF_HD bool gf_w_src(const GfGeom& g, const GfTilePos& tp, unsigned i, unsigne
 
 // first float of the lane's strip in staged row 0 of channel 0, counted from the input's LDS offset x0 (channel c adds
 // c * slot, kernel row r adds r * IWP); 16-byte aligned
-FQ_GF_HD unsigned gf_read_index(const GfGeom& g, const GfLanePos& l) {
+FQ_GEOM_HD unsigned gf_read_index(const GfGeom& g, const GfLanePos& l) {
     return (unsigned)(l.t * g.stride * g.IWP + l.q * kGfStrip * g.stride);
 }
 // the lane's 4 weights of (tap, c) in the LDS weight block; 16-byte aligned
-FQ_GF_HD unsigned gf_w_index(const GfGeom& g, const GfLanePos& l, int tap, int c) {
+FQ_GEOM_HD unsigned gf_w_index(const GfGeom& g, const GfLanePos& l, int tap, int c) {
     return (unsigned)((tap * g.Cgi + c) * g.KC + l.kb * kGfKB);
 }
 
 // the lane's strip in y: how many of its 4 columns exist (0: none; its 4 channels exist together or not at all), and the
 // element offset of the first column of channel kk of its block
-FQ_GF_HD int gf_out_count(const GfGeom& g, const GfTilePos& tp, const GfLanePos& l) {
+FQ_GEOM_HD int gf_out_count(const GfGeom& g, const GfTilePos& tp, const GfLanePos& l) {
     const int oh = tp.oh0 + l.t, ow = tp.ow0 + l.q * kGfStrip;
     if (!l.active || tp.k0 + l.kb * kGfKB >= g.Cgo || oh >= g.Ho || ow >= g.Wo) return 0;
     return g.Wo - ow < kGfStrip ? g.Wo - ow : kGfStrip;
 }
-FQ_GF_HD unsigned gf_out_off(const GfGeom& g, const GfTilePos& tp, const GfLanePos& l, int kk) {
+FQ_GEOM_HD unsigned gf_out_off(const GfGeom& g, const GfTilePos& tp, const GfLanePos& l, int kk) {
     const unsigned plane = tp.n * (unsigned)g.K + tp.grp * (unsigned)g.Cgo + (unsigned)(tp.k0 + l.kb * kGfKB + kk);
     return (plane * (unsigned)g.Ho + (unsigned)(tp.oh0 + l.t)) * (unsigned)g.Wo + (unsigned)(tp.ow0 + l.q * kGfStrip);
 }

@@ -1,6 +1,7 @@
 // fq_host.cpp -- host-only entry points of libfq_hip.so: version/status, and the two scalar formulas
 // of the reference that must run on the host libm to reproduce CPython's math.log(x, 2) bit for bit.
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <thread>
 #include <vector>
@@ -21,6 +22,11 @@ extern "C" const char* fq_status_string(int status) {
         case FQ_ERR_UNSUPPORTED: return "FQ_ERR_UNSUPPORTED";
         default: return "FQ_ERR_UNKNOWN";
     }
+}
+
+int fq::hist_fast_quotient_allowed() {
+    static const int v = [] { const char* e = getenv("FQ_HIST_IEEE_DIV"); return (e && e[0] && e[0] != '0') ? 0 : 1; }();
+    return v;
 }
 
 extern "C" int fq_last_hip_error(void) { return fq::g_last_hip_error; }

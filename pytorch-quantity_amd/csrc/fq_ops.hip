@@ -416,9 +416,9 @@ __global__ __launch_bounds__(kOpsBlock) void quantize_param_i32_kernel(const flo
 using namespace fq;
 
 extern "C" int fq_quandequan_f32(const float* x, float* y, size_t n, int bit, int bitwidth, fq_stream_t stream) {
-    if (!valid_bitwidth(bitwidth) || bit < -120 || bit > 120) return FQ_ERR_INVALID_ARG;
-    const Range r = range_of(bitwidth);
-    return launch_unary(x, y, n, QuanDequanOp{ldexpf(1.0f, bit), ldexpf(1.0f, -bit), r.lo, r.hi}, stream);
+    QdStat qd;
+    if (!qd_from_bit(bit, bitwidth, &qd)) return FQ_ERR_INVALID_ARG;
+    return launch_unary(x, y, n, QuanDequanOp{qd.scale, qd.inv, qd.lo, qd.hi}, stream);
 }
 
 extern "C" int fq_quantity_f32(const float* x, float* y, size_t n, int ib, int bitwidth, fq_stream_t stream) {
@@ -579,11 +579,6 @@ extern "C" int fq_add_absmax_f32(const float* x, const float* y, float* z, size_
     return FQ_OK;
 }
 
-static int ops_hist_fast_quotient() {          // FQ_HIST_IEEE_DIV=1 forces the IEEE divide sequence (as in fq_calib.hip)
-    static const int v = [] { const char* e = getenv("FQ_HIST_IEEE_DIV"); return (e && e[0] && e[0] != '0') ? 0 : 1; }();
-    return v;
-}
-
 extern "C" int fq_bias_add_hist_f32(float* y, const float* bias, int N, int C, int HW, const float* interval,
                                     int64_t* hist_row, float* relu_out, fq_stream_t stream) {
     using namespace fq;
@@ -598,13 +593,13 @@ extern "C" int fq_bias_add_hist_f32(float* y, const float* bias, int N, int C, i
         const unsigned nvec = (unsigned)(n >> 2);
         if (n * (relu_out ? 12 : 8) > kStreamBytes)
             hipLaunchKernelGGL((bias_add_hist_kernel<true, true>), dim3(grid_for(nvec, producer_wg_per_cu(8))), dim3(kOpsBlock), 0, st, y, bias,
-                               nvec, (unsigned)(HW >> 2), (unsigned)C, interval, h, relu_out, ops_hist_fast_quotient());
+                               nvec, (unsigned)(HW >> 2), (unsigned)C, interval, h, relu_out, hist_fast_quotient_allowed());
         else
             hipLaunchKernelGGL((bias_add_hist_kernel<true, false>), dim3(grid_for(nvec, 2)), dim3(kOpsBlock), 0, st, y, bias, nvec,
-                               (unsigned)(HW >> 2), (unsigned)C, interval, h, relu_out, ops_hist_fast_quotient());
+                               (unsigned)(HW >> 2), (unsigned)C, interval, h, relu_out, hist_fast_quotient_allowed());
     } else {
         hipLaunchKernelGGL((bias_add_hist_kernel<false, false>), dim3(grid_for(n, 2)), dim3(kOpsBlock), 0, st, y, bias, (unsigned)n,
-                           (unsigned)HW, (unsigned)C, interval, h, relu_out, ops_hist_fast_quotient());
+                           (unsigned)HW, (unsigned)C, interval, h, relu_out, hist_fast_quotient_allowed());
     }
     FQ_LAUNCH_CHECK();
     return FQ_OK;
@@ -624,12 +619,12 @@ extern "C" int fq_add_hist_f32(const float* x, const float* y, float* z, size_t 
         hipLaunchKernelGGL(add_hist_kernel<true>, dim3(grid_for(nvec, producer_wg_per_cu(4))), dim3(kOpsBlock), 0, as_stream(stream),
                            reinterpret_cast<const f4v*>(x), reinterpret_cast<const f4v*>(y), reinterpret_cast<f4v*>(z), nvec,
                            x + (nvec << 2), y + (nvec << 2), z + (nvec << 2), tail, interval,
-                           reinterpret_cast<unsigned long long*>(hist_row), relu_out, ops_hist_fast_quotient());
+                           reinterpret_cast<unsigned long long*>(hist_row), relu_out, hist_fast_quotient_allowed());
     else
         hipLaunchKernelGGL(add_hist_kernel<false>, dim3(grid_for(nvec ? nvec : 1, 2)), dim3(kOpsBlock), 0, as_stream(stream),
                            reinterpret_cast<const f4v*>(x), reinterpret_cast<const f4v*>(y), reinterpret_cast<f4v*>(z), nvec,
                            x + (nvec << 2), y + (nvec << 2), z + (nvec << 2), tail, interval,
-                           reinterpret_cast<unsigned long long*>(hist_row), relu_out, ops_hist_fast_quotient());
+                           reinterpret_cast<unsigned long long*>(hist_row), relu_out, hist_fast_quotient_allowed());
     FQ_LAUNCH_CHECK();
     return FQ_OK;
 }

@@ -1,7 +1,8 @@
 // fq_producer_stat.h -- what a producer kernel does with each output value while it is still in registers: the running
 // abs-max of calibration pass 1 (distribution_collector.py:70-78) or the 2048-bin histogram of pass 2
 // (distribution_collector.py:127-135).  Shared by the elementwise producers (fq_ops.hip) and the fp32 1x1 convolution
-// (fq_conv1x1_f32.hip).
+// (fq_conv1x1_f32.hip), and by every other float convolution of the calibration forward: what rides on such a convolution's
+// output -- nothing, the abs-max, the histogram, a ReLU copy, or QuanDequan -- is written here once.
 #pragma once
 #include "fq_common.h"
 #include "fq_hist_bin.h"
@@ -12,6 +13,11 @@ namespace fq {
 // (the obvious  v > 0 ? v : (v != v ? v : 0)  is two compares, a scalar or and the select -- and every vector instruction of an
 // epilogue is time the matrix pipe does not get)
 __device__ __forceinline__ float relu_like_torch(float v) { return !(v <= 0.0f) ? v : 0.0f; }
+
+struct NoStat {
+    __device__ __forceinline__ void add(float) {}
+};
+struct HistTag {};                                            // the histogram form: HistStat<fast> or HistStat<slow>, chosen by the interval at run time
 
 struct MaxStat {
     float m = 0.0f;
@@ -28,6 +34,14 @@ struct QdStat {
         return (q < lo ? lo : (q > hi ? hi : q)) * inv;       // NaN fails both compares and passes through
     }
 };
+// host: the map of QuanDequan(bit) at a bit width; false for a bit width other than 8 / 16 or a bit outside [-120, 120]
+inline bool qd_from_bit(int bit, int bitwidth, QdStat* qd) {
+    if (!valid_bitwidth(bitwidth) || bit < -120 || bit > 120) return false;
+    qd->scale = ldexpf(1.0f, bit); qd->inv = ldexpf(1.0f, -bit);
+    qd->lo = bitwidth == 8 ? -128.0f : -32768.0f; qd->hi = bitwidth == 8 ? 127.0f : 32767.0f;
+    return true;
+}
+
 template <typename S> __device__ __forceinline__ float stat_map(const S&, float v) { return v; }
 __device__ __forceinline__ float stat_map(const QdStat& s, float v) { return s.map(v); }
 
@@ -62,6 +76,29 @@ __device__ __forceinline__ void hist_flush(unsigned int* s_bins, unsigned long l
         const unsigned int c = s_bins[b];
         if (c) atomicAdd(dst + b, (unsigned long long)c);
     }
+}
+
+// what a producer kernel's launch carries for whichever statistic it was instantiated on
+struct ProducerStatArgs {
+    unsigned int* max_bits;
+    const float* interval;
+    unsigned long long* hist_row;
+    int allow_fast;
+    QdStat qd;
+};
+
+// host: the pointer rules the producers share -- one statistic at most, an interval with the histogram, y unless only the ReLU
+// copy is wanted (never with QuanDequan), 4-byte aligned floats and an 8-byte aligned histogram row
+inline int producer_args_ok(const float* x, const float* w, const float* bias, const float* y, const float* relu_out,
+                            const float* max_inout, const float* interval, const int64_t* hist_row, const QdStat* qd) {
+    if (max_inout && hist_row) return FQ_ERR_INVALID_ARG;
+    if (hist_row && !interval) return FQ_ERR_INVALID_ARG;
+    if (!x || !w || (!y && (!relu_out || qd))) return FQ_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(y) |
+         reinterpret_cast<uintptr_t>(relu_out) | reinterpret_cast<uintptr_t>(max_inout) | reinterpret_cast<uintptr_t>(interval)) & 3u)
+        return FQ_ERR_INVALID_ARG;
+    if (reinterpret_cast<uintptr_t>(hist_row) & 7u) return FQ_ERR_INVALID_ARG;
+    return FQ_OK;
 }
 
 }  // namespace fq

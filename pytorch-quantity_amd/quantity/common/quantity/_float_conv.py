@@ -77,14 +77,20 @@ def depthwise_enabled():
     return os.environ.get("FQ_OWN_DWCONV", "0") == "1"
 
 
+def _window_ok(m, h, w, kernels):
+    """What the depthwise and the grouped kernel ask of the window alike: a square kernel out of `kernels`, stride 1 or 2, no
+    dilation, symmetric zero padding smaller than the kernel, and a padded plane no smaller than the kernel."""
+    k, s, p, d = m.kernel_size, m.stride, m.padding, m.dilation
+    return (tuple(k) in kernels and tuple(s) in ((1, 1), (2, 2)) and tuple(d) == (1, 1)
+            and not isinstance(p, str) and m.padding_mode == "zeros" and p[0] == p[1] and 0 <= p[0] < k[0]
+            and h + 2 * p[0] >= k[0] and w + 2 * p[1] >= k[1])
+
+
 def _dw_ok(m, h, w):
     """Does fq_dwconv_f32 take the nn.Conv2d m on an h x w plane?  Host arithmetic on the module alone (what
     fq_dwconv_f32_supported answers for the same numbers, plus what the C ABI cannot see: the bias, the padding mode)."""
-    k, s, p, d = m.kernel_size, m.stride, m.padding, m.dilation
     return (m.groups > 0 and m.groups == m.in_channels == m.out_channels and m.bias is not None
-            and tuple(k) in ((3, 3), (5, 5)) and tuple(s) in ((1, 1), (2, 2)) and tuple(d) == (1, 1)
-            and not isinstance(p, str) and m.padding_mode == "zeros" and p[0] == p[1] and 0 <= p[0] < k[0]
-            and h + 2 * p[0] >= k[0] and w + 2 * p[1] >= k[1])
+            and _window_ok(m, h, w, ((3, 3), (5, 5))))
 
 
 def grouped_enabled():
@@ -96,14 +102,12 @@ def grouped_enabled():
 def _g_ok(m, h, w):
     """Does fq_gconv_f32 take the nn.Conv2d m on an h x w plane?  Host arithmetic on the module alone (what
     fq_gconv_f32_supported answers for the same numbers, plus what the C ABI cannot see: the bias, the padding mode)."""
-    k, s, p, d, g = m.kernel_size, m.stride, m.padding, m.dilation, m.groups
+    g = m.groups
     if g < 2 or m.in_channels % g or m.out_channels % g or m.bias is None:
         return False
     cgi, cgo = m.in_channels // g, m.out_channels // g
     return (cgi % 4 == 0 and cgo % 4 == 0 and 4 <= cgi <= 64 and 4 <= cgo <= 64
-            and tuple(k) in ((1, 1), (3, 3)) and tuple(s) in ((1, 1), (2, 2)) and tuple(d) == (1, 1)
-            and not isinstance(p, str) and m.padding_mode == "zeros" and p[0] == p[1] and 0 <= p[0] < k[0]
-            and h + 2 * p[0] >= k[0] and w + 2 * p[1] >= k[1])
+            and _window_ok(m, h, w, ((1, 1), (3, 3))))
 
 
 def _is_depthwise(m):

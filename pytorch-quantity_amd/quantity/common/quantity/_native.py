@@ -613,6 +613,44 @@ def _sb(wt):
     return False, int(wt.shape[0]), int(wt.shape[1])
 
 
+def _conv_f32(name, x, w_ptr, bias, shape, ints, max_dev, interval_dev, hist_dev, row, relu_out, out, qd, workspace=False,
+              entry=None):
+    """The one call path of the float convolutions: what rides on the output of entry point `name` (`entry` where the kernel
+    family differs from the contract's name) -- nothing, the abs-max (max_dev/row), the histogram (interval_dev/hist_dev/row),
+    a ReLU copy (relu_out; out=False: the copy alone), or QuanDequan (qd: the `..._qd_f32` entry with ints + (bit, bitwidth)).
+    The wrapper has validated x and its weight operand; shape is the output's, ints the integer arguments in the ABI's order,
+    workspace whether the tail-split workspace goes between the statistic pointers and the stream.  Returns y."""
+    if out is False:                                            # only the ReLU's output is wanted: y is not written
+        assert relu_out is not None and qd is None and tuple(relu_out.shape) == shape
+        y = None
+    else:
+        y = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else out
+        assert tuple(y.shape) == shape and y.is_contiguous() and y.dtype == torch.float32 and y.is_cuda
+    if bias is not None:
+        _need_cuda(bias, torch.float32, name)
+        assert bias.is_contiguous() and bias.numel() == shape[1]
+    bp = None if bias is None else bias.data_ptr()
+    if entry is None:
+        entry = name
+    if qd is not None:
+        qd_name = name[:-3] + "qd_f32"
+        bit, bw = _qd_args(qd, max_dev, hist_dev, relu_out, qd_name)
+        _check(getattr(lib(), entry[:-3] + "qd_f32")(x.data_ptr(), w_ptr, bp, y.data_ptr(), *ints, bit, bw,
+                                                     *(conv_workspace(x) if workspace else ()), _stream(x)), qd_name)
+        return y
+    mp = ivp = hp = None
+    if hist_dev is not None:
+        ivp, hp = _hist_row_ptrs(interval_dev, hist_dev, row)
+    elif max_dev is not None:
+        _need_cuda(max_dev, torch.float32, name)
+        assert max_dev.is_contiguous() and 0 <= row < max_dev.numel()
+        mp = max_dev.data_ptr() + 4 * int(row)
+    rp = None if relu_out is None else _relu_ptr(relu_out, relu_out if y is None else y)
+    _check(getattr(lib(), entry)(x.data_ptr(), w_ptr, bp, None if y is None else y.data_ptr(), rp, *ints, mp, ivp, hp,
+                                 *(conv_workspace(x) if workspace else ()), _stream(x)), name)
+    return y
+
+
 def conv1x1_f32(x, wt, bias, stride=1, max_dev=None, interval_dev=None, hist_dev=None, row=None, relu_out=None, out=None, qd=None):
     """fq_conv1x1_f32: the float 1x1 convolution (padding 0, groups 1) of x [N, Cin, H, W] with the TRANSPOSED weights
     wt [Cin, Cout] on the fp32 matrix cores; max_dev/row: abs-max of the output folded into max_dev[row]; interval_dev/
@@ -621,35 +659,11 @@ def conv1x1_f32(x, wt, bias, stride=1, max_dev=None, interval_dev=None, hist_dev
     _need_cuda(x, torch.float32, "fq_conv1x1_f32")
     sb, wcin, Cout = _sb(wt)                                    # (an int16 [3, Cout, Cin] pack: the split-bf16 kernels)
     assert x.dim() == 4 and x.is_contiguous() and wcin == x.shape[1]
-    N, Cin, H, W = (int(v) for v in x.shape)
+    N, Cin, H, W = x.shape
     s = int(stride)
-    fn, fn_qd = (lib().fq_conv1x1_sb_f32, lib().fq_conv1x1_sb_qd_f32) if sb else (lib().fq_conv1x1_f32, lib().fq_conv1x1_qd_f32)
     shape = (N, Cout, (H - 1) // s + 1, (W - 1) // s + 1)
-    if out is False:                                            # only the ReLU's output is wanted: y is not written
-        assert relu_out is not None and qd is None and tuple(relu_out.shape) == shape
-        y = None
-    else:
-        y = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else out
-        assert tuple(y.shape) == shape and y.is_contiguous() and y.dtype == torch.float32 and y.is_cuda
-    if bias is not None:
-        _need_cuda(bias, torch.float32, "fq_conv1x1_f32")
-        assert bias.is_contiguous() and bias.numel() == Cout
-    if qd is not None:
-        bit, bw = _qd_args(qd, max_dev, hist_dev, relu_out, "fq_conv1x1_qd_f32")
-        _check(fn_qd(x.data_ptr(), wt.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(),
-                     N, Cin, H, W, Cout, s, bit, bw, *conv_workspace(x), _stream(x)), "fq_conv1x1_qd_f32")
-        return y
-    mp = ivp = hp = None
-    if hist_dev is not None:
-        ivp, hp = _hist_row_ptrs(interval_dev, hist_dev, row)
-    elif max_dev is not None:
-        _need_cuda(max_dev, torch.float32, "fq_conv1x1_f32")
-        assert max_dev.is_contiguous() and 0 <= row < max_dev.numel()
-        mp = max_dev.data_ptr() + 4 * int(row)
-    _check(fn(x.data_ptr(), wt.data_ptr(), None if bias is None else bias.data_ptr(),
-              None if y is None else y.data_ptr(), _relu_ptr(relu_out, relu_out if y is None else y), N, Cin, H, W,
-              Cout, s, mp, ivp, hp, *conv_workspace(x), _stream(x)), "fq_conv1x1_f32")
-    return y
+    return _conv_f32("fq_conv1x1_f32", x, wt.data_ptr(), bias, shape, (N, Cin, H, W, Cout, s), max_dev, interval_dev, hist_dev, row,
+                     relu_out, out, qd, True, "fq_conv1x1_sb_f32" if sb else None)
 
 
 def conv1x1_add_f32(x, wt, bias, stride, res, max_dev, row_y, row_sum, relu_out, out=None, sum_out=None):
@@ -713,34 +727,11 @@ def conv_kxk_f32(x, wt, bias, kernel, stride, pad, max_dev=None, interval_dev=No
     _need_cuda(wt, torch.float32, "fq_conv_kxk_f32")
     R, S = int(kernel[0]), int(kernel[1])
     assert x.dim() == 4 and x.is_contiguous() and wt.dim() == 2 and wt.is_contiguous() and wt.shape[0] == R * S * x.shape[1]
-    N, Cin, H, W = (int(v) for v in x.shape)
+    N, Cin, H, W = x.shape
     Cout, st, pd = int(wt.shape[1]), int(stride), int(pad)
     shape = (N, Cout, (H + 2 * pd - R) // st + 1, (W + 2 * pd - S) // st + 1)
-    if out is False:                                            # only the ReLU's output is wanted: y is not written
-        assert relu_out is not None and qd is None and tuple(relu_out.shape) == shape
-        y = None
-    else:
-        y = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else out
-        assert tuple(y.shape) == shape and y.is_contiguous() and y.dtype == torch.float32 and y.is_cuda
-    if bias is not None:
-        _need_cuda(bias, torch.float32, "fq_conv_kxk_f32")
-        assert bias.is_contiguous() and bias.numel() == Cout
-    if qd is not None:
-        bit, bw = _qd_args(qd, max_dev, hist_dev, relu_out, "fq_conv_kxk_qd_f32")
-        _check(lib().fq_conv_kxk_qd_f32(x.data_ptr(), wt.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(),
-                                        N, Cin, H, W, Cout, R, S, st, pd, bit, bw, *conv_workspace(x), _stream(x)), "fq_conv_kxk_qd_f32")
-        return y
-    mp = ivp = hp = None
-    if hist_dev is not None:
-        ivp, hp = _hist_row_ptrs(interval_dev, hist_dev, row)
-    elif max_dev is not None:
-        _need_cuda(max_dev, torch.float32, "fq_conv_kxk_f32")
-        assert max_dev.is_contiguous() and 0 <= row < max_dev.numel()
-        mp = max_dev.data_ptr() + 4 * int(row)
-    _check(lib().fq_conv_kxk_f32(x.data_ptr(), wt.data_ptr(), None if bias is None else bias.data_ptr(),
-                                 None if y is None else y.data_ptr(), _relu_ptr(relu_out, relu_out if y is None else y), N, Cin, H, W,
-                                 Cout, R, S, st, pd, mp, ivp, hp, *conv_workspace(x), _stream(x)), "fq_conv_kxk_f32")
-    return y
+    return _conv_f32("fq_conv_kxk_f32", x, wt.data_ptr(), bias, shape, (N, Cin, H, W, Cout, R, S, st, pd), max_dev, interval_dev,
+                     hist_dev, row, relu_out, out, qd, True)
 
 
 def dwconv_f32_supported(c, kernel, stride, pad, dilation, h, w):
@@ -757,35 +748,11 @@ def dwconv_f32(x, w, bias, kernel, stride, pad, max_dev=None, interval_dev=None,
     _need_cuda(w, torch.float32, "fq_dwconv_f32")
     R, S = int(kernel[0]), int(kernel[1])
     assert x.dim() == 4 and x.is_contiguous() and w.is_contiguous() and tuple(w.shape) == (x.shape[1], 1, R, S)
-    N, C, H, W = (int(v) for v in x.shape)
+    N, C, H, W = x.shape
     st, pd = int(stride), int(pad)
     shape = (N, C, (H + 2 * pd - R) // st + 1, (W + 2 * pd - S) // st + 1)
-    if out is False:                                            # only the ReLU's output is wanted: y is not written
-        assert relu_out is not None and qd is None and tuple(relu_out.shape) == shape
-        y = None
-    else:
-        y = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else out
-        assert tuple(y.shape) == shape and y.is_contiguous() and y.dtype == torch.float32 and y.is_cuda
-    if bias is not None:
-        _need_cuda(bias, torch.float32, "fq_dwconv_f32")
-        assert bias.is_contiguous() and bias.numel() == C
-    bp = None if bias is None else bias.data_ptr()
-    if qd is not None:
-        bit, bw = _qd_args(qd, max_dev, hist_dev, relu_out, "fq_dwconv_qd_f32")
-        _check(lib().fq_dwconv_qd_f32(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), N, C, H, W, R, S, st, pd, bit, bw, _stream(x)),
-               "fq_dwconv_qd_f32")
-        return y
-    mp = ivp = hp = None
-    if hist_dev is not None:
-        ivp, hp = _hist_row_ptrs(interval_dev, hist_dev, row)
-    elif max_dev is not None:
-        _need_cuda(max_dev, torch.float32, "fq_dwconv_f32")
-        assert max_dev.is_contiguous() and 0 <= row < max_dev.numel()
-        mp = max_dev.data_ptr() + 4 * int(row)
-    _check(lib().fq_dwconv_f32(x.data_ptr(), w.data_ptr(), bp, None if y is None else y.data_ptr(),
-                               _relu_ptr(relu_out, relu_out if y is None else y), N, C, H, W, R, S, st, pd, mp, ivp, hp, _stream(x)),
-           "fq_dwconv_f32")
-    return y
+    return _conv_f32("fq_dwconv_f32", x, w.data_ptr(), bias, shape, (N, C, H, W, R, S, st, pd), max_dev, interval_dev, hist_dev, row,
+                     relu_out, out, qd)
 
 
 def gconv_f32_supported(c, k, groups, kernel, stride, pad, dilation, h, w):
@@ -806,35 +773,11 @@ def gconv_f32(x, w, bias, groups, kernel, stride, pad, max_dev=None, interval_de
     R, S, G = int(kernel[0]), int(kernel[1]), int(groups)
     assert x.dim() == 4 and x.is_contiguous() and w.is_contiguous() and w.dim() == 4 and G >= 1 and x.shape[1] % G == 0
     assert tuple(w.shape[1:]) == (x.shape[1] // G, R, S)
-    N, C, H, W = (int(v) for v in x.shape)
+    N, C, H, W = x.shape
     K, st, pd = int(w.shape[0]), int(stride), int(pad)
     shape = (N, K, (H + 2 * pd - R) // st + 1, (W + 2 * pd - S) // st + 1)
-    if out is False:                                            # only the ReLU's output is wanted: y is not written
-        assert relu_out is not None and qd is None and tuple(relu_out.shape) == shape
-        y = None
-    else:
-        y = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else out
-        assert tuple(y.shape) == shape and y.is_contiguous() and y.dtype == torch.float32 and y.is_cuda
-    if bias is not None:
-        _need_cuda(bias, torch.float32, "fq_gconv_f32")
-        assert bias.is_contiguous() and bias.numel() == K
-    bp = None if bias is None else bias.data_ptr()
-    if qd is not None:
-        bit, bw = _qd_args(qd, max_dev, hist_dev, relu_out, "fq_gconv_qd_f32")
-        _check(lib().fq_gconv_qd_f32(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), N, C, H, W, K, G, R, S, st, pd, bit, bw,
-                                     _stream(x)), "fq_gconv_qd_f32")
-        return y
-    mp = ivp = hp = None
-    if hist_dev is not None:
-        ivp, hp = _hist_row_ptrs(interval_dev, hist_dev, row)
-    elif max_dev is not None:
-        _need_cuda(max_dev, torch.float32, "fq_gconv_f32")
-        assert max_dev.is_contiguous() and 0 <= row < max_dev.numel()
-        mp = max_dev.data_ptr() + 4 * int(row)
-    _check(lib().fq_gconv_f32(x.data_ptr(), w.data_ptr(), bp, None if y is None else y.data_ptr(),
-                              _relu_ptr(relu_out, relu_out if y is None else y), N, C, H, W, K, G, R, S, st, pd, mp, ivp, hp,
-                              _stream(x)), "fq_gconv_f32")
-    return y
+    return _conv_f32("fq_gconv_f32", x, w.data_ptr(), bias, shape, (N, C, H, W, K, G, R, S, st, pd), max_dev, interval_dev, hist_dev,
+                     row, relu_out, out, qd)
 
 
 def conv_wino_enabled():
@@ -864,35 +807,11 @@ def conv_wino_f32(x, u, bias, cout, max_dev=None, interval_dev=None, hist_dev=No
     _need_cuda(x, torch.float32, "fq_conv3x3_wino_f32")
     _need_cuda(u, torch.float32, "fq_conv3x3_wino_f32")
     assert x.dim() == 4 and x.is_contiguous() and u.is_contiguous()
-    N, Cin, H, W = (int(v) for v in x.shape)
+    N, Cin, H, W = x.shape
     Cout = int(cout)
     assert u.numel() == 16 * Cin * Cout
-    shape = (N, Cout, H, W)
-    if out is False:                                            # only the ReLU's output is wanted: y is not written
-        assert relu_out is not None and tuple(relu_out.shape) == shape
-        y = None
-    else:
-        y = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else out
-        assert tuple(y.shape) == shape and y.is_contiguous() and y.dtype == torch.float32 and y.is_cuda
-    if bias is not None:
-        _need_cuda(bias, torch.float32, "fq_conv3x3_wino_f32")
-        assert bias.is_contiguous() and bias.numel() == Cout
-    if qd is not None:
-        bit, bw = _qd_args(qd, max_dev, hist_dev, relu_out, "fq_conv3x3_wino_qd_f32")
-        _check(lib().fq_conv3x3_wino_qd_f32(x.data_ptr(), u.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(),
-                                            N, Cin, H, W, Cout, bit, bw, _stream(x)), "fq_conv3x3_wino_qd_f32")
-        return y
-    mp = ivp = hp = None
-    if hist_dev is not None:
-        ivp, hp = _hist_row_ptrs(interval_dev, hist_dev, row)
-    elif max_dev is not None:
-        _need_cuda(max_dev, torch.float32, "fq_conv3x3_wino_f32")
-        assert max_dev.is_contiguous() and 0 <= row < max_dev.numel()
-        mp = max_dev.data_ptr() + 4 * int(row)
-    _check(lib().fq_conv3x3_wino_f32(x.data_ptr(), u.data_ptr(), None if bias is None else bias.data_ptr(),
-                                     None if y is None else y.data_ptr(), _relu_ptr(relu_out, relu_out if y is None else y), N, Cin,
-                                     H, W, Cout, mp, ivp, hp, _stream(x)), "fq_conv3x3_wino_f32")
-    return y
+    return _conv_f32("fq_conv3x3_wino_f32", x, u.data_ptr(), bias, (N, Cout, H, W), (N, Cin, H, W, Cout), max_dev, interval_dev,
+                     hist_dev, row, relu_out, out, qd)
 
 
 def conv_stem_f32_supported(weight, stride):
@@ -918,35 +837,11 @@ def conv_stem_f32(x, wp, bias, cout, kernel, stride, pad, max_dev=None, interval
     _need_cuda(x, torch.float32, "fq_conv_stem_f32")
     _need_cuda(wp, torch.float32, "fq_conv_stem_f32")
     assert x.dim() == 4 and x.is_contiguous() and wp.is_contiguous()
-    N, Cin, H, W = (int(v) for v in x.shape)
-    R, S = int(kernel[0]), int(kernel[1])
-    shape = (N, int(cout), (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1)
-    if out is False:                                            # only the ReLU's output is wanted: y is not written
-        assert relu_out is not None and qd is None and tuple(relu_out.shape) == shape
-        y = None
-    else:
-        y = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else out
-        assert tuple(y.shape) == shape and y.is_contiguous() and y.dtype == torch.float32 and y.is_cuda
-    if bias is not None:
-        _need_cuda(bias, torch.float32, "fq_conv_stem_f32")
-        assert bias.is_contiguous() and bias.numel() == cout
-    if qd is not None:
-        bit, bw = _qd_args(qd, max_dev, hist_dev, relu_out, "fq_conv_stem_qd_f32")
-        _check(lib().fq_conv_stem_qd_f32(x.data_ptr(), wp.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(),
-                                         N, Cin, H, W, int(cout), R, S, int(stride), int(pad), bit, bw, _stream(x)),
-               "fq_conv_stem_qd_f32")
-        return y
-    mp = ivp = hp = None
-    if hist_dev is not None:
-        ivp, hp = _hist_row_ptrs(interval_dev, hist_dev, row)
-    elif max_dev is not None:
-        _need_cuda(max_dev, torch.float32, "fq_conv_stem_f32")
-        assert max_dev.is_contiguous() and 0 <= row < max_dev.numel()
-        mp = max_dev.data_ptr() + 4 * int(row)
-    _check(lib().fq_conv_stem_f32(x.data_ptr(), wp.data_ptr(), None if bias is None else bias.data_ptr(),
-                                  None if y is None else y.data_ptr(), _relu_ptr(relu_out, relu_out if y is None else y), N, Cin, H, W,
-                                  int(cout), R, S, int(stride), int(pad), mp, ivp, hp, _stream(x)), "fq_conv_stem_f32")
-    return y
+    N, Cin, H, W = x.shape
+    Cout, R, S, st, pd = int(cout), int(kernel[0]), int(kernel[1]), int(stride), int(pad)
+    shape = (N, Cout, (H + 2 * pd - R) // st + 1, (W + 2 * pd - S) // st + 1)
+    return _conv_f32("fq_conv_stem_f32", x, wp.data_ptr(), bias, shape, (N, Cin, H, W, Cout, R, S, st, pd), max_dev, interval_dev,
+                     hist_dev, row, relu_out, out, qd)
 
 
 def maxpool2d_f32(x, kernel, stride, pad):

@@ -24,7 +24,7 @@ static void fail(const char* what, const Shape& s) {
 static long run(const Shape& s, bool hist) {
     DwfGeom g;
     if (!dwf_plan(g, s.N, s.C, s.H, s.W, s.R, s.stride, s.pad)) fail("the plan declines a shape of the list", s);
-    const int R = s.R, nrd = dwf_strip_reads(R, s.stride);
+    const int R = s.R, nrd = geom_strip_reads(R, s.stride);
     const size_t in_elems = (size_t)s.N * s.C * s.H * s.W, out_elems = (size_t)s.N * s.C * g.Ho * g.Wo;
     if (g.fill > (unsigned)kDwfLdsFloats || g.PP > kDwfMaxPP || g.PP < 1 || g.TH * g.QW * g.PP > kDwfBlock || (g.IWP & 3))
         fail("tile larger than the workgroup or its LDS", s);
@@ -33,14 +33,14 @@ static long run(const Shape& s, bool hist) {
     const unsigned G = dwf_grid(g, hist);
     long loads = 0;
     for (unsigned b = 0; b < G; ++b) {
-        for (unsigned tile = dwf_first_tile(b, G); tile < g.tiles; tile += G) {
+        for (unsigned tile = geom_first_tile(b, G); tile < g.tiles; tile += G) {
             const DwfTilePos tp = dwf_tile_pos(g, tile);
             if (tp.plane0 >= g.planes || tp.oh0 >= g.Ho || tp.ow0 >= g.Wo) fail("tile outside the tensor", s);
             for (unsigned e = 0; e < g.fill; ++e) {       // (lane e % 256 in step e / 256: every e < fill exactly once)
                 unsigned off = 0;
                 const bool ld = dwf_fill_src(g, tp, e, &off);
                 const unsigned pi = e / g.slot, rem = e % g.slot, r = rem / g.IWP, col = rem % g.IWP;
-                if (dwf_mulhi(e, g.m_slot) != pi || dwf_mulhi(rem, g.m_pitch) != r) fail("reciprocal division is off", s);
+                if (geom_mulhi(e, g.m_slot) != pi || geom_mulhi(rem, g.m_pitch) != r) fail("reciprocal division is off", s);
                 const long ih = (long)tp.oh0 * s.stride - s.pad + r, iw = (long)tp.ow0 * s.stride - s.pad + col;
                 const bool want = tp.plane0 + pi < g.planes && ih >= 0 && ih < s.H && iw >= 0 && iw < s.W;
                 if (ld != want) fail("staging predicate is off", s);

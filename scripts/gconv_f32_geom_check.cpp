@@ -27,7 +27,7 @@ static long run(const Shape& s, bool hist) {
     GfGeom g;
     const int C = s.G * s.Cgi, K = s.G * s.Cgo, R = s.R, RR = R * R;
     if (!gf_plan(g, s.N, C, s.H, s.W, K, s.G, R, s.stride, s.pad)) fail("the plan declines a shape of the list", s);
-    const int nrd = gf_strip_reads(R, s.stride);
+    const int nrd = geom_strip_reads(R, s.stride);
     const size_t in_elems = (size_t)s.N * C * s.H * s.W, out_elems = (size_t)s.N * K * g.Ho * g.Wo;
     const size_t w_elems = (size_t)K * s.Cgi * RR;
     if (g.fill > g.in_floats || g.in_floats < (unsigned)kGfMinInFloats || g.b0 != g.wfill || g.x0 < g.b0 + (unsigned)g.KC || (g.x0 & 3u) ||
@@ -41,7 +41,7 @@ static long run(const Shape& s, bool hist) {
     const unsigned G = gf_grid(g, hist);
     long loads = 0;
     for (unsigned b = 0; b < G; ++b) {
-        for (unsigned tile = gf_first_tile(b, G); tile < g.tiles; tile += G) {
+        for (unsigned tile = geom_first_tile(b, G); tile < g.tiles; tile += G) {
             const GfTilePos tp = gf_tile_pos(g, tile);
             if (tp.n >= (unsigned)s.N || tp.grp >= (unsigned)s.G || tp.k0 >= s.Cgo || tp.oh0 >= g.Ho || tp.ow0 >= g.Wo)
                 fail("tile outside the tensor", s);
@@ -49,7 +49,7 @@ static long run(const Shape& s, bool hist) {
                 unsigned off = 0;
                 const bool ld = gf_fill_src(g, tp, e, &off);
                 const unsigned c = e / g.slot, rem = e % g.slot, r = rem / g.IWP, col = rem % g.IWP;
-                if (gf_mulhi(e, g.m_slot) != c || gf_mulhi(rem, g.m_pitch) != r) fail("reciprocal division is off", s);
+                if (geom_mulhi(e, g.m_slot) != c || geom_mulhi(rem, g.m_pitch) != r) fail("reciprocal division is off", s);
                 const long ih = (long)tp.oh0 * s.stride - s.pad + r, iw = (long)tp.ow0 * s.stride - s.pad + col;
                 const bool want = ih >= 0 && ih < s.H && iw >= 0 && iw < s.W;
                 if (ld != want) fail("staging predicate is off", s);
@@ -65,7 +65,7 @@ static long run(const Shape& s, bool hist) {
                 unsigned off = 0, dst = 0;
                 const bool ld = gf_w_src(g, tp, i, &off, &dst);
                 const unsigned kk = i / g.ckr, rem = i % g.ckr, c = rem / RR, tap = rem % RR;
-                if (gf_mulhi(i, g.m_ckr) != kk || (RR != 1 && gf_mulhi(rem, g.m_rr) != c)) fail("reciprocal division is off (weights)", s);
+                if (geom_mulhi(i, g.m_ckr) != kk || (RR != 1 && geom_mulhi(rem, g.m_rr) != c)) fail("reciprocal division is off (weights)", s);
                 if (dst >= g.wfill) fail("LDS weight index outside the staged block", s);
                 if (dst != (tap * s.Cgi + c) * g.KC + kk) fail("weight staged to the wrong LDS float", s);
                 if (wsrc[dst] != -2) fail("LDS weight float staged twice", s);

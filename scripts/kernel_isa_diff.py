@@ -5,7 +5,9 @@
 Unbundles the gfx950 code object of each library (clang-offload-bundler), disassembles it with llvm-objdump and compares
 every kernel symbol present in both builds.  Kernel-argument offsets (s_load offsets off the kernarg pointer) and
 branch targets differ whenever a parameter struct grows at its end, so each instruction is compared with its
-immediate offsets masked; the script prints how many kernels match exactly, how many match after masking, which differ,
+immediate offsets masked; a type that moved or was renamed changes the mangled names of the kernels instantiated on it, so
+the symbols are matched by their demangled names (c++filt) after the MOVED substitutions; the script prints how many
+kernels match exactly, how many match after masking, which differ,
 and which symbols exist in one build only.  Needs no GPU.
 """
 import os
@@ -19,6 +21,26 @@ LLVM = "/opt/rocm/llvm/bin"
 RENAMED = {
     "_ZN2fq21linear_i8_wave_kernelEPKaS1_PKfPfNS_10ConvParamsE": "_ZN2fq21linear_i8_wave_kernelILb0EEEvPKaS2_PKfPfNS_10ConvParamsE",
 }
+# types that moved between namespaces or were renamed, applied in order to the demangled symbol names of both builds
+MOVED = [
+    (r"\(anonymous namespace\)::(?:Dwf|Gf)?NoStat\b", "NoStat"),            # the five NoStat of the float convolutions -> fq::NoStat
+    (r"\(anonymous namespace\)::(?:Dwf|Gf)HistTag\b", "HistTag"),           # -> fq::HistTag
+    (r"\(anonymous namespace\)::(?:Dwf|Gf)StatArgs\b", "ProducerStatArgs"), # -> fq::ProducerStatArgs
+]
+
+
+def normalised(syms):
+    """The kernels keyed by their demangled names with the MOVED substitutions applied."""
+    names = sorted(syms)
+    plain = subprocess.check_output(["c++filt"], input="\n".join(names) + "\n", text=True).splitlines()
+    assert len(plain) == len(names)
+    out = {}
+    for name, text in zip(names, plain):
+        for pat, rep in MOVED:
+            text = re.sub(pat, rep, text)
+        assert text not in out, text
+        out[text] = syms[name]
+    return out
 
 
 def code_objects(so, tmp):
@@ -88,6 +110,7 @@ def main(old_so, new_so):
         a = renamed(b)
         if a != b and a in old and a not in new:
             new[a] = new.pop(b)
+    old, new = normalised(old), normalised(new)
     same = exact = 0
     diff = []
     for k in sorted(set(old) & set(new)):
