@@ -326,6 +326,31 @@ int fq_conv_kxk_f32(const float* x, const float* wt, const float* bias, float* y
                     int Win, int Cout, int R, int S, int stride, int pad, float* max_inout, const float* interval,
                     int64_t* hist_row, void* workspace, size_t workspace_bytes, fq_stream_t stream);
 
+/* ---- a ReLU copy other than nn.ReLU's: the `_act` entry points of the float convolutions ------------------------------
+ * fq_conv1x1_f32, fq_conv1x1_sb_f32, fq_conv_kxk_f32 and fq_dwconv_f32 with `float act_cap` behind relu_out:
+ *   relu_out = clamp(y, 0, act_cap), bit for bit what torch's nn.ReLU6 (hardtanh(0, 6); act_cap = 6) gives for the stored y on the
+ *   same device: NaN stays NaN, -0 and everything below become +0, everything above act_cap (+inf too) becomes act_cap; act_cap
+ *   itself and the neighbours of act_cap and of 0 pass unchanged.
+ * relu_out must be given (FQ_ERR_INVALID_ARG otherwise, as for an act_cap that is not positive and finite); y may be NULL as
+ * in the entry point without `_act` (only the copy is written).  y, the abs-max and the histogram are those of the call without an
+ * activation: the statistic is taken from the UNCLIPPED value.  There is no QuanDequan and no `_add_` form.  Every other argument,
+ * limit and error code is the plain entry point's; the kernels are further instantiations of the same templates (the
+ * activation is a template parameter of their one epilogue helper), the existing instantiations are unchanged.
+ * Not served, their callers leave an nn.ReLU6 to torch: fq_conv3x3_wino_f32, fq_conv_stem_f32, fq_gconv_f32, the `_add_` forms and
+ * the fq_bias_add_* / fq_add_* producers. */
+int fq_conv1x1_f32_act(const float* x, const float* wt, const float* bias, float* y, float* relu_out, float act_cap, int N, int Cin,
+                       int Hin, int Win, int Cout, int stride, float* max_inout, const float* interval, int64_t* hist_row,
+                       void* workspace, size_t workspace_bytes, fq_stream_t stream);
+int fq_conv1x1_sb_f32_act(const float* x, const void* wsb, const float* bias, float* y, float* relu_out, float act_cap, int N, int Cin,
+                          int Hin, int Win, int Cout, int stride, float* max_inout, const float* interval, int64_t* hist_row,
+                          void* workspace, size_t workspace_bytes, fq_stream_t stream);
+int fq_conv_kxk_f32_act(const float* x, const float* wt, const float* bias, float* y, float* relu_out, float act_cap, int N, int Cin,
+                        int Hin, int Win, int Cout, int R, int S, int stride, int pad, float* max_inout, const float* interval,
+                        int64_t* hist_row, void* workspace, size_t workspace_bytes, fq_stream_t stream);
+int fq_dwconv_f32_act(const float* x, const float* w_crs, const float* bias, float* y, float* relu_out, float act_cap, int N, int C,
+                      int H, int W, int R, int S, int stride, int pad, float* max_inout, const float* interval, int64_t* hist_row,
+                      fq_stream_t stream);
+
 /* The stride-1, pad-1 3x3 convolutions of the same forward as Winograd F(2x2, 3x3) on the fp32 matrix cores: 16 products per
  * 2x2 output tile, input channel and output channel instead of 36 (fq_conv_kxk_f32's direct sum), the transforms fused into
  * the kernel, same epilogue contract as fq_conv1x1_f32 (bias, relu_out, y may be NULL with relu_out given, exactly one of
@@ -638,6 +663,46 @@ int fq_gconv2d_i8_resident_pcs(const int8_t* x_nhwc, const int8_t* w_pack, const
                                int rs_max, int8_t* q_nhwc, int Cpad, int Kpad, int relu, int N, int H, int W, int C, int K,
                                int groups, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
                                int ob, fq_stream_t stream);
+
+/* ---- a fused activation other than nn.ReLU: the `_act` entry points ---------------------------------------------
+ * Each integer producer above has a sibling that takes the Sp range of its output integers, `int act_lo, int act_hi`, in the place
+ * of `int relu`:   q = min(max(RightShift(acc, rs) + qbias[k], act_lo), act_hi)   (RightShift still saturates to [-128, 127]).
+ *   relu = 0 is (act_lo, act_hi) = (-128, 127); relu = 1 is (0, 127): the bytes of the plain entry point;
+ *   an nn.ReLU6 behind a layer with output grid ob >= -1 is (0, min(127, 6 * 2^ob)), because the clip commutes with the scale:
+ *   min(max(q * 2^-ob, 0), 6) = min(max(q, 0), 6 * 2^ob) * 2^-ob whenever 6 * 2^ob is an integer (ob = -1: 3; ob >= 5: 127, a
+ *   plain ReLU).  For ob <= -2 the value 6 is not on the output grid and there is no such range: callers keep the fp32 form.
+ * -128 <= act_lo <= 0 <= act_hi <= 127, FQ_ERR_INVALID_ARG otherwise (0 inside the range: the padding channels stay zero; the
+ * range inside [-128, 127]: the bias clamp of the integer tail and the accumulator bound made from it hold unchanged).  8-bit
+ * outputs only.  Every other argument, limit, error and the kernel the dispatch picks are those of the entry point without
+ * `_act`; fq_conv2d_i8_resident_act applies the range to y_nchw and q_nhwc alike.  No kernel is instantiated for these: the
+ * range is a launch parameter of the existing ones. */
+int fq_conv2d_i8_resident_act(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, float* y_nchw, int8_t* q_nhwc,
+                              int Kpad, int act_lo, int act_hi, int N, int H, int W, int C, int K, int R, int S, int stride_h,
+                              int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int rs, int ob, fq_stream_t stream);
+int fq_conv2d_i8_resident_pcs_act(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, const int32_t* rs_k, int rs_min,
+                                  int rs_max, float* y_nchw, int8_t* q_nhwc, int Kpad, int act_lo, int act_hi, int N, int H, int W,
+                                  int C, int K, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                                  int ob, fq_stream_t stream);
+int fq_conv2d_i8_stem_act(const float* x_nchw, const int8_t* w_stem, const float* qbias, int8_t* q_nhwc, int Kpad, int act_lo,
+                          int act_hi, int N, int C, int H, int W, int K, int R, int S, int stride_h, int stride_w, int pad_h,
+                          int pad_w, int ib, int rs, int ob, fq_stream_t stream);
+int fq_conv2d_i8_stem_pcs_act(const float* x_nchw, const int8_t* w_stem, const float* qbias, const int32_t* rs_k, int rs_min,
+                              int rs_max, int8_t* q_nhwc, int Kpad, int act_lo, int act_hi, int N, int C, int H, int W, int K, int R,
+                              int S, int stride_h, int stride_w, int pad_h, int pad_w, int ib, int ob, fq_stream_t stream);
+int fq_dwconv2d_i8_resident_act(const int8_t* x_nhwc, const int8_t* w_rsc, const float* qbias, int8_t* q_nhwc, int Cpad, int act_lo,
+                                int act_hi, int N, int H, int W, int C, int R, int S, int stride_h, int stride_w, int pad_h,
+                                int pad_w, int dil_h, int dil_w, int rs, int ob, fq_stream_t stream);
+int fq_dwconv2d_i8_resident_pcs_act(const int8_t* x_nhwc, const int8_t* w_rsc, const float* qbias, const int32_t* rs_k, int rs_min,
+                                    int rs_max, int8_t* q_nhwc, int Cpad, int act_lo, int act_hi, int N, int H, int W, int C, int R,
+                                    int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int ob,
+                                    fq_stream_t stream);
+int fq_gconv2d_i8_resident_act(const int8_t* x_nhwc, const int8_t* w_pack, const float* qbias, int8_t* q_nhwc, int Cpad, int Kpad,
+                               int act_lo, int act_hi, int N, int H, int W, int C, int K, int groups, int R, int S, int stride_h,
+                               int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int rs, int ob, fq_stream_t stream);
+int fq_gconv2d_i8_resident_pcs_act(const int8_t* x_nhwc, const int8_t* w_pack, const float* qbias, const int32_t* rs_k, int rs_min,
+                                   int rs_max, int8_t* q_nhwc, int Cpad, int Kpad, int act_lo, int act_hi, int N, int H, int W,
+                                   int C, int K, int groups, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                                   int dil_h, int dil_w, int ob, fq_stream_t stream);
 
 /* Channel concatenation (the Concat marker layer, torch.cat along dim 1) and nearest upsampling (nn.UpsamplingNearest2d with an
  * integer factor) of resident int8 NHWC activations that share ONE grid: moving the integers is concatenating the values, and

@@ -137,7 +137,7 @@ __device__ __forceinline__ void c1_epilogue(const f16v (&acc)[WM][WN], const C1A
                         const int row4 = (int)(dm * a.HWout * 4u);                     // uniform
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val), yrs, (int)col4, row4, aux);
                         if (kRelu)
-                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, relu_like_torch(val)), rrs, (int)col4,
+                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, stat_act(stat, val)), rrs, (int)col4,
                                                                   row4, aux);
                         stat.add(val);
                     }
@@ -748,6 +748,42 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(2))) void co
     hist_flush<kT>(s_bins, hist_row);
 }
 
+// the three forms above with the ReLU copy clipped at `cap` (fq_conv1x1_sb_f32_act): the statistic wrapped in Clipped<>
+template <int WM, int WN>
+__global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(2))) void conv1x1_sb_act_kernel(const C1Args a, const float cap) {
+    extern __shared__ __attribute__((aligned(16))) char sb_smem[];
+    Clipped<NoStat> st{{}, cap};
+    conv1x1_tiles_sb<WM, WN>(a, st, sb_smem);
+}
+
+template <int WM, int WN>
+__global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(2))) void conv1x1_sb_absmax_act_kernel(const C1Args a, unsigned int* __restrict__ max_bits,
+                                                                                                       const float cap) {
+    extern __shared__ __attribute__((aligned(16))) char sb_smem[];
+    Clipped<MaxStat> st{{}, cap};
+    conv1x1_tiles_sb<WM, WN>(a, st, sb_smem);
+    publish_max<kT>(st.m, max_bits);
+}
+
+template <int WM, int WN>
+__global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(2))) void conv1x1_sb_hist_act_kernel(
+    const C1Args a, const float* __restrict__ interval, unsigned long long* __restrict__ hist_row, const int allow_fast, const float cap) {
+    extern __shared__ __attribute__((aligned(16))) char sb_smem[];
+    __shared__ unsigned int s_bins[FQ_BINS + kWave];
+    for (int b = threadIdx.x; b < FQ_BINS + kWave; b += kT) s_bins[b] = 0u;
+    __syncthreads();
+    const float iv = *interval;
+    unsigned int* park = s_bins + FQ_BINS + (threadIdx.x & (kWave - 1));
+    if (allow_fast && fast_quotient_ok(iv)) {
+        Clipped<HistStat<true>> st{{s_bins, park, iv, 1.0f / iv}, cap};
+        conv1x1_tiles_sb<WM, WN>(a, st, sb_smem);
+    } else {
+        Clipped<HistStat<false>> st{{s_bins, park, iv, 1.0f / iv}, cap};
+        conv1x1_tiles_sb<WM, WN>(a, st, sb_smem);
+    }
+    hist_flush<kT>(s_bins, hist_row);
+}
+
 template <int WM, int WN>
 __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(2))) void conv1x1_sb_add_absmax_kernel(
     const C1Args a, unsigned int* __restrict__ max_y_bits, unsigned int* __restrict__ max_sum_bits) {
@@ -808,6 +844,43 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(kTailK == 1 
     MaxStat st;
     conv1x1_tiles<WM, WN, step_of<WM>(), kTailK>(a, st, smem);
     publish_max<kT>(st.m, max_bits);
+}
+
+// the plain, abs-max and histogram forms with the ReLU copy clipped at `cap` (fq_conv1x1_f32_act / fq_conv_kxk_f32_act): the
+// statistic wrapped in Clipped<>, everything else -- tiles, registers per wave, LDS -- as in the forms without
+template <int WM, int WN, int kTailK>
+__global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(kTailK == 1 ? 3 : 4))) void conv1x1_f32_act_kernel(const C1Args a, const float cap) {
+    __shared__ __attribute__((aligned(16))) float smem[Shape<WM, WN, step_of<WM>()>::kFloats];
+    Clipped<NoStat> st{{}, cap};
+    conv1x1_tiles<WM, WN, step_of<WM>(), kTailK>(a, st, smem);
+}
+
+template <int WM, int WN, int kTailK>
+__global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(kTailK == 1 ? 3 : 4))) void conv1x1_f32_absmax_act_kernel(
+    const C1Args a, unsigned int* __restrict__ max_bits, const float cap) {
+    __shared__ __attribute__((aligned(16))) float smem[Shape<WM, WN, step_of<WM>()>::kFloats];
+    Clipped<MaxStat> st{{}, cap};
+    conv1x1_tiles<WM, WN, step_of<WM>(), kTailK>(a, st, smem);
+    publish_max<kT>(st.m, max_bits);
+}
+
+template <int WM, int WN, int BK, int kTailK>
+__global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(3))) void conv1x1_f32_hist_act_kernel(
+    const C1Args a, const float* __restrict__ interval, unsigned long long* __restrict__ hist_row, const int allow_fast, const float cap) {
+    __shared__ __attribute__((aligned(16))) float smem[Shape<WM, WN, BK>::kFloats];
+    __shared__ unsigned int s_bins[FQ_BINS + kWave];
+    for (int b = threadIdx.x; b < FQ_BINS + kWave; b += kT) s_bins[b] = 0u;
+    __syncthreads();
+    const float iv = *interval;
+    unsigned int* park = s_bins + FQ_BINS + (threadIdx.x & (kWave - 1));
+    if (allow_fast && fast_quotient_ok(iv)) {
+        Clipped<HistStat<true>> st{{s_bins, park, iv, 1.0f / iv}, cap};
+        conv1x1_tiles<WM, WN, BK, kTailK>(a, st, smem);
+    } else {
+        Clipped<HistStat<false>> st{{s_bins, park, iv, 1.0f / iv}, cap};
+        conv1x1_tiles<WM, WN, BK, kTailK>(a, st, smem);
+    }
+    hist_flush<kT>(s_bins, hist_row);
 }
 
 // conv3 + Eltwise + ReLU of a bottleneck in one kernel (pass 1: both tensors' abs-max)
@@ -910,13 +983,30 @@ void plan_split(C1Args& a, unsigned nk, void* workspace, size_t workspace_bytes)
 
 template <int WM, int WN, int kTailK>
 void launch(C1Args a, unsigned cols, float* max_inout, const float* interval, int64_t* hist_row, int hist_per_cu, int fast,
-            const QdStat* qd, void* workspace, size_t workspace_bytes, hipStream_t st) {
+            const QdStat* qd, void* workspace, size_t workspace_bytes, hipStream_t st, const float* cap = nullptr) {
     typedef Shape<WM, WN> S;
     a.tiles_m = (a.Cout + S::BM - 1) / S::BM;
     a.tiles = ((cols + S::BN - 1) / S::BN) * a.tiles_m;
     constexpr unsigned BK = (unsigned)step_of<WM>();
     plan_split(a, kTailK == 2 ? (unsigned)(a.R * a.S) * (a.Cin / BK) : (a.Cin + BK - 1) / BK, workspace, workspace_bytes);
-    if (qd) {
+    if (cap) {                                               // the `_act` entry points: the same three launches on the clipped kernels
+        if (hist_row) {
+            static const int resident = [] {
+                int n = 0;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv1x1_f32_hist_act_kernel<WM, WN, step_of<WM>(), kTailK>, kT, 0) != hipSuccess || n < 1) n = 1;
+                return n;
+            }();
+            unsigned grid = (unsigned)kCUs * (unsigned)(hist_per_cu > 0 ? hist_per_cu : resident);
+            if (grid > a.work) grid = a.work;
+            hipLaunchKernelGGL((conv1x1_f32_hist_act_kernel<WM, WN, step_of<WM>(), kTailK>), dim3(grid), dim3(kT), 0, st, a, interval,
+                               reinterpret_cast<unsigned long long*>(hist_row), fast, *cap);
+        } else if (max_inout) {
+            hipLaunchKernelGGL((conv1x1_f32_absmax_act_kernel<WM, WN, kTailK>), dim3(a.work), dim3(kT), 0, st, a,
+                               reinterpret_cast<unsigned int*>(max_inout), *cap);
+        } else {
+            hipLaunchKernelGGL((conv1x1_f32_act_kernel<WM, WN, kTailK>), dim3(a.work), dim3(kT), 0, st, a, *cap);
+        }
+    } else if (qd) {
         hipLaunchKernelGGL((conv1x1_f32_qd_kernel<WM, WN, kTailK>), dim3(a.work), dim3(kT), 0, st, a, *qd);
     } else if (hist_row) {
         // every workgroup flushes up to 2048 bins with 64-bit atomics at its end: a persistent grid of exactly the
@@ -942,7 +1032,7 @@ void launch(C1Args a, unsigned cols, float* max_inout, const float* interval, in
 template <int WM, int WN>
 int launch_sb(C1Args a, float* max_inout, const float* interval, int64_t* hist_row, int fast, const QdStat* qd, const float* res_interval_y,
               int64_t* hist_y, const float* interval_sum, int64_t* hist_sum, float* max_y, float* max_sum, bool add, void* workspace,
-              size_t workspace_bytes, hipStream_t st) {
+              size_t workspace_bytes, hipStream_t st, const float* cap = nullptr) {
     typedef ShapeSb<WM, WN> S;
     a.tiles_m = (a.Cout + S::BM - 1) / S::BM;
     a.tiles = ((a.cols + S::BN - 1) / S::BN) * a.tiles_m;
@@ -955,7 +1045,24 @@ int launch_sb(C1Args a, float* max_inout, const float* interval, int64_t* hist_r
         (void)static_lds;
         return (unsigned)n;
     };
-    if (add) {
+    if (cap) {                                               // fq_conv1x1_sb_f32_act (never the add or the QuanDequan form)
+        static bool c_plain[kMaxDevices], c_max[kMaxDevices], c_hist[kMaxDevices];
+        if (hist_row) {
+            const void* k = reinterpret_cast<const void*>(conv1x1_sb_hist_act_kernel<WM, WN>);
+            if (!ensure_dynamic_lds(k, lds, c_hist)) return FQ_ERR_HIP;
+            unsigned grid = (unsigned)kCUs * resident(k, 0);
+            if (grid > a.work) grid = a.work;
+            hipLaunchKernelGGL((conv1x1_sb_hist_act_kernel<WM, WN>), dim3(grid), dim3(kT), lds, st, a, interval,
+                               reinterpret_cast<unsigned long long*>(hist_row), fast, *cap);
+        } else if (max_inout) {
+            if (!ensure_dynamic_lds(reinterpret_cast<const void*>(conv1x1_sb_absmax_act_kernel<WM, WN>), lds, c_max)) return FQ_ERR_HIP;
+            hipLaunchKernelGGL((conv1x1_sb_absmax_act_kernel<WM, WN>), dim3(a.work), dim3(kT), lds, st, a,
+                               reinterpret_cast<unsigned int*>(max_inout), *cap);
+        } else {
+            if (!ensure_dynamic_lds(reinterpret_cast<const void*>(conv1x1_sb_act_kernel<WM, WN>), lds, c_plain)) return FQ_ERR_HIP;
+            hipLaunchKernelGGL((conv1x1_sb_act_kernel<WM, WN>), dim3(a.work), dim3(kT), lds, st, a, *cap);
+        }
+    } else if (add) {
         if (hist_y) {
             const void* k = reinterpret_cast<const void*>(conv1x1_sb_add_hist_kernel<WM, WN>);
             if (!ensure_dynamic_lds(k, lds, d_ah)) return FQ_ERR_HIP;
@@ -1000,7 +1107,9 @@ namespace {
 int conv_f32_launch(const float* x, const float* wt, const float* bias, float* y, float* relu_out, int N, int Cin, int Hin, int Win,
                     int Cout, int R, int S, int stride, int pad, float* max_inout, const float* interval, int64_t* hist_row,
                     void* workspace, size_t workspace_bytes, fq_stream_t stream, const QdStat* qd = nullptr,
-                    const unsigned short* wsb = nullptr) {
+                    const unsigned short* wsb = nullptr, const float* cap = nullptr) {
+    // (cap: the `_act` entry points -- relu_out receives clamp(y, 0, *cap) instead of max(y, 0); no QuanDequan form)
+    if (cap && (!relu_out || qd || !act_cap_ok(*cap))) return FQ_ERR_INVALID_ARG;
     if (N < 0 || Cin <= 0 || Hin <= 0 || Win <= 0 || Cout <= 0 || stride < 1 || R < 1 || S < 1 || pad < 0) return FQ_ERR_INVALID_ARG;
     if (wsb) wt = reinterpret_cast<const float*>(wsb);                                        // (the checks below: non-null, 16-byte aligned)
     if (Hin + 2 * pad < R || Win + 2 * pad < S) return FQ_ERR_INVALID_ARG;
@@ -1045,14 +1154,14 @@ int conv_f32_launch(const float* x, const float* wt, const float* bias, float* y
     const size_t tiles22 = ((cols + 127) / 128) * (size_t)((Cout + 127) / 128);
     const int shape = forced ? forced : ((Cout <= 64 || tiles22 <= (size_t)kCUs * 4) ? 12 : 22);
     if (wsb) {
-        if (shape == 12) return launch_sb<1, 2>(a, max_inout, interval, hist_row, fast, qd, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, workspace, workspace_bytes, st);
-        return launch_sb<2, 2>(a, max_inout, interval, hist_row, fast, qd, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, workspace, workspace_bytes, st);
+        if (shape == 12) return launch_sb<1, 2>(a, max_inout, interval, hist_row, fast, qd, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, workspace, workspace_bytes, st, cap);
+        return launch_sb<2, 2>(a, max_inout, interval, hist_row, fast, qd, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, workspace, workspace_bytes, st, cap);
     }
 #define FQ_C1_LAUNCH(WM, WN)                                                                                       \
     do {                                                                                                           \
-        if (mode == 2) launch<WM, WN, 2>(a, a.cols, max_inout, interval, hist_row, hist_per_cu, fast, qd, workspace, workspace_bytes, st);     \
-        else if (mode == 1) launch<WM, WN, 1>(a, a.cols, max_inout, interval, hist_row, hist_per_cu, fast, qd, workspace, workspace_bytes, st); \
-        else launch<WM, WN, 0>(a, a.cols, max_inout, interval, hist_row, hist_per_cu, fast, qd, workspace, workspace_bytes, st);               \
+        if (mode == 2) launch<WM, WN, 2>(a, a.cols, max_inout, interval, hist_row, hist_per_cu, fast, qd, workspace, workspace_bytes, st, cap);     \
+        else if (mode == 1) launch<WM, WN, 1>(a, a.cols, max_inout, interval, hist_row, hist_per_cu, fast, qd, workspace, workspace_bytes, st, cap); \
+        else launch<WM, WN, 0>(a, a.cols, max_inout, interval, hist_row, hist_per_cu, fast, qd, workspace, workspace_bytes, st, cap);               \
     } while (0)
     if (shape == 12) FQ_C1_LAUNCH(1, 2);
     else FQ_C1_LAUNCH(2, 2);
@@ -1078,6 +1187,22 @@ extern "C" int fq_conv_kxk_f32(const float* x, const float* wt, const float* bia
                                fq_stream_t stream) {
     return conv_f32_launch(x, wt, bias, y, relu_out, N, Cin, Hin, Win, Cout, R, S, stride, pad, max_inout, interval, hist_row,
                            workspace, workspace_bytes, stream);
+}
+
+// fq_conv1x1_f32 / fq_conv_kxk_f32 with relu_out = clamp(y, 0, act_cap) (nn.ReLU6: 6) in place of max(y, 0)
+extern "C" int fq_conv1x1_f32_act(const float* x, const float* wt, const float* bias, float* y, float* relu_out, float act_cap, int N,
+                                  int Cin, int Hin, int Win, int Cout, int stride, float* max_inout, const float* interval,
+                                  int64_t* hist_row, void* workspace, size_t workspace_bytes, fq_stream_t stream) {
+    return conv_f32_launch(x, wt, bias, y, relu_out, N, Cin, Hin, Win, Cout, 1, 1, stride, 0, max_inout, interval, hist_row,
+                           workspace, workspace_bytes, stream, nullptr, nullptr, &act_cap);
+}
+
+extern "C" int fq_conv_kxk_f32_act(const float* x, const float* wt, const float* bias, float* y, float* relu_out, float act_cap, int N,
+                                   int Cin, int Hin, int Win, int Cout, int R, int S, int stride, int pad, float* max_inout,
+                                   const float* interval, int64_t* hist_row, void* workspace, size_t workspace_bytes,
+                                   fq_stream_t stream) {
+    return conv_f32_launch(x, wt, bias, y, relu_out, N, Cin, Hin, Win, Cout, R, S, stride, pad, max_inout, interval, hist_row,
+                           workspace, workspace_bytes, stream, nullptr, nullptr, &act_cap);
 }
 
 // The last 1x1 convolution of a residual block together with the Eltwise (fabu_layer.py:5-11) and the ReLU behind it:
@@ -1218,6 +1343,14 @@ extern "C" int fq_conv1x1_sb_f32(const float* x, const void* wsb, const float* b
     if (!wsb) return FQ_ERR_INVALID_ARG;
     return conv_f32_launch(x, nullptr, bias, y, relu_out, N, Cin, Hin, Win, Cout, 1, 1, stride, 0, max_inout, interval, hist_row,
                            workspace, workspace_bytes, stream, nullptr, static_cast<const unsigned short*>(wsb));
+}
+
+extern "C" int fq_conv1x1_sb_f32_act(const float* x, const void* wsb, const float* bias, float* y, float* relu_out, float act_cap, int N,
+                                     int Cin, int Hin, int Win, int Cout, int stride, float* max_inout, const float* interval,
+                                     int64_t* hist_row, void* workspace, size_t workspace_bytes, fq_stream_t stream) {
+    if (!wsb) return FQ_ERR_INVALID_ARG;
+    return conv_f32_launch(x, nullptr, bias, y, relu_out, N, Cin, Hin, Win, Cout, 1, 1, stride, 0, max_inout, interval, hist_row,
+                           workspace, workspace_bytes, stream, nullptr, static_cast<const unsigned short*>(wsb), &act_cap);
 }
 
 extern "C" int fq_conv1x1_sb_qd_f32(const float* x, const void* wsb, const float* bias, float* y, int N, int Cin, int Hin, int Win,

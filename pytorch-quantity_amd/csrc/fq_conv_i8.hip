@@ -1734,8 +1734,10 @@ __global__ __launch_bounds__(64 * kLinWaves) void linear_i8_wave_kernel(const in
 static int conv2d_i8_dispatch(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, float* y_nchw, int8_t* q_nhwc,
                               int Kpad, int relu, const FusedAdd& fa, int N, int H, int W, int C, int K, int R, int S, int stride_h, int stride_w,
                               int pad_h, int pad_w, int dil_h, int dil_w, int rs, int ob, int bitwidth, fq_stream_t stream,
-                              const int32_t* rs_k = nullptr, int rs_max = 0) {
+                              const int32_t* rs_k = nullptr, int rs_max = 0, const SpRange* act = nullptr) {
     // (rs_k: one shift per output channel, in [rs, rs_max] -- the caller's bounds; rs_k == nullptr: rs is the layer's shift)
+    // (act: the Sp range of the _act entry points in place of relu -- 8-bit outputs only)
+    if (act && (relu || bitwidth != 8 || !sp_range_valid(*act))) return FQ_ERR_INVALID_ARG;
     if (!valid_bitwidth(bitwidth) || rs < -120 || rs > 120 || ob < -120 || ob > 120) return FQ_ERR_INVALID_ARG;
     if (rs_k && (rs_max < rs || rs_max > 120 || (reinterpret_cast<uintptr_t>(rs_k) & 15u))) return FQ_ERR_INVALID_ARG;
     if (N < 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || R <= 0 || S <= 0 || stride_h <= 0 || stride_w <= 0 ||
@@ -1765,6 +1767,9 @@ static int conv2d_i8_dispatch(const int8_t* x_nhwc, const int8_t* w_krsc, const 
     if (bitwidth == 8) { p.lo = -128.0f; p.hi = 127.0f; p.ilo = -128; p.ihi = 127; }
     else { p.lo = -32768.0f; p.hi = 32767.0f; p.ilo = -32768; p.ihi = 32767; }
     if (relu) p.lo = 0.0f;                                // ReLU commutes with the positive scale 2^-ob
+    // (a clip at c = hi * 2^-ob likewise: min(max(q, 0), hi) * 2^-ob = min(max(q * 2^-ob, 0), c).  What the host proves from the
+    //  range below still holds: [lo, hi] lies inside [-128, 127], so tail_consts' bias clamp stays inside [-255, 255] = qmax)
+    if (act) { p.lo = (float)act->lo; p.hi = (float)act->hi; }
     // integer tail where it is provably the same function (see conv_tail_i)
     // (... and with the bias folded into the rounding constant -- tail_consts: |qb| <= shi - ilo after its clamp, shifted by rs)
     const long qmax = bitwidth == 8 ? 255 : 65535;
@@ -1860,6 +1865,15 @@ extern "C" int fq_conv2d_i8_resident(const int8_t* x_nhwc, const int8_t* w_krsc,
                               pad_w, dil_h, dil_w, rs, ob, 8, stream);
 }
 
+extern "C" int fq_conv2d_i8_resident_act(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, float* y_nchw,
+                                         int8_t* q_nhwc, int Kpad, int act_lo, int act_hi, int N, int H, int W, int C, int K, int R,
+                                         int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int rs, int ob,
+                                         fq_stream_t stream) {
+    const SpRange act{act_lo, act_hi};
+    return conv2d_i8_dispatch(x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, Kpad, 0, FusedAdd{}, N, H, W, C, K, R, S, stride_h, stride_w, pad_h,
+                              pad_w, dil_h, dil_w, rs, ob, 8, stream, nullptr, 0, &act);
+}
+
 extern "C" int fq_conv2d_i8_add_resident(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, const void* res,
                                          int res_bytes, int g_res, int16_t* wide, int g_wide, int8_t* narrow, int ib, int relu,
                                          int Kpad, int N, int H, int W, int C, int K, int R, int S, int stride_h, int stride_w,
@@ -1888,6 +1902,16 @@ extern "C" int fq_conv2d_i8_resident_pcs(const int8_t* x_nhwc, const int8_t* w_k
     if (!rs_k && N > 0) return FQ_ERR_INVALID_ARG;
     return conv2d_i8_dispatch(x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, Kpad, relu, FusedAdd{}, N, H, W, C, K, R, S, stride_h, stride_w, pad_h,
                               pad_w, dil_h, dil_w, rs_min, ob, 8, stream, rs_k, rs_max);
+}
+
+extern "C" int fq_conv2d_i8_resident_pcs_act(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, const int32_t* rs_k,
+                                             int rs_min, int rs_max, float* y_nchw, int8_t* q_nhwc, int Kpad, int act_lo, int act_hi,
+                                             int N, int H, int W, int C, int K, int R, int S, int stride_h, int stride_w, int pad_h,
+                                             int pad_w, int dil_h, int dil_w, int ob, fq_stream_t stream) {
+    if (!rs_k && N > 0) return FQ_ERR_INVALID_ARG;
+    const SpRange act{act_lo, act_hi};
+    return conv2d_i8_dispatch(x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, Kpad, 0, FusedAdd{}, N, H, W, C, K, R, S, stride_h, stride_w, pad_h,
+                              pad_w, dil_h, dil_w, rs_min, ob, 8, stream, rs_k, rs_max, &act);
 }
 
 extern "C" int fq_conv2d_i8_add_resident_pcs(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, const int32_t* rs_k,

@@ -110,7 +110,7 @@ __device__ __forceinline__ void dwf_tiles(const DwfArgs& a, Stat& stat, float* s
             for (int j = 0; j < kDwfStrip; ++j) {
                 const float val = acc[j] + b;
                 out[j] = stat_map(stat, val);
-                rl[j] = relu_like_torch(val);
+                rl[j] = stat_act(stat, val);
                 if (j < cnt) stat.add(val);
             }
             if (a.y) {
@@ -168,6 +168,42 @@ __global__ __launch_bounds__(kT) void dwconv_f32_kernel(const DwfArgs a, const P
     }
 }
 
+// the same with the ReLU copy clipped at `cap` (fq_dwconv_f32_act): the statistic wrapped in Clipped<>
+template <int R, int STRIDE, typename Stat>
+__global__ __launch_bounds__(kT) void dwconv_f32_act_kernel(const DwfArgs a, const ProducerStatArgs sa, const float cap) {
+    __shared__ __attribute__((aligned(16))) float smem[kDwfLdsFloats + kDwfMaxPP * (R * R + 1)];
+    if constexpr (__is_same(Stat, HistTag)) {
+        __shared__ unsigned int s_bins[FQ_BINS + kWave];
+        for (int b = threadIdx.x; b < FQ_BINS + kWave; b += kT) s_bins[b] = 0u;
+        __syncthreads();
+        const float iv = *sa.interval;
+        unsigned int* park = s_bins + FQ_BINS + (threadIdx.x & (kWave - 1));
+        if (sa.allow_fast && fast_quotient_ok(iv)) {
+            Clipped<HistStat<true>> st{{s_bins, park, iv, 1.0f / iv}, cap};
+            dwf_tiles<R, STRIDE>(a, st, smem);
+        } else {
+            Clipped<HistStat<false>> st{{s_bins, park, iv, 1.0f / iv}, cap};
+            dwf_tiles<R, STRIDE>(a, st, smem);
+        }
+        hist_flush<kT>(s_bins, sa.hist_row);
+    } else if constexpr (__is_same(Stat, MaxStat)) {
+        Clipped<MaxStat> st{{}, cap};
+        dwf_tiles<R, STRIDE>(a, st, smem);
+        publish_max<kT>(st.m, sa.max_bits);
+    } else {
+        Clipped<NoStat> st{{}, cap};
+        dwf_tiles<R, STRIDE>(a, st, smem);
+    }
+}
+
+template <typename Stat>
+void dwf_launch_act(int R, int stride, unsigned grid, hipStream_t st, const DwfArgs& a, const ProducerStatArgs& sa, float cap) {
+    if (R == 3 && stride == 1) hipLaunchKernelGGL((dwconv_f32_act_kernel<3, 1, Stat>), dim3(grid), dim3(kT), 0, st, a, sa, cap);
+    else if (R == 3) hipLaunchKernelGGL((dwconv_f32_act_kernel<3, 2, Stat>), dim3(grid), dim3(kT), 0, st, a, sa, cap);
+    else if (stride == 1) hipLaunchKernelGGL((dwconv_f32_act_kernel<5, 1, Stat>), dim3(grid), dim3(kT), 0, st, a, sa, cap);
+    else hipLaunchKernelGGL((dwconv_f32_act_kernel<5, 2, Stat>), dim3(grid), dim3(kT), 0, st, a, sa, cap);
+}
+
 template <typename Stat>
 void dwf_launch(int R, int stride, unsigned grid, hipStream_t st, const DwfArgs& a, const ProducerStatArgs& sa) {
     if (R == 3 && stride == 1) hipLaunchKernelGGL((dwconv_f32_kernel<3, 1, Stat>), dim3(grid), dim3(kT), 0, st, a, sa);
@@ -182,7 +218,10 @@ bool dwf_supported(int C, int R, int S, int stride_h, int stride_w, int pad_h, i
 }
 
 int dwf_dispatch(const float* x, const float* w, const float* bias, float* y, float* relu_out, int N, int C, int H, int W, int R, int S,
-                 int stride, int pad, float* max_inout, const float* interval, int64_t* hist_row, const QdStat* qd, fq_stream_t stream) {
+                 int stride, int pad, float* max_inout, const float* interval, int64_t* hist_row, const QdStat* qd, fq_stream_t stream,
+                 const float* cap = nullptr) {
+    // (cap: the `_act` entry point -- relu_out receives clamp(y, 0, *cap) instead of max(y, 0); no QuanDequan form)
+    if (cap && (!relu_out || qd || !act_cap_ok(*cap))) return FQ_ERR_INVALID_ARG;
     if (N < 1 || C < 1 || H < 1 || W < 1 || R < 1 || S < 1 || stride < 1 || pad < 0) return FQ_ERR_INVALID_ARG;
     if (const int rc = producer_args_ok(x, w, bias, y, relu_out, max_inout, interval, hist_row, qd)) return rc;
     if (!dwf_supported(C, R, S, stride, stride, pad, pad, 1, 1, H, W)) return FQ_ERR_UNSUPPORTED;
@@ -200,7 +239,11 @@ int dwf_dispatch(const float* x, const float* w, const float* bias, float* y, fl
     sa.qd = qd ? *qd : QdStat{1.0f, 1.0f, -128.0f, 127.0f};
     hipStream_t st = as_stream(stream);
     const unsigned grid = dwf_grid(a.g, hist_row != nullptr);
-    if (qd) dwf_launch<QdStat>(R, stride, grid, st, a, sa);
+    if (cap) {
+        if (hist_row) dwf_launch_act<HistTag>(R, stride, grid, st, a, sa, *cap);
+        else if (max_inout) dwf_launch_act<MaxStat>(R, stride, grid, st, a, sa, *cap);
+        else dwf_launch_act<NoStat>(R, stride, grid, st, a, sa, *cap);
+    } else if (qd) dwf_launch<QdStat>(R, stride, grid, st, a, sa);
     else if (hist_row) dwf_launch<HistTag>(R, stride, grid, st, a, sa);
     else if (max_inout) dwf_launch<MaxStat>(R, stride, grid, st, a, sa);
     else dwf_launch<NoStat>(R, stride, grid, st, a, sa);
@@ -222,6 +265,13 @@ extern "C" int fq_dwconv_f32(const float* x, const float* w_crs, const float* bi
                              int W, int R, int S, int stride, int pad, float* max_inout, const float* interval, int64_t* hist_row,
                              fq_stream_t stream) {
     return dwf_dispatch(x, w_crs, bias, y, relu_out, N, C, H, W, R, S, stride, pad, max_inout, interval, hist_row, nullptr, stream);
+}
+
+extern "C" int fq_dwconv_f32_act(const float* x, const float* w_crs, const float* bias, float* y, float* relu_out, float act_cap, int N,
+                                 int C, int H, int W, int R, int S, int stride, int pad, float* max_inout, const float* interval,
+                                 int64_t* hist_row, fq_stream_t stream) {
+    return dwf_dispatch(x, w_crs, bias, y, relu_out, N, C, H, W, R, S, stride, pad, max_inout, interval, hist_row, nullptr, stream,
+                        &act_cap);
 }
 
 // TestConv.forward of a depthwise layer in one kernel: QuanDequan(bit) of the value fq_dwconv_f32 would have stored

@@ -170,8 +170,9 @@ static void dw_launch(int R, int stride, unsigned blocks, hipStream_t st, const 
 }
 
 static int dwconv_dispatch(const int8_t* x_nhwc, const int8_t* w_rsc, const float* qbias, const int32_t* rs_k, int rs_min,
-                           int rs_max, int8_t* q_nhwc, int Cpad, int relu, int N, int H, int W, int C, int R, int S, int stride_h,
+                           int rs_max, int8_t* q_nhwc, int Cpad, SpRange sp, int N, int H, int W, int C, int R, int S, int stride_h,
                            int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int ob, fq_stream_t stream) {
+    if (!sp_range_valid(sp)) return FQ_ERR_INVALID_ARG;   // (the Sp range: [-128, 127], [0, 127] with a ReLU, or an _act caller's)
     if (rs_min < -120 || rs_max > 120 || rs_min > rs_max || ob < -120 || ob > 120) return FQ_ERR_INVALID_ARG;
     if (rs_k && (reinterpret_cast<uintptr_t>(rs_k) & 15u)) return FQ_ERR_INVALID_ARG;
     if (N < 0 || H <= 0 || W <= 0 || C <= 0 || R <= 0 || S <= 0 || stride_h <= 0 || stride_w <= 0 || pad_h < 0 || pad_w < 0 ||
@@ -200,7 +201,8 @@ static int dwconv_dispatch(const int8_t* x_nhwc, const int8_t* w_rsc, const floa
     p.C = C;
     // accumulator bound of the integer tail (fq_int_tail.h): 25 * 128 * 128 < 2^19, bias term below 2^(9 + 16)
     p.rs = rs_min; p.half_rs = 1 << (rs_min - 1);
-    p.ilo = -128; p.ihi = 127; p.slo = relu ? 0 : -128; p.shi = 127;
+    // (any Sp range inside [-128, 127] keeps tail_consts' bias clamp inside [-255, 255])
+    p.ilo = -128; p.ihi = 127; p.slo = sp.lo; p.shi = sp.hi;
     const long lanes = tiles * g.C4;
     long blocks = (lanes + kDwBlock - 1) / kDwBlock;
     if (blocks > kDwMaxBlocks) blocks = kDwMaxBlocks;
@@ -224,7 +226,7 @@ extern "C" int fq_dwconv2d_i8_supported(int C, int R, int S, int stride_h, int s
 extern "C" int fq_dwconv2d_i8_resident(const int8_t* x_nhwc, const int8_t* w_rsc, const float* qbias, int8_t* q_nhwc, int Cpad,
                                        int relu, int N, int H, int W, int C, int R, int S, int stride_h, int stride_w, int pad_h,
                                        int pad_w, int dil_h, int dil_w, int rs, int ob, fq_stream_t stream) {
-    return dwconv_dispatch(x_nhwc, w_rsc, qbias, nullptr, rs, rs, q_nhwc, Cpad, relu, N, H, W, C, R, S, stride_h, stride_w, pad_h,
+    return dwconv_dispatch(x_nhwc, w_rsc, qbias, nullptr, rs, rs, q_nhwc, Cpad, sp_range_relu(relu), N, H, W, C, R, S, stride_h, stride_w, pad_h,
                            pad_w, dil_h, dil_w, ob, stream);
 }
 
@@ -233,6 +235,23 @@ extern "C" int fq_dwconv2d_i8_resident_pcs(const int8_t* x_nhwc, const int8_t* w
                                            int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
                                            int ob, fq_stream_t stream) {
     if (!rs_k && N > 0) return FQ_ERR_INVALID_ARG;
-    return dwconv_dispatch(x_nhwc, w_rsc, qbias, rs_k, rs_min, rs_max, q_nhwc, Cpad, relu, N, H, W, C, R, S, stride_h, stride_w,
+    return dwconv_dispatch(x_nhwc, w_rsc, qbias, rs_k, rs_min, rs_max, q_nhwc, Cpad, sp_range_relu(relu), N, H, W, C, R, S, stride_h, stride_w,
                            pad_h, pad_w, dil_h, dil_w, ob, stream);
+}
+
+extern "C" int fq_dwconv2d_i8_resident_act(const int8_t* x_nhwc, const int8_t* w_rsc, const float* qbias, int8_t* q_nhwc, int Cpad,
+                                           int act_lo, int act_hi, int N, int H, int W, int C, int R, int S, int stride_h,
+                                           int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int rs, int ob,
+                                           fq_stream_t stream) {
+    return dwconv_dispatch(x_nhwc, w_rsc, qbias, nullptr, rs, rs, q_nhwc, Cpad, SpRange{act_lo, act_hi}, N, H, W, C, R, S, stride_h,
+                           stride_w, pad_h, pad_w, dil_h, dil_w, ob, stream);
+}
+
+extern "C" int fq_dwconv2d_i8_resident_pcs_act(const int8_t* x_nhwc, const int8_t* w_rsc, const float* qbias, const int32_t* rs_k,
+                                               int rs_min, int rs_max, int8_t* q_nhwc, int Cpad, int act_lo, int act_hi, int N, int H,
+                                               int W, int C, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                                               int dil_h, int dil_w, int ob, fq_stream_t stream) {
+    if (!rs_k && N > 0) return FQ_ERR_INVALID_ARG;
+    return dwconv_dispatch(x_nhwc, w_rsc, qbias, rs_k, rs_min, rs_max, q_nhwc, Cpad, SpRange{act_lo, act_hi}, N, H, W, C, R, S,
+                           stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, ob, stream);
 }

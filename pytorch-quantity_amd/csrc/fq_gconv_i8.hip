@@ -135,9 +135,10 @@ static void gc_launch(int R, int stride, unsigned blocks, size_t lds, hipStream_
 }
 
 static int gconv_dispatch(const int8_t* x_nhwc, const int8_t* w_pack, const float* qbias, const int32_t* rs_k, int rs_min,
-                          int rs_max, int8_t* q_nhwc, int Cpad, int Kpad, int relu, int N, int H, int W, int C, int K, int groups,
+                          int rs_max, int8_t* q_nhwc, int Cpad, int Kpad, SpRange sp, int N, int H, int W, int C, int K, int groups,
                           int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int ob,
                           fq_stream_t stream) {
+    if (!sp_range_valid(sp)) return FQ_ERR_INVALID_ARG;   // (the Sp range: [-128, 127], [0, 127] with a ReLU, or an _act caller's)
     if (rs_min < -120 || rs_max > 120 || rs_min > rs_max || ob < -120 || ob > 120) return FQ_ERR_INVALID_ARG;
     if (rs_k && (reinterpret_cast<uintptr_t>(rs_k) & 15u)) return FQ_ERR_INVALID_ARG;
     if (N < 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || groups <= 0 || R <= 0 || S <= 0 || stride_h <= 0 || stride_w <= 0 ||
@@ -160,7 +161,8 @@ static int gconv_dispatch(const int8_t* x_nhwc, const int8_t* w_pack, const floa
     if (!gc_setup(p.g, N, H, W, C, K, groups, R, stride_h, pad_h, pad_w)) return FQ_ERR_UNSUPPORTED;
     // accumulator bound of the integer tail (fq_int_tail.h): 9 * 64 * 128 * 128 < 2^24, bias term below 2^(9 + 16)
     p.rs = rs_min; p.half_rs = 1 << (rs_min - 1);
-    p.ilo = -128; p.ihi = 127; p.slo = relu ? 0 : -128; p.shi = 127;
+    // (any Sp range inside [-128, 127] keeps tail_consts' bias clamp inside [-255, 255])
+    p.ilo = -128; p.ihi = 127; p.slo = sp.lo; p.shi = sp.hi;
     hipStream_t st = as_stream(stream);
     const unsigned blocks = gc_blocks(p.g);
     const size_t lds = (size_t)p.g.units * kGcUnit;
@@ -184,7 +186,7 @@ extern "C" int fq_gconv2d_i8_resident(const int8_t* x_nhwc, const int8_t* w_pack
                                       int Kpad, int relu, int N, int H, int W, int C, int K, int groups, int R, int S,
                                       int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int rs, int ob,
                                       fq_stream_t stream) {
-    return gconv_dispatch(x_nhwc, w_pack, qbias, nullptr, rs, rs, q_nhwc, Cpad, Kpad, relu, N, H, W, C, K, groups, R, S, stride_h,
+    return gconv_dispatch(x_nhwc, w_pack, qbias, nullptr, rs, rs, q_nhwc, Cpad, Kpad, sp_range_relu(relu), N, H, W, C, K, groups, R, S, stride_h,
                           stride_w, pad_h, pad_w, dil_h, dil_w, ob, stream);
 }
 
@@ -193,6 +195,23 @@ extern "C" int fq_gconv2d_i8_resident_pcs(const int8_t* x_nhwc, const int8_t* w_
                                           int W, int C, int K, int groups, int R, int S, int stride_h, int stride_w, int pad_h,
                                           int pad_w, int dil_h, int dil_w, int ob, fq_stream_t stream) {
     if (!rs_k && N > 0) return FQ_ERR_INVALID_ARG;
-    return gconv_dispatch(x_nhwc, w_pack, qbias, rs_k, rs_min, rs_max, q_nhwc, Cpad, Kpad, relu, N, H, W, C, K, groups, R, S,
+    return gconv_dispatch(x_nhwc, w_pack, qbias, rs_k, rs_min, rs_max, q_nhwc, Cpad, Kpad, sp_range_relu(relu), N, H, W, C, K, groups, R, S,
                           stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, ob, stream);
+}
+
+extern "C" int fq_gconv2d_i8_resident_act(const int8_t* x_nhwc, const int8_t* w_pack, const float* qbias, int8_t* q_nhwc, int Cpad,
+                                          int Kpad, int act_lo, int act_hi, int N, int H, int W, int C, int K, int groups, int R,
+                                          int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int rs,
+                                          int ob, fq_stream_t stream) {
+    return gconv_dispatch(x_nhwc, w_pack, qbias, nullptr, rs, rs, q_nhwc, Cpad, Kpad, SpRange{act_lo, act_hi}, N, H, W, C, K, groups,
+                          R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, ob, stream);
+}
+
+extern "C" int fq_gconv2d_i8_resident_pcs_act(const int8_t* x_nhwc, const int8_t* w_pack, const float* qbias, const int32_t* rs_k,
+                                              int rs_min, int rs_max, int8_t* q_nhwc, int Cpad, int Kpad, int act_lo, int act_hi,
+                                              int N, int H, int W, int C, int K, int groups, int R, int S, int stride_h, int stride_w,
+                                              int pad_h, int pad_w, int dil_h, int dil_w, int ob, fq_stream_t stream) {
+    if (!rs_k && N > 0) return FQ_ERR_INVALID_ARG;
+    return gconv_dispatch(x_nhwc, w_pack, qbias, rs_k, rs_min, rs_max, q_nhwc, Cpad, Kpad, SpRange{act_lo, act_hi}, N, H, W, C, K,
+                          groups, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, ob, stream);
 }

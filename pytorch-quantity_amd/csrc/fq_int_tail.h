@@ -99,4 +99,12 @@ __device__ __forceinline__ unsigned pack4(int b0, int b1, int b2, int b3) {
     return __builtin_amdgcn_perm(p23, p01, 0x05040100u);
 }
 
+// The Sp range a producer's `_act` entry point takes in place of `relu` (include/fq.h): the output integers are clamped to
+// [lo, hi] instead of [-128, 127] (relu: [0, 127]).  lo <= 0 <= hi keeps what every kernel relies on for its padding channels --
+// zero weights and a zero bias give the integer 0 -- and [lo, hi] inside [-128, 127] keeps tail_consts' bias clamp
+// [slo - ihi, shi - ilo] inside [-255, 255], the bound the hosts' accumulator checks are made with.
+struct SpRange { int lo, hi; };
+inline SpRange sp_range_relu(int relu) { return SpRange{relu ? 0 : -128, 127}; }
+inline bool sp_range_valid(const SpRange& r) { return -128 <= r.lo && r.lo <= 0 && 0 <= r.hi && r.hi <= 127; }
+
 }  // namespace fq

@@ -13,6 +13,13 @@ namespace fq {
 // (the obvious  v > 0 ? v : (v != v ? v : 0)  is two compares, a scalar or and the select -- and every vector instruction of an
 // epilogue is time the matrix pipe does not get)
 __device__ __forceinline__ float relu_like_torch(float v) { return !(v <= 0.0f) ? v : 0.0f; }
+// torch's clamp(x, 0, cap) -- nn.ReLU6 is hardtanh(x, 0, 6) -- bit for bit: NaN stays NaN (fminf(fmaxf(.)) would lose it: "r > cap"
+// is false for NaN and hands r on), -0 and everything below become +0, everything above cap (+inf too) becomes cap, and cap
+// itself, its neighbours and the neighbours of 0 pass through untouched.  relu_like_torch, one compare and one select more.
+__device__ __forceinline__ float relu6_like_torch(float v, float cap) {
+    const float r = relu_like_torch(v);
+    return r > cap ? cap : r;
+}
 
 struct NoStat {
     __device__ __forceinline__ void add(float) {}
@@ -44,6 +51,20 @@ inline bool qd_from_bit(int bit, int bitwidth, QdStat* qd) {
 
 template <typename S> __device__ __forceinline__ float stat_map(const S&, float v) { return v; }
 __device__ __forceinline__ float stat_map(const QdStat& s, float v) { return s.map(v); }
+
+// The activation of the copy a producer writes next to its output (relu_out) rides on the same object: stat_act(stat, v) is
+// nn.ReLU's max(v, 0) for every statistic above, and nn.ReLU6's clamp(v, 0, cap) for the same statistic wrapped in Clipped<> --
+// the `_act` entry points (include/fq.h) instantiate their kernels on Clipped<NoStat / MaxStat / HistStat<>>, every other kernel
+// is instantiated as before.  The statistic itself is untouched: it is taken from the UNCLIPPED value, as the hook on the
+// convolution sees it.
+template <typename S>
+struct Clipped : S {
+    float cap;
+};
+template <typename S> __device__ __forceinline__ float stat_act(const S&, float v) { return relu_like_torch(v); }
+template <typename S> __device__ __forceinline__ float stat_act(const Clipped<S>& s, float v) { return relu6_like_torch(v, s.cap); }
+// host: a cap an `_act` entry point accepts (positive and finite; nn.ReLU6: 6)
+inline bool act_cap_ok(float cap) { return cap > 0.0f && cap <= 3.0e38f; }
 
 template <bool kFast>
 struct HistStat {

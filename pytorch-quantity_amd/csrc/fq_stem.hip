@@ -197,11 +197,12 @@ __global__ __launch_bounds__(kStemBlock) __attribute__((amdgpu_waves_per_eu(4)))
 }  // namespace fq
 
 // fp32 NCHW image -> int8 NHWC activations of the stem convolution (see include/fq.h)
-static int stem_dispatch(const float* x_nchw, const int8_t* w_stem, const float* qbias, int8_t* q_nhwc, int Kpad, int relu,
+static int stem_dispatch(const float* x_nchw, const int8_t* w_stem, const float* qbias, int8_t* q_nhwc, int Kpad, fq::SpRange sp,
                          int N, int C, int H, int W, int K, int R, int S, int stride_h, int stride_w, int pad_h,
                          int pad_w, int ib, int rs, int ob, fq_stream_t stream, const int32_t* rs_k) {
     using namespace fq;
     (void)ob;                                             // the output integers stand for q * 2^-ob; nothing to scale here
+    if (!sp_range_valid(sp)) return FQ_ERR_INVALID_ARG;   // (the Sp range: [-128, 127], [0, 127] with a ReLU, or an _act caller's)
     if (N < 0 || C < 1 || C > 4 || H < 1 || W < 1 || K < 1 || K > kStemK || R < 1 || R > kStemMaxR || S < 1 || S > 8)
         return FQ_ERR_INVALID_ARG;
     if (stride_h < 1 || stride_w < 1 || pad_h < 0 || pad_w < 0) return FQ_ERR_INVALID_ARG;
@@ -236,7 +237,7 @@ static int stem_dispatch(const float* x_nchw, const int8_t* w_stem, const float*
     p.rs = rs; p.half_rs = 1 << (rs - 1);
     p.rs_k = rs_k;
     p.ilo = -128; p.ihi = 127;
-    p.slo = relu ? 0 : -128; p.shi = 127;
+    p.slo = sp.lo; p.shi = sp.hi;
     static const int per_cu = [] { const char* e = getenv("FQ_STEM_WG_PER_CU"); return e ? atoi(e) : 0; }();
     long grid = (long)kCUs * (per_cu > 0 ? per_cu : 4);
     if (grid > ntiles) grid = ntiles;
@@ -265,8 +266,16 @@ static int stem_dispatch(const float* x_nchw, const int8_t* w_stem, const float*
 extern "C" int fq_conv2d_i8_stem(const float* x_nchw, const int8_t* w_stem, const float* qbias, int8_t* q_nhwc, int Kpad, int relu,
                                  int N, int C, int H, int W, int K, int R, int S, int stride_h, int stride_w, int pad_h,
                                  int pad_w, int ib, int rs, int ob, fq_stream_t stream) {
-    return stem_dispatch(x_nchw, w_stem, qbias, q_nhwc, Kpad, relu, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, ib, rs, ob,
-                         stream, nullptr);
+    return stem_dispatch(x_nchw, w_stem, qbias, q_nhwc, Kpad, fq::sp_range_relu(relu), N, C, H, W, K, R, S, stride_h, stride_w, pad_h,
+                         pad_w, ib, rs, ob, stream, nullptr);
+}
+
+// the same with the Sp range given in place of relu (a fused nn.ReLU6: [0, min(127, 6 * 2^ob)])
+extern "C" int fq_conv2d_i8_stem_act(const float* x_nchw, const int8_t* w_stem, const float* qbias, int8_t* q_nhwc, int Kpad,
+                                     int act_lo, int act_hi, int N, int C, int H, int W, int K, int R, int S, int stride_h,
+                                     int stride_w, int pad_h, int pad_w, int ib, int rs, int ob, fq_stream_t stream) {
+    return stem_dispatch(x_nchw, w_stem, qbias, q_nhwc, Kpad, fq::SpRange{act_lo, act_hi}, N, C, H, W, K, R, S, stride_h, stride_w,
+                         pad_h, pad_w, ib, rs, ob, stream, nullptr);
 }
 
 // the same with one shift per output channel: rs_k device int32[K], rs_min <= rs_k[k] <= rs_max, both in [1, 16]
@@ -275,6 +284,16 @@ extern "C" int fq_conv2d_i8_stem_pcs(const float* x_nchw, const int8_t* w_stem, 
                                      int stride_h, int stride_w, int pad_h, int pad_w, int ib, int ob, fq_stream_t stream) {
     if (rs_min < 1 || rs_max > 16 || rs_min > rs_max) return FQ_ERR_INVALID_ARG;
     if (N > 0 && (!rs_k || (reinterpret_cast<uintptr_t>(rs_k) & 3u))) return FQ_ERR_INVALID_ARG;
-    return stem_dispatch(x_nchw, w_stem, qbias, q_nhwc, Kpad, relu, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, ib, rs_min, ob,
-                         stream, N > 0 ? rs_k : nullptr);
+    return stem_dispatch(x_nchw, w_stem, qbias, q_nhwc, Kpad, fq::sp_range_relu(relu), N, C, H, W, K, R, S, stride_h, stride_w, pad_h,
+                         pad_w, ib, rs_min, ob, stream, N > 0 ? rs_k : nullptr);
+}
+
+extern "C" int fq_conv2d_i8_stem_pcs_act(const float* x_nchw, const int8_t* w_stem, const float* qbias, const int32_t* rs_k,
+                                         int rs_min, int rs_max, int8_t* q_nhwc, int Kpad, int act_lo, int act_hi, int N, int C, int H,
+                                         int W, int K, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int ib, int ob,
+                                         fq_stream_t stream) {
+    if (rs_min < 1 || rs_max > 16 || rs_min > rs_max) return FQ_ERR_INVALID_ARG;
+    if (N > 0 && (!rs_k || (reinterpret_cast<uintptr_t>(rs_k) & 3u))) return FQ_ERR_INVALID_ARG;
+    return stem_dispatch(x_nchw, w_stem, qbias, q_nhwc, Kpad, fq::SpRange{act_lo, act_hi}, N, C, H, W, K, R, S, stride_h, stride_w,
+                         pad_h, pad_w, ib, rs_min, ob, stream, N > 0 ? rs_k : nullptr);
 }

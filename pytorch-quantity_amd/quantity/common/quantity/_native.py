@@ -220,6 +220,12 @@ def lib():
     L.fq_gconv2d_i8_resident.argtypes = [vp, vp, vp, vp] + [ci] * 19 + [vp]
     L.fq_gconv2d_i8_resident_pcs.restype = ci
     L.fq_gconv2d_i8_resident_pcs.argtypes = [vp, vp, vp, vp, ci, ci, vp] + [ci] * 18 + [vp]
+    # the `_act` siblings of the integer producers: `int act_lo, int act_hi` where those take `int relu`
+    for name in ("fq_conv2d_i8_resident", "fq_conv2d_i8_resident_pcs", "fq_conv2d_i8_stem", "fq_conv2d_i8_stem_pcs",
+                 "fq_dwconv2d_i8_resident", "fq_dwconv2d_i8_resident_pcs", "fq_gconv2d_i8_resident", "fq_gconv2d_i8_resident_pcs"):
+        getattr(L, name + "_act").restype = ci
+        plain = getattr(L, name).argtypes                     # (..., int relu, ints ..., stream) -> (..., int act_lo, int act_hi, ints ..., stream)
+        getattr(L, name + "_act").argtypes = plain[:-1] + [ci, plain[-1]]
     L.fq_dwconv_f32_supported.restype = ci
     L.fq_dwconv_f32_supported.argtypes = [ci] * 11
     L.fq_dwconv_f32.restype = ci
@@ -250,6 +256,11 @@ def lib():
     L.fq_avgpool_global_nhwc.argtypes = [vp, ci, ci, vp, ci, ci, ci, ci, vp]
     L.fq_json_dump_i32.restype = ci
     L.fq_json_dump_i32.argtypes = [ctypes.c_char_p, vp, ci, vp, ci]
+    # the `_act` siblings of the float convolutions: `float act_cap` behind relu_out
+    for name in ("fq_conv1x1_f32", "fq_conv1x1_sb_f32", "fq_conv_kxk_f32", "fq_dwconv_f32"):
+        plain = getattr(L, name).argtypes
+        getattr(L, name + "_act").restype = ci
+        getattr(L, name + "_act").argtypes = plain[:5] + [ctypes.c_float] + plain[5:]
     _lib = L
     return L
 
@@ -614,12 +625,16 @@ def _sb(wt):
 
 
 def _conv_f32(name, x, w_ptr, bias, shape, ints, max_dev, interval_dev, hist_dev, row, relu_out, out, qd, workspace=False,
-              entry=None):
+              entry=None, act=None):
     """The one call path of the float convolutions: what rides on the output of entry point `name` (`entry` where the kernel
     family differs from the contract's name) -- nothing, the abs-max (max_dev/row), the histogram (interval_dev/hist_dev/row),
     a ReLU copy (relu_out; out=False: the copy alone), or QuanDequan (qd: the `..._qd_f32` entry with ints + (bit, bitwidth)).
     The wrapper has validated x and its weight operand; shape is the output's, ints the integer arguments in the ABI's order,
-    workspace whether the tail-split workspace goes between the statistic pointers and the stream.  Returns y."""
+    workspace whether the tail-split workspace goes between the statistic pointers and the stream.  act (None, or a cap: 6.0 for
+    an nn.ReLU6): the `<entry>_act` sibling, whose relu_out receives clamp(y, 0, act) instead of max(y, 0); without it the call is
+    the plain entry point's, argument for argument.  Returns y."""
+    if act is not None and (relu_out is None or qd is not None):
+        raise FqError(name + "_act: an activation cap needs relu_out and takes no QuanDequan epilogue")
     if out is False:                                            # only the ReLU's output is wanted: y is not written
         assert relu_out is not None and qd is None and tuple(relu_out.shape) == shape
         y = None
@@ -646,16 +661,22 @@ def _conv_f32(name, x, w_ptr, bias, shape, ints, max_dev, interval_dev, hist_dev
         assert max_dev.is_contiguous() and 0 <= row < max_dev.numel()
         mp = max_dev.data_ptr() + 4 * int(row)
     rp = None if relu_out is None else _relu_ptr(relu_out, relu_out if y is None else y)
+    if act is not None:
+        _check(getattr(lib(), entry + "_act")(x.data_ptr(), w_ptr, bp, None if y is None else y.data_ptr(), rp, float(act), *ints,
+                                              mp, ivp, hp, *(conv_workspace(x) if workspace else ()), _stream(x)), name + "_act")
+        return y
     _check(getattr(lib(), entry)(x.data_ptr(), w_ptr, bp, None if y is None else y.data_ptr(), rp, *ints, mp, ivp, hp,
                                  *(conv_workspace(x) if workspace else ()), _stream(x)), name)
     return y
 
 
-def conv1x1_f32(x, wt, bias, stride=1, max_dev=None, interval_dev=None, hist_dev=None, row=None, relu_out=None, out=None, qd=None):
+def conv1x1_f32(x, wt, bias, stride=1, max_dev=None, interval_dev=None, hist_dev=None, row=None, relu_out=None, out=None, qd=None,
+                act=None):
     """fq_conv1x1_f32: the float 1x1 convolution (padding 0, groups 1) of x [N, Cin, H, W] with the TRANSPOSED weights
     wt [Cin, Cout] on the fp32 matrix cores; max_dev/row: abs-max of the output folded into max_dev[row]; interval_dev/
     hist_dev/row: the output histogrammed into hist_dev[row]; relu_out: also receives max(y, 0).  qd = bit or (bit, bitwidth):
-    fq_conv1x1_qd_f32 instead -- QuanDequan(bit) applied in the epilogue (TestConv.forward in one kernel).  Returns y."""
+    fq_conv1x1_qd_f32 instead -- QuanDequan(bit) applied in the epilogue (TestConv.forward in one kernel).  act = 6.0:
+    fq_conv1x1_f32_act -- relu_out receives clamp(y, 0, 6), nn.ReLU6's result, instead.  Returns y."""
     _need_cuda(x, torch.float32, "fq_conv1x1_f32")
     sb, wcin, Cout = _sb(wt)                                    # (an int16 [3, Cout, Cin] pack: the split-bf16 kernels)
     assert x.dim() == 4 and x.is_contiguous() and wcin == x.shape[1]
@@ -663,7 +684,7 @@ def conv1x1_f32(x, wt, bias, stride=1, max_dev=None, interval_dev=None, hist_dev
     s = int(stride)
     shape = (N, Cout, (H - 1) // s + 1, (W - 1) // s + 1)
     return _conv_f32("fq_conv1x1_f32", x, wt.data_ptr(), bias, shape, (N, Cin, H, W, Cout, s), max_dev, interval_dev, hist_dev, row,
-                     relu_out, out, qd, True, "fq_conv1x1_sb_f32" if sb else None)
+                     relu_out, out, qd, True, "fq_conv1x1_sb_f32" if sb else None, act)
 
 
 def conv1x1_add_f32(x, wt, bias, stride, res, max_dev, row_y, row_sum, relu_out, out=None, sum_out=None):
@@ -720,9 +741,9 @@ def pack_kxk_weight(weight):
 
 
 def conv_kxk_f32(x, wt, bias, kernel, stride, pad, max_dev=None, interval_dev=None, hist_dev=None, row=None, relu_out=None,
-                 out=None, qd=None):
+                 out=None, qd=None, act=None):
     """fq_conv_kxk_f32: the float R x S convolution (zero padding `pad`, dilation 1, groups 1) of x [N, Cin, H, W] with the
-    weights packed by pack_kxk_weight; statistics / relu_out / out as in conv1x1_f32.  Returns y."""
+    weights packed by pack_kxk_weight; statistics / relu_out / out / act as in conv1x1_f32.  Returns y."""
     _need_cuda(x, torch.float32, "fq_conv_kxk_f32")
     _need_cuda(wt, torch.float32, "fq_conv_kxk_f32")
     R, S = int(kernel[0]), int(kernel[1])
@@ -731,7 +752,7 @@ def conv_kxk_f32(x, wt, bias, kernel, stride, pad, max_dev=None, interval_dev=No
     Cout, st, pd = int(wt.shape[1]), int(stride), int(pad)
     shape = (N, Cout, (H + 2 * pd - R) // st + 1, (W + 2 * pd - S) // st + 1)
     return _conv_f32("fq_conv_kxk_f32", x, wt.data_ptr(), bias, shape, (N, Cin, H, W, Cout, R, S, st, pd), max_dev, interval_dev,
-                     hist_dev, row, relu_out, out, qd, True)
+                     hist_dev, row, relu_out, out, qd, True, None, act)
 
 
 def dwconv_f32_supported(c, kernel, stride, pad, dilation, h, w):
@@ -741,9 +762,9 @@ def dwconv_f32_supported(c, kernel, stride, pad, dilation, h, w):
 
 
 def dwconv_f32(x, w, bias, kernel, stride, pad, max_dev=None, interval_dev=None, hist_dev=None, row=None, relu_out=None, out=None,
-               qd=None):
+               qd=None, act=None):
     """fq_dwconv_f32: the float depthwise convolution (groups == channels, zero padding `pad`, dilation 1) of x [N, C, H, W] with
-    the module's own weight w [C, 1, R, S]; statistics / relu_out / out / qd as in conv1x1_f32.  Returns y."""
+    the module's own weight w [C, 1, R, S]; statistics / relu_out / out / qd / act as in conv1x1_f32.  Returns y."""
     _need_cuda(x, torch.float32, "fq_dwconv_f32")
     _need_cuda(w, torch.float32, "fq_dwconv_f32")
     R, S = int(kernel[0]), int(kernel[1])
@@ -752,7 +773,7 @@ def dwconv_f32(x, w, bias, kernel, stride, pad, max_dev=None, interval_dev=None,
     st, pd = int(stride), int(pad)
     shape = (N, C, (H + 2 * pd - R) // st + 1, (W + 2 * pd - S) // st + 1)
     return _conv_f32("fq_dwconv_f32", x, w.data_ptr(), bias, shape, (N, C, H, W, R, S, st, pd), max_dev, interval_dev, hist_dev, row,
-                     relu_out, out, qd)
+                     relu_out, out, qd, act=act)
 
 
 def gconv_f32_supported(c, k, groups, kernel, stride, pad, dilation, h, w):
@@ -1086,9 +1107,31 @@ def conv2d_i8(xq, wq, qbias, stride, padding, dilation, rs, ob, bitwidth=8):
     return y.view(N, K) if linear else y
 
 
-def conv2d_i8_resident(xq, wq, qbias, stride, padding, dilation, rs, ob, want_f32, want_i8, relu):
+def relu6_clip(ob):
+    """The Sp range (lo, hi) that stands for an nn.ReLU6 behind an 8-bit layer with output grid `ob`, or None where the value 6 is
+    not on that grid (ob <= -2): min(max(q * 2^-ob, 0), 6) = min(max(q, 0), 6 * 2^ob) * 2^-ob.  From ob = 5 on the bound is 127,
+    the Sp bound itself: a plain ReLU."""
+    ob = int(ob)
+    if ob < -1:
+        return None
+    return (0, 127 if ob >= 5 else (6 << ob if ob >= 0 else 3))
+
+
+def _act_call(name, clip, relu):
+    """(entry point, its activation arguments): `name` with `1 if relu else 0`, or -- clip = (lo, hi) given -- its `_act` sibling
+    with the Sp range.  A clip replaces relu; it is the caller's statement of the whole range."""
+    if clip is None:
+        return getattr(lib(), name), (1 if relu else 0,), name
+    lo, hi = int(clip[0]), int(clip[1])
+    if not (-128 <= lo <= 0 <= hi <= 127):
+        raise FqError("%s_act: the Sp range must satisfy -128 <= lo <= 0 <= hi <= 127, got (%d, %d)" % (name, lo, hi))
+    return getattr(lib(), name + "_act"), (lo, hi), name + "_act"
+
+
+def conv2d_i8_resident(xq, wq, qbias, stride, padding, dilation, rs, ob, want_f32, want_i8, relu, clip=None):
     """fq_conv2d_i8_resident: returns (y fp32 [N,K,P,Q] or None, q int8 [N,P,Q,Kpad] or None).  q holds the
-    integers before DeQuantity (value = q * 2^-ob), channels zero-padded to a multiple of 16."""
+    integers before DeQuantity (value = q * 2^-ob), channels zero-padded to a multiple of 16.  clip = (lo, hi): the `_act` entry
+    point with that Sp range in place of relu (relu6_clip)."""
     _need_cuda(xq, torch.int8, "fq_conv2d_i8_resident")
     _need_cuda(wq, torch.int8, "fq_conv2d_i8_resident")
     _need_cuda(qbias, torch.float32, "fq_conv2d_i8_resident")
@@ -1102,16 +1145,18 @@ def conv2d_i8_resident(xq, wq, qbias, stride, padding, dilation, rs, ob, want_f3
     q = torch.empty(N, P, Q, kpad, dtype=torch.int8, device=xq.device) if want_i8 else None
     if isinstance(rs, ShiftVec):
         rk = _shift_vec(rs, K, xq.device, "fq_conv2d_i8_resident_pcs")
-        _check(lib().fq_conv2d_i8_resident_pcs(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi,
-                                               y.data_ptr() if want_f32 else None, q.data_ptr() if want_i8 else None, kpad,
-                                               1 if relu else 0, N, H, W, C, K, R, S, stride[0], stride[1], padding[0], padding[1],
-                                               dilation[0], dilation[1], int(ob), _stream(xq)), "fq_conv2d_i8_resident_pcs")
+        fn, act, what = _act_call("fq_conv2d_i8_resident_pcs", clip, relu)
+        _check(fn(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi,
+                  y.data_ptr() if want_f32 else None, q.data_ptr() if want_i8 else None, kpad,
+                  *act, N, H, W, C, K, R, S, stride[0], stride[1], padding[0], padding[1],
+                  dilation[0], dilation[1], int(ob), _stream(xq)), what)
         _note_variant()
         return y, q
-    _check(lib().fq_conv2d_i8_resident(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(),
-                                       y.data_ptr() if want_f32 else None, q.data_ptr() if want_i8 else None, kpad,
-                                       1 if relu else 0, N, H, W, C, K, R, S, stride[0], stride[1], padding[0], padding[1],
-                                       dilation[0], dilation[1], int(rs), int(ob), _stream(xq)), "fq_conv2d_i8_resident")
+    fn, act, what = _act_call("fq_conv2d_i8_resident", clip, relu)
+    _check(fn(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(),
+              y.data_ptr() if want_f32 else None, q.data_ptr() if want_i8 else None, kpad,
+              *act, N, H, W, C, K, R, S, stride[0], stride[1], padding[0], padding[1],
+              dilation[0], dilation[1], int(rs), int(ob), _stream(xq)), what)
     _note_variant()
     return y, q
 
@@ -1137,8 +1182,9 @@ def pack_weight_stem(w):
     return out.view(R, STEM_MAX_K, 32).contiguous()
 
 
-def conv2d_i8_stem(x, w_stem, qbias, K, S, stride, padding, ib, rs, ob, relu):
-    """fq_conv2d_i8_stem: fp32 NCHW image -> int8 [N,P,Q,Kpad] (the integers before DeQuantity(ob), ReLU folded in)."""
+def conv2d_i8_stem(x, w_stem, qbias, K, S, stride, padding, ib, rs, ob, relu, clip=None):
+    """fq_conv2d_i8_stem: fp32 NCHW image -> int8 [N,P,Q,Kpad] (the integers before DeQuantity(ob), ReLU folded in).  clip = (lo, hi):
+    the `_act` entry point with that Sp range in place of relu."""
     _need_cuda(x, torch.float32, "fq_conv2d_i8_stem")
     _need_cuda(w_stem, torch.int8, "fq_conv2d_i8_stem")
     _need_cuda(qbias, torch.float32, "fq_conv2d_i8_stem")
@@ -1151,14 +1197,16 @@ def conv2d_i8_stem(x, w_stem, qbias, K, S, stride, padding, ib, rs, ob, relu):
     q = torch.empty(N, P, Q, kpad, dtype=torch.int8, device=x.device)
     if isinstance(rs, ShiftVec):
         rk = _shift_vec(rs, K, x.device, "fq_conv2d_i8_stem_pcs")
-        _check(lib().fq_conv2d_i8_stem_pcs(x.data_ptr(), w_stem.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi, q.data_ptr(),
-                                           kpad, 1 if relu else 0, N, C, H, W, K, R, S, stride[0], stride[1], padding[0], padding[1],
-                                           int(ib), int(ob), _stream(x)), "fq_conv2d_i8_stem_pcs")
+        fn, act, what = _act_call("fq_conv2d_i8_stem_pcs", clip, relu)
+        _check(fn(x.data_ptr(), w_stem.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi, q.data_ptr(),
+                  kpad, *act, N, C, H, W, K, R, S, stride[0], stride[1], padding[0], padding[1],
+                  int(ib), int(ob), _stream(x)), what)
         _note_variant()
         return q
-    _check(lib().fq_conv2d_i8_stem(x.data_ptr(), w_stem.data_ptr(), qbias.contiguous().data_ptr(), q.data_ptr(), kpad,
-                                   1 if relu else 0, N, C, H, W, K, R, S, stride[0], stride[1], padding[0], padding[1],
-                                   int(ib), int(rs), int(ob), _stream(x)), "fq_conv2d_i8_stem")
+    fn, act, what = _act_call("fq_conv2d_i8_stem", clip, relu)
+    _check(fn(x.data_ptr(), w_stem.data_ptr(), qbias.contiguous().data_ptr(), q.data_ptr(), kpad,
+              *act, N, C, H, W, K, R, S, stride[0], stride[1], padding[0], padding[1],
+              int(ib), int(rs), int(ob), _stream(x)), what)
     _note_variant()
     return q
 
@@ -1182,9 +1230,10 @@ def pack_weight_dw(w, cpad=None):
     return out.contiguous()
 
 
-def dwconv2d_i8_resident(xq, wq, qbias, stride, padding, rs, ob, relu):
+def dwconv2d_i8_resident(xq, wq, qbias, stride, padding, rs, ob, relu, clip=None):
     """fq_dwconv2d_i8_resident: xq int8 [N,H,W,Cpad], wq int8 [R,S,Cpad] (pack_weight_dw), qbias fp32 [C]; returns q int8
-    [N,P,Q,Cpad], the integers before DeQuantity(ob) with the ReLU folded in.  rs: an int, or a ShiftVec (the _pcs entry point)."""
+    [N,P,Q,Cpad], the integers before DeQuantity(ob) with the ReLU folded in.  rs: an int, or a ShiftVec (the _pcs entry point).
+    clip = (lo, hi): the `_act` entry point with that Sp range in place of relu."""
     _need_cuda(xq, torch.int8, "fq_dwconv2d_i8_resident")
     _need_cuda(wq, torch.int8, "fq_dwconv2d_i8_resident")
     _need_cuda(qbias, torch.float32, "fq_dwconv2d_i8_resident")
@@ -1199,13 +1248,15 @@ def dwconv2d_i8_resident(xq, wq, qbias, stride, padding, rs, ob, relu):
     q = torch.empty(N, P, Q, cpad, dtype=torch.int8, device=xq.device)
     if isinstance(rs, ShiftVec):
         rk = _shift_vec(rs, C, xq.device, "fq_dwconv2d_i8_resident_pcs")
-        _check(lib().fq_dwconv2d_i8_resident_pcs(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi,
-                                                 q.data_ptr(), cpad, 1 if relu else 0, N, H, W, C, R, S, stride[0], stride[1],
-                                                 padding[0], padding[1], 1, 1, int(ob), _stream(xq)), "fq_dwconv2d_i8_resident_pcs")
+        fn, act, what = _act_call("fq_dwconv2d_i8_resident_pcs", clip, relu)
+        _check(fn(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi,
+                  q.data_ptr(), cpad, *act, N, H, W, C, R, S, stride[0], stride[1],
+                  padding[0], padding[1], 1, 1, int(ob), _stream(xq)), what)
     else:
-        _check(lib().fq_dwconv2d_i8_resident(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), q.data_ptr(), cpad,
-                                             1 if relu else 0, N, H, W, C, R, S, stride[0], stride[1], padding[0], padding[1], 1, 1,
-                                             int(rs), int(ob), _stream(xq)), "fq_dwconv2d_i8_resident")
+        fn, act, what = _act_call("fq_dwconv2d_i8_resident", clip, relu)
+        _check(fn(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), q.data_ptr(), cpad,
+                  *act, N, H, W, C, R, S, stride[0], stride[1], padding[0], padding[1], 1, 1,
+                  int(rs), int(ob), _stream(xq)), what)
     _note_variant()
     return q
 
@@ -1232,10 +1283,11 @@ def pack_weight_grouped(w, groups, kpad=None):
     return out.reshape(kpad // 4, R * S, cgi // 4, 4, 4).contiguous()
 
 
-def gconv2d_i8_resident(xq, wq, qbias, K, groups, stride, padding, rs, ob, relu):
+def gconv2d_i8_resident(xq, wq, qbias, K, groups, stride, padding, rs, ob, relu, clip=None):
     """fq_gconv2d_i8_resident: xq int8 [N,H,W,Cpad], wq int8 (pack_weight_grouped), qbias fp32 [K]; returns q int8
     [N,P,Q,Kpad], the integers before DeQuantity(ob) with the ReLU folded in.  The input channel count is groups * Cgi, Cgi
-    read off wq, as is the (square) kernel's size.  rs: an int, or a ShiftVec (the _pcs entry point)."""
+    read off wq, as is the (square) kernel's size.  rs: an int, or a ShiftVec (the _pcs entry point).  clip = (lo, hi): the `_act`
+    entry point with that Sp range in place of relu."""
     _need_cuda(xq, torch.int8, "fq_gconv2d_i8_resident")
     _need_cuda(wq, torch.int8, "fq_gconv2d_i8_resident")
     _need_cuda(qbias, torch.float32, "fq_gconv2d_i8_resident")
@@ -1253,14 +1305,15 @@ def gconv2d_i8_resident(xq, wq, qbias, K, groups, stride, padding, rs, ob, relu)
     q = torch.empty(N, P, Q, kpad, dtype=torch.int8, device=xq.device)
     if isinstance(rs, ShiftVec):
         rk = _shift_vec(rs, K, xq.device, "fq_gconv2d_i8_resident_pcs")
-        _check(lib().fq_gconv2d_i8_resident_pcs(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi,
-                                                q.data_ptr(), cpad, kpad, 1 if relu else 0, N, H, W, C, K, groups, R, R,
-                                                stride[0], stride[1], padding[0], padding[1], 1, 1, int(ob), _stream(xq)),
-               "fq_gconv2d_i8_resident_pcs")
+        fn, act, what = _act_call("fq_gconv2d_i8_resident_pcs", clip, relu)
+        _check(fn(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi,
+                  q.data_ptr(), cpad, kpad, *act, N, H, W, C, K, groups, R, R,
+                  stride[0], stride[1], padding[0], padding[1], 1, 1, int(ob), _stream(xq)), what)
     else:
-        _check(lib().fq_gconv2d_i8_resident(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), q.data_ptr(), cpad, kpad,
-                                            1 if relu else 0, N, H, W, C, K, groups, R, R, stride[0], stride[1], padding[0],
-                                            padding[1], 1, 1, int(rs), int(ob), _stream(xq)), "fq_gconv2d_i8_resident")
+        fn, act, what = _act_call("fq_gconv2d_i8_resident", clip, relu)
+        _check(fn(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), q.data_ptr(), cpad, kpad,
+                  *act, N, H, W, C, K, groups, R, R, stride[0], stride[1], padding[0],
+                  padding[1], 1, 1, int(rs), int(ob), _stream(xq)), what)
     _note_variant()
     return q
 

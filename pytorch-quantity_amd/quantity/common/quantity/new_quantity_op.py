@@ -198,13 +198,14 @@ def _pack_grouped(layer):                   # _w_gc: fq_gconv2d_i8_resident
     return _native.pack_weight_grouped(layer.weight.detach(), layer.groups)
 
 
-def _launch_depthwise(self, conv, xq, wq, relu):
-    return _native.dwconv2d_i8_resident(xq, wq, self.quantized_bias, conv.stride, conv.padding, self._rs(), self.output_bit, relu)
+def _launch_depthwise(self, conv, xq, wq, relu, **act):
+    return _native.dwconv2d_i8_resident(xq, wq, self.quantized_bias, conv.stride, conv.padding, self._rs(), self.output_bit, relu,
+                                        **act)
 
 
-def _launch_grouped(self, conv, xq, wq, relu):
+def _launch_grouped(self, conv, xq, wq, relu, **act):
     return _native.gconv2d_i8_resident(xq, wq, self.quantized_bias, conv.out_channels, conv.groups, conv.stride, conv.padding,
-                                       self._rs(), self.output_bit, relu)
+                                       self._rs(), self.output_bit, relu, **act)
 
 
 class _IntegerSimLayer(nn.Module):
@@ -317,6 +318,18 @@ class _IntegerSimLayer(nn.Module):
             return _native.ShiftVec(self.rs_vec, self.rs_min, self.rs_max)
         return self.rs_bit
 
+    def _act_of(self, plan):
+        """What a producer's launch gets besides `relu`: nothing ({}), or -- the fused activation is an nn.ReLU6
+        (resident.enable(relu6=True), Plan.clip) -- {"clip": (0, 6 * 2^output_bit)}, the Sp range of the `_act` entry point,
+        computed from the layer's output_bit at launch.  From output_bit = 5 on the bound is 127: a plain fused ReLU, {}."""
+        if plan is None or not plan.clip:
+            return {}
+        clip = _native.relu6_clip(self.output_bit)
+        if clip is None:
+            raise _native.FqError("a fused ReLU6 needs output_bit >= -1 (6 is not on the grid 2^%d); the bit table changed since "
+                                  "resident.enable(): call it again" % -self.output_bit)
+        return {} if clip[1] >= 127 else {"clip": clip}
+
     def _tail(self, acc):
         return _native.recon_epilogue(acc, self.quantized_bias, self._rs(), self.output_bit,
                                       8 if QUANTIZE_BIT == 8 else 16, out=acc)
@@ -353,7 +366,8 @@ class NewConv2d(_IntegerSimLayer):
                 x = as_f32(input)
                 q = _native.conv2d_i8_stem(x if x.is_contiguous() else x.contiguous(), self._packed("_w_stem", conv, _pack_stem),
                                            self.quantized_bias, conv.out_channels, conv.kernel_size[1], conv.stride,
-                                           conv.padding, self.input_bit, self._rs(), self.output_bit, plan.relu)
+                                           conv.padding, self.input_bit, self._rs(), self.output_bit, plan.relu,
+                                           **self._act_of(plan))
                 return QHandle.int8(q, conv.out_channels, self.output_bit, plan.relu)
             if fold:
                 input = as_f32(input)
@@ -371,7 +385,7 @@ class NewConv2d(_IntegerSimLayer):
             if plan.defer:
                 return DeferredConv(self, xq, wq, geom)   # the resident NewAdd that consumes it runs it
             y, q = _native.conv2d_i8_resident(xq, wq, self.quantized_bias, geom[0], geom[1], geom[2], self._rs(),
-                                              self.output_bit, plan.emit_f32, plan.emit_int, plan.relu)
+                                              self.output_bit, plan.emit_f32, plan.emit_int, plan.relu, **self._act_of(plan))
             if q is None:                                 # fp32 consumers only: the kernel wrote y and no integers
                 if plan.relu:
                     y._fq_relu_done = True
@@ -389,7 +403,8 @@ class NewConv2d(_IntegerSimLayer):
         if xq is None:
             xq = _xq_cache.get(as_f32(input), self.input_bit, cpad)
         relu = plan is not None and plan.relu
-        return _emit(plan, QHandle.int8(launch(self, conv, xq, wq, relu), conv.out_channels, self.output_bit, relu))
+        return _emit(plan, QHandle.int8(launch(self, conv, xq, wq, relu, **self._act_of(plan)), conv.out_channels, self.output_bit,
+                                        relu))
 
     def _resident_input(self, input, cpad):
         """int8 NHWC operand already in HBM (left by the producer), or None."""

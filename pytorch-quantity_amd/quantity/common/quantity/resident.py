@@ -154,7 +154,7 @@ def as_f32(x):
 class Plan(object):
     """What one producer emits.  Plain data (pickles with the module)."""
     __slots__ = ("relu", "emit_f32", "emit_int", "narrow_bit", "want_wide", "grid", "resident_add", "defer", "fuse_arg",
-                 "fuse_next", "narrow_to_hbm", "fuse_proj", "depthwise", "up", "grouped")
+                 "fuse_next", "narrow_to_hbm", "fuse_proj", "depthwise", "up", "grouped", "clip")
 
     def __init__(self):
         self.relu = False            # the nn.ReLU that consumes this output is fused
@@ -172,6 +172,7 @@ class Plan(object):
         self.depthwise = False       # NewConv2d: a depthwise layer taken by enable(depthwise=True); runs on fq_dwconv2d_i8_resident
         self.up = None               # nearest upsampling taken by enable(concat=True): its factor (with `defer`: the Concat applies it)
         self.grouped = False         # NewConv2d: a grouped layer taken by enable(grouped=True); runs on fq_gconv2d_i8_resident
+        self.clip = False            # NewConv2d with `relu`: the fused activation is an nn.ReLU6 (enable(relu6=True)): clipped at 6
 
     def __getstate__(self):
         return {k: getattr(self, k) for k in self.__slots__}
@@ -199,7 +200,7 @@ class _InstanceForward(object):
 
 
 class _ReluPassThrough(_InstanceForward):
-    """Instance-level forward of an nn.ReLU whose producer already applied it."""
+    """Instance-level forward of an nn.ReLU (or, with enable(relu6=True), an nn.ReLU6) whose producer already applied it."""
 
     def __call__(self, x):
         if type(x) is QHandle:
@@ -397,6 +398,7 @@ class _Tracer(TorchFunctionMode):
     def __init__(self, avgpool=False):
         super(_Tracer, self).__init__()
         self.avgpool = bool(avgpool)     # enable(avgpool=True): an nn.AvgPool2d output is a traced value
+        self.relu6_seen = []             # (enable(relu6=True)) every hooked nn.ReLU6 module, in execution order
         self.values = {}             # id(tensor) -> _Value
         self.keep = []               # keeps traced tensors alive so ids are not reused
         self.depth = 0
@@ -416,6 +418,8 @@ class _Tracer(TorchFunctionMode):
     def pre(self, module, args):
         self.depth += 1
         self.calls[module] = self.calls.get(module, 0) + 1
+        if isinstance(module, nn.ReLU6) and module not in self.relu6_seen:
+            self.relu6_seen.append(module)
         for pos, a in enumerate(args):
             v = self.values.get(id(a)) if isinstance(a, torch.Tensor) else None
             if v is not None:
@@ -435,7 +439,7 @@ class _Tracer(TorchFunctionMode):
 
     @staticmethod
     def _kind(module):
-        if isinstance(module, nn.ReLU):
+        if isinstance(module, (nn.ReLU, nn.ReLU6)):         # (nn.ReLU6 is hooked only with enable(relu6=True))
             return "relu"
         if isinstance(module, nn.MaxPool2d):
             return "maxpool"
@@ -480,6 +484,7 @@ def _clear(model):
         if isinstance(fwd, _InstanceForward):
             del m.__dict__["forward"]
     model.__dict__.pop("_fq_resident_enabled", None)
+    model.__dict__.pop("_fq_resident_relu6", None)
 
 
 def disable(model):
@@ -501,12 +506,13 @@ class _Planning(object):
     """The plan of one traced forward.  enable() calls the passes below in order; they decide on the trace alone and change
     nothing on the model until install() writes the plans and the instance-level forwards to the modules."""
 
-    def __init__(self, tracer, depthwise, concat, avgpool, grouped):
+    def __init__(self, tracer, depthwise, concat, avgpool, grouped, relu6=False):
         from .new_quantity_op import NewConv2d, NewAdd
         from .fabu_layer import Concat
         self.conv_type, self.concat_type = NewConv2d, Concat
         self.tracer = tracer
-        self.depthwise, self.grouped = bool(depthwise), bool(grouped)
+        self.depthwise, self.grouped, self.relu6 = bool(depthwise), bool(grouped), bool(relu6)
+        self.relu6_left = {}             # (relu6=True) nn.ReLU6 module that stays torch's -> why
         self.relu_value = dict((id(c.src), c) for c in tracer.relu_values)
         self.fmt = {}                    # id(effective _Value) -> (bytes, grid)
         self.eff_of = {}                 # id(produced _Value) -> (effective _Value, relu module)
@@ -530,6 +536,8 @@ class _Planning(object):
             self.summary["resident_avgpools"] = 0
         if grouped:
             self.summary["resident_grouped"] = 0
+        if relu6:
+            self.summary["fused_relu6s"] = 0
 
     # ---- what a value is and what a module can do
 
@@ -538,12 +546,50 @@ class _Planning(object):
         return self.tracer.calls.get(m, 0) == 1
 
     def effective(self, v):
-        """(value the consumers see, fused ReLU module or None)"""
-        if v.kind != "maxpool" and not v.foreign and len(v.consumers) == 1 and isinstance(v.consumers[0][0], nn.ReLU):
+        """(value the consumers see, fused ReLU / ReLU6 module or None)"""
+        if v.kind != "maxpool" and not v.foreign and len(v.consumers) == 1 and isinstance(v.consumers[0][0], (nn.ReLU, nn.ReLU6)):
+            act = v.consumers[0][0]
             after = self.relu_value.get(id(v))
-            if after is not None:
-                return after, v.consumers[0][0]
+            if after is not None and (isinstance(act, nn.ReLU) or self.takes_relu6(v)):
+                return after, act
         return v, None
+
+    def takes_relu6(self, v):
+        """`relu6=True` fuses an nn.ReLU6 that is the only reader of a NewConv2d's output like an nn.ReLU: the producer (dense,
+        stem, depthwise with `depthwise=True`, grouped with `grouped=True`) clamps its integers to [0, 6 * 2^output_bit]
+        (fq_*_act, _native.relu6_clip; from output_bit = 5 on that is the plain fused ReLU).  Not taken, and left to torch on the
+        fp32 tensor exactly as without the argument: a layer with output_bit <= -2 (6 is not on its output grid), a producer
+        that is no integer convolution of this plan, and a ReLU6 behind a NewAdd, a Concat, a pool or an upsampling.  16-bit
+        models have no plan at all.  The summary then gains `fused_relu6s`; describe() names what was left."""
+        m = v.producer
+        if not self.relu6 or v.kind != "contraction" or not self.conv_can_emit(m):
+            return False
+        return _native.relu6_clip(m.output_bit) is not None
+
+    def _relu6_reasons(self):
+        """Why each hooked nn.ReLU6 that no producer fused stays torch's (for describe())."""
+        fused = set(m for (m, forward) in self.forwards if isinstance(forward, _ReluPassThrough))
+        source = {}
+        for r in self.tracer.relu_values:
+            source.setdefault(r.producer, r.src)
+        for act in self.tracer.relu6_seen:
+            if act in fused:
+                continue
+            v = source.get(act)
+            if v is None:
+                why = "its input is not the output of a planned layer"
+            elif v.kind != "contraction":
+                why = "behind %s: only a ReLU6 behind a convolution is fused" % {"add": "a NewAdd", "concat": "a Concat"}.get(
+                    v.kind, "a pool or an upsampling")
+            elif not self.conv_can_emit(v.producer):
+                why = "its producer is not an integer convolution of this plan (fp32 form)"
+            elif _native.relu6_clip(v.producer.output_bit) is None:
+                why = "output_bit %d <= -2: the value 6 is not on the output grid (fp32 form)" % v.producer.output_bit
+            elif v.foreign or len(v.consumers) != 1:
+                why = "the convolution's output has other readers"
+            else:
+                why = "the ReLU6 was called more than once"
+            self.relu6_left[act] = why
 
     def is_dw(self, m):
         """A depthwise layer that this plan runs on fq_dwconv2d_i8_resident: `depthwise=True` plans depthwise NewConv2d layers
@@ -690,10 +736,11 @@ class _Planning(object):
         """Module m emits what `plan` says, with the nn.ReLU behind it (if any) fused and, for a module that is no integer
         layer itself, `forward` as its instance-level forward."""
         plan.relu = relu_mod is not None
+        plan.clip = isinstance(relu_mod, nn.ReLU6)
         self.plans[m] = plan
         if plan.relu:
             self.forwards.append((relu_mod, _ReluPassThrough(relu_mod)))
-            self.summary["fused_relus"] += 1
+            self.summary["fused_relu6s" if plan.clip else "fused_relus"] += 1
         if forward is not None:
             self.forwards.append((m, forward(m)))
         self.summary["fp32_outputs" if plan.emit_f32 else "int_only_outputs"] += 1
@@ -774,7 +821,10 @@ class _Planning(object):
             readers = [c for (c, _pos) in self.eff_of[id(va)][0].consumers if self.conv_can_read(c)]
             for c in readers:
                 cp = self.plans.get(c)
-                if (cp is not None and not cp.defer and not cp.grouped and cp.emit_int and not cp.emit_f32 and self.once(c)
+                # (not cp.clip: the second tail of fq_block_tail_i8 has the plain ReLU's range only; a 1x1 with a fused ReLU6
+                #  stays a launch of its own)
+                if (cp is not None and not cp.defer and not cp.grouped and not cp.clip and cp.emit_int and not cp.emit_f32
+                        and self.once(c)
                         and _pointwise_conv(c.Conv) and c.input_bit == plan.narrow_bit
                         and conv3.Conv.out_channels == c.Conv.in_channels
                         and _native.block_tail_supported(conv3.Conv.in_channels, conv3.Conv.out_channels, c.Conv.out_channels,
@@ -844,13 +894,18 @@ class _Planning(object):
         for m, forward in self.forwards:
             m.__dict__["forward"] = forward
         model.__dict__["_fq_resident_enabled"] = True
+        if self.relu6:
+            self._relu6_reasons()
+            names = dict((m, name) for name, m in model.named_modules())
+            model.__dict__["_fq_resident_relu6"] = (self.summary["fused_relu6s"],
+                                                    dict((names.get(m, "?"), why) for m, why in self.relu6_left.items()))
 
 
-def _trace(model, example_input, concat, avgpool):
+def _trace(model, example_input, concat, avgpool, relu6=False):
     """One forward of `model` in eval mode under the tracer: (tracer, the outputs of that forward)."""
     from .new_quantity_op import NewConv2d, NewLinear, NewAdd
     from .fabu_layer import Concat
-    planned_types = (NewConv2d, NewLinear, NewAdd, nn.ReLU, nn.MaxPool2d, nn.AvgPool2d)
+    planned_types = (NewConv2d, NewLinear, NewAdd, nn.ReLU, nn.MaxPool2d, nn.AvgPool2d) + ((nn.ReLU6,) if relu6 else ())
     tracer = _Tracer(avgpool)
     hooks = []
     for m in model.modules():
@@ -874,7 +929,7 @@ def _trace(model, example_input, concat, avgpool):
     return tracer, traced_out
 
 
-def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False, grouped=False):
+def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False, grouped=False, relu6=False):
     """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
     on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
     nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
@@ -884,13 +939,14 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
     Opt-in, each adding its own keys to the summary and leaving the plan as it was when off:
     `depthwise=True` also plans depthwise NewConv2d layers (_Planning.is_dw), `grouped=True` grouped ones (_Planning.is_gc);
     `concat=True` also plans the Concat marker layer and nearest upsampling by 2 or 4 (_Planning._concat_format, defer_upsamples);
-    `avgpool=True` also plans a windowed nn.AvgPool2d between an int8 activation and convolutions (_plan_avgpool_window)."""
+    `avgpool=True` also plans a windowed nn.AvgPool2d between an int8 activation and convolutions (_plan_avgpool_window);
+    `relu6=True` also fuses an nn.ReLU6 behind a NewConv2d, as an nn.ReLU is fused (_Planning.takes_relu6)."""
     from .new_quantity_op import QUANTIZE_BIT
     _clear(model)
     if QUANTIZE_BIT != 8:
         raise _native.FqError("resident activations are defined for QUANTIZE_BIT = 8")
-    tracer, traced_out = _trace(model, example_input, concat, avgpool)
-    planning = _Planning(tracer, depthwise, concat, avgpool, grouped)
+    tracer, traced_out = _trace(model, example_input, concat, avgpool, relu6)
+    planning = _Planning(tracer, depthwise, concat, avgpool, grouped, relu6)
     planning.plan_formats()
     planning.plan_outputs()
     planning.defer_convs()
@@ -911,9 +967,18 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
     return planning.summary
 
 
+class _Description(dict):
+    """describe()'s {module name: Plan}.  After enable(relu6=True) it also says what became of the nn.ReLU6 modules:
+    `fused_relu6s`, how many a producer fused, and `relu6_left`, {module name: why} for each one that stays torch's."""
+    fused_relu6s = 0
+    relu6_left = {}
+
+
 def describe(model):
-    """{module name: Plan} of the current plan (for logs and tests)."""
-    return dict((name, m.__dict__["_resident"]) for name, m in model.named_modules() if "_resident" in m.__dict__)
+    """{module name: Plan} of the current plan (for logs and tests); see _Description for the ReLU6 report."""
+    d = _Description((name, m.__dict__["_resident"]) for name, m in model.named_modules() if "_resident" in m.__dict__)
+    d.fused_relu6s, d.relu6_left = model.__dict__.get("_fq_resident_relu6", (0, {}))
+    return d
 
 
 class GraphedForward(object):

@@ -11,7 +11,8 @@ of model/resnet/ResNet_18_fabu.py.  It is the model the depthwise integer kernel
   * an identity shortcut (Eltwise) around every stride-1 block whose input and output widths match -- the pointwise layer then
     carries no ReLU of its own, the ReLU follows the add;
   * 5x5 depthwise kernels (padding 2) in the last stage (the two 1024-wide blocks: stride 2 and stride 1).
-nn.ReLU only: nn.ReLU6 is not something the resident plan fuses.
+nn.ReLU only, as the paper has it; the ReLU6 network is model/mobilenetv2/MobileNetV2_fabu.py (the resident plan fuses an nn.ReLU6
+with resident.enable(..., relu6=True)).
 """
 import sys
 

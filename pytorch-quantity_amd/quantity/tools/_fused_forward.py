@@ -16,6 +16,9 @@ same call fires -- and each fusion is a small state machine over them.  States l
 | | deferred not empty | the forward ends | RuntimeError: the model left the path the probe saw (`_forward_with_stats`) |
 | the proofs | poison = _DeferralProbe, mode learn / poison | two probe forwards before the first batch | `_probe_forward`, `_prove_deferral` (NaN poisoning + the keeper scan, `_hook_state._DeferralProbe`) |
 
+An out-of-place nn.ReLU6 takes the two conv -> ReLU rows as well when Quantity.fuse_relu6 is on (off by default), behind the own
+1x1 / R x S / depthwise convolutions only: the producer is told which of the two activations to write (`act=6.0`).
+
 Every fusion falls back to the unfused form of the same arithmetic; none changes a table (tests/test_gpu_conv_add_fusion.py,
 tests/test_gpu_float_forward_kernels.py, tests/test_gpu_r50_tables.py)."""
 import weakref
@@ -36,6 +39,9 @@ class _StopForward(Exception):
 # Once-per-process check results, per module.  Kept in _float_conv's WeakKeyDictionary, never on the module: the reference
 # pickles whole models (reconstruction.py:107-140) and nothing of this package may travel into that file.
 _RELU_VERIFIED = "relu_fusion_verified"
+_RELU6_VERIFIED = "relu6_fusion_verified"         # the clipped copy gave torch's nn.ReLU6 bits here
+# the own convolutions whose `_act` entry point writes nn.ReLU6's copy (_float_conv.kind): the others leave a ReLU6 to torch
+_RELU6_KINDS = ("c1", "kxk", "dw")
 _POOL_VERIFIED = "pool_verified"                  # the own pooling kernel gave torch's bits here
 _POOL_OFF = "pool_off"
 _FUSION_VERIFIED = "bias_fusion_verified"         # conv-without-bias + fq_bias_add_absmax_f32 == its forward
@@ -166,8 +172,10 @@ class _FusedForward(object):
                     m.forward = forward
                     patched.append(m)
         # an out-of-place nn.ReLU fed directly by one of the modules above is served by that module's kernel
+        # (... and, with fuse_relu6, an out-of-place nn.ReLU6: without the switch such a module is not touched at all)
+        served = (torch.nn.ReLU, torch.nn.ReLU6) if self.fuse_relu6 else (torch.nn.ReLU,)
         for m in model.modules():
-            if type(m) is not torch.nn.ReLU or m.inplace or "forward" in m.__dict__:
+            if type(m) not in served or m.inplace or "forward" in m.__dict__:
                 continue
 
             def forward(x, m=m):
@@ -181,7 +189,7 @@ class _FusedForward(object):
                 if ready is not None and ready[0] is x and ready[2] is m and ready[3] == x._version:
                     ctl.relu_ready = None                 # (same tensor object, not written to since)
                     return ready[1]
-                return torch.nn.functional.relu(x)
+                return torch.nn.functional.relu(x) if type(m) is torch.nn.ReLU else type(m).forward(m, x)
             m.forward = forward
             patched.append(m)
         return patched
@@ -201,8 +209,8 @@ class _FusedForward(object):
                     and ctl.eager is not None):
                 ctl.deferred[id(output)] = (output, m, x, key, row, output._version, x._version)       # (see below)
                 return True
-            self._run_with_relu(m, output, lambda r, o: run(interval_dev=coll.interval_device, hist_dev=coll.hist_device, row=row,
-                                                            relu_out=r, out=o), key)
+            self._run_with_relu(m, output, lambda r, o, **act: run(interval_dev=coll.interval_device, hist_dev=coll.hist_device,
+                                                                   row=row, relu_out=r, out=o, **act), key, kind in _RELU6_KINDS)
             ctl.hist_fused += 1
             return True
         ref = _float_conv.verified(m, run, x, kind)            # first use of this kernel: against torch, once per process
@@ -215,7 +223,8 @@ class _FusedForward(object):
             # is an allocation nobody reads -- which the poison probe has shown for this model
             ctl.deferred[id(output)] = (output, m, x, key, row, output._version, x._version)
             return True
-        self._run_with_relu(m, output, lambda r, o: run(max_dev=coll.max_device, row=row, relu_out=r, out=o), key)
+        self._run_with_relu(m, output, lambda r, o, **act: run(max_dev=coll.max_device, row=row, relu_out=r, out=o, **act), key,
+                            kind in _RELU6_KINDS)
         coll.note_max_refreshed()
         ctl.own_conv1x1 = ctl.own_conv1x1 + 1
         return True
@@ -268,6 +277,8 @@ class _FusedForward(object):
         coll = ctl.fuse_collector
         other = b if t3 is a else a
         relu = ctl.relu_after.get(m) if self.fuse_relu else None
+        if type(relu) is torch.nn.ReLU6:
+            relu = None                                         # (the one-kernel tail writes nn.ReLU's copy only)
         keep = lambda name: self.materialize_all or (ctl.keep_feats and (ctl.keep_names is None or name in ctl.keep_names))
         keep_y, keep_s = keep(conv_key), keep(key) if key is not None else True
         # Both wanted by pass 2's cache: the sum is conv3's output + the shortcut, and the shortcut exists anyway -- so the sum is
@@ -327,27 +338,38 @@ class _FusedForward(object):
             return False
         return ctl.keep_feats and (ctl.keep_names is None or key in ctl.keep_names)
 
-    def _run_with_relu(self, m, output, run, key=None):
+    def _run_with_relu(self, m, output, run, key=None, serves_relu6=False):
         """run(relu_out, out) launches m's fused kernel (out: where the module's own output goes).  When an out-of-place
         nn.ReLU is known to consume `output` directly, the kernel writes that ReLU's result as well and the patched ReLU.forward
         hands it out instead of launching -- and when that ReLU is PROVEN to be the only reader of `output` (relu_only_ok) and
-        pass 2 does not want the tensor, `output` itself is not written (out = False)."""
+        pass 2 does not want the tensor, `output` itself is not written (out = False).  An nn.ReLU6 in that place (fuse_relu6)
+        is served by a producer that can write the clipped copy (serves_relu6: run takes act=6.0) and left to torch by the others."""
         ctl = self._hook_ctl
-        relu = ctl.relu_after.get(m) if self.fuse_relu else None
+        relu = ctl.relu_after.get(m) if (self.fuse_relu or self.fuse_relu6) else None
+        clip = type(relu) is torch.nn.ReLU6
+        if relu is not None and not ((self.fuse_relu6 and serves_relu6) if clip else self.fuse_relu):
+            relu = None
         if relu is None:
             run(None, output)
             return
+        done = _RELU6_VERIFIED if clip else _RELU_VERIFIED
         r = torch.empty_like(output)
-        skip = (key is not None and self.skip_unread_outputs and m in ctl.relu_only_ok and _flag(m, _RELU_VERIFIED)
+        skip = (key is not None and self.skip_unread_outputs and m in ctl.relu_only_ok and _flag(m, done)
                 and ctl.eager is not None and not self._wanted(key))
-        run(r, False if skip else output)
+        if clip:
+            run(r, False if skip else output, act=6.0)
+        else:
+            run(r, False if skip else output)
         if skip:
             ctl.skipped_outputs += 1
-        if not _flag(m, _RELU_VERIFIED):              # once per process: the same bits as torch's ReLU?
-            if not torch.equal(r, torch.nn.functional.relu(output)):
-                self.fuse_relu = False
+        if not _flag(m, done):                        # once per process: the same bits as torch's ReLU / ReLU6?
+            if not torch.equal(r, type(relu).forward(relu, output) if clip else torch.nn.functional.relu(output)):
+                if clip:
+                    self.fuse_relu6 = False
+                else:
+                    self.fuse_relu = False
                 return
-            _set_flag(m, _RELU_VERIFIED)
+            _set_flag(m, done)
         ctl.relu_ready = (output, r, relu, output._version)      # holds the tensor itself: identity, not a reusable id
         ctl.fused_relus.add(relu)
 
@@ -487,7 +509,7 @@ class _FusedForward(object):
         cared = set(self.net_info.keys())
         for elt, conv in (probe.pairs.items() if self.fuse_conv_add else ()):
             relu = ctl.relu_after.get(elt)
-            if (relu is None or probe.keys.get(conv) not in cared or probe.keys.get(elt) not in cared
+            if (type(relu) is not torch.nn.ReLU or probe.keys.get(conv) not in cared or probe.keys.get(elt) not in cared
                     or conv.kernel_size != (1, 1) or conv.padding != (0, 0)
                     or not _native.conv1x1_add_f32_supported(conv.in_channels, conv.out_channels)
                     or not (self._only_our_hook(conv) and self._only_our_hook(elt) and self._only_our_hook(relu))

@@ -131,7 +131,9 @@ class _DeferralProbe(object):
 
     def relu(self, m, x):
         r = self.real(x, m) if self.mode == "poison" else None
-        return None if r is None else torch.nn.functional.relu(r)
+        if r is None:
+            return None
+        return torch.nn.functional.relu6(r) if type(m) is torch.nn.ReLU6 else torch.nn.functional.relu(r)   # (Quantity.fuse_relu6)
 
     @staticmethod
     def holders(tensors, ours):

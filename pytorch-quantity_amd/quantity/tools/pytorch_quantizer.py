@@ -87,6 +87,10 @@ class Quantity(_FusedForward, _FileInputs):
     # ... and when an out-of-place nn.ReLU consumes that output directly, the same kernel writes the ReLU's result too
     # (one more 4-byte write instead of the ReLU's own 8-byte pass); the patched ReLU.forward hands it out.
     fuse_relu = True
+    # Opt-in, off by default (like own_depthwise): an out-of-place nn.ReLU6 is served in the same way -- by the producers that can
+    # write the clipped copy, the own 1x1 / R x S / depthwise convolutions (fq_*_f32_act).  Behind any other producer (the library
+    # convolution + bias add, an Eltwise, the Winograd, stem and grouped kernels) a ReLU6 stays torch's, as it does when off.
+    fuse_relu6 = False
     # Pass 2: the same producers histogram their own output (fq_bias_add_hist_f32 / fq_add_hist_f32) for every tensor the
     # second forward re-computes, instead of handing it to the streaming histogram kernel right after writing it (which
     # costs a second 4 B/element read and runs that kernel against the write-back of its own input).

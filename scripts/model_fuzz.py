@@ -11,7 +11,9 @@
      where the KL search has a near tie (seen: 1 model in 300, one line, one bit) -- reported as a note, not as a finding.
 What it is for: the dataflow proofs (deferral, relu-only, keepers) on graphs nobody wrote a test for -- two consumers of one tensor,
 a shortcut that is itself a convolution output, concatenations, in-place ReLUs, pools in odd places.
-usage: model_fuzz.py [models=40] [seed=1]"""
+`relu6`: about half of the nn.ReLU modules the generator drew become nn.ReLU6 (with_relu6), and A, B and D also switch on
+Quantity.fuse_relu6, own_depthwise and own_grouped -- everything on against everything off.
+usage: model_fuzz.py [models=40] [seed=1] [odd] [share] [bn] [relu6] [cache | channels]"""
 import os, sys, random
 import numpy as np
 import torch
@@ -22,6 +24,7 @@ from tools import Quantity
 from workdir_util import product_workdir
 
 SWITCHES = ("fuse_bias_absmax", "fuse_relu", "fuse_hist", "own_pools", "fuse_conv_add", "skip_unread_outputs", "own_conv1x1")
+RELU6_ON = ("fuse_relu6", "own_depthwise", "own_grouped")          # the opt-in switches of the `relu6` mode's fused arms
 
 
 from cases import RandomNet as Net, random_net      # (tests/golden/cases.py: the generator is shared with golden G11)
@@ -40,7 +43,19 @@ def fold(drawn):
     return (model,) + tuple(drawn[1:])
 
 
-def calibrate(model, size, batches, off=(), cache_gb=None, plan=None):
+def with_relu6(drawn, index, seed, share=0.5):
+    """The `relu6` mode: random_net()'s tuple with about half of its nn.ReLU modules replaced by nn.ReLU6 (in place where the ReLU
+    was), decided by a generator of its own -- the same (index, seed) gives the same model every time, and the graphs drawn without
+    the mode stay what they were.  A module that serves several places of the graph (`share`) is replaced in all of them."""
+    model = drawn[0]
+    rnd = random.Random(seed * 1000003 + index * 101 + 6)
+    for name, m in list(model.named_children()):
+        if type(m) is nn.ReLU and rnd.random() < share:
+            setattr(model, name, nn.ReLU6(m.inplace))
+    return drawn
+
+
+def calibrate(model, size, batches, off=(), cache_gb=None, plan=None, on=()):
     """One calibration.  cache_gb: what pass 1 may keep for pass 2 (FQ_ACT_CACHE_GB; None: the engine's own rule -- nothing in a
     process without a warm pool); plan: "A" / "B" forces the cache plan (FQ_CACHE_PLAN)."""
     saved = {k: os.environ.get(k) for k in ("FQ_ACT_CACHE_GB", "FQ_CACHE_PLAN")}
@@ -50,7 +65,7 @@ def calibrate(model, size, batches, off=(), cache_gb=None, plan=None):
         else:
             os.environ[k] = str(v)
     try:
-        return _calibrate(model, size, batches, off)
+        return _calibrate(model, size, batches, off, on)
     finally:
         for k, v in saved.items():
             if v is None:
@@ -59,11 +74,13 @@ def calibrate(model, size, batches, off=(), cache_gb=None, plan=None):
                 os.environ[k] = v
 
 
-def _calibrate(model, size, batches, off=()):
+def _calibrate(model, size, batches, off=(), on=()):
     with product_workdir(input_shape="1,%d,%d,%d" % (getattr(model, "cin", 3), size, size), device="gpu", max_cali_img_num=len(batches) - 1) as tmp:
         q = Quantity(model)
         for s in off:
             setattr(q, s, False)
+        for s in on:
+            setattr(q, s, True)
         out = sys.stdout; sys.stdout = open(os.devnull, "w")
         try:
             bits = q.activation_quantize(batches)
@@ -151,24 +168,31 @@ def run_cache(n, seed, log=print, odd=False, share=False, bn=False):
     return bad, plans
 
 
-def run(n, seed, log=print, odd=False, share=False, bn=False):
+def run(n, seed, log=print, odd=False, share=False, bn=False, relu6=False):
     """n random models; returns (models with a finding, what the fused forwards launched in all).  odd: with depthwise / dilated
-    convolutions and nearest-neighbour upsampling here and there."""
+    convolutions and nearest-neighbour upsampling here and there.  relu6: see with_relu6; `seen` then also counts the nn.ReLU6
+    modules of the models and the activations (of either kind) a producer served."""
     # (layers the own kernels do not take run on the convolution library, whose default kernels do not give the same bits from call
     #  to call; its deterministic mode makes A = B a meaningful test for such models too)
     torch.backends.cudnn.deterministic = bool(odd)
     bad, seen = 0, {"conv_add_launches": 0, "conv_add_hist_launches": 0, "conv_add_chains_proven": 0, "relu_only_chains_proven": 0,
                     "launches_without_own_output": 0, "own_conv1x1_launches": 0, "fused_hist_launches": 0, "refused": 0}
+    on = RELU6_ON if relu6 else ()
+    if relu6:
+        seen.update({"relu6_modules": 0, "fused_relus": 0})
     for i in range(n):
         model, size, bs, rng = fold(random_net(i, seed, odd, "cuda", share, bn))
+        if relu6:
+            with_relu6((model,), i, seed)
+            seen["relu6_modules"] += sum(1 for m in model.modules() if type(m) is nn.ReLU6)
         batches = [(torch.randn(bs, model.cin, size, size, device="cuda"), torch.zeros(bs, dtype=torch.long)) for _ in range(3)]   # (data, label)
         if odd and rng.random() < 0.5:                           # a ragged last batch
             batches[-1] = (batches[-1][0][:3].contiguous(), batches[-1][1][:3])
         try:
-            a = calibrate(model, size, batches)
-            b = calibrate(model, size, batches, off=("fuse_conv_add", "skip_unread_outputs"))
+            a = calibrate(model, size, batches, on=on)
+            b = calibrate(model, size, batches, off=("fuse_conv_add", "skip_unread_outputs"), on=on)
             c = calibrate(model, size, batches, off=SWITCHES)
-            d = calibrate(model, size, batches, off=("fuse_hist",))     # pass 2 on the plain own kernels, statistics from the hooks
+            d = calibrate(model, size, batches, off=("fuse_hist",), on=on)     # pass 2 on the plain own kernels, statistics from the hooks
         except Exception as e:                                   # a crash is a finding too
             bad += 1
             log("model %d (seed %d): %s: %s" % (i, seed, type(e).__name__, str(e)[:300]))
@@ -227,8 +251,10 @@ def main():
     if "channels" in sys.argv[3:]:
         print("model_fuzz channels%s: %d random models (seed %d), %d with a finding" % (" odd" if odd else "", n, seed, run_channels(n, seed, odd=odd, share=share, bn=bn)))
         return
-    bad, seen = run(n, seed, odd=odd, share=share, bn=bn)
-    print("model_fuzz%s: %d random models (seed %d), %d with a finding; fused launches seen: %s" % ((" odd" if odd else "") + (" share" if share else "") + (" bn" if bn else ""), n, seed, bad, seen))
+    relu6 = "relu6" in sys.argv[3:]
+    bad, seen = run(n, seed, odd=odd, share=share, bn=bn, relu6=relu6)
+    print("model_fuzz%s: %d random models (seed %d), %d with a finding; fused launches seen: %s"
+          % ((" odd" if odd else "") + (" share" if share else "") + (" bn" if bn else "") + (" relu6" if relu6 else ""), n, seed, bad, seen))
 
 
 if __name__ == "__main__":

@@ -4,7 +4,9 @@ scripts/model_fuzz.py): calibrate, rewrite, rebuild as ReconModel, then the logi
 form) against the logits of the resident plan (int8 / int16 hand-offs, fused ReLUs, conv + NewAdd in one kernel, block tails, pools
 on integers), eagerly and as one HIP graph: bit for bit.  The planner decides per edge who may hand over integers; a wrong decision
 on a graph nobody wrote a test for shows here.
-usage: recon_fuzz.py [models=40] [seed=1]"""
+`relu6`: about half of the nn.ReLU modules become nn.ReLU6 (model_fuzz.with_relu6) and the plan is made with every opt-in argument on
+(depthwise, concat, avgpool, grouped, relu6) -- everything on against the fp32 module boundaries.
+usage: recon_fuzz.py [models=40] [seed=1] [odd] [share] [bn] [big] [relu6]"""
 import importlib.util, os, random, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,8 +19,13 @@ from tools import Quantity, Reconstruction
 from workdir_util import product_workdir
 
 
-def build(i, seed, odd=False, share=False, bn=False):
+EVERYTHING = dict(depthwise=True, concat=True, avgpool=True, grouped=True, relu6=True)
+
+
+def build(i, seed, odd=False, share=False, bn=False, relu6=False):
     model, size, bs, _rng = mf.fold(mf.random_net(i, seed, odd, "cuda", share, bn))
+    if relu6:
+        mf.with_relu6((model,), i, seed)
     return model, size, bs
 
 
@@ -38,20 +45,22 @@ def recon_of(model, twin, data):
         sys.stdout = out
 
 
-def run(n, seed, log=print, odd=False, share=False, bn=False, big=False, variants=None):
+def run(n, seed, log=print, odd=False, share=False, bn=False, big=False, variants=None, relu6=False):
     bad, seen = 0, {}
     variants = variants if variants is not None else {}
     for i in range(n):
-        model, size, bs, rng = mf.fold(mf.random_net(i, seed, odd, "cuda", share, bn))
+        model, size, bs = build(i, seed, odd, share, bn, relu6)
         data = [(torch.randn(bs, model.cin, size, size, device="cuda"), torch.zeros(bs, dtype=torch.long)) for _ in range(2)]
         out = sys.stdout
         try:
             with product_workdir(input_shape="1,%d,%d,%d" % (model.cin, size, size), device="gpu", max_cali_img_num=1):
-                net = recon_of(model, build(i, seed, odd, share, bn)[0], data)
+                net = recon_of(model, build(i, seed, odd, share, bn, relu6)[0], data)
                 x = data[0][0]
                 with torch.no_grad():
                     plain = net(x)
-                    summary = resident.enable(net, x)
+                    summary = resident.enable(net, x, **(EVERYTHING if relu6 else {}))
+                    if relu6:
+                        seen["relu6_modules"] = seen.get("relu6_modules", 0) + sum(1 for m in net.modules() if type(m) is torch.nn.ReLU6)
                     got = net(x)
                     x2 = torch.flip(x, dims=[0]) * 0.5
                     got2 = net(x2)
@@ -108,8 +117,9 @@ if __name__ == "__main__":
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     odd, share, bn, big = "odd" in sys.argv[3:], "share" in sys.argv[3:], "bn" in sys.argv[3:], "big" in sys.argv[3:]
+    relu6 = "relu6" in sys.argv[3:]
     variants = {}
-    bad, seen = run(n, seed, odd=odd, share=share, bn=bn, big=big, variants=variants)
+    bad, seen = run(n, seed, odd=odd, share=share, bn=bn, big=big, variants=variants, relu6=relu6)
     if big:
         print("integer kernels at 256 images:", dict(sorted(variants.items())))
-    print("recon_fuzz%s: %d random models (seed %d), %d with a finding; plans in all: %s" % ((" odd" if odd else "") + (" share" if share else "") + (" bn" if bn else ""), n, seed, bad, seen))
+    print("recon_fuzz%s: %d random models (seed %d), %d with a finding; plans in all: %s" % ((" odd" if odd else "") + (" share" if share else "") + (" bn" if bn else "") + (" relu6" if relu6 else ""), n, seed, bad, seen))
