@@ -726,6 +726,31 @@ int fq_concat_i8_nhwc_supported(const int* C, const int* up, int nsrc);
 int fq_concat_i8_nhwc(const fq_cat_src* srcs, int nsrc, int8_t* out, int Cpad_out, int relu, int N, int H, int W,
                       fq_stream_t stream);
 
+/* The same concatenation for up to FQ_CONCAT_N_MAX_SRC sources in ONE launch, each with its own nearest-upsampling factor and
+ * its own ReLU: what nested Concat markers compute (the four branches of an Inception block, an SPP block, an ASPP head) without
+ * the intermediate tensors.  With base_i = C_0 + ... + C_{i-1}:
+ *   out[n][h][w][c] = f_i(src_i[n][h / up_i][w / up_i][c - base_i])   for base_i <= c < base_i + C_i
+ *                   = 0                                                for sum C <= c < Cpad_out, whatever the sources' padding holds
+ *   f_i = max(., 0) where relu_i == 1, the identity where relu_i == 0 (per source: a flattened inner Concat may carry a fused
+ *   ReLU that the outer one lacks; a ReLU on the whole output is every flag set).
+ * Source i: int8 [N][H / up_i][W / up_i][Cpad_i], 16-byte aligned, Cpad_i % 16 == 0, 1 <= C_i <= Cpad_i, up_i in {1, 2, 4} with
+ *   H % up_i == 0 and W % up_i == 0.  No further restriction on the C_i: sources of 1, 2 or 3 channels in the middle are legal,
+ *   one 16-byte chunk of the output may hold bytes of all eight sources.
+ * out: int8 [N][H][W][Cpad_out], 16-byte aligned, Cpad_out == pad16(sum C); it must not overlap a source.  Only aligned loads
+ *   are issued and no byte outside [q_i, q_i + N (H / up_i) (W / up_i) Cpad_i) is read.
+ * Return codes: FQ_ERR_INVALID_ARG for nsrc < 1, a null or misaligned pointer, C_i < 1, up_i < 1, Cpad_i < C_i, relu_i outside
+ *   {0, 1}, a wrong Cpad_out and the call with nothing to do (nsrc == 1, up == 1, relu == 0); FQ_ERR_UNSUPPORTED for nsrc > 8,
+ *   another factor, H or W no multiple of it, Cpad_i % 16 != 0, sum C > 65536, or an output or a source of 2^31 - 1 bytes or
+ *   more.  N == 0 is FQ_OK without a launch.
+ * Not built: zero-copy concatenation (producers storing at a channel offset), more than eight sources per launch.
+ * fq_concat_n_i8_nhwc_supported: 1 when the channel counts and factors alone are taken (host arithmetic, no GPU needed).
+ * fq_concat_i8_nhwc is unchanged and keeps answering FQ_ERR_UNSUPPORTED for three sources. */
+#define FQ_CONCAT_N_MAX_SRC 8
+typedef struct fq_cat_src_n { const int8_t* q; int C; int Cpad; int up; int relu; } fq_cat_src_n;
+int fq_concat_n_i8_nhwc_supported(const int* C, const int* up, int nsrc);
+int fq_concat_n_i8_nhwc(const fq_cat_src_n* srcs, int nsrc, int8_t* out, int Cpad_out, int N, int H, int W,
+                        fq_stream_t stream);
+
 /* The tail of a bottleneck block and the head of the next one in ONE kernel (round 4):
  *   NewConv2d.forward of conv3 (1x1, C -> K3; new_quantity_op.py:124-133)  ->  NewAdd.forward with the shortcut (:166-174)
  *   -> nn.ReLU -> the next block's conv1: NewConv2d.forward again (1x1, K3 -> C2, Quantity(ib) on the sum, its own tail and

@@ -44,6 +44,14 @@ class _CatSrc(ctypes.Structure):
     _fields_ = [("q", ctypes.c_void_p), ("C", ctypes.c_int32), ("Cpad", ctypes.c_int32), ("up", ctypes.c_int32)]
 
 
+class _CatSrcN(ctypes.Structure):
+    _fields_ = [("q", ctypes.c_void_p), ("C", ctypes.c_int32), ("Cpad", ctypes.c_int32), ("up", ctypes.c_int32),
+                ("relu", ctypes.c_int32)]
+
+
+CONCAT_N_MAX_SRC = 8         # FQ_CONCAT_N_MAX_SRC
+
+
 class _ChanSeg(ctypes.Structure):
     _fields_ = [("ptr", ctypes.c_void_p), ("N", ctypes.c_int32), ("C", ctypes.c_int32), ("HW", ctypes.c_int64),
                 ("row0", ctypes.c_int32), ("reserved", ctypes.c_int32)]
@@ -242,6 +250,10 @@ def lib():
     L.fq_concat_i8_nhwc_supported.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci), ci]
     L.fq_concat_i8_nhwc.restype = ci
     L.fq_concat_i8_nhwc.argtypes = [ctypes.POINTER(_CatSrc), ci, vp, ci, ci, ci, ci, ci, vp]
+    L.fq_concat_n_i8_nhwc_supported.restype = ci
+    L.fq_concat_n_i8_nhwc_supported.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci), ci]
+    L.fq_concat_n_i8_nhwc.restype = ci
+    L.fq_concat_n_i8_nhwc.argtypes = [ctypes.POINTER(_CatSrcN), ci, vp, ci, ci, ci, ci, vp]
     L.fq_avgpool_i8_nhwc_supported.restype = ci
     L.fq_avgpool_i8_nhwc_supported.argtypes = [ci] * 7
     L.fq_avgpool_i8_nhwc.restype = ci
@@ -1557,6 +1569,47 @@ def concat_i8_nhwc(srcs, relu, out=None):
         _need_cuda(out, torch.int8, "fq_concat_i8_nhwc")
         assert tuple(out.shape) == (N, H, W, cpad) and out.is_contiguous()
     _check(lib().fq_concat_i8_nhwc(arr, n, out.data_ptr(), cpad, 1 if relu else 0, N, H, W, _stream(out)), "fq_concat_i8_nhwc")
+    return out
+
+
+def concat_n_supported(Cs, ups):
+    """True when fq_concat_n_i8_nhwc takes sources of these channel counts and nearest-upsampling factors (include/fq.h): one to
+    eight sources, every C >= 1, every factor 1, 2 or 4, at most 65536 channels in all.  Pure host arithmetic (no GPU needed)."""
+    n = len(Cs)
+    if n != len(ups) or n < 1:
+        return False
+    ci = ctypes.c_int * n
+    return bool(lib().fq_concat_n_i8_nhwc_supported(ci(*[int(c) for c in Cs]), ci(*[int(u) for u in ups]), n))
+
+
+def concat_n_i8_nhwc(srcs, out=None):
+    """fq_concat_n_i8_nhwc.  srcs = [(q, C, up, relu), ...]: one to eight int8 [N, H / up, W / up, Cpad] tensors on ONE grid with C
+    real channels each, `up` the nearest-upsampling factor of that operand and `relu` whether max(., 0) is applied to ITS bytes.
+    Returns int8 [N, H, W, pad16(sum C)]: the operands one behind the other along the channels, the padding channels zero.
+    `out`: write there instead (that shape, dense, 16-byte aligned).  Launches on the current stream and does not synchronise."""
+    n = len(srcs)
+    arr = (_CatSrcN * max(n, 1))()
+    plane, total = None, 0
+    for i, (q, C, up, relu) in enumerate(srcs):
+        _need_cuda(q, torch.int8, "fq_concat_n_i8_nhwc")
+        assert q.dim() == 4 and q.is_contiguous()
+        here = (int(q.shape[0]), int(q.shape[1]) * int(up), int(q.shape[2]) * int(up))
+        if plane is None:
+            plane = here
+        elif here != plane:
+            raise FqError("fq_concat_n_i8_nhwc: the operands give different output planes (%s, %s)" % (plane, here))
+        arr[i].q, arr[i].C, arr[i].Cpad, arr[i].up, arr[i].relu = q.data_ptr(), int(C), int(q.shape[3]), int(up), 1 if relu else 0
+        total += int(C)
+    if plane is None:
+        raise FqError("fq_concat_n_i8_nhwc: no operand")
+    N, H, W = plane
+    cpad = pad16(total)
+    if out is None:
+        out = torch.empty(N, H, W, cpad, dtype=torch.int8, device=srcs[0][0].device)
+    else:
+        _need_cuda(out, torch.int8, "fq_concat_n_i8_nhwc")
+        assert tuple(out.shape) == (N, H, W, cpad) and out.is_contiguous()
+    _check(lib().fq_concat_n_i8_nhwc(arr, n, out.data_ptr(), cpad, N, H, W, _stream(out)), "fq_concat_n_i8_nhwc")
     return out
 
 

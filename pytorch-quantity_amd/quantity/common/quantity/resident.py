@@ -115,6 +115,42 @@ class DeferredUpsample(object):
         return self.materialise().to_f32()
 
 
+MAX_CONCAT_LEAVES = _native.CONCAT_N_MAX_SRC       # sources of one fq_concat_n_i8_nhwc launch
+
+
+def _concat_launch(leaves):
+    """One launch for the leaves [(handle, up, relu), ...] of a (flattened) Concat: the two-source function where it can say the
+    same -- at most two leaves whose ReLU flags agree --, the N-source function otherwise."""
+    flags = set(bool(r) for _h, _up, r in leaves)
+    if len(leaves) <= 2 and len(flags) == 1:
+        return _native.concat_i8_nhwc([(h.exact, h.shape[1], up) for h, up, _r in leaves], flags.pop())
+    return _native.concat_n_i8_nhwc([(h.exact, h.shape[1], up, bool(r)) for h, up, r in leaves])
+
+
+class DeferredConcat(object):
+    """A resident Concat whose only consumer is another resident Concat (enable(concat=True, flatten=True)): nothing has been
+    launched, the consumer takes these leaves -- (handle, upsampling factor, ReLU flag), the flag being this Concat's own fused
+    nn.ReLU -- into its own source list and launches once (fq_concat_n_i8_nhwc), so the intermediate tensor is neither written
+    nor read back.  Anything else that touches it materialises the concatenated activation."""
+    __slots__ = ("leaves", "grid", "_out")
+
+    def __init__(self, leaves, grid):
+        self.leaves, self.grid, self._out = list(leaves), grid, None
+
+    @property
+    def relu_done(self):
+        return all(r or h.relu_done for h, _up, r in self.leaves)
+
+    def materialise(self):
+        if self._out is None:
+            q = _concat_launch(self.leaves)
+            self._out = QHandle.int8(q, sum(h.shape[1] for h, _up, _r in self.leaves), self.grid, self.relu_done)
+        return self._out
+
+    def to_f32(self):
+        return self.materialise().to_f32()
+
+
 def block_tail_enabled():
     """FQ_BLOCK_TAIL=0: keep conv3 + add and the next conv1 as two launches (A/B timing).  Read at every call."""
     return os.environ.get("FQ_BLOCK_TAIL", "1") != "0"
@@ -139,7 +175,7 @@ def resident_of(x):
     """The integer form of an activation, if it has one (a handle, or an fp32 tensor carrying one that is still current)."""
     if type(x) is QHandle:
         return x
-    if type(x) in (DeferredConv, DeferredUpsample):
+    if type(x) in (DeferredConv, DeferredUpsample, DeferredConcat):
         return x.materialise()
     h = getattr(x, "_fq_resident", None)
     if h is not None and getattr(x, "_fq_resident_version", None) != x._version:
@@ -148,7 +184,7 @@ def resident_of(x):
 
 
 def as_f32(x):
-    return x.to_f32() if type(x) in (QHandle, DeferredConv, DeferredUpsample) else x
+    return x.to_f32() if type(x) in (QHandle, DeferredConv, DeferredUpsample, DeferredConcat) else x
 
 
 class Plan(object):
@@ -203,7 +239,7 @@ class _ReluPassThrough(_InstanceForward):
     """Instance-level forward of an nn.ReLU (or, with enable(relu6=True), an nn.ReLU6) whose producer already applied it."""
 
     def __call__(self, x):
-        if type(x) is QHandle:
+        if type(x) in (QHandle, DeferredConcat):
             if not x.relu_done:
                 raise _native.FqError("resident activation reached a ReLU that its producer did not fuse "
                                       "(dataflow changed since resident.enable(); call it again)")
@@ -343,29 +379,50 @@ class _UpsampleResident(_InstanceForward):
 class _ConcatResident(_InstanceForward):
     """Instance-level forward of a Concat marker whose operands are int8 NHWC on one grid: concatenating the integers is
     concatenating the values (fq_concat_i8_nhwc, the nn.ReLU behind it fused).  An operand that arrives as a DeferredUpsample is
-    upsampled by the same kernel."""
+    upsampled by the same kernel; one that arrives as a DeferredConcat (enable(flatten=True)) is expanded into its leaves, and the
+    whole list goes out in one launch (_concat_launch).  With plan.defer nothing runs here either: the leaves are handed on."""
+
+    @staticmethod
+    def _leaves(operands, expand):
+        out = []
+        for t in operands:
+            if expand and type(t) is DeferredConcat and t._out is None:
+                out.extend(t.leaves)
+            elif type(t) is DeferredUpsample and t._out is None:
+                out.append((t.handle, t.s, False))
+            else:
+                out.append((resident_of(t), 1, False))
+        return out
+
+    @staticmethod
+    def _fits(plan, dim, leaves):
+        ok = plan is not None and dim == 1 and len(leaves) <= MAX_CONCAT_LEAVES
+        for h, _up, _r in leaves:
+            ok = ok and h is not None and h.exact is not None and h.exact.dtype == torch.int8 and h.exact.dim() == 4 \
+                and h.grid == plan.narrow_bit
+        if ok:
+            planes = set((h.exact.shape[0], h.exact.shape[1] * up, h.exact.shape[2] * up) for h, up, _r in leaves)
+            supported = _native.concat_supported if len(leaves) <= 2 else _native.concat_n_supported
+            ok = len(planes) == 1 and supported([h.shape[1] for h, _up, _r in leaves], [up for _h, up, _r in leaves])
+        return ok
 
     def __call__(self, x, y, dim=1):
         m = self.module
         plan = m.__dict__.get("_resident")
-        ops = []
-        for t in (x, y):
-            if type(t) is DeferredUpsample and t._out is None:
-                ops.append((t.handle, t.s))
-            else:
-                ops.append((resident_of(t), 1))
-        ok = plan is not None and dim == 1
-        for h, _up in ops:
-            ok = ok and h is not None and h.exact is not None and h.exact.dtype == torch.int8 and h.exact.dim() == 4 \
-                and h.grid == plan.narrow_bit
-        if ok:
-            planes = [(h.exact.shape[0], h.exact.shape[1] * up, h.exact.shape[2] * up) for h, up in ops]
-            ok = planes[0] == planes[1] and _native.concat_supported([h.shape[1] for h, _up in ops], [up for _h, up in ops])
+        leaves = self._leaves((x, y), True)
+        ok = self._fits(plan, dim, leaves)
+        if not ok and any(type(t) is DeferredConcat and t._out is None for t in (x, y)):
+            leaves = self._leaves((x, y), False)            # the deferred parts are materialised: the two-operand path
+            ok = self._fits(plan, dim, leaves)
         if not ok:
             return type(m).forward(m, as_f32(x), as_f32(y), dim)
-        q = _native.concat_i8_nhwc([(h.exact, h.shape[1], up) for h, up in ops], plan.relu)
-        return _emit(plan, QHandle.int8(q, sum(h.shape[1] for h, _up in ops), plan.narrow_bit,
-                                        plan.relu or all(h.relu_done for h, _up in ops)))
+        if plan.relu:
+            leaves = [(h, up, True) for h, up, _r in leaves]
+        if plan.defer:
+            return DeferredConcat(leaves, plan.narrow_bit)
+        q = _concat_launch(leaves)
+        return _emit(plan, QHandle.int8(q, sum(h.shape[1] for h, _up, _r in leaves), plan.narrow_bit,
+                                        all(r or h.relu_done for h, _up, r in leaves)))
 
 
 # ---- tracing -------------------------------------------------------------------------------------
@@ -506,7 +563,7 @@ class _Planning(object):
     """The plan of one traced forward.  enable() calls the passes below in order; they decide on the trace alone and change
     nothing on the model until install() writes the plans and the instance-level forwards to the modules."""
 
-    def __init__(self, tracer, depthwise, concat, avgpool, grouped, relu6=False):
+    def __init__(self, tracer, depthwise, concat, avgpool, grouped, relu6=False, flatten=False):
         from .new_quantity_op import NewConv2d, NewAdd
         from .fabu_layer import Concat
         self.conv_type, self.concat_type = NewConv2d, Concat
@@ -532,6 +589,8 @@ class _Planning(object):
             self.summary["resident_depthwise"] = 0
         if concat:
             self.summary["resident_concats"] = self.summary["resident_upsamples"] = 0
+        if flatten:
+            self.summary["flattened_concats"] = 0
         if avgpool:
             self.summary["resident_avgpools"] = 0
         if grouped:
@@ -692,8 +751,8 @@ class _Planning(object):
         by an integer scale_factor of 2 or 4, both served by fq_concat_i8_nhwc: a Concat whose two operands are int8 activations
         on ONE grid -- what the calibrator's merge group gives them -- joins the integers, with the nn.ReLU behind it fused.
         Without the argument both are foreign code and their operands leave as fp32.  Left in fp32 form (out of scope): a Concat
-        with a NewAdd sum (int16) as an operand or with operands on different grids, any dim but 1, more than two operands, nested
-        Concats are not flattened, the `size=` form and other factors of an upsampling; a bare torch.cat stays foreign, as a bare
+        with a NewAdd sum (int16) as an operand or with operands on different grids, any dim but 1, more than two operands (nested
+        Concats are flattened by defer_concats, `flatten=True`), the `size=` form and other factors of an upsampling; a bare torch.cat stays foreign, as a bare
         `+` does.  The summary then gains `resident_concats`, `resident_upsamples` and `fused_upsamples` (defer_upsamples)."""
         m = v.producer
         ops = self._integer_operands(m) if self.tracer.concat_ok.get(m) else None
@@ -882,6 +941,44 @@ class _Planning(object):
             plan.defer = True
             self.summary["fused_upsamples"] += 1
 
+    def defer_concats(self):
+        """(`concat=True, flatten=True`) A resident Concat whose value -- behind its own fused nn.ReLU, if it has one -- goes to one
+        operand of one other resident Concat and nowhere else is not launched: the consumer takes its leaves into its own source
+        list and launches once (DeferredConcat, fq_concat_n_i8_nhwc), the inner ReLU as those leaves' flag.  Values are walked
+        in traced order, so an inner Concat's leaf count is final when its consumer is looked at.  A Concat that would push its
+        consumer past MAX_CONCAT_LEAVES is not deferred and launches on its own; an upsampling between two Concats ends the
+        flattening (the inner one launches, the upsampling is still folded into the outer one).  Left out: NewAdd sums as
+        operands, more than eight leaves per launch, factor products through nested upsamplings, a bare torch.cat.  The
+        summary gains `flattened_concats`; `resident_concats` keeps counting planned markers."""
+        cat_of = dict((id(self.eff_of[id(v)][0]), v) for v in self.tracer.produced if v.kind == "concat")
+        leaves = {}                      # id(Concat value) -> sources of its launch
+
+        def count(cat_mod, assume=None):
+            n = 0
+            for op in self.operands[cat_mod]:
+                inner = cat_of.get(id(op))
+                plan = self.plans.get(inner.producer) if inner is not None else None
+                n += leaves[id(inner)] if inner is not None and (inner is assume or (plan is not None and plan.defer)) else 1
+            return n
+
+        for v in self.tracer.produced:
+            plan = self.plans.get(v.producer)
+            if v.kind != "concat" or plan is None or v.producer not in self.int8_resident:
+                continue
+            leaves[id(v)] = count(v.producer)
+            e = self.eff_of[id(v)][0]
+            if v.foreign or e.foreign or plan.emit_f32 or len(e.consumers) != 1:
+                continue
+            cat_mod, pos = e.consumers[0]
+            if (not isinstance(cat_mod, self.concat_type) or cat_mod not in self.int8_resident or cat_mod not in self.plans
+                    or pos > 1):
+                continue
+            ops = self.operands[cat_mod]
+            if ops[pos] is not e or ops[1 - pos] is e or count(cat_mod, assume=v) > MAX_CONCAT_LEAVES:
+                continue
+            plan.defer = True
+            self.summary["flattened_concats"] += 1
+
     def hook_global_pools(self):
         for m in self.tracer.avgpool_shapes:
             if self.avg_can_read(m):
@@ -929,7 +1026,8 @@ def _trace(model, example_input, concat, avgpool, relu6=False):
     return tracer, traced_out
 
 
-def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False, grouped=False, relu6=False):
+def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False, grouped=False, relu6=False,
+           flatten=False):
     """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
     on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
     nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
@@ -940,13 +1038,16 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
     `depthwise=True` also plans depthwise NewConv2d layers (_Planning.is_dw), `grouped=True` grouped ones (_Planning.is_gc);
     `concat=True` also plans the Concat marker layer and nearest upsampling by 2 or 4 (_Planning._concat_format, defer_upsamples);
     `avgpool=True` also plans a windowed nn.AvgPool2d between an int8 activation and convolutions (_plan_avgpool_window);
-    `relu6=True` also fuses an nn.ReLU6 behind a NewConv2d, as an nn.ReLU is fused (_Planning.takes_relu6)."""
+    `relu6=True` also fuses an nn.ReLU6 behind a NewConv2d, as an nn.ReLU is fused (_Planning.takes_relu6);
+    `flatten=True` (with `concat=True`; ValueError without) runs nested Concats as one launch (_Planning.defer_concats)."""
     from .new_quantity_op import QUANTIZE_BIT
+    if flatten and not concat:
+        raise ValueError("resident.enable(flatten=True) needs concat=True: only planned Concats are flattened")
     _clear(model)
     if QUANTIZE_BIT != 8:
         raise _native.FqError("resident activations are defined for QUANTIZE_BIT = 8")
     tracer, traced_out = _trace(model, example_input, concat, avgpool, relu6)
-    planning = _Planning(tracer, depthwise, concat, avgpool, grouped, relu6)
+    planning = _Planning(tracer, depthwise, concat, avgpool, grouped, relu6, flatten)
     planning.plan_formats()
     planning.plan_outputs()
     planning.defer_convs()
@@ -954,6 +1055,8 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
     planning.fuse_projections()
     if concat:
         planning.defer_upsamples()
+    if flatten:
+        planning.defer_concats()
     planning.hook_global_pools()
     planning.install(model)
     if verify:
@@ -969,15 +1072,19 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
 
 class _Description(dict):
     """describe()'s {module name: Plan}.  After enable(relu6=True) it also says what became of the nn.ReLU6 modules:
-    `fused_relu6s`, how many a producer fused, and `relu6_left`, {module name: why} for each one that stays torch's."""
+    `fused_relu6s`, how many a producer fused, and `relu6_left`, {module name: why} for each one that stays torch's.  After
+    enable(flatten=True) `flattened_concats` names the Concats that launch nothing of their own."""
     fused_relu6s = 0
     relu6_left = {}
+    flattened_concats = ()       # names of the Concats that enable(flatten=True) deferred into their consumer's launch
 
 
 def describe(model):
     """{module name: Plan} of the current plan (for logs and tests); see _Description for the ReLU6 report."""
     d = _Description((name, m.__dict__["_resident"]) for name, m in model.named_modules() if "_resident" in m.__dict__)
     d.fused_relu6s, d.relu6_left = model.__dict__.get("_fq_resident_relu6", (0, {}))
+    d.flattened_concats = tuple(name for name, m in model.named_modules()
+                                if type(m).__name__ == "Concat" and name in d and d[name].defer)
     return d
 
 
