@@ -298,7 +298,8 @@ int fq_conv1x1_f32(const float* x, const float* wt, const float* bias, float* y,
  * error codes as the entry points they shadow, except:
  *   wsb: the weights packed by fq_conv1x1_sb_pack from fp32 [Cout][Cin] (NOT transposed) into bf16 [Cin / 16][plane: hi, mid, lo]
  *        [k % 16 / 8][Cout][8] -- the order the kernel's lanes load their MFMA operands in, straight from global memory --
- *        fq_conv1x1_sb_packed_bytes(Cin, Cout) bytes, 16-byte aligned;  Cin % 16 == 0, Cout % 4 == 0 (fq_conv1x1_sb_supported). */
+ *        fq_conv1x1_sb_packed_bytes(Cin, Cout) bytes, 16-byte aligned;  Cin % 16 == 0, Cout % 4 == 0 and a pack that ends below
+ *        4 GiB, 6 * Cin * Cout < 2^32 (fq_conv1x1_sb_supported; FQ_ERR_UNSUPPORTED otherwise). */
 size_t fq_conv1x1_sb_packed_bytes(int Cin, int Cout);
 int fq_conv1x1_sb_supported(int Cin, int Cout);
 int fq_conv1x1_sb_pack(const float* w_kc, void* wsb, int Cin, int Cout, fq_stream_t stream);

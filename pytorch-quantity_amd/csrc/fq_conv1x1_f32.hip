@@ -1103,6 +1103,10 @@ using namespace fq;
 
 namespace {
 
+// The split-bf16 pack of a [Cin][Cout] matrix is 6 * Cin * Cout bytes behind ONE buffer descriptor with 32-bit byte offsets
+// (conv1x1_tiles_sb): it must end below 4 GiB, which is less than the fp32 form's 2^30 weights.
+bool sb_pack_fits(size_t Cin, size_t Cout) { return Cin * Cout * 6 <= 0xffffffffULL; }
+
 // the common host side of fq_conv1x1_f32 (R = S = 1, pad = 0) and fq_conv_kxk_f32
 int conv_f32_launch(const float* x, const float* wt, const float* bias, float* y, float* relu_out, int N, int Cin, int Hin, int Win,
                     int Cout, int R, int S, int stride, int pad, float* max_inout, const float* interval, int64_t* hist_row,
@@ -1124,8 +1128,9 @@ int conv_f32_launch(const float* x, const float* wt, const float* bias, float* y
     const int Hout = (Hin + 2 * pad - R) / stride + 1, Wout = (Win + 2 * pad - S) / stride + 1;
     const size_t cols = (size_t)N * Hout * Wout;
     const size_t in_elems = (size_t)N * Cin * Hin * Win, out_elems = cols * Cout, w_elems = (size_t)R * S * Cin * Cout;
-    // 32-bit BYTE offsets into x, Wt and y
-    if (cols >= 0xffffff00ULL || in_elems >= (1ULL << 30) || w_elems >= (1ULL << 30) || out_elems >= (1ULL << 30))
+    // 32-bit BYTE offsets into x, Wt and y (the split-bf16 pack holds 6 bytes per weight)
+    if (cols >= 0xffffff00ULL || in_elems >= (1ULL << 30) || w_elems >= (1ULL << 30) || out_elems >= (1ULL << 30) ||
+        (wsb && !sb_pack_fits((size_t)Cin, (size_t)Cout)))
         return FQ_ERR_UNSUPPORTED;
     C1Args a;
     a.x = x; a.wt = wt; a.wsb = wsb; a.bias = bias; a.y = y; a.relu = relu_out; a.res = nullptr; a.sum = nullptr; a.store_y = 1;
@@ -1222,7 +1227,8 @@ static int conv_add_launch(const float* x, const float* wt_in, const unsigned sh
     const int Hout = (Hin - 1) / stride + 1, Wout = (Win - 1) / stride + 1;
     const size_t cols = (size_t)N * Hout * Wout;
     const size_t in_elems = (size_t)N * Cin * Hin * Win, out_elems = cols * Cout, w_elems = (size_t)Cin * Cout;
-    if (cols >= 0xffffff00ULL || in_elems >= (1ULL << 30) || w_elems >= (1ULL << 30) || out_elems >= (1ULL << 30))
+    if (cols >= 0xffffff00ULL || in_elems >= (1ULL << 30) || w_elems >= (1ULL << 30) || out_elems >= (1ULL << 30) ||
+        (wsb && !sb_pack_fits((size_t)Cin, (size_t)Cout)))
         return FQ_ERR_UNSUPPORTED;
     C1Args a;
     a.x = x; a.wt = wt; a.wsb = wsb; a.bias = bias; a.y = y; a.relu = relu_out; a.res = res; a.sum = sum; a.store_y = y != nullptr;
@@ -1325,11 +1331,13 @@ extern "C" int fq_conv_kxk_qd_f32(const float* x, const float* wt, const float* 
 // ---- the split-bf16 form of the 1x1 convolutions (conv1x1_tiles_sb): same contracts, weights packed by fq_conv1x1_sb_pack
 extern "C" size_t fq_conv1x1_sb_packed_bytes(int Cin, int Cout) { return (Cin > 0 && Cout > 0) ? (size_t)6 * (size_t)Cin * (size_t)Cout : 0; }
 
-extern "C" int fq_conv1x1_sb_supported(int Cin, int Cout) { return Cin > 0 && Cout > 0 && (Cin % kSbBK) == 0 && (Cout & 3) == 0; }
+extern "C" int fq_conv1x1_sb_supported(int Cin, int Cout) {
+    return Cin > 0 && Cout > 0 && (Cin % kSbBK) == 0 && (Cout & 3) == 0 && sb_pack_fits((size_t)Cin, (size_t)Cout);
+}
 
 extern "C" int fq_conv1x1_sb_pack(const float* w_kc, void* wsb, int Cin, int Cout, fq_stream_t stream) {
     if (!w_kc || !wsb || Cin <= 0 || Cout <= 0) return FQ_ERR_INVALID_ARG;
-    if ((size_t)Cin * Cout >= (1ULL << 30)) return FQ_ERR_UNSUPPORTED;
+    if (!sb_pack_fits((size_t)Cin, (size_t)Cout)) return FQ_ERR_UNSUPPORTED;
     const unsigned n = (unsigned)Cin * (unsigned)Cout;
     hipLaunchKernelGGL(conv1x1_sb_pack_kernel, dim3((n + 255u) / 256u), dim3(256), 0, as_stream(stream), w_kc, static_cast<unsigned short*>(wsb),
                        (unsigned)Cin, (unsigned)Cout);

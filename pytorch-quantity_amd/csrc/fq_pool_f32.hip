@@ -14,6 +14,7 @@ namespace fq {
 namespace {
 
 constexpr int kPoolBlock = 256;
+constexpr size_t kPoolMaxBlocks = (size_t)kCUs * 64;      // the largest grid of the generic max-pool kernel (the quad form: half)
 
 __global__ __launch_bounds__(kPoolBlock) void maxpool2d_f32_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                                    unsigned total, int H, int W, int Ho, int Wo, int kh, int kw,
@@ -96,19 +97,23 @@ extern "C" int fq_maxpool2d_f32(const float* x, float* y, int planes, int H, int
     const size_t total = (size_t)planes * Ho * Wo;
     if (total == 0) return FQ_OK;
     if (!x || !y) return FQ_ERR_INVALID_ARG;
-    if (total >= 0xffffffffULL || (size_t)planes * H * W >= 0xffffffffULL) return FQ_ERR_UNSUPPORTED;
+    // 32-bit output index in both kernels: the grid-stride loops add up to kPoolMaxBlocks * kPoolBlock to an index below
+    // `total` and must not wrap (an index that wraps starts over and the loop never ends); a plane is indexed with an int
+    if (total + kPoolMaxBlocks * kPoolBlock > 0xffffffffULL || (size_t)planes * H * W >= 0xffffffffULL ||
+        (size_t)H * W > 0x7fffffffULL)
+        return FQ_ERR_UNSUPPORTED;
     if (kh == 3 && kw == 3 && sh == 2 && sw == 2 && ph == 1 && pw == 1 && (W & 7) == 0 && (Wo & 3) == 0 && Wo * 2 == W &&
         ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15u) == 0) {
         const size_t quads = total >> 2;
         size_t blocks = (quads + kPoolBlock - 1) / kPoolBlock;
-        if (blocks > (size_t)kCUs * 32) blocks = (size_t)kCUs * 32;
+        if (blocks > kPoolMaxBlocks / 2) blocks = kPoolMaxBlocks / 2;
         hipLaunchKernelGGL(maxpool3x3s2p1_f32_kernel, dim3((unsigned)blocks), dim3(kPoolBlock), 0, as_stream(stream), x, y,
                            (unsigned)quads, H, W, Ho, Wo);
         FQ_LAUNCH_CHECK();
         return FQ_OK;
     }
     size_t blocks = (total + kPoolBlock - 1) / kPoolBlock;
-    if (blocks > (size_t)kCUs * 64) blocks = (size_t)kCUs * 64;
+    if (blocks > kPoolMaxBlocks) blocks = kPoolMaxBlocks;
     hipLaunchKernelGGL(maxpool2d_f32_kernel, dim3((unsigned)blocks), dim3(kPoolBlock), 0, as_stream(stream), x, y, (unsigned)total,
                        H, W, Ho, Wo, kh, kw, sh, sw, ph, pw);
     FQ_LAUNCH_CHECK();

@@ -106,8 +106,19 @@ def _g_ok(m, h, w):
     if g < 2 or m.in_channels % g or m.out_channels % g or m.bias is None:
         return False
     cgi, cgo = m.in_channels // g, m.out_channels // g
+    # (the last term: fq_gconv_f32 reads the weights through 32-bit element offsets and refuses 2^30 of them)
     return (cgi % 4 == 0 and cgo % 4 == 0 and 4 <= cgi <= 64 and 4 <= cgo <= 64
-            and _window_ok(m, h, w, ((1, 1), (3, 3))))
+            and _window_ok(m, h, w, ((1, 1), (3, 3)))
+            and m.out_channels * cgi * m.kernel_size[0] * m.kernel_size[1] < 2 ** 30)
+
+
+def _out_plane(m, h, w):
+    """Output pixels per image and channel of the nn.Conv2d m (no dilation, integer padding) on an h x w plane; 0 where the
+    padded plane is smaller than the kernel.  The kernels' hosts refuse 2^30 OUTPUT elements: the stem at stride 2 writes a
+    quarter of its input plane."""
+    ho = (h + 2 * m.padding[0] - m.kernel_size[0]) // m.stride[0] + 1
+    wo = (w + 2 * m.padding[1] - m.kernel_size[1]) // m.stride[1] + 1
+    return max(ho, 0) * max(wo, 0)
 
 
 def _is_depthwise(m):
@@ -124,7 +135,7 @@ def kind(m, x, wino=True, depthwise=None, grouped=None):
     if (not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or m.weight.dtype != torch.float32 or m.bias is None
             or is_off(m) or m.dilation != (1, 1) or m.stride[0] != m.stride[1] or x.dim() != 4
             or not x.is_contiguous() or isinstance(m.padding, str) or m.padding[0] != m.padding[1] or m.padding_mode != "zeros"
-            or x.numel() >= 2 ** 30 or x.shape[0] * m.out_channels * x.shape[2] * x.shape[3] >= 2 ** 30):
+            or x.numel() >= 2 ** 30 or x.shape[0] * m.out_channels * _out_plane(m, x.shape[2], x.shape[3]) >= 2 ** 30):
         return None
     if m.groups != 1:
         if not _is_depthwise(m):                                # (a depthwise layer is never "g": fewer than 4 channels per group)
@@ -135,7 +146,8 @@ def kind(m, x, wino=True, depthwise=None, grouped=None):
             return None
         return "dw" if _dw_ok(m, x.shape[2], x.shape[3]) else None
     if m.kernel_size == (1, 1) and m.padding == (0, 0) and m.out_channels % 4 == 0:
-        return "c1"
+        # (fq_conv1x1_f32 reads Wt through 32-bit byte offsets as well: a matrix of 2^30 weights keeps torch's convolution)
+        return "c1" if m.in_channels * m.out_channels < 2 ** 30 else None
     if (x.shape[2] + 2 * m.padding[0] >= m.kernel_size[0] and x.shape[3] + 2 * m.padding[1] >= m.kernel_size[1]
             and _native.conv_stem_f32_supported(m.weight, m.stride[0])):
         return "stem"

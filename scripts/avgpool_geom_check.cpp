@@ -4,12 +4,16 @@
 //   c++ -O2 -std=c++17 -o avgpool_geom_check scripts/avgpool_geom_check.cpp
 //   ./avgpool_geom_check                                  the built-in shape list
 //   ./avgpool_geom_check N,H,W,C,kh,kw,sh,sw,ph,pw ...    these cases instead; tests pass the GPU tests' list
+//   ./avgpool_geom_check window=T <cases>                 a size-limit row (10^8 chunks): only the first and the last T output chunks
+//                                                         are walked, by the lanes and in the order the kernel visits them (neither
+//                                                         tensor reaches 2^31 bytes: there is no boundary between)
 // Every case is walked with and without count_include_pad.  One line per case: "case ...: P p Q q chunks n blocks b", then
 // "ok, <loads> loads checked".  Exit status 1 at the first violation.
 // The walk below is the kernel's own: same launch size, same lane -> chunk stepping by the grid size, the same window cut and
 // the same offset stepping along a window row, on a model of memory in which each byte is its own address.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <set>
 #include <utility>
 #include <vector>
@@ -25,6 +29,8 @@ static void fail(const char* what, const Case& c, int cip) {
            c.kh, c.kw, c.sh, c.sw, c.ph, c.pw, cip);
     exit(1);
 }
+
+static unsigned long g_window = 0;          // window=T: chunks [T, nchunks - T) are skipped
 
 static long run(const Case& c, int cip, bool print) {
     if (c.N < 1 || c.H < 1 || c.W < 1 || c.C < 1 || c.kh < 1 || c.kw < 1 || c.sh < 1 || c.sw < 1 || c.ph < 0 || c.pw < 0 ||
@@ -50,10 +56,20 @@ static long run(const Case& c, int cip, bool print) {
                c.pw, g.P, g.Q, g.nchunks, blocks);
 
     const unsigned threads = (unsigned)blocks * kAvgBlock;
-    std::vector<unsigned char> written(g.nchunks, 0);
+    if ((unsigned long)g.nchunks + threads > 0xffffffffUL) fail("the 32-bit chunk index wraps in `i += stride`", c, cip);
+    const bool windowed = g_window && (unsigned long)g.nchunks > 2 * g_window;
+    auto slot = [&](unsigned i) { return !windowed || i < g_window ? (size_t)i : (size_t)(g_window + (i - (g.nchunks - g_window))); };
+    std::vector<unsigned char> written(windowed ? 2 * g_window : g.nchunks, 0);
     long loads = 0;
     for (unsigned gid = 0; gid < threads; ++gid) {
         for (unsigned i = gid; i < g.nchunks; i += threads) {
+            if (windowed && i >= g_window && i < g.nchunks - g_window) {       // jump to this lane's first chunk of the last window
+                const unsigned long steps = ((unsigned long)(g.nchunks - g_window) - i + threads - 1) / threads;
+                const unsigned long next = i + steps * threads;
+                if (next >= g.nchunks) break;
+                i = (unsigned)(next - threads);
+                continue;
+            }
             const AvgChunk ch = avg_chunk(g, i);
             if (ch.n < 0 || ch.n >= c.N || ch.p < 0 || ch.p >= g.P || ch.q < 0 || ch.q >= g.Q || ch.k < 0 || ch.k >= g.CH)
                 fail("chunk index outside the output", c, cip);
@@ -92,7 +108,7 @@ static long run(const Case& c, int cip, bool print) {
                     if (((m >> (8 * j)) & 0xffu) != (16 * ch.k + 4 * t + j < c.C ? 0xffu : 0u)) fail("channel mask", c, cip);
             }
             if (((long)i + 1) * 16 > y_bytes) fail("store outside the output", c, cip);
-            if (written[i]++) fail("output chunk written twice", c, cip);
+            if (written[slot(i)]++) fail("output chunk written twice", c, cip);
         }
     }
     for (unsigned char v : written)
@@ -103,6 +119,7 @@ static long run(const Case& c, int cip, bool print) {
 int main(int argc, char** argv) {
     std::vector<Case> cases;
     for (int a = 1; a < argc; ++a) {
+        if (strncmp(argv[a], "window=", 7) == 0) { g_window = strtoul(argv[a] + 7, nullptr, 10); continue; }
         Case c;
         if (sscanf(argv[a], "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d", &c.N, &c.H, &c.W, &c.C, &c.kh, &c.kw, &c.sh, &c.sw, &c.ph, &c.pw) != 10) {
             printf("cannot read case %s\n", argv[a]);

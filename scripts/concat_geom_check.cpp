@@ -4,6 +4,9 @@
 //   c++ -O2 -std=c++17 -o concat_geom_check scripts/concat_geom_check.cpp
 //   ./concat_geom_check                         the built-in shape list
 //   ./concat_geom_check N,H,W,C0,C1,up0,up1 ...  these cases instead (C1 == 0: one source); tests pass the GPU tests' list
+//   ./concat_geom_check window=P <cases>         a size-limit row (10^8 chunks): only the first and the last P pixels of the
+//                                                output are walked, by the lanes and in the order the kernel visits them; no
+//                                                tensor reaches 2^31 bytes, so there is no boundary between
 // One line per case: "case N,H,W,C0,C1,up0,up1: aligned16 A dword D byte B straddle S" (chunks of one pixel by
 // cat_chunk_class), then "ok, <loads> loads checked".  Exit status 1 at the first violation.
 // The walk below is the kernel's own: same launch size, same lane -> (chunk, first pixel, stride), the same predicates in
@@ -30,6 +33,8 @@ static void fail(const char* what, const Case& c) {
 static void alignbyte(const long (&hi)[4], const long (&lo)[4], int sh, long (&out)[4]) {
     for (int j = 0; j < 4; ++j) out[j] = sh + j < 4 ? lo[sh + j] : hi[sh + j - 4];
 }
+
+static unsigned long g_window = 0;          // window=P: pixels [P, npix - P) are skipped
 
 static long run(const Case& c, bool print) {
     CatGeom g;
@@ -58,7 +63,12 @@ static long run(const Case& c, bool print) {
                cls[0], cls[1], cls[2], cls[3]);
 
     const unsigned threads = (unsigned)cat_blocks(g) * kCatBlock, stride = threads / g.CH;
-    std::vector<unsigned char> written((size_t)g.npix * g.CH, 0);
+    // the kernel's pixel index, lane number and `pix += stride` are 32 bits wide
+    if ((unsigned long)g.npix + stride > 0xffffffffUL || (unsigned long)g.npix * g.CH > 0xffffffffUL) fail("32-bit pixel arithmetic wraps", c);
+    const bool windowed = g_window && (unsigned long)g.npix > 2 * g_window;
+    const unsigned long walked = windowed ? 2 * g_window : g.npix;
+    auto slot = [&](unsigned pix) { return !windowed || pix < g_window ? (size_t)pix : (size_t)(g_window + (pix - (g.npix - g_window))); };
+    std::vector<unsigned char> written((size_t)walked * g.CH, 0);
     long loads = 0;
     for (unsigned gid = 0; gid < threads; ++gid) {
         const int k = gid % g.CH;
@@ -70,6 +80,13 @@ static long run(const Case& c, bool print) {
             if (!part[i].use || !part[i].whole16 || part[1 - i].use) fail("aligned launch: the chunk is not 16 bytes of one source", c);
         }
         for (; pix < g.npix; pix += stride) {
+            if (windowed && pix >= g_window && pix < g.npix - g_window) {      // jump to this lane's first pixel of the last window
+                const unsigned long steps = ((unsigned long)(g.npix - g_window) - pix + stride - 1) / stride;
+                const unsigned long next = pix + steps * stride;
+                if (next >= g.npix) break;
+                pix = (unsigned)(next - stride);
+                continue;
+            }
             // the bytes the kernel assembles, as (source, address) pairs; got[j] = -1: zero
             long got[16];
             int got_src[16];
@@ -131,7 +148,7 @@ static long run(const Case& c, bool print) {
             }
             const size_t chunk = (size_t)pix * g.CH + k;
             if ((chunk + 1) * 16 > (size_t)g.npix * g.Cpad_out) fail("store outside the output", c);
-            if (written[chunk]++) fail("output chunk written twice", c);
+            if (written[slot(pix) * g.CH + k]++) fail("output chunk written twice", c);
         }
     }
     for (unsigned char v : written)
@@ -142,6 +159,7 @@ static long run(const Case& c, bool print) {
 int main(int argc, char** argv) {
     std::vector<Case> cases;
     for (int a = 1; a < argc; ++a) {
+        if (strncmp(argv[a], "window=", 7) == 0) { g_window = strtoul(argv[a] + 7, nullptr, 10); continue; }
         Case c;
         if (sscanf(argv[a], "%d,%d,%d,%d,%d,%d,%d", &c.N, &c.H, &c.W, &c.C[0], &c.C[1], &c.up[0], &c.up[1]) != 7) {
             printf("cannot read case %s\n", argv[a]);

@@ -4,10 +4,17 @@
 // written exactly once.  It also checks that the LDS float a lane reads for a tap is the one the staging filled from that tap's
 // pixel (or with zero, where the pixel lies outside the image), and the reciprocal-multiply divisions against real ones.
 //   c++ -O2 -std=c++17 -o dwconv_f32_geom_check scripts/dwconv_f32_geom_check.cpp && ./dwconv_f32_geom_check
+//   ./dwconv_f32_geom_check window=T N,C,H,W,R,stride,pad     a size-limit row instead of the lists: every workgroup of the plain
+//                                  grid, but only the first and the last T tiles.  A top row's output is 4.29 GB and does cross 2^31
+//                                  bytes in between; the tiles there are not walked, because nothing in this kernel is a byte offset:
+//                                  it indexes plain pointers with UNSIGNED 32-bit ELEMENT offsets, below 2^30 by the host's guard, so
+//                                  bit 31 of a byte address is never a bit of a 32-bit quantity.  Every such offset of the walked
+//                                  tiles is checked against 64-bit arithmetic, and the tile index must not wrap
 // (tests/test_depthwise_f32_cpu.py runs it.)  The walk below is the kernel's own: same plan, same grid, same workgroup -> tiles,
 // same lane -> strip, the same predicates in front of every access.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "../pytorch-quantity_amd/csrc/fq_dwconv_f32_geom.h"
@@ -21,6 +28,8 @@ static void fail(const char* what, const Shape& s) {
     exit(1);
 }
 
+static unsigned long g_window = 0;          // window=T: tiles [T, tiles - T) are skipped
+
 static long run(const Shape& s, bool hist) {
     DwfGeom g;
     if (!dwf_plan(g, s.N, s.C, s.H, s.W, s.R, s.stride, s.pad)) fail("the plan declines a shape of the list", s);
@@ -28,12 +37,34 @@ static long run(const Shape& s, bool hist) {
     const size_t in_elems = (size_t)s.N * s.C * s.H * s.W, out_elems = (size_t)s.N * s.C * g.Ho * g.Wo;
     if (g.fill > (unsigned)kDwfLdsFloats || g.PP > kDwfMaxPP || g.PP < 1 || g.TH * g.QW * g.PP > kDwfBlock || (g.IWP & 3))
         fail("tile larger than the workgroup or its LDS", s);
-    std::vector<unsigned char> written(out_elems, 0);
+    const bool windowed = g_window && (unsigned long)g.tiles > 2 * g_window;
+    // a windowed walk keeps the outputs of the first and the last `keep` elements only: whole plane groups of the two windows
+    const size_t per_grp = (size_t)g.RB * g.CB, grps = (g.planes + g.PP - 1) / g.PP, kgrp = windowed ? g_window / per_grp : 0;
+    const size_t plane_out = (size_t)g.Ho * g.Wo, keep = windowed ? (kgrp + 1) * g.PP * plane_out : out_elems;
+    if (windowed && (kgrp < 1 || 2 * keep > out_elems)) fail("window smaller than one plane group, or as large as the tensor", s);
+    if (in_elems * 4 > 0xffffffffUL || out_elems * 4 > 0xffffffffUL || (unsigned long)g.tiles + kDwfMaxBlocks > 0xffffffffUL ||
+        (unsigned long)grps * per_grp != g.tiles)
+        fail("32-bit tile or offset arithmetic wraps", s);
+    auto slot = [&](size_t o) -> size_t {
+        if (!windowed) return o;
+        if (o < keep) return o;
+        if (o >= out_elems - keep) return keep + (o - (out_elems - keep));
+        fail("a tile of a window stores into the middle of the tensor", s);
+        return 0;
+    };
+    std::vector<unsigned char> written(windowed ? 2 * keep : out_elems, 0);
     std::vector<long> src(g.fill);                        // what the staging left in each LDS float: element offset, or -1 for zero
     const unsigned G = dwf_grid(g, hist);
     long loads = 0;
     for (unsigned b = 0; b < G; ++b) {
         for (unsigned tile = geom_first_tile(b, G); tile < g.tiles; tile += G) {
+            if (windowed && tile >= g_window && tile < g.tiles - g_window) {   // jump to this workgroup's first tile of the last window
+                const unsigned long steps = ((unsigned long)(g.tiles - g_window) - tile + G - 1) / G;
+                const unsigned long next = tile + steps * G;
+                if (next >= g.tiles) break;
+                tile = (unsigned)(next - G);
+                continue;
+            }
             const DwfTilePos tp = dwf_tile_pos(g, tile);
             if (tp.plane0 >= g.planes || tp.oh0 >= g.Ho || tp.ow0 >= g.Wo) fail("tile outside the tensor", s);
             for (unsigned e = 0; e < g.fill; ++e) {       // (lane e % 256 in step e / 256: every e < fill exactly once)
@@ -71,17 +102,39 @@ static long run(const Shape& s, bool hist) {
                 for (int j = 0; j < cnt; ++j) {
                     if ((size_t)o + j >= out_elems) fail("store outside the output", s);
                     if ((long)o + j != (plane * g.Ho + oh) * g.Wo + ow + j) fail("store to the wrong element", s);
-                    if (written[o + j]++) fail("output element written twice", s);
+                    if (written[slot((size_t)o + j)]++) fail("output element written twice", s);
                 }
             }
         }
     }
-    for (unsigned char v : written)
-        if (v != 1) fail("output element not written", s);
+    if (!windowed) {
+        for (unsigned char v : written)
+            if (v != 1) fail("output element not written", s);
+    } else {                                              // the planes of the whole groups that the two windows cover
+        const size_t head = kgrp * g.PP * plane_out, tail0 = (grps - kgrp) * g.PP * plane_out;
+        for (size_t o = 0; o < head; ++o)
+            if (written[slot(o)] != 1) fail("output element of the first planes not written", s);
+        for (size_t o = tail0; o < out_elems; ++o)
+            if (written[slot(o)] != 1) fail("output element of the last planes not written", s);
+    }
     return loads;
 }
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc > 1) {
+        long total = 0;
+        for (int a = 1; a < argc; ++a) {
+            Shape s;
+            if (strncmp(argv[a], "window=", 7) == 0) { g_window = strtoul(argv[a] + 7, nullptr, 10); continue; }
+            if (sscanf(argv[a], "%d,%d,%d,%d,%d,%d,%d", &s.N, &s.C, &s.H, &s.W, &s.R, &s.stride, &s.pad) != 7) {
+                printf("cannot read case %s\n", argv[a]);
+                return 2;
+            }
+            total += run(s, false);
+        }
+        printf("ok, %ld loads\n", total);
+        return 0;
+    }
     // tests/test_gpu_depthwise_f32.py: SHAPES
     const Shape tests[] = {{1, 1, 1, 1, 3, 1, 1},   {2, 3, 3, 3, 3, 1, 0},    {1, 5, 4, 6, 5, 1, 4},   {3, 7, 7, 7, 3, 1, 1},
                            {2, 19, 14, 14, 3, 2, 1}, {2, 4, 13, 9, 5, 2, 2},   {1, 3, 17, 23, 3, 2, 0}, {1, 2, 56, 56, 3, 1, 1},

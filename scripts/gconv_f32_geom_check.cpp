@@ -7,8 +7,15 @@
 //   c++ -O2 -std=c++17 -o gconv_f32_geom_check scripts/gconv_f32_geom_check.cpp && ./gconv_f32_geom_check
 // (tests/test_grouped_f32_cpu.py runs it.)  The walk below is the kernel's own: same plan, same grid, same workgroup -> tiles,
 // same lane -> strip, the same predicates in front of every access.
+//   ./gconv_f32_geom_check window=T N,G,Cgi,Cgo,H,W,R,stride,pad    a size-limit row instead of the lists: every workgroup of the
+//                                  plain grid, but only the first and the last T tiles.  A top row's output is 4.29 GB and does cross
+//                                  2^31 bytes in between; the tiles there are not walked, because nothing in this kernel is a byte
+//                                  offset: it indexes plain pointers with UNSIGNED 32-bit ELEMENT offsets, below 2^30 by the host's
+//                                  guard.  Every such offset of the walked tiles is checked against 64-bit arithmetic, and the tile
+//                                  index must not wrap
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "../pytorch-quantity_amd/csrc/fq_gconv_f32_geom.h"
@@ -23,6 +30,8 @@ static void fail(const char* what, const Shape& s) {
     exit(1);
 }
 
+static unsigned long g_window = 0;          // window=T: tiles [T, tiles - T) are skipped
+
 static long run(const Shape& s, bool hist) {
     GfGeom g;
     const int C = s.G * s.Cgi, K = s.G * s.Cgo, R = s.R, RR = R * R;
@@ -35,13 +44,34 @@ static long run(const Shape& s, bool hist) {
         g.KBN * g.TH * g.QW > kGfBlock || g.TH < 1 || g.QW < 1 || (g.IWP & 3) || g.KC * g.KCN < s.Cgo || g.TH * g.RB < g.Ho ||
         g.QW * g.CB * kGfStrip < g.Wo)
         fail("tile larger than the workgroup or its LDS, or the tiles do not cover the layer", s);
-    std::vector<unsigned char> written(out_elems, 0);
+    const bool windowed = g_window && (unsigned long)g.tiles > 2 * g_window;
+    // a windowed walk keeps the outputs of the first and the last `keep` elements only: whole (image, group) units of the two windows
+    const size_t per_unit = (size_t)g.KCN * g.RB * g.CB, kunit = windowed ? g_window / per_unit : 0;
+    const size_t unit_out = (size_t)s.Cgo * g.Ho * g.Wo, keep = windowed ? (kunit + 1) * unit_out : out_elems;
+    if (windowed && (kunit < 1 || 2 * keep > out_elems)) fail("window smaller than one (image, group) unit, or as large as the tensor", s);
+    if (in_elems * 4 > 0xffffffffUL || out_elems * 4 > 0xffffffffUL || w_elems * 4 > 0xffffffffUL ||
+        (unsigned long)g.tiles + kGfMaxBlocks > 0xffffffffUL || (unsigned long)g.units * per_unit != g.tiles)
+        fail("32-bit tile or offset arithmetic wraps", s);
+    auto slot = [&](size_t o) -> size_t {
+        if (!windowed || o < keep) return o;
+        if (o >= out_elems - keep) return keep + (o - (out_elems - keep));
+        fail("a tile of a window stores into the middle of the tensor", s);
+        return 0;
+    };
+    std::vector<unsigned char> written(windowed ? 2 * keep : out_elems, 0);
     std::vector<long> src(g.fill);                        // what the staging left in each LDS float: element offset, or -1 for zero
     std::vector<long> wsrc(g.wfill);                      // the same for the weight block; -2: not staged
     const unsigned G = gf_grid(g, hist);
     long loads = 0;
     for (unsigned b = 0; b < G; ++b) {
         for (unsigned tile = geom_first_tile(b, G); tile < g.tiles; tile += G) {
+            if (windowed && tile >= g_window && tile < g.tiles - g_window) {   // jump to this workgroup's first tile of the last window
+                const unsigned long steps = ((unsigned long)(g.tiles - g_window) - tile + G - 1) / G;
+                const unsigned long next = tile + steps * G;
+                if (next >= g.tiles) break;
+                tile = (unsigned)(next - G);
+                continue;
+            }
             const GfTilePos tp = gf_tile_pos(g, tile);
             if (tp.n >= (unsigned)s.N || tp.grp >= (unsigned)s.G || tp.k0 >= s.Cgo || tp.oh0 >= g.Ho || tp.ow0 >= g.Wo)
                 fail("tile outside the tensor", s);
@@ -114,18 +144,37 @@ static long run(const Shape& s, bool hist) {
                     for (int j = 0; j < cnt; ++j) {
                         if ((size_t)o + j >= out_elems) fail("store outside the output", s);
                         if ((long)o + j != (plane * g.Ho + oh) * g.Wo + ow + j) fail("store to the wrong element", s);
-                        if (written[o + j]++) fail("output element written twice", s);
+                        if (written[slot((size_t)o + j)]++) fail("output element written twice", s);
                     }
                 }
             }
         }
     }
-    for (unsigned char v : written)
-        if (v != 1) fail("output element not written", s);
+    if (!windowed) {
+        for (unsigned char v : written)
+            if (v != 1) fail("output element not written", s);
+    } else {                                              // the whole units that the two windows cover
+        for (size_t o = 0; o < kunit * unit_out; ++o)
+            if (written[slot(o)] != 1 || written[slot(out_elems - 1 - o)] != 1) fail("output element of the first or last units not written", s);
+    }
     return loads;
 }
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc > 1) {
+        long walked = 0;
+        for (int a = 1; a < argc; ++a) {
+            Shape s;
+            if (strncmp(argv[a], "window=", 7) == 0) { g_window = strtoul(argv[a] + 7, nullptr, 10); continue; }
+            if (sscanf(argv[a], "%d,%d,%d,%d,%d,%d,%d,%d,%d", &s.N, &s.G, &s.Cgi, &s.Cgo, &s.H, &s.W, &s.R, &s.stride, &s.pad) != 9) {
+                printf("cannot read case %s\n", argv[a]);
+                return 2;
+            }
+            walked += run(s, false);
+        }
+        printf("ok, %ld loads\n", walked);
+        return 0;
+    }
     // tests/test_gpu_grouped_f32.py: SHAPES
     const Shape tests[] = {{1, 2, 4, 4, 1, 1, 1, 1, 0},   {1, 2, 4, 4, 1, 1, 3, 1, 1},    {2, 3, 4, 8, 3, 3, 3, 1, 0},   {1, 2, 8, 4, 5, 7, 3, 2, 1},
                            {3, 2, 12, 12, 7, 7, 3, 1, 1}, {1, 2, 4, 4, 6, 6, 3, 1, 2},    {2, 32, 4, 4, 14, 14, 3, 1, 1}, {2, 2, 32, 32, 7, 7, 3, 1, 1},

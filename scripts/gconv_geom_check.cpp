@@ -2,6 +2,9 @@
 // shapes and the ResNeXt model's grouped layers at N = 1, on a model of memory in which each byte is its own address.
 //   c++ -O2 -std=c++17 -o gconv_geom_check scripts/gconv_geom_check.cpp && ./gconv_geom_check
 //   ./gconv_geom_check --list      prints the shape list, one "G Cgi Cgo R stride pad N H W" per line, and walks nothing
+//   ./gconv_geom_check window=T G,Cgi,Cgo,R,stride,pad,N,H,W    a size-limit row instead of the list: every workgroup and lane, but
+//                                  only the first and the last T strip blocks of the launch (neither activation reaches 2^31 bytes:
+//                                  there is no boundary between); the 32-bit strip and offset arithmetic must not wrap
 // (tests/test_grouped_plan_cpu.py runs both and compares the list with the GPU tests' own.)  The walk below is the kernel's own:
 // same launch size, same workgroup -> (channel block, strip blocks), same lane -> (quad, strip), the same predicates in front
 // of every access.  It exits non-zero on a load outside the input or the packed weights, an LDS index outside the staged block
@@ -41,6 +44,8 @@ static std::vector<long> pack_ids(int K, int Kpad, int Cgi, int RS) {
     return ids;
 }
 
+static unsigned long g_window = 0;          // window=T: strip blocks [T, sblocks - T) are skipped
+
 static long run(const Shape& s) {
     const int R = s.R, STRIDE = s.stride, C = s.G * s.Cgi, K = s.G * s.Cgo;
     if (s.H + 2 * s.pad < R || s.W + 2 * s.pad < R) return 0;
@@ -56,7 +61,11 @@ static long run(const Shape& s) {
     const unsigned blocks = gc_blocks(g);
     if (blocks == 0 || blocks > (unsigned)kGcMaxBlocks || blocks % g.KBn) fail("launch size", s);
     const unsigned step = gc_sb_step(g, blocks);
-    std::vector<unsigned char> written(out_bytes / 4, 0);
+    if (in_bytes > 0xffffffffUL || out_bytes > 0xffffffffUL || (unsigned long)g.sblocks * g.SPW + kGcBlock > 0xffffffffUL ||
+        (unsigned long)g.sblocks + step > 0xffffffffUL || (unsigned long)s.N * g.P * g.QS != g.strips)
+        fail("32-bit strip or offset arithmetic wraps", s);
+    const bool windowed = g_window && (unsigned long)g.sblocks > 2 * g_window;
+    std::vector<bool> written(out_bytes / 4, false);
     std::vector<long> lds(g.units);
     long checked = 0;
     for (unsigned b = 0; b < blocks; ++b) {
@@ -81,6 +90,13 @@ static long run(const Shape& s) {
             const bool valid = gc_quad_valid(g, kq);
             if (valid != (4 * kq + 3 < K)) fail("wrong padding-channel mask", s);
             for (unsigned sb = gc_block_sb0(g, b); sb < g.sblocks; sb += step) {
+                if (windowed && sb >= g_window && sb < g.sblocks - g_window) {   // jump to this workgroup's first block of the last window
+                    const unsigned long steps = ((unsigned long)(g.sblocks - g_window) - sb + step - 1) / step;
+                    const unsigned long next = sb + steps * step;
+                    if (next >= g.sblocks) break;
+                    sb = (unsigned)(next - step);
+                    continue;
+                }
                 const unsigned strip = sb * (unsigned)g.SPW + (unsigned)ls;
                 if (strip >= g.strips) continue;
                 const GcStripPos sp = gc_strip_pos(g, strip);
@@ -133,18 +149,40 @@ static long run(const Shape& s) {
                     const unsigned o = gc_out_off(g, sp.n, sp.p, sp.q0 + j, kq);
                     if ((size_t)o + 4 > out_bytes || o % 4) fail("store outside the output", s);
                     if ((long)o != (((long)sp.n * g.P + sp.p) * g.Q + sp.q0 + j) * g.Kpad + 4 * kq) fail("store to another pixel", s);
-                    if (written[o / 4]++) fail("output dword written twice", s);
+                    if (written[o / 4]) fail("output dword written twice", s);
+                    written[o / 4] = true;
                 }
             }
         }
     }
-    for (unsigned char v : written)
-        if (v != 1) fail("output dword not written", s);
+    if (!windowed) {
+        for (bool v : written)
+            if (!v) fail("output dword not written", s);
+    } else {                                              // every output of the whole images that the two windows cover
+        const size_t img = (size_t)g.P * g.Q * g.Kpad / 4, imgs = g_window * g.SPW / ((size_t)g.P * g.QS);
+        if (imgs < 1) fail("window smaller than one image", s);
+        for (size_t i = 0; i < imgs * img; ++i)
+            if (!written[i] || !written[written.size() - 1 - i]) fail("output dword of the first or last images not written", s);
+    }
     return checked;
 }
 
 int main(int argc, char** argv) {
     const bool list = argc > 1 && !strcmp(argv[1], "--list");
+    if (argc > 1 && !list) {
+        long total = 0;
+        for (int a = 1; a < argc; ++a) {
+            Shape s;
+            if (strncmp(argv[a], "window=", 7) == 0) { g_window = strtoul(argv[a] + 7, nullptr, 10); continue; }
+            if (sscanf(argv[a], "%d,%d,%d,%d,%d,%d,%d,%d,%d", &s.G, &s.Cgi, &s.Cgo, &s.R, &s.stride, &s.pad, &s.N, &s.H, &s.W) != 9) {
+                printf("cannot read case %s\n", argv[a]);
+                return 2;
+            }
+            total += run(s);
+        }
+        printf("ok, %ld loads checked\n", total);
+        return 0;
+    }
     std::vector<Shape> shapes;
     // the GPU tests' list (tests/grouped_doubles.py: kernel_shapes())
     const int groups[][3] = {{2, 4, 4}, {8, 4, 4}, {3, 8, 4}, {2, 16, 8}, {2, 32, 32}, {2, 64, 64}, {5, 4, 12}, {32, 4, 4}};
