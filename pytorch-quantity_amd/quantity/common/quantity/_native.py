@@ -296,7 +296,7 @@ def _stream(t):
 
 
 def _need_cuda(t, dtype, what):
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:          # (is_cuda: a third of the cost of t.device.type == "cuda")
         raise FqError("%s: expected a torch.cuda tensor (the MI355X path has no CPU fallback)" % what)
     if t.dtype != dtype:
         raise FqError("%s: expected dtype %s, got %s" % (what, dtype, t.dtype))
@@ -1092,33 +1092,6 @@ def _note_variant():
         log[name] = log.get(name, 0) + 1
 
 
-def conv2d_i8(xq, wq, qbias, stride, padding, dilation, rs, ob, bitwidth=8):
-    """xq int8 [N,H,W,C] (or [N,C] for Linear), wq int8 [K,R,S,C]; returns fp32 [N,K,P,Q] (or [N,K])."""
-    _need_cuda(xq, torch.int8, "fq_conv2d_i8")
-    _need_cuda(wq, torch.int8, "fq_conv2d_i8")
-    _need_cuda(qbias, torch.float32, "fq_conv2d_i8")
-    linear = xq.dim() == 2
-    if linear:
-        xq = xq[:, None, None, :]
-    N, H, W, C = xq.shape
-    K, R, S, Cw = wq.shape
-    assert C == Cw and xq.is_contiguous() and wq.is_contiguous() and qbias.numel() == K
-    P = (H + 2 * padding[0] - dilation[0] * (R - 1) - 1) // stride[0] + 1
-    Q = (W + 2 * padding[1] - dilation[1] * (S - 1) - 1) // stride[1] + 1
-    y = torch.empty(N, K, P, Q, dtype=torch.float32, device=xq.device)
-    if isinstance(rs, ShiftVec):
-        rk = _shift_vec(rs, K, xq.device, "fq_conv2d_i8_pcs")
-        _check(lib().fq_conv2d_i8_pcs(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi, y.data_ptr(), N,
-                                      H, W, C, K, R, S, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
-                                      int(ob), int(bitwidth), _stream(xq)), "fq_conv2d_i8_pcs")
-    else:
-        _check(lib().fq_conv2d_i8(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), y.data_ptr(), N, H, W, C, K, R, S,
-                                  stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], int(rs), int(ob),
-                                  int(bitwidth), _stream(xq)), "fq_conv2d_i8")
-    _note_variant()
-    return y.view(N, K) if linear else y
-
-
 def relu6_clip(ob):
     """The Sp range (lo, hi) that stands for an nn.ReLU6 behind an 8-bit layer with output grid `ob`, or None where the value 6 is
     not on that grid (ob <= -2): min(max(q * 2^-ob, 0), 6) = min(max(q, 0), 6 * 2^ob) * 2^-ob.  From ob = 5 on the bound is 127,
@@ -1140,6 +1113,53 @@ def _act_call(name, clip, relu):
     return getattr(lib(), name + "_act"), (lo, hi), name + "_act"
 
 
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _conv_i8(name, x, w, qbias, rs, K, outs, ints, tail, act=None):
+    """The one call path of the integer convolutions: entry point `name`, its `_pcs` sibling where rs is a ShiftVec (of K
+    entries), and behind either the `_act` sibling where act = (relu, clip) carries a clip (_act_call).  The ABI rule, from
+    include/fq.h (compare fq_conv2d_i8_resident / fq_conv2d_i8_resident_pcs, and every other pair): the `_pcs` entry point takes
+    `rs_k, rs_min, rs_max` right behind qbias and drops the `int rs` in front of the tail (ob, ...); otherwise the two are
+    argument for argument the same.  So a call is
+        x, w, qbias, [rs_k, rs_min, rs_max,] *outs, [relu | act_lo, act_hi,] *ints, [rs,] *tail, stream
+    The wrapper has validated its operands and allocated its outputs; outs are the pointers and integers between qbias and the
+    activation (everything up to the geometry for an entry point without one: act None), ints the geometry in the ABI's order."""
+    pcs = isinstance(rs, ShiftVec)
+    if pcs:
+        name += "_pcs"
+        outs = (_shift_vec(rs, K, x.device, name), rs.lo, rs.hi) + outs
+    fn, a, name = (getattr(lib(), name), (), name) if act is None else _act_call(name, act[1], act[0])
+    _check(fn(x.data_ptr(), w.data_ptr(), qbias.contiguous().data_ptr(), *outs, *a, *ints, *(() if pcs else (int(rs),)), *tail,
+              _stream(x)), name)
+    _note_variant()
+
+
+def _out_hw(H, W, R, S, stride, padding, dilation=(1, 1)):
+    """(P, Q): the output plane of an R x S window over the padded H x W plane (floor mode)."""
+    return ((H + 2 * padding[0] - dilation[0] * (R - 1) - 1) // stride[0] + 1,
+            (W + 2 * padding[1] - dilation[1] * (S - 1) - 1) // stride[1] + 1)
+
+
+def conv2d_i8(xq, wq, qbias, stride, padding, dilation, rs, ob, bitwidth=8):
+    """xq int8 [N,H,W,C] (or [N,C] for Linear), wq int8 [K,R,S,C]; returns fp32 [N,K,P,Q] (or [N,K])."""
+    _need_cuda(xq, torch.int8, "fq_conv2d_i8")
+    _need_cuda(wq, torch.int8, "fq_conv2d_i8")
+    _need_cuda(qbias, torch.float32, "fq_conv2d_i8")
+    linear = xq.dim() == 2
+    if linear:
+        xq = xq[:, None, None, :]
+    N, H, W, C = xq.shape
+    K, R, S, Cw = wq.shape
+    assert C == Cw and xq.is_contiguous() and wq.is_contiguous() and qbias.numel() == K
+    P, Q = _out_hw(H, W, R, S, stride, padding, dilation)
+    y = torch.empty(N, K, P, Q, dtype=torch.float32, device=xq.device)
+    _conv_i8("fq_conv2d_i8", xq, wq, qbias, rs, K, (y.data_ptr(),),
+             (N, H, W, C, K, R, S, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1]), (int(ob), int(bitwidth)))
+    return y.view(N, K) if linear else y
+
+
 def conv2d_i8_resident(xq, wq, qbias, stride, padding, dilation, rs, ob, want_f32, want_i8, relu, clip=None):
     """fq_conv2d_i8_resident: returns (y fp32 [N,K,P,Q] or None, q int8 [N,P,Q,Kpad] or None).  q holds the
     integers before DeQuantity (value = q * 2^-ob), channels zero-padded to a multiple of 16.  clip = (lo, hi): the `_act` entry
@@ -1150,26 +1170,12 @@ def conv2d_i8_resident(xq, wq, qbias, stride, padding, dilation, rs, ob, want_f3
     N, H, W, C = xq.shape
     K, R, S, Cw = wq.shape
     assert C == Cw and xq.is_contiguous() and wq.is_contiguous() and qbias.numel() == K and (want_f32 or want_i8)
-    P = (H + 2 * padding[0] - dilation[0] * (R - 1) - 1) // stride[0] + 1
-    Q = (W + 2 * padding[1] - dilation[1] * (S - 1) - 1) // stride[1] + 1
+    P, Q = _out_hw(H, W, R, S, stride, padding, dilation)
     kpad = pad16(K)
     y = torch.empty(N, K, P, Q, dtype=torch.float32, device=xq.device) if want_f32 else None
     q = torch.empty(N, P, Q, kpad, dtype=torch.int8, device=xq.device) if want_i8 else None
-    if isinstance(rs, ShiftVec):
-        rk = _shift_vec(rs, K, xq.device, "fq_conv2d_i8_resident_pcs")
-        fn, act, what = _act_call("fq_conv2d_i8_resident_pcs", clip, relu)
-        _check(fn(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi,
-                  y.data_ptr() if want_f32 else None, q.data_ptr() if want_i8 else None, kpad,
-                  *act, N, H, W, C, K, R, S, stride[0], stride[1], padding[0], padding[1],
-                  dilation[0], dilation[1], int(ob), _stream(xq)), what)
-        _note_variant()
-        return y, q
-    fn, act, what = _act_call("fq_conv2d_i8_resident", clip, relu)
-    _check(fn(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(),
-              y.data_ptr() if want_f32 else None, q.data_ptr() if want_i8 else None, kpad,
-              *act, N, H, W, C, K, R, S, stride[0], stride[1], padding[0], padding[1],
-              dilation[0], dilation[1], int(rs), int(ob), _stream(xq)), what)
-    _note_variant()
+    _conv_i8("fq_conv2d_i8_resident", xq, wq, qbias, rs, K, (_ptr(y), _ptr(q), kpad),
+             (N, H, W, C, K, R, S, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1]), (int(ob),), (relu, clip))
     return y, q
 
 
@@ -1203,23 +1209,11 @@ def conv2d_i8_stem(x, w_stem, qbias, K, S, stride, padding, ib, rs, ob, relu, cl
     N, C, H, W = x.shape
     R = w_stem.shape[0]
     assert x.is_contiguous() and w_stem.is_contiguous() and tuple(w_stem.shape[1:]) == (STEM_MAX_K, 32) and qbias.numel() == K
-    P = (H + 2 * padding[0] - R) // stride[0] + 1
-    Q = (W + 2 * padding[1] - S) // stride[1] + 1
+    P, Q = _out_hw(H, W, R, S, stride, padding)
     kpad = pad16(K)
     q = torch.empty(N, P, Q, kpad, dtype=torch.int8, device=x.device)
-    if isinstance(rs, ShiftVec):
-        rk = _shift_vec(rs, K, x.device, "fq_conv2d_i8_stem_pcs")
-        fn, act, what = _act_call("fq_conv2d_i8_stem_pcs", clip, relu)
-        _check(fn(x.data_ptr(), w_stem.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi, q.data_ptr(),
-                  kpad, *act, N, C, H, W, K, R, S, stride[0], stride[1], padding[0], padding[1],
-                  int(ib), int(ob), _stream(x)), what)
-        _note_variant()
-        return q
-    fn, act, what = _act_call("fq_conv2d_i8_stem", clip, relu)
-    _check(fn(x.data_ptr(), w_stem.data_ptr(), qbias.contiguous().data_ptr(), q.data_ptr(), kpad,
-              *act, N, C, H, W, K, R, S, stride[0], stride[1], padding[0], padding[1],
-              int(ib), int(rs), int(ob), _stream(x)), what)
-    _note_variant()
+    _conv_i8("fq_conv2d_i8_stem", x, w_stem, qbias, rs, K, (q.data_ptr(), kpad),
+             (N, C, H, W, K, R, S, stride[0], stride[1], padding[0], padding[1], int(ib)), (int(ob),), (relu, clip))
     return q
 
 
@@ -1253,23 +1247,12 @@ def dwconv2d_i8_resident(xq, wq, qbias, stride, padding, rs, ob, relu, clip=None
     R, S, Cw = wq.shape
     C = qbias.numel()
     assert cpad == Cw and xq.is_contiguous() and wq.is_contiguous() and C <= cpad
-    P = (H + 2 * padding[0] - R) // stride[0] + 1
-    Q = (W + 2 * padding[1] - S) // stride[1] + 1
+    P, Q = _out_hw(H, W, R, S, stride, padding)
     if P <= 0 or Q <= 0:
         raise FqError("fq_dwconv2d_i8_resident: the kernel does not fit the padded image")
     q = torch.empty(N, P, Q, cpad, dtype=torch.int8, device=xq.device)
-    if isinstance(rs, ShiftVec):
-        rk = _shift_vec(rs, C, xq.device, "fq_dwconv2d_i8_resident_pcs")
-        fn, act, what = _act_call("fq_dwconv2d_i8_resident_pcs", clip, relu)
-        _check(fn(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi,
-                  q.data_ptr(), cpad, *act, N, H, W, C, R, S, stride[0], stride[1],
-                  padding[0], padding[1], 1, 1, int(ob), _stream(xq)), what)
-    else:
-        fn, act, what = _act_call("fq_dwconv2d_i8_resident", clip, relu)
-        _check(fn(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), q.data_ptr(), cpad,
-                  *act, N, H, W, C, R, S, stride[0], stride[1], padding[0], padding[1], 1, 1,
-                  int(rs), int(ob), _stream(xq)), what)
-    _note_variant()
+    _conv_i8("fq_dwconv2d_i8_resident", xq, wq, qbias, rs, C, (q.data_ptr(), cpad),
+             (N, H, W, C, R, S, stride[0], stride[1], padding[0], padding[1], 1, 1), (int(ob),), (relu, clip))
     return q
 
 
@@ -1310,27 +1293,22 @@ def gconv2d_i8_resident(xq, wq, qbias, K, groups, stride, padding, rs, ob, relu,
     kpad = pad16(K)
     R = int(round(taps ** 0.5))
     assert xq.is_contiguous() and wq.is_contiguous() and kq * 4 == kpad and qbias.numel() == K and R * R == taps
-    P = (H + 2 * padding[0] - R) // stride[0] + 1
-    Q = (W + 2 * padding[1] - R) // stride[1] + 1
+    P, Q = _out_hw(H, W, R, R, stride, padding)
     if P <= 0 or Q <= 0:
         raise FqError("fq_gconv2d_i8_resident: the kernel does not fit the padded image")
     q = torch.empty(N, P, Q, kpad, dtype=torch.int8, device=xq.device)
-    if isinstance(rs, ShiftVec):
-        rk = _shift_vec(rs, K, xq.device, "fq_gconv2d_i8_resident_pcs")
-        fn, act, what = _act_call("fq_gconv2d_i8_resident_pcs", clip, relu)
-        _check(fn(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi,
-                  q.data_ptr(), cpad, kpad, *act, N, H, W, C, K, groups, R, R,
-                  stride[0], stride[1], padding[0], padding[1], 1, 1, int(ob), _stream(xq)), what)
-    else:
-        fn, act, what = _act_call("fq_gconv2d_i8_resident", clip, relu)
-        _check(fn(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), q.data_ptr(), cpad, kpad,
-                  *act, N, H, W, C, K, groups, R, R, stride[0], stride[1], padding[0],
-                  padding[1], 1, 1, int(rs), int(ob), _stream(xq)), what)
-    _note_variant()
+    _conv_i8("fq_gconv2d_i8_resident", xq, wq, qbias, rs, K, (q.data_ptr(), cpad, kpad),
+             (N, H, W, C, K, groups, R, R, stride[0], stride[1], padding[0], padding[1], 1, 1), (int(ob),), (relu, clip))
     return q
 
 
 _INT_BYTES = {torch.int8: 1, torch.int16: 2}
+
+
+def _wide_narrow(shape, device, want_wide, want_narrow):
+    """The two outputs of a resident add: (int16 tensor or None, int8 tensor or None)."""
+    return (torch.empty(shape, dtype=torch.int16, device=device) if want_wide else None,
+            torch.empty(shape, dtype=torch.int8, device=device) if want_narrow else None)
 
 
 def conv2d_i8_add_resident(xq, wq, qbias, stride, padding, dilation, rs, ob, res, g_res, want_wide, g_wide, want_narrow, ib, relu):
@@ -1344,29 +1322,40 @@ def conv2d_i8_add_resident(xq, wq, qbias, stride, padding, dilation, rs, ob, res
     N, H, W, C = xq.shape
     K, R, S, Cw = wq.shape
     assert C == Cw and xq.is_contiguous() and wq.is_contiguous() and res.is_contiguous() and (want_wide or want_narrow)
-    P = (H + 2 * padding[0] - dilation[0] * (R - 1) - 1) // stride[0] + 1
-    Q = (W + 2 * padding[1] - dilation[1] * (S - 1) - 1) // stride[1] + 1
+    P, Q = _out_hw(H, W, R, S, stride, padding, dilation)
     kpad = pad16(K)
     assert tuple(res.shape) == (N, P, Q, kpad), (tuple(res.shape), (N, P, Q, kpad))
-    wide = torch.empty(N, P, Q, kpad, dtype=torch.int16, device=xq.device) if want_wide else None
-    narrow = torch.empty(N, P, Q, kpad, dtype=torch.int8, device=xq.device) if want_narrow else None
-    if isinstance(rs, ShiftVec):
-        rk = _shift_vec(rs, K, xq.device, "fq_conv2d_i8_add_resident_pcs")
-        _check(lib().fq_conv2d_i8_add_resident_pcs(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), rk, rs.lo, rs.hi,
-                                                   res.data_ptr(), _INT_BYTES[res.dtype], int(g_res),
-                                                   wide.data_ptr() if want_wide else None, int(g_wide),
-                                                   narrow.data_ptr() if want_narrow else None, int(ib), 1 if relu else 0, kpad, N, H,
-                                                   W, C, K, R, S, stride[0], stride[1], padding[0], padding[1], dilation[0],
-                                                   dilation[1], int(ob), _stream(xq)), "fq_conv2d_i8_add_resident_pcs")
-        _note_variant()
-        return wide, narrow
-    _check(lib().fq_conv2d_i8_add_resident(xq.data_ptr(), wq.data_ptr(), qbias.contiguous().data_ptr(), res.data_ptr(),
-                                           _INT_BYTES[res.dtype], int(g_res), wide.data_ptr() if want_wide else None, int(g_wide),
-                                           narrow.data_ptr() if want_narrow else None, int(ib), 1 if relu else 0, kpad, N, H, W, C,
-                                           K, R, S, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
-                                           int(rs), int(ob), _stream(xq)), "fq_conv2d_i8_add_resident")
-    _note_variant()
+    wide, narrow = _wide_narrow((N, P, Q, kpad), xq.device, want_wide, want_narrow)
+    _conv_i8("fq_conv2d_i8_add_resident", xq, wq, qbias, rs, K,
+             (res.data_ptr(), _INT_BYTES[res.dtype], int(g_res), _ptr(wide), int(g_wide), _ptr(narrow), int(ib), 1 if relu else 0, kpad),
+             (N, H, W, C, K, R, S, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1]), (int(ob),))
     return wide, narrow
+
+
+def _tail_operands(name, xq, K3, want_wide, want_narrow, w1q, qbias1, shifts):
+    """What block_tail_i8 and block_tail_proj_i8 share behind the validation of their own operands.  The optional next conv1
+    (w1q int8 [C2,1,1,K3], qbias1 fp32 [C2]; C2 = 0 without it), the outputs wide / narrow [N,H,W,K3] and q1 [N,H,W,C2], and the
+    form of the shifts (rs3, [rsp,] rs1 -- the last one conv1's): None when every one is per-tensor, else -- the `_pcs` entry
+    point takes vectors only -- (pointer, lo, hi) for each, a per-tensor neighbour as its cached constant vector (_shift_of),
+    conv1's (None, 1, 1) without a conv1.  Returns wide, narrow, q1, C2, the pointers (w1q, qbias1, q1) or Nones, shifts."""
+    N, H, W, _ = xq.shape
+    C2 = 0
+    if w1q is not None:
+        _need_cuda(w1q, torch.int8, name)
+        _need_cuda(qbias1, torch.float32, name)
+        C2 = int(w1q.shape[0])
+        assert tuple(w1q.shape[1:]) == (1, 1, K3) and w1q.is_contiguous() and qbias1.numel() == C2
+    assert C2 or want_wide or want_narrow
+    wide, narrow = _wide_narrow((N, H, W, K3), xq.device, want_wide, want_narrow)
+    q1 = torch.empty(N, H, W, C2, dtype=torch.int8, device=xq.device) if C2 else None
+    vec = None
+    if any(isinstance(rs, ShiftVec) for rs in shifts):
+        vec = []
+        for rs, K in zip(shifts, (K3,) * (len(shifts) - 1) + (C2,)):
+            v = _shift_of(rs, K, xq.device) if K else None
+            vec.append((_shift_vec(v, K, xq.device, name + "_pcs"), v.lo, v.hi) if K else (None, 1, 1))
+    ptrs = (w1q.data_ptr(), qbias1.contiguous().data_ptr(), q1.data_ptr()) if C2 else (None, None, None)
+    return wide, narrow, q1, C2, ptrs, vec
 
 
 def block_tail_supported(C, K3, C2, rs3, rs1, ob3, g_res, res_bytes, ib):
@@ -1394,36 +1383,19 @@ def block_tail_i8(xq, w3q, qbias3, rs3, ob3, res, g_res, want_wide, g_wide, want
     K3 = int(w3q.shape[0])
     assert tuple(w3q.shape[1:]) == (1, 1, C) and xq.is_contiguous() and w3q.is_contiguous() and res.is_contiguous()
     assert tuple(res.shape) == (N, H, W, K3) and qbias3.numel() == K3
-    C2 = 0
-    if w1q is not None:
-        _need_cuda(w1q, torch.int8, "fq_block_tail_i8")
-        _need_cuda(qbias1, torch.float32, "fq_block_tail_i8")
-        C2 = int(w1q.shape[0])
-        assert tuple(w1q.shape[1:]) == (1, 1, K3) and w1q.is_contiguous() and qbias1.numel() == C2
-    assert C2 or want_wide or want_narrow
-    wide = torch.empty(N, H, W, K3, dtype=torch.int16, device=xq.device) if want_wide else None
-    narrow = torch.empty(N, H, W, K3, dtype=torch.int8, device=xq.device) if want_narrow else None
-    q1 = torch.empty(N, H, W, C2, dtype=torch.int8, device=xq.device) if C2 else None
-    if isinstance(rs3, ShiftVec) or isinstance(rs1, ShiftVec):
-        # per-channel: both shifts as vectors (a per-tensor neighbour as a constant one)
-        v3 = _shift_of(rs3, K3, xq.device)
-        r3 = _shift_vec(v3, K3, xq.device, "fq_block_tail_i8_pcs")
-        v1 = _shift_of(rs1, C2, xq.device) if C2 else None
-        r1 = _shift_vec(v1, C2, xq.device, "fq_block_tail_i8_pcs") if C2 else None
-        _check(lib().fq_block_tail_i8_pcs(xq.data_ptr(), w3q.data_ptr(), qbias3.contiguous().data_ptr(), r3, v3.lo, v3.hi, int(ob3),
-                                          res.data_ptr(), _INT_BYTES[res.dtype], int(g_res), wide.data_ptr() if want_wide else None,
-                                          int(g_wide), narrow.data_ptr() if want_narrow else None, int(ib), 1 if relu else 0,
-                                          w1q.data_ptr() if C2 else None, qbias1.contiguous().data_ptr() if C2 else None, r1,
-                                          v1.lo if C2 else 1, v1.hi if C2 else 1, 1 if relu1 else 0, q1.data_ptr() if C2 else None,
+    wide, narrow, q1, C2, (w1p, b1p, q1p), vec = _tail_operands("fq_block_tail_i8", xq, K3, want_wide, want_narrow, w1q, qbias1,
+                                                                (rs3, rs1))
+    if vec:
+        (r3, lo3, hi3), (r1, lo1, hi1) = vec
+        _check(lib().fq_block_tail_i8_pcs(xq.data_ptr(), w3q.data_ptr(), qbias3.contiguous().data_ptr(), r3, lo3, hi3, int(ob3),
+                                          res.data_ptr(), _INT_BYTES[res.dtype], int(g_res), _ptr(wide), int(g_wide), _ptr(narrow),
+                                          int(ib), 1 if relu else 0, w1p, b1p, r1, lo1, hi1, 1 if relu1 else 0, q1p,
                                           N * H * W, C, K3, C2, _stream(xq)), "fq_block_tail_i8_pcs")
-        _note_variant()
-        return wide, narrow, q1
-    _check(lib().fq_block_tail_i8(xq.data_ptr(), w3q.data_ptr(), qbias3.contiguous().data_ptr(), int(rs3), int(ob3), res.data_ptr(),
-                                  _INT_BYTES[res.dtype], int(g_res), wide.data_ptr() if want_wide else None, int(g_wide),
-                                  narrow.data_ptr() if want_narrow else None, int(ib), 1 if relu else 0,
-                                  w1q.data_ptr() if C2 else None, qbias1.contiguous().data_ptr() if C2 else None, int(rs1),
-                                  1 if relu1 else 0, q1.data_ptr() if C2 else None, N * H * W, C, K3, C2, _stream(xq)),
-           "fq_block_tail_i8")
+    else:
+        _check(lib().fq_block_tail_i8(xq.data_ptr(), w3q.data_ptr(), qbias3.contiguous().data_ptr(), int(rs3), int(ob3),
+                                      res.data_ptr(), _INT_BYTES[res.dtype], int(g_res), _ptr(wide), int(g_wide), _ptr(narrow),
+                                      int(ib), 1 if relu else 0, w1p, b1p, int(rs1), 1 if relu1 else 0, q1p,
+                                      N * H * W, C, K3, C2, _stream(xq)), "fq_block_tail_i8")
     _note_variant()
     return wide, narrow, q1
 
@@ -1451,38 +1423,21 @@ def block_tail_proj_i8(xq, w3q, qbias3, rs3, ob3, xpq, wpq, qbiasp, rsp, obp, st
     assert tuple(w3q.shape[1:]) == (1, 1, C) and tuple(wpq.shape) == (K3, 1, 1, CP) and Np == N
     assert xq.is_contiguous() and w3q.is_contiguous() and xpq.is_contiguous() and wpq.is_contiguous()
     assert qbias3.numel() == K3 and qbiasp.numel() == K3
-    C2 = 0
-    if w1q is not None:
-        _need_cuda(w1q, torch.int8, "fq_block_tail_proj_i8")
-        _need_cuda(qbias1, torch.float32, "fq_block_tail_proj_i8")
-        C2 = int(w1q.shape[0])
-        assert tuple(w1q.shape[1:]) == (1, 1, K3) and w1q.is_contiguous() and qbias1.numel() == C2
-    assert C2 or want_wide or want_narrow
-    wide = torch.empty(N, H, W, K3, dtype=torch.int16, device=xq.device) if want_wide else None
-    narrow = torch.empty(N, H, W, K3, dtype=torch.int8, device=xq.device) if want_narrow else None
-    q1 = torch.empty(N, H, W, C2, dtype=torch.int8, device=xq.device) if C2 else None
-    if isinstance(rs3, ShiftVec) or isinstance(rs1, ShiftVec) or isinstance(rsp, ShiftVec):
-        v3, vp_ = _shift_of(rs3, K3, xq.device), _shift_of(rsp, K3, xq.device)
-        v1 = _shift_of(rs1, C2, xq.device) if C2 else None
-        r3 = _shift_vec(v3, K3, xq.device, "fq_block_tail_proj_i8_pcs")
-        rp = _shift_vec(vp_, K3, xq.device, "fq_block_tail_proj_i8_pcs")
-        r1 = _shift_vec(v1, C2, xq.device, "fq_block_tail_proj_i8_pcs") if C2 else None
-        _check(lib().fq_block_tail_proj_i8_pcs(xq.data_ptr(), w3q.data_ptr(), qbias3.contiguous().data_ptr(), r3, v3.lo, v3.hi, int(ob3),
-                                               xpq.data_ptr(), wpq.data_ptr(), qbiasp.contiguous().data_ptr(), rp, vp_.lo, vp_.hi,
-                                               int(obp), int(stride_p), Hp, Wp, wide.data_ptr() if want_wide else None, int(g_wide),
-                                               narrow.data_ptr() if want_narrow else None, int(ib), 1 if relu else 0,
-                                               w1q.data_ptr() if C2 else None, qbias1.contiguous().data_ptr() if C2 else None, r1,
-                                               v1.lo if C2 else 1, v1.hi if C2 else 1, 1 if relu1 else 0, q1.data_ptr() if C2 else None,
+    wide, narrow, q1, C2, (w1p, b1p, q1p), vec = _tail_operands("fq_block_tail_proj_i8", xq, K3, want_wide, want_narrow, w1q,
+                                                                qbias1, (rs3, rsp, rs1))
+    if vec:
+        (r3, lo3, hi3), (rp, lop, hip), (r1, lo1, hi1) = vec
+        _check(lib().fq_block_tail_proj_i8_pcs(xq.data_ptr(), w3q.data_ptr(), qbias3.contiguous().data_ptr(), r3, lo3, hi3, int(ob3),
+                                               xpq.data_ptr(), wpq.data_ptr(), qbiasp.contiguous().data_ptr(), rp, lop, hip,
+                                               int(obp), int(stride_p), Hp, Wp, _ptr(wide), int(g_wide), _ptr(narrow), int(ib),
+                                               1 if relu else 0, w1p, b1p, r1, lo1, hi1, 1 if relu1 else 0, q1p,
                                                N, H, W, C, K3, C2, CP, _stream(xq)), "fq_block_tail_proj_i8_pcs")
-        _note_variant()
-        return wide, narrow, q1
-    _check(lib().fq_block_tail_proj_i8(xq.data_ptr(), w3q.data_ptr(), qbias3.contiguous().data_ptr(), int(rs3), int(ob3),
-                                       xpq.data_ptr(), wpq.data_ptr(), qbiasp.contiguous().data_ptr(), int(rsp), int(obp),
-                                       int(stride_p), Hp, Wp, wide.data_ptr() if want_wide else None, int(g_wide),
-                                       narrow.data_ptr() if want_narrow else None, int(ib), 1 if relu else 0,
-                                       w1q.data_ptr() if C2 else None, qbias1.contiguous().data_ptr() if C2 else None, int(rs1),
-                                       1 if relu1 else 0, q1.data_ptr() if C2 else None, N, H, W, C, K3, C2, CP, _stream(xq)),
-           "fq_block_tail_proj_i8")
+    else:
+        _check(lib().fq_block_tail_proj_i8(xq.data_ptr(), w3q.data_ptr(), qbias3.contiguous().data_ptr(), int(rs3), int(ob3),
+                                           xpq.data_ptr(), wpq.data_ptr(), qbiasp.contiguous().data_ptr(), int(rsp), int(obp),
+                                           int(stride_p), Hp, Wp, _ptr(wide), int(g_wide), _ptr(narrow), int(ib),
+                                           1 if relu else 0, w1p, b1p, int(rs1), 1 if relu1 else 0, q1p,
+                                           N, H, W, C, K3, C2, CP, _stream(xq)), "fq_block_tail_proj_i8")
     _note_variant()
     return wide, narrow, q1
 
@@ -1493,11 +1448,9 @@ def add_resident(x, gx, y, gy, want_wide, g_wide, want_narrow, ib, relu):
         if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype not in _INT_BYTES:
             raise FqError("fq_add_resident: expected int8 / int16 torch.cuda tensors")
     assert x.shape == y.shape and x.is_contiguous() and y.is_contiguous() and (want_wide or want_narrow)
-    wide = torch.empty(x.shape, dtype=torch.int16, device=x.device) if want_wide else None
-    narrow = torch.empty(x.shape, dtype=torch.int8, device=x.device) if want_narrow else None
+    wide, narrow = _wide_narrow(x.shape, x.device, want_wide, want_narrow)
     _check(lib().fq_add_resident(x.data_ptr(), _INT_BYTES[x.dtype], int(gx), y.data_ptr(), _INT_BYTES[y.dtype], int(gy),
-                                 wide.data_ptr() if want_wide else None, int(g_wide),
-                                 narrow.data_ptr() if want_narrow else None, int(ib), 1 if relu else 0, x.numel(),
+                                 _ptr(wide), int(g_wide), _ptr(narrow), int(ib), 1 if relu else 0, x.numel(),
                                  _stream(x)), "fq_add_resident")
     return wide, narrow
 
@@ -1523,8 +1476,7 @@ def maxpool_i8_nhwc(x, kernel, stride, padding):
     _need_cuda(x, torch.int8, "fq_maxpool_i8_nhwc")
     assert x.dim() == 4 and x.is_contiguous()
     N, H, W, cpad = x.shape
-    P = (H + 2 * padding[0] - kernel[0]) // stride[0] + 1
-    Q = (W + 2 * padding[1] - kernel[1]) // stride[1] + 1
+    P, Q = _out_hw(H, W, kernel[0], kernel[1], stride, padding)
     y = torch.empty(N, P, Q, cpad, dtype=torch.int8, device=x.device)
     _check(lib().fq_maxpool_i8_nhwc(x.data_ptr(), y.data_ptr(), N, H, W, cpad, kernel[0], kernel[1], stride[0], stride[1],
                                     padding[0], padding[1], _stream(x)), "fq_maxpool_i8_nhwc")

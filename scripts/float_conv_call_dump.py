@@ -11,7 +11,6 @@ kernel accepts, two images each.  One line per native call: the function and eve
 message.  The output of the tree before a change of the wrappers is the specification of the tree after it:
 tests/golden/g17_float_conv_calls.txt, compared by tests/test_gpu_float_conv_calls.py.
 """
-import ctypes
 import os
 import sys
 
@@ -19,22 +18,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "pytorch-quantity_amd", "quantity"))
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
 from common.quantity import _native as nat  # noqa: E402
-
-
-class _Recorder(object):
-    """Stands in for the ctypes library: every function called through it is noted as (name, args) and forwarded."""
-
-    def __init__(self, real):
-        self._real, self.calls = real, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._real, name)
-
-        def call(*args):
-            self.calls.append((name, args))
-            return fn(*args)
-        return call
+from native_call_record import Recorder, show_arg  # noqa: E402
 
 
 def _smallest_wino():
@@ -94,7 +80,7 @@ def dump():
     dev = torch.device("cuda")
     ws_ptr, _ = nat.conv_workspace(torch.empty(1, device=dev))                        # allocated before anything is recorded
     lines = []
-    rec = _Recorder(real)
+    rec = Recorder(real)
     nat._lib = rec
     try:
         for label, fn, x, wname, weight, args, shape, forms in cases:
@@ -109,17 +95,9 @@ def dump():
                      ("bad", bad))
 
             def show(a, y):
-                if a is None:
-                    return "null"
-                if isinstance(a, ctypes.c_void_p):
-                    return "stream"
                 if ws_ptr is not None and a == ws_ptr:
                     return "ws"
-                for name, t in named + ((("y", y),) if y is not None else ()):
-                    off = a - t.data_ptr()
-                    if 0 <= off < max(t.numel() * t.element_size(), 1):
-                        return "%s+%d" % (name, off)
-                return repr(a)
+                return show_arg(a, named + ((("y", y),) if y is not None else ()))
 
             table = (
                 ("plain", x, bias, {}),
