@@ -752,6 +752,28 @@ int fq_concat_n_i8_nhwc_supported(const int* C, const int* up, int nsrc);
 int fq_concat_n_i8_nhwc(const fq_cat_src_n* srcs, int nsrc, int8_t* out, int Cpad_out, int N, int H, int W,
                         fq_stream_t stream);
 
+/* Channel shuffle (nn.ChannelShuffle, torch.channel_shuffle) and channel slice (the Slice marker layer, x[:, a:b]) of a resident
+ * int8 NHWC activation, one kernel for both: permuting the integers is permuting the values q * 2^-g, as for the Concat above.
+ *   y[n][h][w][j] = x[n][h][w][c_off + (j mod groups) * (C / groups) + floor(j / groups)]    for 0 <= j < C
+ *                 = 0                                                  for C <= j < Cpad_out, whatever x's padding channels hold
+ * groups == 1 is the slice: the copy of channels [c_off, c_off + C).  c_off == 0 with C the source's width is
+ *   torch.channel_shuffle(x, groups); both at once shuffle a slice.
+ * x: int8 [N][H][W][Cpad_in], 16-byte aligned, Cpad_in % 16 == 0.  c_off and C are BYTE granular: ShuffleNetV2 1.0x splits 116
+ *   channels into 58 + 58, the right half starts at byte 58 of a 128-byte row.
+ * y: int8 [N][H][W][Cpad_out], 16-byte aligned, Cpad_out == pad16(C); it must not overlap x.  Only aligned loads are issued, no
+ *   byte outside [x, x + N H W Cpad_in) is read and none outside [y, y + N H W Cpad_out) is written.
+ * Return codes: FQ_ERR_INVALID_ARG for a null or misaligned pointer with N > 0, N < 0, H < 1, W < 1, C < 1, c_off < 0,
+ *   c_off + C > Cpad_in, groups < 1, C % groups != 0, a wrong Cpad_out and the call with nothing to do (groups == 1, c_off == 0,
+ *   Cpad_in == Cpad_out); FQ_ERR_UNSUPPORTED for Cpad_in % 16 != 0, C > 65536, or a source or an output of 2^31 - 1 bytes or more
+ *   (32-bit element offsets): callers keep the fp32 form there.  N == 0 is FQ_OK without a launch.
+ * Not built: one launch for Concat + shuffle (+ the left slice of the next unit), zero-copy slices (a consumer reading the
+ *   channels in place: the right half's pointer is not 16-byte aligned in general).
+ * fq_shuffle_i8_nhwc_supported: 1 when a source of C_in real channels (stored as pad16(C_in)) with this offset, width and group
+ *   count is taken -- c_off + C <= C_in on top of the rules above (host arithmetic, no GPU needed). */
+int fq_shuffle_i8_nhwc_supported(int C_in, int c_off, int C, int groups);
+int fq_shuffle_i8_nhwc(const int8_t* x, int Cpad_in, int c_off, int8_t* y, int Cpad_out, int C, int groups, int N, int H, int W,
+                       fq_stream_t stream);
+
 /* The tail of a bottleneck block and the head of the next one in ONE kernel (round 4):
  *   NewConv2d.forward of conv3 (1x1, C -> K3; new_quantity_op.py:124-133)  ->  NewAdd.forward with the shortcut (:166-174)
  *   -> nn.ReLU -> the next block's conv1: NewConv2d.forward again (1x1, K3 -> C2, Quantity(ib) on the sum, its own tail and

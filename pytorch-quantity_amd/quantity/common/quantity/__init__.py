@@ -30,6 +30,7 @@ Eltwise = _markers.Eltwise
 Concat = _markers.Concat
 Identity = _markers.Identity
 View = _markers.View
+Slice = _markers.Slice            # (not in the reference: the channel split of a ShuffleNetV2 unit)
 
 # quantize-op modules
 RightShift = _ops.RightShift
@@ -46,7 +47,7 @@ DeQuantity = _ops.DeQuantity
 
 __all__ = [
     "DistributionCollector", "Quantizer", "BitReader", "merge_bn", "walk_dirs", "tid",
-    "Eltwise", "Concat", "Identity", "View",
+    "Eltwise", "Concat", "Identity", "View", "Slice",
     "RightShift", "Sp", "BiasAdd", "NewConv2d", "NewAdd", "NewLinear", "QuanDequan",
     "TestConv", "TestLinear", "Quantity", "DeQuantity",
 ]

@@ -254,6 +254,10 @@ def lib():
     L.fq_concat_n_i8_nhwc_supported.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci), ci]
     L.fq_concat_n_i8_nhwc.restype = ci
     L.fq_concat_n_i8_nhwc.argtypes = [ctypes.POINTER(_CatSrcN), ci, vp, ci, ci, ci, ci, vp]
+    L.fq_shuffle_i8_nhwc_supported.restype = ci
+    L.fq_shuffle_i8_nhwc_supported.argtypes = [ci] * 4
+    L.fq_shuffle_i8_nhwc.restype = ci
+    L.fq_shuffle_i8_nhwc.argtypes = [vp, ci, ci, vp] + [ci] * 6 + [vp]
     L.fq_avgpool_i8_nhwc_supported.restype = ci
     L.fq_avgpool_i8_nhwc_supported.argtypes = [ci] * 7
     L.fq_avgpool_i8_nhwc.restype = ci
@@ -1562,6 +1566,36 @@ def concat_n_i8_nhwc(srcs, out=None):
         _need_cuda(out, torch.int8, "fq_concat_n_i8_nhwc")
         assert tuple(out.shape) == (N, H, W, cpad) and out.is_contiguous()
     _check(lib().fq_concat_n_i8_nhwc(arr, n, out.data_ptr(), cpad, N, H, W, _stream(out)), "fq_concat_n_i8_nhwc")
+    return out
+
+
+def shuffle_supported(c_in, c_off, c, groups):
+    """True when fq_shuffle_i8_nhwc takes a source of c_in real channels (stored as pad16(c_in)), of which channels
+    [c_off, c_off + c) are shuffled in `groups` groups (include/fq.h): c >= 1, c_off >= 0, c_off + c <= c_in, groups >= 1 dividing
+    c, c <= 65536, and not the call with nothing to do.  Pure host arithmetic (no GPU needed)."""
+    return bool(lib().fq_shuffle_i8_nhwc_supported(int(c_in), int(c_off), int(c), int(groups)))
+
+
+def shuffle_i8_nhwc(x_q, c_in, c_off, c, groups, out=None):
+    """fq_shuffle_i8_nhwc.  x_q: int8 [N, H, W, pad16(c_in)] with c_in real channels.  Returns int8 [N, H, W, pad16(c)]:
+    y[..., j] = x_q[..., c_off + (j % groups) * (c // groups) + j // groups] for j < c, the padding channels zero.  groups == 1 is
+    the slice [c_off, c_off + c); c_off == 0 and c == c_in is torch.channel_shuffle.  `out`: write there instead (that shape,
+    dense, 16-byte aligned).  Launches on the current stream and does not synchronise."""
+    _need_cuda(x_q, torch.int8, "fq_shuffle_i8_nhwc")
+    assert x_q.dim() == 4 and x_q.is_contiguous()
+    N, H, W, cpad_in = (int(v) for v in x_q.shape)
+    if cpad_in != pad16(c_in):
+        raise FqError("fq_shuffle_i8_nhwc: a source of %d channels is stored as %d, got %d" % (c_in, pad16(c_in), cpad_in))
+    if int(c_off) + int(c) > int(c_in):
+        raise FqError("fq_shuffle_i8_nhwc: channels [%d, %d) of a source of %d" % (c_off, int(c_off) + int(c), c_in))
+    cpad = pad16(c)
+    if out is None:
+        out = torch.empty(N, H, W, cpad, dtype=torch.int8, device=x_q.device)
+    else:
+        _need_cuda(out, torch.int8, "fq_shuffle_i8_nhwc")
+        assert tuple(out.shape) == (N, H, W, cpad) and out.is_contiguous()
+    _check(lib().fq_shuffle_i8_nhwc(x_q.data_ptr(), cpad_in, int(c_off), out.data_ptr(), cpad, int(c), int(groups), N, H, W,
+                                    _stream(out)), "fq_shuffle_i8_nhwc")
     return out
 
 

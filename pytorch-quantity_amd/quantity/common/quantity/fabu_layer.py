@@ -3,13 +3,14 @@
 
 Drop-in for reference quantity/common/quantity/fabu_layer.py (Eltwise :5-11, Concat :14-20,
 Identity :23-29, View :31-36): same class names, constructor and forward signatures, so pickled
-models and model definitions written against the reference import unchanged.  These layers do no
+models and model definitions written against the reference import unchanged.  `Slice` is this
+project's own (the reference has none): the channel split of a ShuffleNetV2 unit as a module.  These layers do no
 quantisation work themselves; `tools.Reconstruction` swaps Eltwise for `NewAdd`.
 """
 import torch
 from torch import nn
 
-__all__ = ["Eltwise", "Concat", "Identity", "View"]
+__all__ = ["Eltwise", "Concat", "Identity", "View", "Slice"]
 
 
 class _Marker(nn.Module):
@@ -46,3 +47,18 @@ class View(_Marker):
 
     def forward(self, x):
         return x.reshape(x.shape[0], -1).clone()
+
+
+class Slice(_Marker):
+    """Channels [start, stop) of a feature map as a fresh tensor (the channel split at the head of a
+    ShuffleNetV2 unit; a bare ``x[:, a:b]`` is invisible to hooks and an alias of its source)."""
+
+    def __init__(self, start, stop):
+        super(Slice, self).__init__()
+        self.start, self.stop = start, stop
+
+    def forward(self, x):
+        return x[:, self.start:self.stop].clone()
+
+    def extra_repr(self):
+        return "marker, channels [%s, %s)" % (self.start, self.stop)

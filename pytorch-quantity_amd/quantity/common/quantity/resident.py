@@ -190,7 +190,7 @@ def as_f32(x):
 class Plan(object):
     """What one producer emits.  Plain data (pickles with the module)."""
     __slots__ = ("relu", "emit_f32", "emit_int", "narrow_bit", "want_wide", "grid", "resident_add", "defer", "fuse_arg",
-                 "fuse_next", "narrow_to_hbm", "fuse_proj", "depthwise", "up", "grouped", "clip")
+                 "fuse_next", "narrow_to_hbm", "fuse_proj", "depthwise", "up", "grouped", "clip", "perm")
 
     def __init__(self):
         self.relu = False            # the nn.ReLU that consumes this output is fused
@@ -209,6 +209,7 @@ class Plan(object):
         self.up = None               # nearest upsampling taken by enable(concat=True): its factor (with `defer`: the Concat applies it)
         self.grouped = False         # NewConv2d: a grouped layer taken by enable(grouped=True); runs on fq_gconv2d_i8_resident
         self.clip = False            # NewConv2d with `relu`: the fused activation is an nn.ReLU6 (enable(relu6=True)): clipped at 6
+        self.perm = None             # nn.ChannelShuffle / Slice taken by enable(shuffle=True): (c_off, C, groups) of fq_shuffle_i8_nhwc
 
     def __getstate__(self):
         return {k: getattr(self, k) for k in self.__slots__}
@@ -320,6 +321,45 @@ class _AvgPoolWindowResident(_InstanceForward):
             return type(m).forward(m, as_f32(x))
         y = _native.avgpool_i8_nhwc(h.exact, h.shape[1], k, st, pd, m.count_include_pad, plan.narrow_bit - h.grid, plan.relu)
         return QHandle.wide_narrow(h.shape[1], None, None, y, plan.narrow_bit, plan.relu or h.relu_done)
+
+
+def _shuffle_geometry(m, channels):
+    """(c_off, C, groups) of fq_shuffle_i8_nhwc for an nn.ChannelShuffle or a Slice marker that reads `channels` channels, or
+    None: groups that is no positive int or does not divide the channels; start / stop that are no plain ints or do not satisfy
+    0 <= start < stop <= channels."""
+    def plain(v):
+        return type(v) is int
+    if isinstance(m, nn.ChannelShuffle):
+        g = m.groups
+        return (0, int(channels), g) if plain(g) and g >= 1 and channels % g == 0 else None
+    a, b = getattr(m, "start", None), getattr(m, "stop", None)
+    return (a, b - a, 1) if plain(a) and plain(b) and 0 <= a < b <= channels else None
+
+
+class _ShuffleResident(_InstanceForward):
+    """Instance-level forward of an nn.ChannelShuffle between integer layers (enable(shuffle=True)): permuting the channels of
+    the int8 NHWC integers is permuting the values (fq_shuffle_i8_nhwc).  An operand that arrives deferred is materialised first
+    (resident_of).  Whenever a run-time condition fails -- no plan, no int8 exact payload, a geometry other than the planned
+    one -- the module's own forward runs on the fp32 form."""
+
+    def __call__(self, x):
+        m = self.module
+        plan = m.__dict__.get("_resident")
+        h = resident_of(x)
+        geo = None
+        if plan is not None and h is not None and h.exact is not None and h.exact.dtype == torch.int8 and h.exact.dim() == 4:
+            geo = _shuffle_geometry(m, h.shape[1])
+        if geo is None or geo != plan.perm or not _native.shuffle_supported(h.shape[1], *geo):
+            return type(m).forward(m, as_f32(x))
+        c_off, c, g = geo
+        y = _native.shuffle_i8_nhwc(h.exact, h.shape[1], c_off, c, g)
+        narrow = y if (h.narrow is h.exact or h.bit == h.grid) else None
+        return _emit(plan, QHandle.wide_narrow(c, y, h.grid, narrow, h.grid, h.relu_done))
+
+
+class _SliceResident(_ShuffleResident):
+    """Instance-level forward of a Slice marker between integer layers (enable(shuffle=True)): channels [start, stop) of the int8
+    NHWC integers as a tensor of their own, the padding channels zero (fq_shuffle_i8_nhwc with one group)."""
 
 
 def _pool_geometry(m):
@@ -455,6 +495,7 @@ class _Tracer(TorchFunctionMode):
     def __init__(self, avgpool=False):
         super(_Tracer, self).__init__()
         self.avgpool = bool(avgpool)     # enable(avgpool=True): an nn.AvgPool2d output is a traced value
+        self.shuffle_seen = []           # (enable(shuffle=True)) every hooked nn.ChannelShuffle / Slice module, in execution order
         self.relu6_seen = []             # (enable(relu6=True)) every hooked nn.ReLU6 module, in execution order
         self.values = {}             # id(tensor) -> _Value
         self.keep = []               # keeps traced tensors alive so ids are not reused
@@ -477,6 +518,8 @@ class _Tracer(TorchFunctionMode):
         self.calls[module] = self.calls.get(module, 0) + 1
         if isinstance(module, nn.ReLU6) and module not in self.relu6_seen:
             self.relu6_seen.append(module)
+        if self._kind(module) in ("shuffle", "slice") and module not in self.shuffle_seen:
+            self.shuffle_seen.append(module)
         for pos, a in enumerate(args):
             v = self.values.get(id(a)) if isinstance(a, torch.Tensor) else None
             if v is not None:
@@ -504,8 +547,10 @@ class _Tracer(TorchFunctionMode):
             return "avgpool"
         if isinstance(module, nn.Upsample):                 # (hooked only with enable(concat=True))
             return "upsample"
+        if isinstance(module, nn.ChannelShuffle):           # (hooked only with enable(shuffle=True))
+            return "shuffle"
         name = type(module).__name__
-        return {"Concat": "concat", "NewAdd": "add"}.get(name, "contraction")     # (Concat: likewise)
+        return {"Concat": "concat", "NewAdd": "add", "Slice": "slice"}.get(name, "contraction")     # (Concat, Slice: likewise)
 
     def post(self, module, args, output):
         self.depth -= 1
@@ -513,7 +558,7 @@ class _Tracer(TorchFunctionMode):
             return
         kind = self._kind(module)
         src = None
-        if kind in ("relu", "maxpool", "avgpool", "upsample"):     # a value of these kinds exists only behind a traced value
+        if kind in ("relu", "maxpool", "avgpool", "upsample", "shuffle", "slice"):     # a value of these kinds exists only behind a traced value
             if kind == "avgpool" and not self.avgpool:
                 return                                      # its output is an ordinary fp32 tensor
             src = self.values.get(id(args[0])) if args and isinstance(args[0], torch.Tensor) else None
@@ -542,6 +587,7 @@ def _clear(model):
             del m.__dict__["forward"]
     model.__dict__.pop("_fq_resident_enabled", None)
     model.__dict__.pop("_fq_resident_relu6", None)
+    model.__dict__.pop("_fq_resident_shuffle", None)
 
 
 def disable(model):
@@ -555,21 +601,25 @@ def is_enabled(model):
 
 
 _COUNTER = {"contraction": "resident_convs", "add": "resident_adds", "maxpool": "resident_pools", "concat": "resident_concats",
-            "upsample": "resident_upsamples"}
-_FORWARD = {"maxpool": _MaxPoolResident, "concat": _ConcatResident, "upsample": _UpsampleResident}
+            "upsample": "resident_upsamples", "shuffle": "resident_shuffles", "slice": "resident_slices"}
+_FORWARD = {"maxpool": _MaxPoolResident, "concat": _ConcatResident, "upsample": _UpsampleResident, "shuffle": _ShuffleResident,
+            "slice": _SliceResident}
 
 
 class _Planning(object):
     """The plan of one traced forward.  enable() calls the passes below in order; they decide on the trace alone and change
     nothing on the model until install() writes the plans and the instance-level forwards to the modules."""
 
-    def __init__(self, tracer, depthwise, concat, avgpool, grouped, relu6=False, flatten=False):
+    def __init__(self, tracer, depthwise, concat, avgpool, grouped, relu6=False, flatten=False, shuffle=False):
         from .new_quantity_op import NewConv2d, NewAdd
         from .fabu_layer import Concat
         self.conv_type, self.concat_type = NewConv2d, Concat
         self.tracer = tracer
         self.depthwise, self.grouped, self.relu6 = bool(depthwise), bool(grouped), bool(relu6)
         self.relu6_left = {}             # (relu6=True) nn.ReLU6 module that stays torch's -> why
+        self.shuffle = bool(shuffle)
+        self.shuffle_left = {}           # (shuffle=True) nn.ChannelShuffle / Slice module that stays torch's -> why
+        self.perm = {}                   # (shuffle=True) planned nn.ChannelShuffle / Slice module -> (c_off, C, groups)
         self.relu_value = dict((id(c.src), c) for c in tracer.relu_values)
         self.fmt = {}                    # id(effective _Value) -> (bytes, grid)
         self.eff_of = {}                 # id(produced _Value) -> (effective _Value, relu module)
@@ -579,7 +629,7 @@ class _Planning(object):
                 if isinstance(m, (NewAdd, Concat)) and pos < 2:
                     self.operands.setdefault(m, [None, None])[pos] = v
         self.add_resident = set()        # NewAdd modules whose operands arrive as integers
-        self.int8_resident = set()       # nn.MaxPool2d, Concat and nearest-upsampling modules that run on the int8 integers
+        self.int8_resident = set()       # nn.MaxPool2d, Concat, nearest-upsampling, nn.ChannelShuffle and Slice modules that run on the int8 integers
         self.avg_resident = {}           # windowed nn.AvgPool2d that runs on fq_avgpool_i8_nhwc -> (source grid g, consumer bit b)
         self.plans = {}                  # producer module -> Plan
         self.forwards = []               # (module, its instance-level forward)
@@ -597,6 +647,8 @@ class _Planning(object):
             self.summary["resident_grouped"] = 0
         if relu6:
             self.summary["fused_relu6s"] = 0
+        if shuffle:
+            self.summary["resident_shuffles"] = self.summary["resident_slices"] = 0
 
     # ---- what a value is and what a module can do
 
@@ -606,7 +658,7 @@ class _Planning(object):
 
     def effective(self, v):
         """(value the consumers see, fused ReLU / ReLU6 module or None)"""
-        if v.kind != "maxpool" and not v.foreign and len(v.consumers) == 1 and isinstance(v.consumers[0][0], (nn.ReLU, nn.ReLU6)):
+        if v.kind not in ("maxpool", "shuffle", "slice") and not v.foreign and len(v.consumers) == 1 and isinstance(v.consumers[0][0], (nn.ReLU, nn.ReLU6)):
             act = v.consumers[0][0]
             after = self.relu_value.get(id(v))
             if after is not None and (isinstance(act, nn.ReLU) or self.takes_relu6(v)):
@@ -704,6 +756,8 @@ class _Planning(object):
                 self._plan_avgpool_window(v, e)             # (the value itself has no integer format)
             elif v.kind == "concat":
                 f = self._concat_format(v)
+            elif v.kind in ("shuffle", "slice"):
+                f = self._shuffle_format(v)
             else:
                 f = self._add_format(v)
             if f is not None:
@@ -764,6 +818,43 @@ class _Planning(object):
         if not _native.concat_supported([x.shape[1], y.shape[1]], [1, 1]):
             return None
         return fx
+
+    def _shuffle_format(self, v):
+        """`shuffle=True` plans nn.ChannelShuffle and the Slice marker (fabu_layer.Slice, x[:, start:stop]), both served by
+        fq_shuffle_i8_nhwc: a module called once that reads a 4-D int8 activation permutes / copies the integers and hands them on
+        the source's grid; its readers may be convolutions (dense, depthwise, grouped), a Concat, a max-pool, a windowed average
+        pool, another shuffle or slice, or fp32 code.  No ReLU is fused into it (effective): a ReLU behind one reads the fp32
+        form, as behind a max-pool.  Without the argument both are foreign code and their source leaves as fp32.  Left in fp32
+        form (out of scope), each named with its reason by describe(): a NewAdd sum (int16) as the source, a module called twice,
+        `start` / `stop` that are not plain ints with 0 <= start < stop <= C, groups that do not divide C, a non-4-D input, the
+        call with nothing to do (Slice(0, C) of a C-channel source, one group); a Slice has no step and no axis but 1, and a bare
+        chunk, split, slicing or torch.channel_shuffle call stays foreign, as a bare `+` does.  The summary then gains
+        `resident_shuffles` and `resident_slices`."""
+        m = v.producer
+        src = self.fmt.get(id(v.src))
+        why = None
+        if not self.once(m):
+            why = "the module was called more than once"
+        elif src is None:
+            why = "its source has no integer form in this plan (fp32 form)"
+        elif src[0] != 1:
+            why = "its source is a NewAdd sum (int16): only int8 activations are permuted (fp32 form)"
+        elif v.src.shape is None or len(v.src.shape) != 4:
+            why = "its input is not 4-D"
+        else:
+            channels = int(v.src.shape[1])
+            geo = _shuffle_geometry(m, channels)
+            if geo is None:
+                why = ("groups = %r does not divide the %d channels" % (m.groups, channels) if v.kind == "shuffle" else
+                       "start = %r, stop = %r are not plain ints with 0 <= start < stop <= %d" % (m.start, m.stop, channels))
+            elif not _native.shuffle_supported(channels, *geo):
+                why = "fq_shuffle_i8_nhwc does not take (c_off, C, groups) = %r of %d channels (nothing to do, or C > 65536)" % (
+                    geo, channels)
+            else:
+                self.perm[m] = geo
+                return src
+        self.shuffle_left[m] = why
+        return None
 
     def _add_format(self, v):
         """A NewAdd of two integer operands: the exact sum as int16 on the finer of their grids, where that fits."""
@@ -845,6 +936,8 @@ class _Planning(object):
             self.summary["resident_grouped"] += 1
         if v.kind == "upsample":
             plan.up = _upsample_factor(m)
+        if v.kind in ("shuffle", "slice"):
+            plan.perm = self.perm[m]
         self._take(m, plan, relu_mod, _FORWARD.get(v.kind))
         self.summary[_COUNTER[v.kind]] += 1
 
@@ -996,13 +1089,20 @@ class _Planning(object):
             names = dict((m, name) for name, m in model.named_modules())
             model.__dict__["_fq_resident_relu6"] = (self.summary["fused_relu6s"],
                                                     dict((names.get(m, "?"), why) for m, why in self.relu6_left.items()))
+        if self.shuffle:
+            for m in self.tracer.shuffle_seen:
+                if m not in self.plans and m not in self.shuffle_left:
+                    self.shuffle_left[m] = "its input is not the output of a planned layer"
+            names = dict((m, name) for name, m in model.named_modules())
+            model.__dict__["_fq_resident_shuffle"] = dict((names.get(m, "?"), why) for m, why in self.shuffle_left.items())
 
 
-def _trace(model, example_input, concat, avgpool, relu6=False):
+def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False):
     """One forward of `model` in eval mode under the tracer: (tracer, the outputs of that forward)."""
     from .new_quantity_op import NewConv2d, NewLinear, NewAdd
-    from .fabu_layer import Concat
-    planned_types = (NewConv2d, NewLinear, NewAdd, nn.ReLU, nn.MaxPool2d, nn.AvgPool2d) + ((nn.ReLU6,) if relu6 else ())
+    from .fabu_layer import Concat, Slice
+    planned_types = (NewConv2d, NewLinear, NewAdd, nn.ReLU, nn.MaxPool2d, nn.AvgPool2d) + ((nn.ReLU6,) if relu6 else ()) \
+        + ((nn.ChannelShuffle, Slice) if shuffle else ())       # (without the switch both stay foreign code)
     tracer = _Tracer(avgpool)
     hooks = []
     for m in model.modules():
@@ -1027,7 +1127,7 @@ def _trace(model, example_input, concat, avgpool, relu6=False):
 
 
 def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False, grouped=False, relu6=False,
-           flatten=False):
+           flatten=False, shuffle=False):
     """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
     on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
     nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
@@ -1039,15 +1139,16 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
     `concat=True` also plans the Concat marker layer and nearest upsampling by 2 or 4 (_Planning._concat_format, defer_upsamples);
     `avgpool=True` also plans a windowed nn.AvgPool2d between an int8 activation and convolutions (_plan_avgpool_window);
     `relu6=True` also fuses an nn.ReLU6 behind a NewConv2d, as an nn.ReLU is fused (_Planning.takes_relu6);
-    `flatten=True` (with `concat=True`; ValueError without) runs nested Concats as one launch (_Planning.defer_concats)."""
+    `flatten=True` (with `concat=True`; ValueError without) runs nested Concats as one launch (_Planning.defer_concats);
+    `shuffle=True` also plans nn.ChannelShuffle and the Slice marker on the int8 integers (_Planning._shuffle_format)."""
     from .new_quantity_op import QUANTIZE_BIT
     if flatten and not concat:
         raise ValueError("resident.enable(flatten=True) needs concat=True: only planned Concats are flattened")
     _clear(model)
     if QUANTIZE_BIT != 8:
         raise _native.FqError("resident activations are defined for QUANTIZE_BIT = 8")
-    tracer, traced_out = _trace(model, example_input, concat, avgpool, relu6)
-    planning = _Planning(tracer, depthwise, concat, avgpool, grouped, relu6, flatten)
+    tracer, traced_out = _trace(model, example_input, concat, avgpool, relu6, shuffle)
+    planning = _Planning(tracer, depthwise, concat, avgpool, grouped, relu6, flatten, shuffle)
     planning.plan_formats()
     planning.plan_outputs()
     planning.defer_convs()
@@ -1073,9 +1174,11 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
 class _Description(dict):
     """describe()'s {module name: Plan}.  After enable(relu6=True) it also says what became of the nn.ReLU6 modules:
     `fused_relu6s`, how many a producer fused, and `relu6_left`, {module name: why} for each one that stays torch's.  After
-    enable(flatten=True) `flattened_concats` names the Concats that launch nothing of their own."""
+    enable(flatten=True) `flattened_concats` names the Concats that launch nothing of their own.  After enable(shuffle=True)
+    `shuffle_left` is {module name: why} for every hooked nn.ChannelShuffle / Slice that stays torch's."""
     fused_relu6s = 0
     relu6_left = {}
+    shuffle_left = {}
     flattened_concats = ()       # names of the Concats that enable(flatten=True) deferred into their consumer's launch
 
 
@@ -1083,6 +1186,7 @@ def describe(model):
     """{module name: Plan} of the current plan (for logs and tests); see _Description for the ReLU6 report."""
     d = _Description((name, m.__dict__["_resident"]) for name, m in model.named_modules() if "_resident" in m.__dict__)
     d.fused_relu6s, d.relu6_left = model.__dict__.get("_fq_resident_relu6", (0, {}))
+    d.shuffle_left = model.__dict__.get("_fq_resident_shuffle", {})
     d.flattened_concats = tuple(name for name, m in model.named_modules()
                                 if type(m).__name__ == "Concat" and name in d and d[name].defer)
     return d

@@ -6,7 +6,10 @@ on integers), eagerly and as one HIP graph: bit for bit.  The planner decides pe
 on a graph nobody wrote a test for shows here.
 `relu6`: about half of the nn.ReLU modules become nn.ReLU6 (model_fuzz.with_relu6) and the plan is made with every opt-in argument on
 (depthwise, concat, avgpool, grouped, relu6) -- everything on against the fp32 module boundaries.
-usage: recon_fuzz.py [models=40] [seed=1] [odd] [share] [bn] [big] [relu6]"""
+`shuffle`: another generator (tests/shuffle_nets.py: RandomShuffleNet) -- a stem and one to four random steps with Slice markers and
+nn.ChannelShuffle modules: stride-1 units cut anywhere, stride-2 units, a shuffle or a slice alone, overlapping slices joined by a
+Concat, a slice of a slice of a shuffle, group counts over every divisor -- planned with depthwise, concat, flatten and shuffle on.
+usage: recon_fuzz.py [models=40] [seed=1] [odd] [share] [bn] [big] [relu6] [shuffle]"""
 import importlib.util, os, random, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,9 +23,14 @@ from workdir_util import product_workdir
 
 
 EVERYTHING = dict(depthwise=True, concat=True, avgpool=True, grouped=True, relu6=True)
+SHUFFLE = dict(depthwise=True, concat=True, flatten=True, shuffle=True)
 
 
-def build(i, seed, odd=False, share=False, bn=False, relu6=False):
+def build(i, seed, odd=False, share=False, bn=False, relu6=False, shuffle=False):
+    if shuffle:
+        import shuffle_nets
+        model = shuffle_nets.RandomShuffleNet(i, seed).cuda().eval()
+        return model, model.size, model.batch
     model, size, bs, _rng = mf.fold(mf.random_net(i, seed, odd, "cuda", share, bn))
     if relu6:
         mf.with_relu6((model,), i, seed)
@@ -45,20 +53,24 @@ def recon_of(model, twin, data):
         sys.stdout = out
 
 
-def run(n, seed, log=print, odd=False, share=False, bn=False, big=False, variants=None, relu6=False):
+def run(n, seed, log=print, odd=False, share=False, bn=False, big=False, variants=None, relu6=False, shuffle=False):
     bad, seen = 0, {}
     variants = variants if variants is not None else {}
     for i in range(n):
-        model, size, bs = build(i, seed, odd, share, bn, relu6)
+        model, size, bs = build(i, seed, odd, share, bn, relu6, shuffle)
         data = [(torch.randn(bs, model.cin, size, size, device="cuda"), torch.zeros(bs, dtype=torch.long)) for _ in range(2)]
         out = sys.stdout
         try:
             with product_workdir(input_shape="1,%d,%d,%d" % (model.cin, size, size), device="gpu", max_cali_img_num=1):
-                net = recon_of(model, build(i, seed, odd, share, bn, relu6)[0], data)
+                net = recon_of(model, build(i, seed, odd, share, bn, relu6, shuffle)[0], data)
                 x = data[0][0]
                 with torch.no_grad():
                     plain = net(x)
-                    summary = resident.enable(net, x, **(EVERYTHING if relu6 else {}))
+                    summary = resident.enable(net, x, **(SHUFFLE if shuffle else EVERYTHING if relu6 else {}))
+                    if shuffle:
+                        seen["shuffle_modules"] = seen.get("shuffle_modules", 0) + sum(
+                            1 for m in net.modules() if type(m).__name__ in ("ChannelShuffle", "Slice"))
+                        seen["shuffles_left"] = seen.get("shuffles_left", 0) + len(resident.describe(net).shuffle_left)
                     if relu6:
                         seen["relu6_modules"] = seen.get("relu6_modules", 0) + sum(1 for m in net.modules() if type(m) is torch.nn.ReLU6)
                     got = net(x)
@@ -117,9 +129,9 @@ if __name__ == "__main__":
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     odd, share, bn, big = "odd" in sys.argv[3:], "share" in sys.argv[3:], "bn" in sys.argv[3:], "big" in sys.argv[3:]
-    relu6 = "relu6" in sys.argv[3:]
+    relu6, shuffle = "relu6" in sys.argv[3:], "shuffle" in sys.argv[3:]
     variants = {}
-    bad, seen = run(n, seed, odd=odd, share=share, bn=bn, big=big, variants=variants, relu6=relu6)
+    bad, seen = run(n, seed, odd=odd, share=share, bn=bn, big=big, variants=variants, relu6=relu6, shuffle=shuffle)
     if big:
         print("integer kernels at 256 images:", dict(sorted(variants.items())))
-    print("recon_fuzz%s: %d random models (seed %d), %d with a finding; plans in all: %s" % ((" odd" if odd else "") + (" share" if share else "") + (" bn" if bn else "") + (" relu6" if relu6 else ""), n, seed, bad, seen))
+    print("recon_fuzz%s: %d random models (seed %d), %d with a finding; plans in all: %s" % ((" odd" if odd else "") + (" share" if share else "") + (" bn" if bn else "") + (" relu6" if relu6 else "") + (" shuffle" if shuffle else ""), n, seed, bad, seen))
