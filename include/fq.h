@@ -745,7 +745,8 @@ int fq_concat_i8_nhwc(const fq_cat_src* srcs, int nsrc, int8_t* out, int Cpad_ou
  *   more.  N == 0 is FQ_OK without a launch.
  * Not built: zero-copy concatenation (producers storing at a channel offset), more than eight sources per launch.
  * fq_concat_n_i8_nhwc_supported: 1 when the channel counts and factors alone are taken (host arithmetic, no GPU needed).
- * fq_concat_i8_nhwc is unchanged and keeps answering FQ_ERR_UNSUPPORTED for three sources. */
+ * Both functions run one kernel (csrc/fq_concat_i8.hip) built for two and for eight source entries; fq_concat_i8_nhwc keeps
+ * answering FQ_ERR_UNSUPPORTED for three sources. */
 #define FQ_CONCAT_N_MAX_SRC 8
 typedef struct fq_cat_src_n { const int8_t* q; int C; int Cpad; int up; int relu; } fq_cat_src_n;
 int fq_concat_n_i8_nhwc_supported(const int* C, const int* up, int nsrc);

@@ -1,13 +1,16 @@
-// fq_concat_i8_geom.h -- the lane -> (source, offset, mask) arithmetic of the int8 NHWC concatenation / nearest upsampling
-// (fq_concat_i8.hip), kept apart from the kernel so that the same functions compile as host code: scripts/concat_geom_check.cpp
-// walks them over the shapes the GPU tests run and asserts that every load lies inside its source and every output chunk is
-// written exactly once.
+// fq_concat_i8_geom.h -- the lane -> (sources, offsets, masks, loads) arithmetic of the int8 NHWC concatenation / nearest
+// upsampling (fq_concat_i8.hip), kept apart from the kernel so that the same functions compile as host code:
+// scripts/concat_geom_check.cpp walks them over the shapes the GPU tests run and asserts that every load lies inside its source
+// and every output chunk is written exactly once.
 //
 // The output is [N][H][W][Cpad_out] bytes; a CHUNK is 16 consecutive channels of one pixel (one dwordx4 store), CH = Cpad_out / 16
 // chunks per pixel.  Chunk k holds output channels [16k, 16k + 16).  Source i owns output channels [base_i, base_i + C_i),
-// base_0 = 0, base_1 = C_0; relative to the source's pixel row the chunk starts at byte s = 16k - base_i (negative when the
-// chunk begins in the source before).  A lane keeps k for its whole life, so everything below except the pixel is per-lane
-// constant.
+// base_i = C_0 + ... + C_{i-1}; relative to the source's pixel row the chunk starts at byte s = 16k - base_i (negative when the
+// chunk begins in a source before), so one chunk may hold bytes of every source.  A lane keeps k for its whole life, so
+// everything below except the pixel is per-lane constant.
+//
+// Everything is a template on MAXSRC, the number of source entries of the kernel's parameter block: the kernel is instantiated
+// at 2 (fq_concat_i8_nhwc) and at 8 (fq_concat_n_i8_nhwc), and the two-source launch carries two entries, not eight.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -20,16 +23,17 @@ namespace fq {
 
 constexpr int kCatBlock = 256;         // threads per workgroup
 constexpr int kCatMaxBlocks = 2048;    // 256 CUs x 8 workgroups: the lanes walk the rest of the pixels
-constexpr int kCatMaxSrc = 2;
 
 struct CatSrcGeom {
     int C, Cpad;                       // real / stored channels of the source
     int lu;                            // log2 of the nearest-upsampling factor (0, 1, 2), alike on both axes
+    int base;                          // first output channel of the source
 };
 
+template <int MAXSRC>
 struct CatGeom {
     int nsrc;
-    CatSrcGeom s[kCatMaxSrc];
+    CatSrcGeom s[MAXSRC];              // entries at and behind nsrc: C = 0 (nothing of them lies in any chunk)
     int N, H, W;                       // OUTPUT plane; source i is [N][H >> lu][W >> lu][Cpad]
     int Cpad_out, CH;                  // CH = Cpad_out / 16
     unsigned npix;                     // N * H * W
@@ -45,11 +49,11 @@ struct CatPart {
     int whole16;                       // the 16 bytes at row + s are the chunk (s % 16 == 0, lo == 0; hi < 16 only masks the tail)
 };
 
-FQ_CAT_HD CatPart cat_part(const CatGeom& g, int k, int i) {
+template <int MAXSRC>
+FQ_CAT_HD CatPart cat_part(const CatGeom<MAXSRC>& g, int k, int i) {
     CatPart p;
-    const int base = i == 0 ? 0 : g.s[0].C;
     const int C = g.s[i].C;
-    p.s = 16 * k - base;
+    p.s = 16 * k - g.s[i].base;
     p.lo = p.s < 0 ? -p.s : 0;
     p.hi = C - p.s < 16 ? C - p.s : 16;
     p.use = i < g.nsrc && p.lo < p.hi;
@@ -77,29 +81,53 @@ FQ_CAT_HD unsigned cat_dword_mask(int lo, int hi, int t) {
     return below_h & ~below_l;
 }
 
-// pixel index of a source upsampled by 2^lu under output pixel `pix` (row-major over [N][H][W]); lu == 0: the same pixel
-FQ_CAT_HD unsigned cat_src_pix_lu(const CatGeom& g, int lu, unsigned pix) {
-    if (lu == 0) return pix;
-    const unsigned w = pix % (unsigned)g.W, r = pix / (unsigned)g.W;
-    const unsigned h = r % (unsigned)g.H, n = r / (unsigned)g.H;
+// pixel index of a source upsampled by 2^lu under the output pixel (n, h, w)
+template <int MAXSRC>
+FQ_CAT_HD unsigned cat_src_pix(const CatGeom<MAXSRC>& g, int lu, unsigned n, unsigned h, unsigned w) {
     return (n * ((unsigned)g.H >> lu) + (h >> lu)) * ((unsigned)g.W >> lu) + (w >> lu);
 }
-FQ_CAT_HD unsigned cat_src_pix(const CatGeom& g, int i, unsigned pix) { return cat_src_pix_lu(g, g.s[i].lu, pix); }
 
-// How the lanes that own chunk k build it (what tests ask the case list to cover): 0 = one 16-byte load, 1 = aligned dwords
-// (sh == 0) of one source, 2 = byte-shifted dwords of one source, 3 = bytes of both sources (the chunk straddles C_0).
+// every base_i % 16 == 0: each chunk is 16 bytes of exactly one source at a 16-byte-aligned offset (the aligned family)
+template <int MAXSRC>
+FQ_CAT_HD bool cat_aligned(const CatGeom<MAXSRC>& g) {
+    bool a = true;
+    for (int i = 0; i < MAXSRC; ++i) a = a && (i >= g.nsrc || (g.s[i].base & 15) == 0);
+    return a;
+}
+
+// number of sources with a byte in chunk k
+template <int MAXSRC>
+FQ_CAT_HD int cat_owners(const CatGeom<MAXSRC>& g, int k) {
+    int n = 0;
+    for (int i = 0; i < MAXSRC; ++i) n += cat_part(g, k, i).use;
+    return n;
+}
+
+// The chunk is one 16-byte load of source i: nobody else has a byte in it and it starts on a 16-byte boundary of the source's
+// row (hi < 16 only behind the last source: the tail mask).  Both families take this path for such a chunk.
+template <int MAXSRC>
+FQ_CAT_HD bool cat_one16(const CatGeom<MAXSRC>& g, int k, int i) {
+    const CatPart p = cat_part(g, k, i);
+    return p.use && p.whole16 && cat_owners(g, k) == 1;
+}
+
+// How the lanes that own chunk k build it (what tests ask the case list to cover): kCatAligned16 one 16-byte load, kCatDword
+// aligned dwords (sh == 0) of one source, kCatByte byte-shifted dwords of one source, kCatStraddle bytes of two or more sources.
 enum CatClass { kCatAligned16 = 0, kCatDword = 1, kCatByte = 2, kCatStraddle = 3 };
-FQ_CAT_HD int cat_chunk_class(const CatGeom& g, int k) {
-    const CatPart p0 = cat_part(g, k, 0), p1 = cat_part(g, k, 1);
-    if (p0.use && p1.use) return kCatStraddle;
-    const CatPart& p = p0.use ? p0 : p1;
-    if (p.whole16) return kCatAligned16;
-    return p.sh == 0 ? kCatDword : kCatByte;
+template <int MAXSRC>
+FQ_CAT_HD int cat_chunk_class(const CatGeom<MAXSRC>& g, int k) {
+    if (cat_owners(g, k) > 1) return kCatStraddle;
+    for (int i = 0; i < MAXSRC; ++i) {
+        const CatPart p = cat_part(g, k, i);
+        if (p.use) return p.whole16 ? kCatAligned16 : (p.sh == 0 ? kCatDword : kCatByte);
+    }
+    return kCatAligned16;                                   // (not reached: Cpad_out == pad16(sum C), every chunk has an owner)
 }
 
 // The launch: lane gid owns chunk k = gid % CH of the pixels gid / CH, + stride, + 2 stride, ... with stride = threads / CH;
 // lanes whose first pixel is >= stride do nothing (they would repeat another lane's pixels).
-FQ_CAT_HD long cat_blocks(const CatGeom& g) {
+template <int MAXSRC>
+FQ_CAT_HD long cat_blocks(const CatGeom<MAXSRC>& g) {
     long b = ((long)g.npix * g.CH + kCatBlock - 1) / kCatBlock;
     return b > kCatMaxBlocks ? kCatMaxBlocks : b;
 }

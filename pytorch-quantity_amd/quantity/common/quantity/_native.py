@@ -1487,14 +1487,55 @@ def maxpool_i8_nhwc(x, kernel, stride, padding):
     return y
 
 
-def concat_supported(Cs, ups):
-    """True when fq_concat_i8_nhwc takes sources of these channel counts and nearest-upsampling factors (include/fq.h): one or
-    two sources, every C >= 1, every factor 1, 2 or 4.  Pure host arithmetic (no GPU needed)."""
+def _concat_supported(entry, Cs, ups):
     n = len(Cs)
     if n != len(ups) or n < 1:
         return False
     ci = ctypes.c_int * n
-    return bool(lib().fq_concat_i8_nhwc_supported(ci(*[int(c) for c in Cs]), ci(*[int(u) for u in ups]), n))
+    return bool(getattr(lib(), entry + "_supported")(ci(*[int(c) for c in Cs]), ci(*[int(u) for u in ups]), n))
+
+
+def concat_supported(Cs, ups):
+    """True when fq_concat_i8_nhwc takes sources of these channel counts and nearest-upsampling factors (include/fq.h): one or
+    two sources, every C >= 1, every factor 1, 2 or 4.  Pure host arithmetic (no GPU needed)."""
+    return _concat_supported("fq_concat_i8_nhwc", Cs, ups)
+
+
+def concat_n_supported(Cs, ups):
+    """True when fq_concat_n_i8_nhwc takes sources of these channel counts and nearest-upsampling factors (include/fq.h): one to
+    eight sources, every C >= 1, every factor 1, 2 or 4, at most 65536 channels in all.  Pure host arithmetic (no GPU needed)."""
+    return _concat_supported("fq_concat_n_i8_nhwc", Cs, ups)
+
+
+def _concat_operands(entry, struct, srcs, out):
+    """What both concat entry points do in front of the call: srcs = [(q, C, up, relu or None), ...] checked and packed into an
+    array of `struct` (relu only where the struct has the field), the operands' output planes compared, `out` allocated or
+    checked.  Returns (arr, n, out, cpad, N, H, W)."""
+    n = len(srcs)
+    arr = (struct * max(n, 1))()
+    plane, total = None, 0
+    for i, (q, C, up, relu) in enumerate(srcs):
+        _need_cuda(q, torch.int8, entry)
+        assert q.dim() == 4 and q.is_contiguous()
+        here = (int(q.shape[0]), int(q.shape[1]) * int(up), int(q.shape[2]) * int(up))
+        if plane is None:
+            plane = here
+        elif here != plane:
+            raise FqError("%s: the operands give different output planes (%s, %s)" % (entry, plane, here))
+        arr[i].q, arr[i].C, arr[i].Cpad, arr[i].up = q.data_ptr(), int(C), int(q.shape[3]), int(up)
+        if relu is not None:
+            arr[i].relu = 1 if relu else 0
+        total += int(C)
+    if plane is None:
+        raise FqError("%s: no operand" % entry)
+    N, H, W = plane
+    cpad = pad16(total)
+    if out is None:
+        out = torch.empty(N, H, W, cpad, dtype=torch.int8, device=srcs[0][0].device)
+    else:
+        _need_cuda(out, torch.int8, entry)
+        assert tuple(out.shape) == (N, H, W, cpad) and out.is_contiguous()
+    return arr, n, out, cpad, N, H, W
 
 
 def concat_i8_nhwc(srcs, relu, out=None):
@@ -1502,40 +1543,9 @@ def concat_i8_nhwc(srcs, relu, out=None):
     channels each, `up` the nearest-upsampling factor of that operand.  Returns int8 [N, H, W, pad16(sum C)]: the operands one
     behind the other along the channels, the padding channels zero, max(., 0) applied when relu.  `out`: write there instead
     (that shape, dense, 16-byte aligned).  Launches on the current stream and does not synchronise."""
-    n = len(srcs)
-    arr = (_CatSrc * max(n, 1))()
-    plane, total = None, 0
-    for i, (q, C, up) in enumerate(srcs):
-        _need_cuda(q, torch.int8, "fq_concat_i8_nhwc")
-        assert q.dim() == 4 and q.is_contiguous()
-        here = (int(q.shape[0]), int(q.shape[1]) * int(up), int(q.shape[2]) * int(up))
-        if plane is None:
-            plane = here
-        elif here != plane:
-            raise FqError("fq_concat_i8_nhwc: the operands give different output planes (%s, %s)" % (plane, here))
-        arr[i].q, arr[i].C, arr[i].Cpad, arr[i].up = q.data_ptr(), int(C), int(q.shape[3]), int(up)
-        total += int(C)
-    if plane is None:
-        raise FqError("fq_concat_i8_nhwc: no operand")
-    N, H, W = plane
-    cpad = pad16(total)
-    if out is None:
-        out = torch.empty(N, H, W, cpad, dtype=torch.int8, device=srcs[0][0].device)
-    else:
-        _need_cuda(out, torch.int8, "fq_concat_i8_nhwc")
-        assert tuple(out.shape) == (N, H, W, cpad) and out.is_contiguous()
+    arr, n, out, cpad, N, H, W = _concat_operands("fq_concat_i8_nhwc", _CatSrc, [(q, C, up, None) for q, C, up in srcs], out)
     _check(lib().fq_concat_i8_nhwc(arr, n, out.data_ptr(), cpad, 1 if relu else 0, N, H, W, _stream(out)), "fq_concat_i8_nhwc")
     return out
-
-
-def concat_n_supported(Cs, ups):
-    """True when fq_concat_n_i8_nhwc takes sources of these channel counts and nearest-upsampling factors (include/fq.h): one to
-    eight sources, every C >= 1, every factor 1, 2 or 4, at most 65536 channels in all.  Pure host arithmetic (no GPU needed)."""
-    n = len(Cs)
-    if n != len(ups) or n < 1:
-        return False
-    ci = ctypes.c_int * n
-    return bool(lib().fq_concat_n_i8_nhwc_supported(ci(*[int(c) for c in Cs]), ci(*[int(u) for u in ups]), n))
 
 
 def concat_n_i8_nhwc(srcs, out=None):
@@ -1543,28 +1553,7 @@ def concat_n_i8_nhwc(srcs, out=None):
     real channels each, `up` the nearest-upsampling factor of that operand and `relu` whether max(., 0) is applied to ITS bytes.
     Returns int8 [N, H, W, pad16(sum C)]: the operands one behind the other along the channels, the padding channels zero.
     `out`: write there instead (that shape, dense, 16-byte aligned).  Launches on the current stream and does not synchronise."""
-    n = len(srcs)
-    arr = (_CatSrcN * max(n, 1))()
-    plane, total = None, 0
-    for i, (q, C, up, relu) in enumerate(srcs):
-        _need_cuda(q, torch.int8, "fq_concat_n_i8_nhwc")
-        assert q.dim() == 4 and q.is_contiguous()
-        here = (int(q.shape[0]), int(q.shape[1]) * int(up), int(q.shape[2]) * int(up))
-        if plane is None:
-            plane = here
-        elif here != plane:
-            raise FqError("fq_concat_n_i8_nhwc: the operands give different output planes (%s, %s)" % (plane, here))
-        arr[i].q, arr[i].C, arr[i].Cpad, arr[i].up, arr[i].relu = q.data_ptr(), int(C), int(q.shape[3]), int(up), 1 if relu else 0
-        total += int(C)
-    if plane is None:
-        raise FqError("fq_concat_n_i8_nhwc: no operand")
-    N, H, W = plane
-    cpad = pad16(total)
-    if out is None:
-        out = torch.empty(N, H, W, cpad, dtype=torch.int8, device=srcs[0][0].device)
-    else:
-        _need_cuda(out, torch.int8, "fq_concat_n_i8_nhwc")
-        assert tuple(out.shape) == (N, H, W, cpad) and out.is_contiguous()
+    arr, n, out, cpad, N, H, W = _concat_operands("fq_concat_n_i8_nhwc", _CatSrcN, [(q, C, up, bool(relu)) for q, C, up, relu in srcs], out)
     _check(lib().fq_concat_n_i8_nhwc(arr, n, out.data_ptr(), cpad, N, H, W, _stream(out)), "fq_concat_n_i8_nhwc")
     return out
 

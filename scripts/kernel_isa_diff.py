@@ -26,6 +26,9 @@ MOVED = [
     (r"\(anonymous namespace\)::(?:Dwf|Gf)?NoStat\b", "NoStat"),            # the five NoStat of the float convolutions -> fq::NoStat
     (r"\(anonymous namespace\)::(?:Dwf|Gf)HistTag\b", "HistTag"),           # -> fq::HistTag
     (r"\(anonymous namespace\)::(?:Dwf|Gf)StatArgs\b", "ProducerStatArgs"), # -> fq::ProducerStatArgs
+    # the two concat kernels became the MAXSRC = 8 and MAXSRC = 2 instantiations of one template
+    (r"concat_n_i8_kernel<(\w+), (\w+)>\(signed char\*, fq::CatNParams\)", r"concat_i8_kernel<8, \1, \2>(signed char*, fq::CatParams<8>)"),
+    (r"concat_i8_kernel<(true|false), (\w+)>\(signed char\*, fq::CatParams\)", r"concat_i8_kernel<2, \1, \2>(signed char*, fq::CatParams<2>)"),
 ]
 
 

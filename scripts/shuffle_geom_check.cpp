@@ -1,5 +1,5 @@
 // Host check of the channel shuffle / slice kernel's address arithmetic (csrc/fq_shuffle_i8_geom.h), after the pattern of
-// concat_n_geom_check.cpp: every address a lane may touch -- a 16-byte stage load, its LDS destination, an LDS or global byte
+// concat_geom_check.cpp: every address a lane may touch -- a 16-byte stage load, its LDS destination, an LDS or global byte
 // read, a 16-byte store -- lies inside its tensor and is aligned, every output byte is written exactly once, and every output
 // byte comes from the channel the rule names (bytes j >= C from nowhere: they are zero).
 //   c++ -O2 -std=c++17 -o shuffle_geom_check scripts/shuffle_geom_check.cpp      (tests add -fsanitize=address,undefined)

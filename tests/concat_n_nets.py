@@ -242,7 +242,7 @@ def check_net(nat, tag, device):
     return on
 
 
-# ---------------------------------------------------------------- the walker's classification (scripts/concat_n_geom_check.cpp)
+# ---------------------------------------------------------------- the walker's classification (scripts/concat_geom_check.cpp)
 KINDS = ("aligned16", "dword", "byte", "straddle")
 
 
@@ -258,7 +258,7 @@ def class_rows(lines):
 
 
 def check_paths_reached(rows):
-    """Through the geometry header's own classification (catn_chunk_class): the case list reaches one 16-byte load, aligned
+    """Through the geometry header's own classification (cat_chunk_class): the case list reaches one 16-byte load, aligned
     dwords, byte-shifted dwords and chunks of two or more sources, each once without and once with an upsampled source; an
     aligned case holds 16-byte chunks only."""
     assert set(rows) == set(case_arg(c) for c in KERNEL_CASES)

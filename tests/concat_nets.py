@@ -25,7 +25,9 @@ KERNEL_CASES = TWO_SOURCE_CASES + ONE_SOURCE_CASES
 
 
 def case_arg(case):
-    return ",".join(str(v) for v in case)
+    """The case as scripts/concat_geom_check.cpp reads it: N,H,W/C0,C1/up0,up1, one source as N,H,W/C0/up0."""
+    N, H, W, c0, c1, u0, u1 = case
+    return "%d,%d,%d/%d,%d/%d,%d" % case if c1 else "%d,%d,%d/%d/%d" % (N, H, W, c0, u0)
 
 
 def conv(cin, cout, k, ib, ob, stride=1, padding=0, seed=0):

@@ -176,9 +176,9 @@ REFUSALS = [
        prod(512, 256, 256, 64), I31),
     _r("cat_src", "fq_concat_i8_nhwc", (32, 256, 256, 1, 1024, 1, 1, 16, 1), "fq_concat_i8.hip: fq_concat_i8_nhwc", "N*(H/up)*(W/up)*Cpad_src",
        prod(32, 256, 256, 1024), I31),
-    _r("catn_out", "fq_concat_n_i8_nhwc", (512, 256, 256, 32, 32, 1, 32, 32, 1), "fq_concat_n_i8.hip: fq_concat_n_i8_nhwc", "N*H*W*Cpad_out",
+    _r("catn_out", "fq_concat_n_i8_nhwc", (512, 256, 256, 32, 32, 1, 32, 32, 1), "fq_concat_i8.hip: fq_concat_n_i8_nhwc", "N*H*W*Cpad_out",
        prod(512, 256, 256, 64), I31),
-    _r("catn_src", "fq_concat_n_i8_nhwc", (32, 256, 256, 1, 1024, 1, 1, 16, 1), "fq_concat_n_i8.hip: fq_concat_n_i8_nhwc",
+    _r("catn_src", "fq_concat_n_i8_nhwc", (32, 256, 256, 1, 1024, 1, 1, 16, 1), "fq_concat_i8.hip: fq_concat_n_i8_nhwc",
        "N*(H/up)*(W/up)*Cpad_src", prod(32, 256, 256, 1024), I31),
     _r("bt_mk3", "fq_block_tail_i8", (1 << 23, 64, 128, 0), "fq_block_tail_i8.hip: block_tail_dispatch", "M*K3", (1 << 23) * 128, I30),
     _r("btp_mk3", "fq_block_tail_proj_i8", (128, 256, 256, 64, 128, 0, 64, 1), "fq_block_tail_i8.hip: block_tail_proj_dispatch", "M*K3",
@@ -308,7 +308,7 @@ GPU_CASES = [
     _g("cat_top", "fq_concat_i8_nhwc", (520, 254, 254, 20, 2, 44, 1), "top", "fq_concat_i8.hip: fq_concat_i8_nhwc", "N*H*W*Cpad_out",
        prod(520, 254, 254, 64), I31, prod(520, 254, 254, 64), prod(520, 254, 254, 64) + prod(520, 127, 127, 32) + prod(520, 254, 254, 48),
        ragged=(("C0", 20, 16),)),
-    _g("catn_top", "fq_concat_n_i8_nhwc", (520, 254, 254, 20, 2, 3, 1, 41, 1), "top", "fq_concat_n_i8.hip: fq_concat_n_i8_nhwc",
+    _g("catn_top", "fq_concat_n_i8_nhwc", (520, 254, 254, 20, 2, 3, 1, 41, 1), "top", "fq_concat_i8.hip: fq_concat_n_i8_nhwc",
        "N*H*W*Cpad_out", prod(520, 254, 254, 64), I31, prod(520, 254, 254, 64),
        prod(520, 254, 254, 64) + prod(520, 127, 127, 32) + prod(520, 254, 254, 16) + prod(520, 254, 254, 48),
        ragged=(("C0", 20, 16), ("C0 + C1", 23, 16))),
@@ -359,8 +359,8 @@ GPU_CASES = [
 # walker program (scripts/) -> its arguments for the top row of the same name: the first and the last 4096 pixels of the launch,
 # walked on the host before the row ran on a device (tests/test_size_guards_cpu.py runs them)
 WALKER_ROWS = {
-    "cat_top": ("concat_geom_check.cpp", ["window=4096", "520,254,254,20,44,2,1"]),
-    "catn_top": ("concat_n_geom_check.cpp", ["window=4096", "520,254,254/20,3,41/2,1,1"]),
+    "cat_top": ("concat_geom_check.cpp", ["window=4096", "maxsrc=2", "520,254,254/20,44/2,1"]),
+    "catn_top": ("concat_geom_check.cpp", ["window=4096", "520,254,254/20,3,41/2,1,1"]),
     "avgi_top": ("avgpool_geom_check.cpp", ["window=65536", "4160,127,127,19,3,3,1,1,1,1"]),
     "dwf_top": ("dwconv_f32_geom_check.cpp", ["window=4096", "128,520,127,127,3,1,1"]),
     "gf_top": ("gconv_f32_geom_check.cpp", ["window=2048", "1109,5,4,12,127,127,3,1,1"]),

@@ -1,7 +1,7 @@
 """resident.enable(..., concat=True, flatten=True) on a box without a GPU: the tracer, the plan, the handles and the module glue
 run for real; the kernel entry points are doubles (tests/native_doubles.py, concat_doubles.py, avgpool_doubles.py and
 concat_n_doubles.py, the rule of include/fq.h in torch).  Every comparison is exact.  The N-source kernel's address arithmetic
-is walked on the host over the GPU tests' shape list (scripts/concat_n_geom_check.cpp), and the byte accounting of
+is walked on the host over the GPU tests' shape list (scripts/concat_geom_check.cpp), and the byte accounting of
 scripts/concat_flat_cost.py is held against the closed form."""
 import copy
 import io
@@ -215,13 +215,13 @@ def test_concat_n_supported_is_host_arithmetic():
 
 # ---------------------------------------------------------------- 3. the kernel's address arithmetic
 def test_kernel_address_arithmetic_stays_inside_its_tensors(tmp_path):
-    """csrc/fq_concat_n_i8_geom.h holds the kernel's lane -> (sources, offsets, masks, loads) functions and compiles as host
-    code: scripts/concat_n_geom_check.cpp walks every lane of every launch and exits non-zero on a load outside its source, an
+    """csrc/fq_concat_i8_geom.h holds the kernel's lane -> (sources, offsets, masks, loads) functions and compiles as host
+    code: scripts/concat_geom_check.cpp walks every lane of every launch and exits non-zero on a load outside its source, an
     unaligned load, a byte that is not the byte the index rule names, an output chunk written twice or not at all, or an aligned
     launch that holds anything but 16-byte loads -- over its built-in list and over the GPU tests' shape list.  The list reaches
     each path (16-byte, aligned dwords, byte-shifted dwords, chunks of two or more sources) without and with an upsampled source."""
-    exe = str(tmp_path / "concat_n_geom_check")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "scripts", "concat_n_geom_check.cpp")])
+    exe = str(tmp_path / "concat_geom_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "scripts", "concat_geom_check.cpp")])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.startswith("ok,"), out.stdout + out.stderr
     out = subprocess.run([exe] + [nn_.case_arg(c) for c in nn_.KERNEL_CASES], capture_output=True, text=True)

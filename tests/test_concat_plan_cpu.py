@@ -235,6 +235,7 @@ def test_kernel_address_arithmetic_stays_inside_its_tensors(tmp_path):
     subprocess.check_call(["c++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "scripts", "concat_geom_check.cpp")])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.startswith("ok,"), out.stdout + out.stderr
-    out = subprocess.run([exe] + [cn.case_arg(c) for c in cn.KERNEL_CASES], capture_output=True, text=True)
-    lines = out.stdout.splitlines()
-    assert out.returncode == 0 and lines[-1].startswith("ok,") and len(lines) == len(cn.KERNEL_CASES) + 1, out.stdout + out.stderr
+    for limit in ("maxsrc=2", "maxsrc=8"):          # the two-source entry point's instantiation, and the N-source one's on the same cases
+        out = subprocess.run([exe, limit] + [cn.case_arg(c) for c in cn.KERNEL_CASES], capture_output=True, text=True)
+        lines = out.stdout.splitlines()
+        assert out.returncode == 0 and lines[-1].startswith("ok,") and len(lines) == len(cn.KERNEL_CASES) + 1, out.stdout + out.stderr
