@@ -4,9 +4,8 @@
 // (NewLinear.forward) run Quantity -> fp32 conv over integer-valued tensors -> RightShift -> BiasAdd
 // -> Sp -> DeQuantity as 7+ separate passes.  Here:
 //
-//   quantize_i8_nhwc_kernel   x fp32 NCHW -> int8 NHWC (clamp(rint(x * 2^ib))), channels zero-padded
-//                             to a multiple of 16.  HBM bound: 4 B read + 1 B written per element.
-//   conv2d_i8_kernel          implicit GEMM  D[k_out][pixel] = sum_{r,s,c} W[k][r][s][c] * X[n][ih][iw][c]
+//   (fq_quantize_i8.hip)      x fp32 NCHW -> int8 NHWC, channels zero-padded to a multiple of 16: the input of everything here
+//   conv2d_i8_kernel        implicit GEMM  D[k_out][pixel] = sum_{r,s,c} W[k][r][s][c] * X[n][ih][iw][c]
 //                             on v_mfma_i32_32x32x32_i8 (int32 accumulation: exact, where the
 //                             reference's fp32 conv is exact only below 2^24), with the whole tail
 //                             (shift, round half away, bias, saturate, dequantise) fused into the
@@ -28,8 +27,10 @@
 //                             (fq_resident.h); integer tail where the host proved it equal to the fp32 chain.
 //   workgroup order           1-D grid decoded so that all output-channel tiles of a pixel tile run on one XCD
 //                             (conv_tile_of): the activation tile is fetched into that XCD's L2 once.
-//   quantize_i8_unfold_w*     stem layers outside fq_conv2d_i8_stem's limits (fq_stem.hip): kernel width folded
-//                             into the channel axis.
+//   linear_i8_wave_kernel     a 1x1 plane with an fp32 output (NewLinear): one small workgroup per 32 x 32 tile, no LDS staging.
+//
+// The file reads in three parts: the kernels; fq_conv_i8_select.h, the pure function that picks one of them with its template
+// integers, grid and LDS (walked on the host by scripts/conv_i8_select_check.cpp); validation and the one launch path.
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -1232,430 +1233,6 @@ __global__ __launch_bounds__(kConvBlock) void conv3x3_i8_c64_kernel(const int8_t
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// ---- fp32 NCHW -> int8 NHWC with Quantity fused (new_quantity_op.py:52-58) -----------------------
-// q8 (one element): fq_int_tail.h
-
-// block = (64 hw) x (64 c) tile of one image.  Each thread loads a 4(c) x 4(hw) patch with four
-// 16-byte loads along hw, quantises, and writes the patch transposed (4 dwords of 4 channels) into an
-// LDS tile [hw][c]; the tile is then read back 16 channels at a time and stored with 16-byte stores.
-// kVec = false: scalar loads for planes whose rows are not 16-byte aligned (HW % 4 != 0).
-template <bool kVec>
-__global__ __launch_bounds__(256) void quantize_i8_nhwc_kernel(const float* __restrict__ x, int8_t* __restrict__ y, int C, int HW,
-                                                               int Cpad, float scale) {
-    constexpr int RS = 17;                                // LDS row stride in dwords (64 c bytes + 4 pad)
-    __shared__ unsigned tile[64 * RS];                    // [hw][c / 4]
-    const int n = blockIdx.z, hw0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-    const int tid = threadIdx.x;
-    const float* __restrict__ src = x + (long)n * C * HW;
-    const int hwg = tid & 15, cg = tid >> 4;              // 16 hw groups of 4, 16 channel groups of 4
-    const int hw = hw0 + 4 * hwg;
-    float v[4][4];                                        // [channel i][hw e]
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = c0 + 4 * cg + i;
-        const bool c_ok = c < C;
-        if (kVec) {
-            const bool ok = c_ok && hw < HW;              // HW % 4 == 0: a group is all in or all out
-            const float4 f = *reinterpret_cast<const float4*>(ok ? src + (long)c * HW + hw : src);
-            v[i][0] = ok ? f.x : 0.0f; v[i][1] = ok ? f.y : 0.0f; v[i][2] = ok ? f.z : 0.0f; v[i][3] = ok ? f.w : 0.0f;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[i][e] = (c_ok && hw + e < HW) ? src[(long)c * HW + hw + e] : 0.0f;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const unsigned packed = q8(v[0][e], scale) | (q8(v[1][e], scale) << 8) | (q8(v[2][e], scale) << 16) |
-                                (q8(v[3][e], scale) << 24);
-        tile[(4 * hwg + e) * RS + cg] = packed;
-    }
-    __syncthreads();
-    // store: thread -> (hw = tid >> 2, 16 channels = tid & 3)
-    const int shw = tid >> 2, cq = tid & 3;
-    const int ohw = hw0 + shw, oc = c0 + 16 * cq;
-    if (ohw < HW && oc < Cpad) {
-        const unsigned* row = &tile[shw * RS + 4 * cq];
-        int8_t* dst = y + ((long)n * HW + ohw) * Cpad + oc;
-        if (oc + 16 <= Cpad && (Cpad & 15) == 0) {
-            uint4 o; o.x = row[0]; o.y = row[1]; o.z = row[2]; o.w = row[3];
-            *reinterpret_cast<uint4*>(dst) = o;
-        } else {
-#pragma unroll
-            for (int d = 0; d < 4; ++d)
-                if (oc + 4 * d < Cpad) *reinterpret_cast<unsigned*>(dst + 4 * d) = row[d];
-        }
-    }
-}
-
-// C <= 4 (the image going into the stem convolution), Cpad == 16: one pixel per thread -- C coalesced
-// plane reads, one 16-byte store of [c0 c1 c2 c3 0 ... 0].
-__global__ __launch_bounds__(256) void quantize_i8_nhwc_smallc_kernel(const float* __restrict__ x, int8_t* __restrict__ y, int C,
-                                                                      int HW, long total_pixels, float scale) {
-    long i = (long)blockIdx.x * 256 + threadIdx.x;
-    const long stride = (long)gridDim.x * 256;
-    for (; i < total_pixels; i += stride) {
-        const long n = i / HW;
-        const int hw = (int)(i - n * HW);
-        const float* __restrict__ src = x + n * C * HW + hw;
-        unsigned packed = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (c < C) packed |= q8(src[(long)c * HW], scale) << (8 * c);
-        uint4 o; o.x = packed; o.y = 0; o.z = 0; o.w = 0;
-        *reinterpret_cast<uint4*>(y + i * 16) = o;
-    }
-}
-
-// Stem layers (C <= 4, e.g. 7x7 stride-2 on RGB): channel padding to 16 would waste 13/16 of every
-// MFMA.  Instead the kernel width is folded into the channel axis: y[n][ih][q][s*C + c] =
-// Quantity(x[n][c][ih][q*stride_w - pad_w + s*dil_w]) (zero outside the image / beyond S*C), Cpad2 bytes
-// per output column q.  The convolution then runs with S = 1, stride_w = 1, pad_w = 0 over width Q and
-// "channels" Cpad2: an R x 1 kernel with R * Cpad2 reduction bytes instead of R * S * 16.
-__global__ __launch_bounds__(256) void quantize_i8_unfold_w_kernel(const float* __restrict__ x, int8_t* __restrict__ y, int C, int H,
-                                                                   int W, int S, int stride_w, int pad_w, int dil_w, int Q,
-                                                                   int Cpad2, long total, float scale) {
-    long i = (long)blockIdx.x * 256 + threadIdx.x;
-    const long stride = (long)gridDim.x * 256;
-    for (; i < total; i += stride) {                      // i = (n*H + ih)*Q + q
-        const int q = (int)(i % Q);
-        const long nih = i / Q;
-        const int ih = (int)(nih % H);
-        const long n = nih / H;
-        const float* __restrict__ src = x + (n * C * H + ih) * (long)W;     // + c*H*W + iw
-        int8_t* dst = y + i * Cpad2;
-        const int iw0 = q * stride_w - pad_w;
-        for (int b0 = 0; b0 < Cpad2; b0 += 4) {           // one dword (4 folded channels) at a time
-            unsigned packed = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int f = b0 + e;                      // folded channel = s*C + c
-                const int s_ = f / C, c = f - s_ * C;
-                const int iw = iw0 + s_ * dil_w;
-                if (s_ < S && (unsigned)iw < (unsigned)W) packed |= q8(src[(long)c * H * W + iw], scale) << (8 * e);
-            }
-            *reinterpret_cast<unsigned*>(dst + b0) = packed;
-        }
-    }
-}
-
-// The common stem (C <= 4 channels, S <= 8 taps, S*C <= 32 folded channels): C is a template parameter and
-// the tap loop is fully unrolled, so every folded-channel index is a compile-time constant -- no division per
-// element, the 32 output bytes are assembled in registers and leave as two 16-byte stores.  Neighbouring
-// threads (q, q+1) read overlapping input columns, which the L1 absorbs.
-template <int C>
-__global__ __launch_bounds__(256) void quantize_i8_unfold_w_small_kernel(const float* __restrict__ x, int8_t* __restrict__ y, int H, int W,
-                                                                         int S, int stride_w, int pad_w, int dil_w, int Q, int Cpad2,
-                                                                         long total, float scale) {
-    long i = (long)blockIdx.x * 256 + threadIdx.x;
-    const long stride = (long)gridDim.x * 256;
-    const long plane = (long)H * W;
-    for (; i < total; i += stride) {                      // i = (n*H + ih)*Q + q
-        const int q = (int)(i % Q);
-        const long nih = i / Q;
-        const int ih = (int)(nih % H);
-        const long n = nih / H;
-        const float* __restrict__ src = x + (n * C * H + ih) * (long)W;     // + c*H*W + iw
-        const int iw0 = q * stride_w - pad_w;
-        unsigned out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) {
-            const int iw = iw0 + s_ * dil_w;
-            const bool ok = s_ < S && (unsigned)iw < (unsigned)W;
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const int f = s_ * C + c;                  // compile-time after unrolling
-                const float v = ok ? src[c * plane + iw] : 0.0f;
-                out[f >> 2] |= q8(v, scale) << (8 * (f & 3));
-            }
-        }
-        int8_t* dst = y + i * Cpad2;
-        uint4 o0; o0.x = out[0]; o0.y = out[1]; o0.z = out[2]; o0.w = out[3];
-        *reinterpret_cast<uint4*>(dst) = o0;
-        if (Cpad2 > 16) {
-            uint4 o1; o1.x = out[4]; o1.y = out[5]; o1.z = out[6]; o1.w = out[7];
-            *reinterpret_cast<uint4*>(dst + 16) = o1;
-        }
-    }
-}
-
-// HW == 1 (Linear input [N][F]): layouts coincide, plain element-wise with channel padding
-__global__ __launch_bounds__(256) void quantize_i8_rows_kernel(const float* __restrict__ x, int8_t* __restrict__ y, int C, int Cpad,
-                                                               long rows, float scale) {
-    long i = (long)blockIdx.x * 256 + threadIdx.x;
-    const long total = rows * Cpad, stride = (long)gridDim.x * 256;
-    for (; i < total; i += stride) {
-        const long rrow = i / Cpad;
-        const int c = (int)(i - rrow * Cpad);
-        float v = c < C ? x[rrow * C + c] : 0.0f;
-        float q = rintf(v * scale);
-        q = q < -128.0f ? -128.0f : (q > 127.0f ? 127.0f : q);
-        y[i] = (int8_t)(int)q;
-    }
-}
-
-}  // namespace fq
-
-using namespace fq;
-
-extern "C" int fq_quantize_i8_nhwc(const float* x_nchw, int8_t* y_nhwc, int N, int C, int HW, int Cpad, int ib,
-                                   fq_stream_t stream) {
-    if (N < 0 || C <= 0 || HW < 0 || Cpad < C || (Cpad & 3) || ib < -120 || ib > 120) return FQ_ERR_INVALID_ARG;
-    if (N == 0 || HW == 0) return FQ_OK;
-    if (!x_nchw || !y_nhwc) return FQ_ERR_INVALID_ARG;
-    if (reinterpret_cast<uintptr_t>(y_nhwc) & 3u) return FQ_ERR_INVALID_ARG;
-    hipStream_t st = as_stream(stream);
-    const float scale = ldexpf(1.0f, ib);
-    if (HW == 1) {
-        const long total = (long)N * Cpad;
-        long g = (total + 255) / 256;
-        if (g > kCUs * 16) g = kCUs * 16;
-        hipLaunchKernelGGL(quantize_i8_rows_kernel, dim3((unsigned)g), dim3(256), 0, st, x_nchw, y_nhwc, C, Cpad, (long)N, scale);
-    } else if (C <= 4 && Cpad == 16 && (reinterpret_cast<uintptr_t>(y_nhwc) & 15u) == 0) {
-        const long total = (long)N * HW;
-        long g = (total + 255) / 256;
-        if (g > kCUs * 32) g = kCUs * 32;
-        hipLaunchKernelGGL(quantize_i8_nhwc_smallc_kernel, dim3((unsigned)g), dim3(256), 0, st, x_nchw, y_nhwc, C, HW, total, scale);
-    } else {
-        if (N > 65535) return FQ_ERR_UNSUPPORTED;
-        dim3 grid((HW + 63) / 64, (Cpad + 63) / 64, N);
-        const bool vec = (HW % 4 == 0) && ((reinterpret_cast<uintptr_t>(x_nchw) & 15u) == 0);
-        if (vec)
-            hipLaunchKernelGGL(quantize_i8_nhwc_kernel<true>, grid, dim3(256), 0, st, x_nchw, y_nhwc, C, HW, Cpad, scale);
-        else
-            hipLaunchKernelGGL(quantize_i8_nhwc_kernel<false>, grid, dim3(256), 0, st, x_nchw, y_nhwc, C, HW, Cpad, scale);
-    }
-    FQ_LAUNCH_CHECK();
-    return FQ_OK;
-}
-
-extern "C" int fq_quantize_i8_unfold_w(const float* x_nchw, int8_t* y, int N, int C, int H, int W, int S, int stride_w,
-                                       int pad_w, int dil_w, int Cpad2, int ib, fq_stream_t stream) {
-    if (N < 0 || C <= 0 || H <= 0 || W <= 0 || S <= 0 || stride_w <= 0 || pad_w < 0 || dil_w <= 0 || ib < -120 || ib > 120)
-        return FQ_ERR_INVALID_ARG;
-    if (Cpad2 < S * C || (Cpad2 & 15)) return FQ_ERR_INVALID_ARG;
-    const int Q = (W + 2 * pad_w - dil_w * (S - 1) - 1) / stride_w + 1;
-    if (Q <= 0) return FQ_ERR_INVALID_ARG;
-    if (N == 0) return FQ_OK;
-    if (!x_nchw || !y || (reinterpret_cast<uintptr_t>(y) & 15u)) return FQ_ERR_INVALID_ARG;
-    const long total = (long)N * H * Q;
-    long g = (total + 255) / 256;
-    if (g > kCUs * 32) g = kCUs * 32;
-    const float scale = ldexpf(1.0f, ib);
-    hipStream_t st = as_stream(stream);
-    if (C <= 4 && S <= 8 && S * C <= 32 && Cpad2 <= 32) {
-        switch (C) {
-            case 1: hipLaunchKernelGGL(quantize_i8_unfold_w_small_kernel<1>, dim3((unsigned)g), dim3(256), 0, st, x_nchw, y, H, W, S,
-                                       stride_w, pad_w, dil_w, Q, Cpad2, total, scale); break;
-            case 2: hipLaunchKernelGGL(quantize_i8_unfold_w_small_kernel<2>, dim3((unsigned)g), dim3(256), 0, st, x_nchw, y, H, W, S,
-                                       stride_w, pad_w, dil_w, Q, Cpad2, total, scale); break;
-            case 3: hipLaunchKernelGGL(quantize_i8_unfold_w_small_kernel<3>, dim3((unsigned)g), dim3(256), 0, st, x_nchw, y, H, W, S,
-                                       stride_w, pad_w, dil_w, Q, Cpad2, total, scale); break;
-            default: hipLaunchKernelGGL(quantize_i8_unfold_w_small_kernel<4>, dim3((unsigned)g), dim3(256), 0, st, x_nchw, y, H, W, S,
-                                        stride_w, pad_w, dil_w, Q, Cpad2, total, scale); break;
-        }
-    } else {
-        hipLaunchKernelGGL(quantize_i8_unfold_w_kernel, dim3((unsigned)g), dim3(256), 0, st, x_nchw, y, C, H, W, S, stride_w, pad_w,
-                           dil_w, Q, Cpad2, total, scale);
-    }
-    FQ_LAUNCH_CHECK();
-    return FQ_OK;
-}
-
-namespace fq {
-
-// FQ_CONV_XCD=0 keeps the plain 2-D grid (A/B timing)
-static ConvParams xcd_order(dim3& grid, const ConvParams& p0) {
-    static const bool on = [] { const char* e = getenv("FQ_CONV_XCD"); return !(e && e[0] == '0'); }();
-    ConvParams p = p0;
-    p.xcd_kt = 0;
-    p.tiles_m = (int)grid.x;
-    if (on && grid.y > 1 && (long)((grid.x + 7) / 8) * 8 * grid.y < 0x7fffffffL) {
-        p.xcd_kt = (int)grid.y;
-        grid = dim3(((grid.x + 7) / 8) * 8 * grid.y, 1);
-    }
-    return p;
-}
-
-template <int TK, int STAGES>
-static void launch_conv_dma_stages(dim3 grid, hipStream_t st, const int8_t* x, const int8_t* w, const float* qbias, float* y,
-                                   int8_t* q, const ConvParams& p0) {
-    const ConvParams p = xcd_order(grid, p0);
-#define FQ_DMA(OUT)                                                                                                      \
-    do {                                                                                                                 \
-        if (p.rs_k) hipLaunchKernelGGL((conv2d_i8_dma_kernel<TK, (OUT) | kOutPcs, STAGES>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p); \
-        else hipLaunchKernelGGL((conv2d_i8_dma_kernel<TK, OUT, STAGES>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p); \
-    } while (0)
-    if (p.res) FQ_DMA(kOutI8 | kOutAdd);
-    else if (y && q) FQ_DMA(kOutF32 | kOutI8);
-    else if (q) FQ_DMA(kOutI8);
-    else FQ_DMA(kOutF32);
-#undef FQ_DMA
-}
-
-template <int TK>
-static void launch_conv_dma(dim3 grid, hipStream_t st, const int8_t* x, const int8_t* w, const float* qbias, float* y,
-                            int8_t* q, const ConvParams& p) {
-    // A ring of 3 takes the DMA latency off the per-step critical path (one wave's step: 1 960 -> 1 700 cycles) but
-    // needs 96 / 72 KB of LDS, i.e. one workgroup fewer per CU: it pays exactly when the launch cannot put a
-    // second workgroup on the CUs anyway (the 7x7 layers at batch 128, most layers at small batch) and costs
-    // 20-50 % otherwise (measured per layer, scripts/conv_bench.py with FQ_CONV_STAGES=2/3).
-    static const int stages_env = [] { const char* e = getenv("FQ_CONV_STAGES"); return e ? atoi(e) : 0; }();
-    const bool three = stages_env ? stages_env == 3 : (long)grid.x * grid.y <= kCUs;
-    if (three) launch_conv_dma_stages<TK, 3>(grid, st, x, w, qbias, y, q, p);
-    else launch_conv_dma_stages<TK, 2>(grid, st, x, w, qbias, y, q, p);
-    note_conv_variant(three ? kVarDma3 : kVarDma2, TK);
-}
-
-template <int TK, int kPath>
-static void launch_conv_tile(dim3 grid, hipStream_t st, const int8_t* x, const int8_t* w, const float* qbias, float* y,
-                             int8_t* q, const ConvParams& p0) {
-    const ConvParams p = xcd_order(grid, p0);
-    note_conv_variant(kPath == kPathC128 ? kVarTileC128 : (kPath == kPathC64 ? kVarTileC64 : kVarTileGeneral), TK);
-    // (kOutResEarly -- the residual requested behind the first K-step's operand loads -- is kept in the kernel as a template flag
-    //  and NOT instantiated: measured twice in round 4, the second time without the scratch traffic that spoilt the first, it is
-    //  slower everywhere inside the network at 256 images: 86 -> 97 us on the 28 x 28 tail, 63.6 -> 74.5 on the 14 x 14 ones,
-    //  38.8 -> 41.6 at 7 x 7; 333 -> 374 us on the 56 x 56 tail from HBM.  The burst of 32 KB per workgroup ahead of the other
-    //  resident workgroups' operand requests delays THEIR matrix work by more than it saves this one.)
-#define FQ_TILE(OUT)                                                                                                     \
-    do {                                                                                                                 \
-        if (p.rs_k) hipLaunchKernelGGL((conv2d_i8_kernel<TK, kPath, (OUT) | kOutPcs>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p); \
-        else hipLaunchKernelGGL((conv2d_i8_kernel<TK, kPath, OUT>), grid, dim3(kConvBlock), 0, st, x, w, qbias, y, q, p); \
-    } while (0)
-    if (p.res) FQ_TILE(kOutI8 | kOutAdd);
-    else if (y && q) FQ_TILE(kOutF32 | kOutI8);
-    else if (q) FQ_TILE(kOutI8);
-    else FQ_TILE(kOutF32);
-#undef FQ_TILE
-}
-
-// Dynamic LDS a kernel of the halo family may ask for and still run two workgroups per CU (160 KB): half the CU's LDS minus what
-// the kernel declares STATICALLY beside its dynamic carve-out -- sLH[2][TK] ints, the merged clamp bounds of the integer tail --
-// and the allocation granule.  (The budget used to ignore the static part; no shape fell into the gap, but one layout change
-// could have halved the occupancy silently.)
-// (pcs: a kOutPcs kernel also declares sRs[TK], each channel's shift)
-static constexpr size_t two_per_cu_lds(int tk, bool pcs = false) { return (size_t)80 * 1024 - 64 - (size_t)(pcs ? 12 : 8) * tk; }
-
-// the halo form of the 3 x 3 layers; false when the layer is not of that shape
-template <int TK>
-static bool launch_conv_halo(hipStream_t st, const int8_t* x, const int8_t* w, const float* qbias, float* y, int8_t* q,
-                             const ConvParams& p0) {
-    static const bool on = [] { const char* e = getenv("FQ_CONV_HALO"); return !(e && e[0] == '0'); }();
-    if (!on || p0.R != 3 || p0.S != 3 || p0.stride_h != 1 || p0.stride_w != 1 || p0.pad_h != 1 || p0.pad_w != 1 || p0.dil_h != 1 ||
-        p0.dil_w != 1 || (p0.C & 127) || (p0.K % TK) || p0.res)
-        return false;
-    static const int st_env = [] { const char* e = getenv("FQ_HALO_STAGES"); return e ? atoi(e) : 0; }();
-    const bool pcs = p0.rs_k != nullptr;
-    static const int np_env = [] { const char* e = getenv("FQ_HALO_NP"); return e ? atoi(e) : 0; }();
-    // 256-pixel tiles on eight waves (conv3x3_i8_halo8_kernel): FQ_HALO8=0 keeps the 128-pixel form
-    static const int eight = [] { const char* e = getenv("FQ_HALO8"); return e ? atoi(e) : 1; }();
-    if (eight && !np_env && (eight > 1 || (long)((p0.M + 255) / 256) * (p0.K / TK) >= kCUs)) {
-        HaloParams hp8;
-        hp8.slab_rows = (2 * 128 + 2 + 2 * p0.W + 7) & ~7;
-        hp8.total_pixels = p0.N * p0.H * p0.W;
-        const size_t fixed8 = (size_t)TK * 8 + 128 + (size_t)hp8.slab_rows * 128;
-        const int stages8 = st_env ? st_env : 2;
-        const size_t lds8 = (size_t)stages8 * TK * 128 + fixed8;
-        if (lds8 <= two_per_cu_lds(TK, pcs) && (stages8 == 2 || stages8 == 3)) {
-            dim3 grid8((unsigned)(((long)p0.M + 255) / 256), (unsigned)(p0.K / TK));
-            const ConvParams p8 = xcd_order(grid8, p0);
-#define FQ_HALO8_K(OUT, STG)                                                                                             \
-    do {                                                                                                                 \
-        auto k = conv3x3_i8_halo8_kernel<TK, OUT, STG>;                                                                  \
-        static bool lds_ok[kMaxDevices] = {};                                                                            \
-        if (!ensure_dynamic_lds(reinterpret_cast<const void*>(k), 80 * 1024, lds_ok)) return false;                      \
-        hipLaunchKernelGGL(k, grid8, dim3(2 * kConvBlock), lds8, st, x, w, qbias, y, q, p8, hp8);                        \
-    } while (0)
-#define FQ_HALO8_S(OUT) do { if (stages8 == 3) FQ_HALO8_K(OUT, 3); else FQ_HALO8_K(OUT, 2); } while (0)
-#define FQ_HALO8(OUT) do { if (pcs) FQ_HALO8_S((OUT) | kOutPcs); else FQ_HALO8_S(OUT); } while (0)
-            if (y && q) FQ_HALO8(kOutF32 | kOutI8);
-            else if (q) FQ_HALO8(kOutI8);
-            else FQ_HALO8(kOutF32);
-#undef FQ_HALO8
-#undef FQ_HALO8_S
-#undef FQ_HALO8_K
-            note_conv_variant(kVarHalo8, TK);
-            return true;
-        }
-    }
-    // 128-pixel tiles.  (FQ_HALO_NP=2: 256-pixel tiles, two sub-tiles per wave -- bit-exact, fewer LDS reads and barriers per
-    // MFMA, and 20-35 % SLOWER on ResNet-50's layers at 256 images: 48.7 vs 39.9 us on 256 -> 256 @14x14.)
-    const int np = np_env ? np_env : 1;
-    HaloParams hp;
-    hp.slab_rows = (128 * np + 2 + 2 * p0.W + 7) & ~7;
-    hp.total_pixels = p0.N * p0.H * p0.W;
-    const size_t fixed = (size_t)TK * 8 + 128 + (size_t)hp.slab_rows * 128;
-    const int stages = st_env ? st_env : ((size_t)3 * TK * 128 + fixed <= two_per_cu_lds(TK, pcs) ? 3 : 2);
-    const size_t lds = (size_t)stages * TK * 128 + fixed;
-    if (lds > two_per_cu_lds(TK, pcs) || (stages != 2 && stages != 3) || (np != 1 && np != 2)) return false;   // two workgroups per CU
-    dim3 grid((unsigned)(((long)p0.M + 128 * np - 1) / (128 * np)), (unsigned)(p0.K / TK));
-    const ConvParams p = xcd_order(grid, p0);
-#define FQ_HALO_K(OUT, STG, NPX)                                                                                         \
-    do {                                                                                                                 \
-        auto k = conv3x3_i8_halo_kernel<TK, OUT, STG, NPX>;                                                              \
-        static bool lds_ok[kMaxDevices] = {};                                                                            \
-        if (!ensure_dynamic_lds(reinterpret_cast<const void*>(k), 80 * 1024, lds_ok)) return false;                      \
-        hipLaunchKernelGGL(k, grid, dim3(kConvBlock), lds, st, x, w, qbias, y, q, p, hp);                                \
-    } while (0)
-#define FQ_HALO_S(OUT)                                                                                                   \
-    do {                                                                                                                 \
-        if (np == 2) { if (stages == 3) FQ_HALO_K(OUT, 3, 2); else FQ_HALO_K(OUT, 2, 2); }                               \
-        else { if (stages == 3) FQ_HALO_K(OUT, 3, 1); else FQ_HALO_K(OUT, 2, 1); }                                      \
-    } while (0)
-#define FQ_HALO(OUT) do { if (pcs) FQ_HALO_S((OUT) | kOutPcs); else FQ_HALO_S(OUT); } while (0)
-    if (y && q) FQ_HALO(kOutF32 | kOutI8);
-    else if (q) FQ_HALO(kOutI8);
-    else FQ_HALO(kOutF32);
-#undef FQ_HALO
-#undef FQ_HALO_S
-#undef FQ_HALO_K
-    note_conv_variant(kVarHalo, TK);
-    return true;
-}
-
-static bool launch_conv_c64(hipStream_t st, const int8_t* x, const int8_t* w, const float* qbias, float* y, int8_t* q,
-                            const ConvParams& p0) {
-    static const bool on = [] { const char* e = getenv("FQ_CONV_C64_HALO"); return !(e && e[0] == '0'); }();
-    if (!on || p0.R != 3 || p0.S != 3 || p0.stride_h != 1 || p0.stride_w != 1 || p0.pad_h != 1 || p0.pad_w != 1 || p0.dil_h != 1 ||
-        p0.dil_w != 1 || p0.C != 64 || p0.K > 64 || p0.res)
-        return false;
-    C64Params cp;
-    cp.slab_rows = (130 + 2 * p0.W + 15) & ~15;
-    cp.total_pixels = p0.N * p0.H * p0.W;
-    cp.tiles = (p0.M + kTP - 1) / kTP;
-    static const bool xcd_order = [] { const char* e = getenv("FQ_C64_XCD"); return !(e && e[0] == '0'); }();
-    cp.xcd_chunk = xcd_order ? (cp.tiles + 7) / 8 : 0;
-    const size_t lds = (size_t)9 * 64 * 64 + 64 * 8 + 64 + (size_t)kTP * 80 + (size_t)2 * cp.slab_rows * 64;
-    const bool pcs = p0.rs_k != nullptr;
-    if (lds > two_per_cu_lds(64, pcs)) return false;       // two workgroups per CU
-    ConvParams p = p0;
-    p.xcd_kt = 0; p.tiles_m = cp.tiles;
-    static const int per_cu = [] { const char* e = getenv("FQ_C64_WG_PER_CU"); return e ? atoi(e) : 2; }();
-    unsigned grid = (unsigned)(kCUs * per_cu);
-    if ((long)grid > cp.tiles) grid = (unsigned)cp.tiles;
-#define FQ_C64_S(OUT)                                                                                                    \
-    do {                                                                                                                 \
-        auto k = conv3x3_i8_c64_kernel<OUT>;                                                                             \
-        static bool lds_ok[kMaxDevices] = {};                                                                            \
-        if (!ensure_dynamic_lds(reinterpret_cast<const void*>(k), 80 * 1024, lds_ok)) return false;                      \
-        hipLaunchKernelGGL(k, dim3(grid), dim3(kConvBlock), lds, st, x, w, qbias, y, q, p, cp);                          \
-    } while (0)
-#define FQ_C64(OUT) do { if (pcs) FQ_C64_S((OUT) | kOutPcs); else FQ_C64_S(OUT); } while (0)
-    if (y && q) FQ_C64(kOutF32 | kOutI8);
-    else if (q) FQ_C64(kOutI8);
-    else FQ_C64(kOutF32);
-#undef FQ_C64
-#undef FQ_C64_S
-    note_conv_variant(kVarC64Halo, 64);
-    return true;
-}
-
-struct FusedAdd {                        // residual operand and outputs of a fused NewAdd (res == nullptr: none)
-    const void* res = nullptr;
-    int res_bytes = 0;
-    int16_t* wide = nullptr;
-    AddResParams ap = {};
-};
-
 // A linear layer (NewLinear: N x C activations, K x C weights, fp32 [N][K] out) as one small workgroup per 32 x 32 output tile
 // (round 5).  The tiled kernels give a 256 x 1000 classifier 32 workgroups that each walk the whole reduction through LDS and
 // barriers: 24 us for 0.5 GMAC.  Here both operand fragments come straight from L2 into the MFMA's registers (a row of either
@@ -1731,10 +1308,115 @@ __global__ __launch_bounds__(64 * kLinWaves) void linear_i8_wave_kernel(const in
     }
 }
 
+}  // namespace fq
+
+// ---- which kernel: a pure function of geometry, wanted outputs and switches ---------------------------------------------------
+#include "fq_conv_i8_select.h"
+
+// ---- validation and launch ------------------------------------------------------------------------------------------------------
+namespace fq {
+
+// the selector's own copies of what it shares with the kernels
+static_assert(sel::kCUs == kCUs && sel::kTP == kTP && sel::kConvBlock == kConvBlock && sel::kLinWaves == kLinWaves);
+static_assert(sel::kVarC64Halo == kVarC64Halo && sel::kVarHalo8 == kVarHalo8 && sel::kVarHalo == kVarHalo && sel::kVarDma2 == kVarDma2 &&
+              sel::kVarDma3 == kVarDma3 && sel::kVarTileC128 == kVarTileC128 && sel::kVarTileC64 == kVarTileC64 &&
+              sel::kVarTileGeneral == kVarTileGeneral && sel::kVarLinearWave == kVarLinearWave);
+static_assert(sel::kOutF32 == kOutF32 && sel::kOutI8 == kOutI8 && sel::kOutAdd == kOutAdd && sel::kOutPcs == kOutPcs &&
+              sel::kPathGeneral == kPathGeneral && sel::kPathC128 == kPathC128 && sel::kPathC64 == kPathC64);
+
+// the FQ_* switches of this dispatch, read once per process (the only getenv of this file)
+static const sel::ConvSwitches& conv_switches() {
+    static const sel::ConvSwitches s = sel::read_conv_switches([](const char* name) -> const char* { return getenv(name); });
+    return s;
+}
+
+// Run-time integers to template integers: pick(f, Ints<a, b>{}, v, Ints<c, d, e>{}, w) calls f.template operator()<V, W>() for the
+// listed V == v and W == w and returns what f returns; false when a value is not in its list.  The lists ARE the set of
+// instantiated kernels: every combination of them and nothing else.
+template <int...> struct Ints {};
+template <int... Done, class F>
+static bool pick(F&& f) { return f.template operator()<Done...>(); }
+template <int... Done, class F, int... Vs, class... Rest>
+static bool pick(F&& f, Ints<Vs...>, int v, Rest... rest) {
+    bool r = false;
+    (void)((v == Vs && ((r = pick<Done..., Vs>(f, rest...)), true)) || ...);
+    return r;
+}
+// kOut of (y, q, per-channel shift), and with the fused add (the register-staged and the LDS-DMA kernel only)
+using OutBits = Ints<kOutF32, kOutI8, kOutF32 | kOutI8, kOutF32 | kOutPcs, kOutI8 | kOutPcs, kOutF32 | kOutI8 | kOutPcs>;
+using OutBitsAdd = Ints<kOutF32, kOutI8, kOutF32 | kOutI8, kOutI8 | kOutAdd, kOutF32 | kOutPcs, kOutI8 | kOutPcs, kOutF32 | kOutI8 | kOutPcs,
+                        kOutI8 | kOutAdd | kOutPcs>;
+using TileRows = Ints<64, 128>;
+using Ring = Ints<2, 3>;
+
+// A kernel that needs the dynamic-LDS attribute: set once per kernel and device (ensure_dynamic_lds); false when the runtime
+// refuses it -- nothing was launched, the dispatcher asks the selector for the next family.
+template <auto kKernel, class... Args>
+static bool launch_dyn_lds(const sel::ConvChoice& c, hipStream_t st, Args... args) {
+    static bool lds_ok[kMaxDevices] = {};
+    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(kKernel), 80 * 1024, lds_ok)) return false;
+    hipLaunchKernelGGL(kKernel, dim3(c.grid_x, c.grid_y), dim3(c.block), c.lds, st, args...);
+    return true;
+}
+
+// The one launch path: the kernel template of the choice's family at the choice's template integers, grid, block and LDS.
+static bool launch_conv(const sel::ConvChoice& c, hipStream_t st, const int8_t* x, const int8_t* w, const float* qbias, float* y,
+                        int8_t* q, ConvParams p) {
+    p.xcd_kt = c.xcd_kt;
+    p.tiles_m = c.tiles_m;
+    const dim3 grid(c.grid_x, c.grid_y), block(c.block);
+    switch (c.family) {
+        case sel::kFamC64Halo: {
+            const C64Params cp{c.slab_rows, c.total_pixels, c.tiles, c.xcd_chunk};
+            return pick([&]<int kOut>() { return launch_dyn_lds<conv3x3_i8_c64_kernel<kOut>>(c, st, x, w, qbias, y, q, p, cp); },
+                        OutBits{}, c.out);
+        }
+        case sel::kFamHalo: {
+            const HaloParams hp{c.slab_rows, c.total_pixels};
+            if (c.variant == kVarHalo8)
+                return pick([&]<int TK, int ST, int kOut>() {
+                    return launch_dyn_lds<conv3x3_i8_halo8_kernel<TK, kOut, ST>>(c, st, x, w, qbias, y, q, p, hp);
+                }, TileRows{}, c.tk, Ring{}, c.stages, OutBits{}, c.out);
+            return pick([&]<int TK, int ST, int NP, int kOut>() {
+                return launch_dyn_lds<conv3x3_i8_halo_kernel<TK, kOut, ST, NP>>(c, st, x, w, qbias, y, q, p, hp);
+            }, TileRows{}, c.tk, Ring{}, c.stages, Ints<1, 2>{}, c.np, OutBits{}, c.out);
+        }
+        case sel::kFamDma:
+            return pick([&]<int TK, int ST, int kOut>() {
+                hipLaunchKernelGGL((conv2d_i8_dma_kernel<TK, kOut, ST>), grid, block, 0, st, x, w, qbias, y, q, p);
+                return true;
+            }, TileRows{}, c.tk, Ring{}, c.stages, OutBitsAdd{}, c.out);
+        case sel::kFamTile:
+            // (kOutResEarly -- the residual requested behind the first K-step's operand loads -- is kept in the kernel as a template flag
+            //  and NOT instantiated: measured twice in round 4, the second time without the scratch traffic that spoilt the first, it is
+            //  slower everywhere inside the network at 256 images: 86 -> 97 us on the 28 x 28 tail, 63.6 -> 74.5 on the 14 x 14 ones,
+            //  38.8 -> 41.6 at 7 x 7; 333 -> 374 us on the 56 x 56 tail from HBM.  The burst of 32 KB per workgroup ahead of the other
+            //  resident workgroups' operand requests delays THEIR matrix work by more than it saves this one.)
+            return pick([&]<int TK, int kPath, int kOut>() {
+                hipLaunchKernelGGL((conv2d_i8_kernel<TK, kPath, kOut>), grid, block, 0, st, x, w, qbias, y, q, p);
+                return true;
+            }, TileRows{}, c.tk, Ints<kPathGeneral, kPathC128, kPathC64>{}, c.path, OutBitsAdd{}, c.out);
+        case sel::kFamLinear:
+            return pick([&]<int kPcs>() {
+                hipLaunchKernelGGL(linear_i8_wave_kernel<(kPcs != 0)>, grid, block, 0, st, x, w, qbias, y, p);
+                return true;
+            }, Ints<0, kOutPcs>{}, c.out & kOutPcs);
+    }
+    return false;
+}
+
+struct FusedAdd {                        // residual operand and outputs of a fused NewAdd (res == nullptr: none)
+    const void* res = nullptr;
+    int res_bytes = 0;
+    int16_t* wide = nullptr;
+    AddResParams ap = {};
+};
+
 static int conv2d_i8_dispatch(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, float* y_nchw, int8_t* q_nhwc,
                               int Kpad, int relu, const FusedAdd& fa, int N, int H, int W, int C, int K, int R, int S, int stride_h, int stride_w,
                               int pad_h, int pad_w, int dil_h, int dil_w, int rs, int ob, int bitwidth, fq_stream_t stream,
                               const int32_t* rs_k = nullptr, int rs_max = 0, const SpRange* act = nullptr) {
+    // validate, and fill the kernels' parameter block
     // (rs_k: one shift per output channel, in [rs, rs_max] -- the caller's bounds; rs_k == nullptr: rs is the layer's shift)
     // (act: the Sp range of the _act entry points in place of relu -- 8-bit outputs only)
     if (act && (relu || bitwidth != 8 || !sp_range_valid(*act))) return FQ_ERR_INVALID_ARG;
@@ -1787,67 +1469,33 @@ static int conv2d_i8_dispatch(const int8_t* x_nhwc, const int8_t* w_krsc, const 
     p.x_bytes = (unsigned)((long)N * H * W * C);
     p.w_bytes = (unsigned)((long)K * R * S * C);
     hipStream_t st = as_stream(stream);
-    // the 64 -> 64 3x3 layers: stationary weights, persistent workgroups
-    if (launch_conv_c64(st, x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, p)) {
-        FQ_LAUNCH_CHECK();
-        return FQ_OK;
+    // select, launch.  The selector is pure: the family order is c64_halo, the streaming 1x1 kernel's own attempt (fq_conv1x1_i8.hip,
+    // made once unless the choice is c64_halo), linear_wave, the tiles.  A family whose dynamic LDS the runtime refuses is excluded
+    // and the selector asked again.
+    const sel::ConvOuts outs{y_nchw != nullptr, q_nhwc != nullptr, fa.res != nullptr, rs_k != nullptr};
+    sel::ConvChoice c = {};
+    bool stream_asked = false;
+    for (unsigned excluded = 0;; excluded |= c.family) {
+        c = sel::select_conv_i8(p, outs, conv_switches(), excluded);
+        if (excluded & c.family) return FQ_ERR_UNSUPPORTED;       // (not reached: an excluded family is never chosen again)
+        if (c.family != sel::kFamC64Halo && !stream_asked) {
+            stream_asked = true;
+            if (launch_conv1x1_stream(st, x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, p)) {
+                c = sel::ConvChoice{};
+                c.variant = kVarStream;
+                break;
+            }
+        }
+        if (launch_conv(c, st, x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, p)) break;
     }
-    // 1x1 layers with an int8 output: the streaming kernel with stationary weights (fq_conv1x1_i8.hip) where it applies
-    if (launch_conv1x1_stream(st, x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, p)) {
-        note_conv_variant(kVarStream, 0);
-        FQ_LAUNCH_CHECK();
-        return FQ_OK;
-    }
-    // a linear layer with an fp32 output: one wave per 32 x 32 tile, operands straight from L2 (FQ_LINEAR_WAVE=0: the tiled kernels)
-    static const bool thin = [] { const char* e = getenv("FQ_LINEAR_WAVE"); return !(e && e[0] == '0'); }();
-    // (pad 0, dilation 1: with padding and a stride >= 3 the one output pixel would sample the zero border, not x)
-    if (thin && H == 1 && W == 1 && R == 1 && S == 1 && P == 1 && Q == 1 && pad_h == 0 && pad_w == 0 && dil_h == 1 && dil_w == 1 && y_nchw && !q_nhwc && !fa.res && (M + 31) / 32 <= 65535) {
-        const dim3 lgrid((unsigned)((K + 31) / 32), (unsigned)((M + 31) / 32));
-        if (rs_k) hipLaunchKernelGGL(linear_i8_wave_kernel<true>, lgrid, dim3(64 * kLinWaves), 0, st, x_nhwc, w_krsc, qbias, y_nchw, p);
-        else hipLaunchKernelGGL(linear_i8_wave_kernel<false>, lgrid, dim3(64 * kLinWaves), 0, st, x_nhwc, w_krsc, qbias, y_nchw, p);
-        note_conv_variant(kVarLinearWave, 32);
-        FQ_LAUNCH_CHECK();
-        return FQ_OK;
-    }
-    const unsigned gx = (unsigned)((M + kTP - 1) / kTP);
-    // 64-row tiles when the output is narrow, or when 128-row tiles would not even give one workgroup per CU
-    const long wg128 = (long)gx * ((K + 127) / 128);
-    // Deep reductions (>= 8 K-steps: the 3x3 layers and the wide 1x1 reductions) are bound by L1/L2 request
-    // throughput and run faster with coalesced LDS-DMA staging; shallow ones are output-bound, and there the
-    // register-staged kernel's smaller LDS footprint (3 workgroups per CU instead of 2) wins.  Measured per
-    // layer on ResNet-50 at batch 128 (scripts/conv_bench.py); FQ_CONV_DMA=0/1 forces one of them.
-    static const int dma_env = [] { const char* e = getenv("FQ_CONV_DMA"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
-    const bool use_dma = dma_env < 0 ? (p.chunks >> 3) >= 8 : dma_env == 1;
-    static const int force_tk = [] { const char* e = getenv("FQ_CONV_TK"); return e ? atoi(e) : 0; }();
-    static const bool use_c64 = [] { const char* e = getenv("FQ_CONV_C64"); return !(e && e[0] == '0'); }();
-    if ((K <= 64 || wg128 < kCUs || force_tk == 64) && force_tk != 128) {
-        if (C % 128 == 0 && K % 64 == 0 && use_dma && launch_conv_halo<64>(st, x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, p))
-            ;
-        else if (C % 128 == 0 && K % 64 == 0 && use_dma)
-            launch_conv_dma<64>(dim3(gx, K / 64), st, x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, p);
-        else if (C % 128 == 0 && K % 64 == 0)
-            launch_conv_tile<64, kPathC128>(dim3(gx, K / 64), st, x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, p);
-        else if (C == 64 && use_c64)
-            launch_conv_tile<64, kPathC64>(dim3(gx, (K + 63) / 64), st, x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, p);
-        else
-            launch_conv_tile<64, kPathGeneral>(dim3(gx, (K + 63) / 64), st, x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, p);
-    } else {
-        if (C % 128 == 0 && K % 128 == 0 && use_dma && launch_conv_halo<128>(st, x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, p))
-            ;
-        else if (C % 128 == 0 && K % 128 == 0 && use_dma)
-            launch_conv_dma<128>(dim3(gx, K / 128), st, x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, p);
-        else if (C % 128 == 0 && K % 128 == 0)
-            launch_conv_tile<128, kPathC128>(dim3(gx, K / 128), st, x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, p);
-        else if (C == 64 && use_c64)
-            launch_conv_tile<128, kPathC64>(dim3(gx, (K + 127) / 128), st, x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, p);
-        else
-            launch_conv_tile<128, kPathGeneral>(dim3(gx, (K + 127) / 128), st, x_nhwc, w_krsc, qbias, y_nchw, q_nhwc, p);
-    }
+    note_conv_variant(c.variant, c.tk);
     FQ_LAUNCH_CHECK();
     return FQ_OK;
 }
 
 }  // namespace fq
+
+using namespace fq;
 
 extern "C" int fq_conv2d_i8(const int8_t* x_nhwc, const int8_t* w_krsc, const float* qbias, float* y_nchw, int N, int H,
                             int W, int C, int K, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
