@@ -775,6 +775,25 @@ int fq_shuffle_i8_nhwc_supported(int C_in, int c_off, int C, int groups);
 int fq_shuffle_i8_nhwc(const int8_t* x, int Cpad_in, int c_off, int8_t* y, int Cpad_out, int C, int groups, int N, int H, int W,
                        fq_stream_t stream);
 
+/* An elementwise activation f between two integer layers (nn.LeakyReLU, nn.Hardswish, nn.SiLU, ...: anything that is no clamp) on
+ * a resident int8 NHWC activation, as a table of 256 bytes.  Between a producer's int8 output q on grid g and a consumer's
+ * Quantity(b), f is a function of 256 values: table256[q + 128] = Quantity_b(f(DeQuantity_g(q))), made once by the caller with
+ * fq_dequantity_f32, the module's own forward and fq_quantity_f32 (_native.build_act_table) -- the ops the fp32 path runs on every
+ * element, so the integers are that path's bit for bit.  The kernel has no arithmetic:
+ *   y[n][h][w][c] = table256[x[n][h][w][c] + 128]     for 0 <= c < C
+ *                 = 0                                 for C <= c < Cpad, whatever table256[128] holds (f(0) != 0 for a Sigmoid)
+ * x, y: int8 [N][H][W][Cpad], 16-byte aligned, Cpad >= C (the project's padding has Cpad == pad16(C); any other row length is
+ *   taken too, the bytes behind the last whole 16 then go one by one); y must not overlap x.
+ * table256: 256 bytes of device memory, any alignment; the result is on the consumer's grid b, and it is Quantity_b(f(x)), not
+ *   f(x): it stands for the value only where every reader applies Quantity_b next (the lossy-value rule).
+ * Return codes: FQ_ERR_INVALID_ARG for a null or misaligned pointer, N < 1, H < 1, W < 1, C < 1 or Cpad < C; FQ_ERR_UNSUPPORTED
+ *   for N*H*W*Cpad > 2^31 - 2 bytes (32-bit byte offsets, the limit of the other int8 NHWC entry points): callers keep the fp32
+ *   form there.  Both are decided on the host before anything is launched.  No global state, no environment variable.
+ * fq_act_lut_i8_nhwc_supported: 1 for C >= 1 (host arithmetic, no GPU needed). */
+int fq_act_lut_i8_nhwc_supported(int C);
+int fq_act_lut_i8_nhwc(const int8_t* x, int8_t* y, const int8_t* table256 /* device, index q + 128 */,
+                       int N, int H, int W, int C, int Cpad, fq_stream_t stream);
+
 /* The tail of a bottleneck block and the head of the next one in ONE kernel (round 4):
  *   NewConv2d.forward of conv3 (1x1, C -> K3; new_quantity_op.py:124-133)  ->  NewAdd.forward with the shortcut (:166-174)
  *   -> nn.ReLU -> the next block's conv1: NewConv2d.forward again (1x1, K3 -> C2, Quantity(ib) on the sum, its own tail and

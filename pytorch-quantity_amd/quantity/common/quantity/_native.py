@@ -258,6 +258,10 @@ def lib():
     L.fq_shuffle_i8_nhwc_supported.argtypes = [ci] * 4
     L.fq_shuffle_i8_nhwc.restype = ci
     L.fq_shuffle_i8_nhwc.argtypes = [vp, ci, ci, vp] + [ci] * 6 + [vp]
+    L.fq_act_lut_i8_nhwc_supported.restype = ci
+    L.fq_act_lut_i8_nhwc_supported.argtypes = [ci]
+    L.fq_act_lut_i8_nhwc.restype = ci
+    L.fq_act_lut_i8_nhwc.argtypes = [vp, vp, vp] + [ci] * 5 + [vp]
     L.fq_avgpool_i8_nhwc_supported.restype = ci
     L.fq_avgpool_i8_nhwc_supported.argtypes = [ci] * 7
     L.fq_avgpool_i8_nhwc.restype = ci
@@ -1586,6 +1590,51 @@ def shuffle_i8_nhwc(x_q, c_in, c_off, c, groups, out=None):
     _check(lib().fq_shuffle_i8_nhwc(x_q.data_ptr(), cpad_in, int(c_off), out.data_ptr(), cpad, int(c), int(groups), N, H, W,
                                     _stream(out)), "fq_shuffle_i8_nhwc")
     return out
+
+
+ACT_LUT_MAX_BYTES = (1 << 31) - 2      # fq_act_lut_i8_nhwc: N * H * W * Cpad (include/fq.h)
+
+
+def act_lut_supported(c):
+    """True when fq_act_lut_i8_nhwc takes an activation of c real channels (include/fq.h): c >= 1.  Pure host arithmetic (no GPU
+    needed); a tensor above ACT_LUT_MAX_BYTES is refused by the entry point itself."""
+    return bool(lib().fq_act_lut_i8_nhwc_supported(int(c)))
+
+
+def act_lut_i8_nhwc(x_q, c, table, out=None):
+    """fq_act_lut_i8_nhwc.  x_q: int8 [N, H, W, pad16(c)] with c real channels; table: 256 int8 on the same device
+    (build_act_table), entry q + 128 for the integer q.  Returns int8 of x_q's shape: y[..., j] = table[x_q[..., j] + 128] for
+    j < c, the padding channels zero.  `out`: write there instead (that shape, dense, 16-byte aligned, not x_q).  Launches on the
+    current stream and does not synchronise."""
+    _need_cuda(x_q, torch.int8, "fq_act_lut_i8_nhwc")
+    _need_cuda(table, torch.int8, "fq_act_lut_i8_nhwc")
+    assert x_q.dim() == 4 and x_q.is_contiguous() and table.is_contiguous() and table.numel() == 256
+    N, H, W, cpad = (int(v) for v in x_q.shape)
+    if cpad != pad16(c):
+        raise FqError("fq_act_lut_i8_nhwc: an activation of %d channels is stored as %d, got %d" % (c, pad16(c), cpad))
+    if out is None:
+        out = torch.empty_like(x_q)
+    else:
+        _need_cuda(out, torch.int8, "fq_act_lut_i8_nhwc")
+        assert tuple(out.shape) == (N, H, W, cpad) and out.is_contiguous() and out.data_ptr() != x_q.data_ptr()
+    _check(lib().fq_act_lut_i8_nhwc(x_q.data_ptr(), out.data_ptr(), table.data_ptr(), N, H, W, int(c), cpad, _stream(out)),
+           "fq_act_lut_i8_nhwc")
+    return out
+
+
+def build_act_table(module, grid, bit):
+    """The 256-byte table of fq_act_lut_i8_nhwc for the elementwise `module` between a producer on grid `grid` and a consumer's
+    Quantity(bit): entry q + 128 = Quantity_bit(module(DeQuantity_grid(q))) for q = -128 ... 127, made with the ops the fp32 path
+    runs on every element -- fq_dequantity_f32, type(module).forward, fq_quantity_f32 -- on the device of the module's parameters
+    (the current one for a module without), then cast to int8.  Runs under torch.no_grad() on a fresh tensor of shape
+    [1, 1, 16, 16]: one channel, which a single-parameter nn.PReLU broadcasts over.  Never writes to the module: an
+    `inplace=True` module writes to that fresh tensor only."""
+    p = next(module.parameters(), None)
+    device = p.device if p is not None else torch.device("cuda", torch.cuda.current_device())
+    with torch.no_grad():
+        q = torch.arange(-128, 128, dtype=torch.float32, device=device).reshape(1, 1, 16, 16)
+        t = quantity(type(module).forward(module, dequantity(q, int(grid))).contiguous(), int(bit))
+        return t.reshape(256).to(torch.int8)
 
 
 def avgpool_supported(kernel, stride, padding, shift):

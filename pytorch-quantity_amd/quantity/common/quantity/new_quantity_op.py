@@ -454,6 +454,7 @@ class NewAdd(nn.Module):
                 return fused
             hx, hy = resident_of(x), resident_of(y)
             if (hx is not None and hy is not None and hx.exact is not None and hy.exact is not None
+                    and not hx.lossy and not hy.lossy      # (a table activation's integers are no summand: as_f32 below raises)
                     and hx.exact.shape == hy.exact.shape and max(0, hx.grid, hy.grid) == plan.grid):
                 want_wide, want_narrow = plan.sum_outputs()
                 wide, narrow = _native.add_resident(hx.exact, hx.grid, hy.exact, hy.grid, want_wide, plan.grid, want_narrow,
@@ -485,7 +486,7 @@ def _newadd_fused_conv_add(self, plan, x, y):
         return None
     h = resident_of(other)
     L = d.layer
-    if h is None or h.exact is None or max(0, L.output_bit, h.grid) != plan.grid or plan.emit_f32:
+    if h is None or h.exact is None or h.lossy or max(0, L.output_bit, h.grid) != plan.grid or plan.emit_f32:
         return None
     want_wide, want_narrow = plan.sum_outputs()
     if h.exact.shape[0] != d.xq.shape[0] or h.exact.shape[-1] != _native.pad16(L.Conv.out_channels):

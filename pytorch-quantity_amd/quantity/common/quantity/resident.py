@@ -40,13 +40,16 @@ class QHandle(object):
     exact : int8 / int16 NHWC tensor, value = exact * 2^-grid (the reference's fp32 value, exactly)
     narrow: int8 NHWC tensor = Quantity(value, bit) for the next conv (conv outputs: the same tensor)
     """
-    __slots__ = ("shape", "exact", "grid", "narrow", "bit", "relu_done", "next_out")
+    __slots__ = ("shape", "exact", "grid", "narrow", "bit", "relu_done", "next_out", "lossy")
 
     def __init__(self, shape, exact, grid, narrow, bit, relu_done):
         self.shape, self.exact, self.grid, self.narrow, self.bit, self.relu_done = shape, exact, grid, narrow, bit, relu_done
         # (consumer NewConv2d, its finished output handle): set by a NewAdd that ran that consumer inside its own kernel
         # (fq_block_tail_i8, Plan.fuse_next) -- the consumer hands it out instead of launching
         self.next_out = None
+        # made by the table kernel (enable(activations=True)), or moved from such a handle: the integers are Quantity_bit(f(x)),
+        # not f(x) -- right for a convolution at that bit and for nothing else (to_f32 raises)
+        self.lossy = False
 
     @classmethod
     def int8(cls, q, channels, bit, relu_done):
@@ -63,6 +66,9 @@ class QHandle(object):
         """The fp32 NCHW tensor this handle stands for (DeQuantity + layout change, one kernel)."""
         if self.exact is None:
             raise _native.FqError("resident activation without an exact payload cannot leave the integer domain")
+        if self.lossy:
+            raise _native.FqError("the integers of a table activation are already quantised for the convolutions behind it and "
+                                  "stand for no fp32 value (dataflow changed since resident.enable(); call it again)")
         return _native.dequant_nhwc_to_nchw(self.exact, self.grid, self.shape[1])
 
     def __repr__(self):
@@ -108,7 +114,7 @@ class DeferredUpsample(object):
         if self._out is None:
             h = self.handle
             y = _native.concat_i8_nhwc([(h.exact, h.shape[1], self.s)], False)
-            self._out = QHandle.int8(y, h.shape[1], h.grid, h.relu_done)
+            self._out = _moved(QHandle.int8(y, h.shape[1], h.grid, h.relu_done), h)
         return self._out
 
     def to_f32(self):
@@ -144,11 +150,18 @@ class DeferredConcat(object):
     def materialise(self):
         if self._out is None:
             q = _concat_launch(self.leaves)
-            self._out = QHandle.int8(q, sum(h.shape[1] for h, _up, _r in self.leaves), self.grid, self.relu_done)
+            self._out = _moved(QHandle.int8(q, sum(h.shape[1] for h, _up, _r in self.leaves), self.grid, self.relu_done),
+                               *[h for h, _up, _r in self.leaves])
         return self._out
 
     def to_f32(self):
         return self.materialise().to_f32()
+
+
+def _moved(out, *sources):
+    """`out`, a handle made by pure data movement or a max-pool of `sources`: it is lossy where one of them is."""
+    out.lossy = any(h.lossy for h in sources)
+    return out
 
 
 def block_tail_enabled():
@@ -190,7 +203,7 @@ def as_f32(x):
 class Plan(object):
     """What one producer emits.  Plain data (pickles with the module)."""
     __slots__ = ("relu", "emit_f32", "emit_int", "narrow_bit", "want_wide", "grid", "resident_add", "defer", "fuse_arg",
-                 "fuse_next", "narrow_to_hbm", "fuse_proj", "depthwise", "up", "grouped", "clip", "perm")
+                 "fuse_next", "narrow_to_hbm", "fuse_proj", "depthwise", "up", "grouped", "clip", "perm", "table")
 
     def __init__(self):
         self.relu = False            # the nn.ReLU that consumes this output is fused
@@ -210,6 +223,7 @@ class Plan(object):
         self.grouped = False         # NewConv2d: a grouped layer taken by enable(grouped=True); runs on fq_gconv2d_i8_resident
         self.clip = False            # NewConv2d with `relu`: the fused activation is an nn.ReLU6 (enable(relu6=True)): clipped at 6
         self.perm = None             # nn.ChannelShuffle / Slice taken by enable(shuffle=True): (c_off, C, groups) of fq_shuffle_i8_nhwc
+        self.table = None            # elementwise activation taken by enable(activations=True): the 256 int8 of fq_act_lut_i8_nhwc, from grid `grid` to bit `narrow_bit`
 
     def __getstate__(self):
         return {k: getattr(self, k) for k in self.__slots__}
@@ -288,7 +302,7 @@ class _MaxPoolResident(_InstanceForward):
             return type(m).forward(m, as_f32(x))
         y = _native.maxpool_i8_nhwc(h.exact, *_pool_geometry(m))
         narrow = y if (h.narrow is h.exact or h.bit == h.grid) else None
-        return _emit(plan, QHandle.wide_narrow(h.shape[1], y, h.grid, narrow, h.grid, h.relu_done))
+        return _emit(plan, _moved(QHandle.wide_narrow(h.shape[1], y, h.grid, narrow, h.grid, h.relu_done), h))
 
 
 class _AvgPoolResident(_InstanceForward):
@@ -297,7 +311,7 @@ class _AvgPoolResident(_InstanceForward):
     def __call__(self, x):
         m = self.module
         h = resident_of(x)
-        if h is not None and h.exact is not None and _avgpool_is_global(m, h.exact.shape[1], h.exact.shape[2]):
+        if h is not None and h.exact is not None and not h.lossy and _avgpool_is_global(m, h.exact.shape[1], h.exact.shape[2]):
             return _native.avgpool_global_nhwc(h.exact, h.grid, h.shape[1])
         return type(m).forward(m, as_f32(x))
 
@@ -312,7 +326,7 @@ class _AvgPoolWindowResident(_InstanceForward):
         m = self.module
         plan = m.__dict__.get("_resident")
         h = resident_of(x)
-        if (plan is None or plan.narrow_bit is None or plan.grid is None or h is None or h.exact is None
+        if (plan is None or plan.narrow_bit is None or plan.grid is None or h is None or h.exact is None or h.lossy
                 or h.exact.dtype != torch.int8 or h.exact.dim() != 4 or h.grid != plan.grid or not _avgpool_window_ok(m)):
             return type(m).forward(m, as_f32(x))
         k, st, pd = _pool_geometry(m)
@@ -354,12 +368,41 @@ class _ShuffleResident(_InstanceForward):
         c_off, c, g = geo
         y = _native.shuffle_i8_nhwc(h.exact, h.shape[1], c_off, c, g)
         narrow = y if (h.narrow is h.exact or h.bit == h.grid) else None
-        return _emit(plan, QHandle.wide_narrow(c, y, h.grid, narrow, h.grid, h.relu_done))
+        return _emit(plan, _moved(QHandle.wide_narrow(c, y, h.grid, narrow, h.grid, h.relu_done), h))
 
 
 class _SliceResident(_ShuffleResident):
     """Instance-level forward of a Slice marker between integer layers (enable(shuffle=True)): channels [start, stop) of the int8
     NHWC integers as a tensor of their own, the padding channels zero (fq_shuffle_i8_nhwc with one group)."""
+
+
+ACTIVATION_TYPES = (nn.LeakyReLU, nn.PReLU, nn.Hardswish, nn.Hardsigmoid, nn.SiLU, nn.Sigmoid, nn.Tanh, nn.ELU, nn.Hardtanh, nn.Mish,
+                    nn.GELU)
+
+
+def _is_table_activation(m):
+    """An elementwise activation module that enable(activations=True) hooks.  nn.ReLU and nn.ReLU6 (a subclass of nn.Hardtanh)
+    keep their own paths: they are clamps, fused as an Sp range."""
+    return isinstance(m, ACTIVATION_TYPES) and not isinstance(m, (nn.ReLU, nn.ReLU6))
+
+
+class _ActTableResident(_InstanceForward):
+    """Instance-level forward of an elementwise activation between integer layers (enable(activations=True)): the int8 NHWC
+    integers on the planned grid go through the module's 256-entry table (fq_act_lut_i8_nhwc) and come out as the integers the
+    convolutions behind it would quantise to.  The handle is marked `lossy`: it stands for Quantity_b(f(x)), not for f(x).
+    Whenever a run-time condition fails -- no plan, no int8 exact payload, another grid than the planned one -- the module's own
+    forward runs on the fp32 form."""
+
+    def __call__(self, x):
+        m = self.module
+        plan = m.__dict__.get("_resident")
+        h = resident_of(x)
+        if (plan is None or plan.table is None or h is None or h.exact is None or h.lossy or h.exact.dtype != torch.int8
+                or h.exact.dim() != 4 or h.grid != plan.grid or not _native.act_lut_supported(h.shape[1])):
+            return type(m).forward(m, as_f32(x))
+        out = QHandle.int8(_native.act_lut_i8_nhwc(h.exact, h.shape[1], plan.table), h.shape[1], plan.narrow_bit, False)
+        out.lossy = True
+        return _emit(plan, out)
 
 
 def _pool_geometry(m):
@@ -413,7 +456,7 @@ class _UpsampleResident(_InstanceForward):
         if plan.defer and not plan.relu:
             return DeferredUpsample(h, plan.up)
         y = _native.concat_i8_nhwc([(h.exact, h.shape[1], plan.up)], plan.relu)
-        return _emit(plan, QHandle.int8(y, h.shape[1], h.grid, plan.relu or h.relu_done))
+        return _emit(plan, _moved(QHandle.int8(y, h.shape[1], h.grid, plan.relu or h.relu_done), h))
 
 
 class _ConcatResident(_InstanceForward):
@@ -461,8 +504,8 @@ class _ConcatResident(_InstanceForward):
         if plan.defer:
             return DeferredConcat(leaves, plan.narrow_bit)
         q = _concat_launch(leaves)
-        return _emit(plan, QHandle.int8(q, sum(h.shape[1] for h, _up, _r in leaves), plan.narrow_bit,
-                                        all(r or h.relu_done for h, _up, r in leaves)))
+        return _emit(plan, _moved(QHandle.int8(q, sum(h.shape[1] for h, _up, _r in leaves), plan.narrow_bit,
+                                               all(r or h.relu_done for h, _up, r in leaves)), *[h for h, _up, _r in leaves]))
 
 
 # ---- tracing -------------------------------------------------------------------------------------
@@ -497,6 +540,8 @@ class _Tracer(TorchFunctionMode):
         self.avgpool = bool(avgpool)     # enable(avgpool=True): an nn.AvgPool2d output is a traced value
         self.shuffle_seen = []           # (enable(shuffle=True)) every hooked nn.ChannelShuffle / Slice module, in execution order
         self.relu6_seen = []             # (enable(relu6=True)) every hooked nn.ReLU6 module, in execution order
+        self.act_seen = []               # (enable(activations=True)) every hooked table activation, in execution order
+        self.act_inplace = set()         # ... those that returned their own input tensor
         self.values = {}             # id(tensor) -> _Value
         self.keep = []               # keeps traced tensors alive so ids are not reused
         self.depth = 0
@@ -520,6 +565,8 @@ class _Tracer(TorchFunctionMode):
             self.relu6_seen.append(module)
         if self._kind(module) in ("shuffle", "slice") and module not in self.shuffle_seen:
             self.shuffle_seen.append(module)
+        if _is_table_activation(module) and module not in self.act_seen:
+            self.act_seen.append(module)
         for pos, a in enumerate(args):
             v = self.values.get(id(a)) if isinstance(a, torch.Tensor) else None
             if v is not None:
@@ -549,6 +596,8 @@ class _Tracer(TorchFunctionMode):
             return "upsample"
         if isinstance(module, nn.ChannelShuffle):           # (hooked only with enable(shuffle=True))
             return "shuffle"
+        if _is_table_activation(module):                    # (hooked only with enable(activations=True))
+            return "act"
         name = type(module).__name__
         return {"Concat": "concat", "NewAdd": "add", "Slice": "slice"}.get(name, "contraction")     # (Concat, Slice: likewise)
 
@@ -558,7 +607,9 @@ class _Tracer(TorchFunctionMode):
             return
         kind = self._kind(module)
         src = None
-        if kind in ("relu", "maxpool", "avgpool", "upsample", "shuffle", "slice"):     # a value of these kinds exists only behind a traced value
+        if kind == "act" and args and output is args[0]:
+            self.act_inplace.add(module)
+        if kind in ("relu", "maxpool", "avgpool", "upsample", "shuffle", "slice", "act"):     # a value of these kinds exists only behind a traced value
             if kind == "avgpool" and not self.avgpool:
                 return                                      # its output is an ordinary fp32 tensor
             src = self.values.get(id(args[0])) if args and isinstance(args[0], torch.Tensor) else None
@@ -588,6 +639,7 @@ def _clear(model):
     model.__dict__.pop("_fq_resident_enabled", None)
     model.__dict__.pop("_fq_resident_relu6", None)
     model.__dict__.pop("_fq_resident_shuffle", None)
+    model.__dict__.pop("_fq_resident_act", None)
 
 
 def disable(model):
@@ -601,16 +653,19 @@ def is_enabled(model):
 
 
 _COUNTER = {"contraction": "resident_convs", "add": "resident_adds", "maxpool": "resident_pools", "concat": "resident_concats",
-            "upsample": "resident_upsamples", "shuffle": "resident_shuffles", "slice": "resident_slices"}
+            "upsample": "resident_upsamples", "shuffle": "resident_shuffles", "slice": "resident_slices",
+            "act": "resident_activations"}
 _FORWARD = {"maxpool": _MaxPoolResident, "concat": _ConcatResident, "upsample": _UpsampleResident, "shuffle": _ShuffleResident,
-            "slice": _SliceResident}
+            "slice": _SliceResident, "act": _ActTableResident}
+_MOVES = ("maxpool", "concat", "upsample", "shuffle", "slice")       # what Quantity_b commutes with: data movement and max
 
 
 class _Planning(object):
     """The plan of one traced forward.  enable() calls the passes below in order; they decide on the trace alone and change
     nothing on the model until install() writes the plans and the instance-level forwards to the modules."""
 
-    def __init__(self, tracer, depthwise, concat, avgpool, grouped, relu6=False, flatten=False, shuffle=False):
+    def __init__(self, tracer, depthwise, concat, avgpool, grouped, relu6=False, flatten=False, shuffle=False, activations=False,
+                 revoked=None, names=None):
         from .new_quantity_op import NewConv2d, NewAdd
         from .fabu_layer import Concat
         self.conv_type, self.concat_type = NewConv2d, Concat
@@ -620,6 +675,12 @@ class _Planning(object):
         self.shuffle = bool(shuffle)
         self.shuffle_left = {}           # (shuffle=True) nn.ChannelShuffle / Slice module that stays torch's -> why
         self.perm = {}                   # (shuffle=True) planned nn.ChannelShuffle / Slice module -> (c_off, C, groups)
+        self.activations = bool(activations)
+        self.revoked = dict(revoked or {})   # (activations=True) module that an earlier round planned and verify_lossy() took back -> why
+        self.names = names or {}         # module -> its name in the model (for the reasons)
+        self.act_left = {}               # (activations=True) hooked table activation that stays torch's -> why
+        self.act_grids = {}              # (activations=True) planned table activation -> (source grid g, consumer bit b)
+        self.value_of = dict((v.producer, v) for v in tracer.produced)
         self.relu_value = dict((id(c.src), c) for c in tracer.relu_values)
         self.fmt = {}                    # id(effective _Value) -> (bytes, grid)
         self.eff_of = {}                 # id(produced _Value) -> (effective _Value, relu module)
@@ -649,6 +710,8 @@ class _Planning(object):
             self.summary["fused_relu6s"] = 0
         if shuffle:
             self.summary["resident_shuffles"] = self.summary["resident_slices"] = 0
+        if activations:
+            self.summary["resident_activations"] = 0
 
     # ---- what a value is and what a module can do
 
@@ -658,7 +721,7 @@ class _Planning(object):
 
     def effective(self, v):
         """(value the consumers see, fused ReLU / ReLU6 module or None)"""
-        if v.kind not in ("maxpool", "shuffle", "slice") and not v.foreign and len(v.consumers) == 1 and isinstance(v.consumers[0][0], (nn.ReLU, nn.ReLU6)):
+        if v.kind not in ("maxpool", "shuffle", "slice", "act") and not v.foreign and len(v.consumers) == 1 and isinstance(v.consumers[0][0], (nn.ReLU, nn.ReLU6)):
             act = v.consumers[0][0]
             after = self.relu_value.get(id(v))
             if after is not None and (isinstance(act, nn.ReLU) or self.takes_relu6(v)):
@@ -758,6 +821,8 @@ class _Planning(object):
                 f = self._concat_format(v)
             elif v.kind in ("shuffle", "slice"):
                 f = self._shuffle_format(v)
+            elif v.kind == "act":
+                f = self._act_format(v)
             else:
                 f = self._add_format(v)
             if f is not None:
@@ -856,6 +921,107 @@ class _Planning(object):
         self.shuffle_left[m] = why
         return None
 
+    def _name(self, m):
+        return self.names.get(m) or type(m).__name__
+
+    def _act_format(self, v):
+        """`activations=True` plans the elementwise activations of ACTIVATION_TYPES (nn.LeakyReLU, nn.PReLU with one weight,
+        nn.Hardswish, nn.Hardsigmoid, nn.SiLU, nn.Sigmoid, nn.Tanh, nn.ELU, nn.Hardtanh, nn.Mish, nn.GELU) on fq_act_lut_i8_nhwc:
+        between an int8 activation q on grid g and convolutions that quantise at bit b, f is the table
+        T[q + 128] = Quantity_b(f(DeQuantity_g(q))), built at enable() time with the library's own ops and the module's own
+        forward (_native.build_act_table) and kept on the module's plan -- changing an nn.PReLU weight afterwards needs a new
+        enable().  The table's output is Quantity_b(f(x)), not f(x) (the lossy-value rule): it is planned as an
+        int8 value on grid b only where every transitive reader -- through max-pools, Concats, nearest upsamplings, shuffles
+        and slices, with which Quantity_b commutes -- is an integer convolution with input_bit == b (_lossy_walk), and
+        verify_lossy() takes it back where a later pass left one of those readers in fp32 form.  Left to torch, each named with
+        its reason by describe().activations_left: a module called twice, a NewAdd sum (int16) as the source, a non-4-D input, a
+        per-channel nn.PReLU, a source without an integer form, readers at two bits, any fp32 reader (an average pool, a NewAdd, a
+        second table activation, a model output, foreign code), and `inplace=True` modules: the planned forward returns a new
+        activation and cannot rewrite the tensor that other readers may hold by its earlier name.  The summary then gains
+        `resident_activations`."""
+        m = v.producer
+        src = self.fmt.get(id(v.src))
+        why = None
+        if not self.once(m):
+            why = "the module was called more than once"
+        elif m in self.tracer.act_inplace or getattr(m, "inplace", False):
+            why = "inplace=True: the module rewrites its input tensor, a table activation returns a new one (fp32 form)"
+        elif isinstance(m, nn.PReLU) and m.num_parameters != 1:
+            why = "a per-channel nn.PReLU (%d weights) is no function of the integer alone" % m.num_parameters
+        elif v.src.shape is None or len(v.src.shape) != 4:
+            why = "its input is not 4-D"
+        elif src is None:
+            why = "its source has no integer form in this plan (fp32 form)"
+        elif src[0] != 1:
+            why = "its source is a NewAdd sum (int16): only int8 activations go through the table (fp32 form)"
+        elif not _native.act_lut_supported(int(v.src.shape[1])):
+            why = "fq_act_lut_i8_nhwc does not take %d channels" % int(v.src.shape[1])
+        elif m in self.revoked:
+            why = self.revoked[m]
+        else:
+            bits, why = self._lossy_walk(v)
+            if why is None and len(bits) != 1:
+                why = "its readers quantise at different bits %s" % sorted(bits)
+            if why is None:
+                self.act_grids[m] = (src[1], bits.pop())
+                return (1, self.act_grids[m][1])
+        self.act_left[m] = why
+        return None
+
+    def _lossy_walk(self, v):
+        """({input bits of the convolutions that read v, directly or through _MOVES}, None), or (_, why not): the first reader
+        that would see the value in fp32 form.  Decided on the trace alone, before the movement modules are planned."""
+        bits = set()
+        e, _relu = self.effective(v)
+        if e.foreign or v.foreign:
+            return bits, "read as fp32 by code outside the plan, or it is a model output"
+        if not e.consumers:
+            return bits, "nothing reads it"
+        for (c, _pos) in e.consumers:
+            if self.conv_can_read(c):
+                bits.add(c.input_bit)
+                continue
+            nxt = self.value_of.get(c)
+            if nxt is not None and nxt.kind in _MOVES and self.once(c):
+                more, why = self._lossy_walk(nxt)
+                if why is not None:
+                    return bits, why
+                bits |= more
+                continue
+            what = {"add": "the NewAdd", "avgpool": "the average pool", "act": "the table activation", "relu": "the ReLU"}.get(
+                self.tracer._kind(c) if not isinstance(c, nn.AvgPool2d) else "avgpool", "the module")
+            return bits, "read as fp32 by %s %s" % (what, self._name(c))
+        return bits, None
+
+    def verify_lossy(self):
+        """{table activation: why} for every planned one whose value, after all passes, somebody would read in fp32 form: a
+        producer on the way that emits fp32, or a reader that turned out unplanned (a Concat whose other operand sits on another
+        grid).  enable() plans again without them: the activation stays torch's and its source leaves as fp32, as without the
+        switch.  At most one round per activation."""
+        bad = {}
+        for m, (_g, b) in self.act_grids.items():
+            why = self._lossy_violation(self.value_of[m], b)
+            if why is not None:
+                bad[m] = "revoked by the lossy rule: " + why
+        return bad
+
+    def _lossy_violation(self, v, b):
+        e = self.eff_of[id(v)][0]
+        for (c, _pos) in e.consumers:
+            if self.conv_can_read(c) and c.input_bit == b:
+                continue
+            nxt = self.value_of.get(c)
+            if c in self.int8_resident and c in self.plans and nxt is not None and nxt.kind in _MOVES:
+                why = self._lossy_violation(nxt, b)
+                if why is not None:
+                    return why
+                continue
+            return "read as fp32 by %s" % self._name(c)
+        plan = self.plans.get(v.producer)
+        if plan is None or plan.emit_f32 or e.foreign:
+            return "read as fp32 behind %s" % self._name(v.producer)
+        return None
+
     def _add_format(self, v):
         """A NewAdd of two integer operands: the exact sum as int16 on the finer of their grids, where that fits."""
         ops = self._integer_operands(v.producer)
@@ -938,6 +1104,8 @@ class _Planning(object):
             plan.up = _upsample_factor(m)
         if v.kind in ("shuffle", "slice"):
             plan.perm = self.perm[m]
+        if v.kind == "act":
+            plan.grid = self.act_grids[m][0]
         self._take(m, plan, relu_mod, _FORWARD.get(v.kind))
         self.summary[_COUNTER[v.kind]] += 1
 
@@ -1095,9 +1263,18 @@ class _Planning(object):
                     self.shuffle_left[m] = "its input is not the output of a planned layer"
             names = dict((m, name) for name, m in model.named_modules())
             model.__dict__["_fq_resident_shuffle"] = dict((names.get(m, "?"), why) for m, why in self.shuffle_left.items())
+        if self.activations:
+            for m, (g, b) in self.act_grids.items():
+                self.plans[m].table = _native.build_act_table(m, g, b)
+            for m in self.tracer.act_seen:
+                if m not in self.plans and m not in self.act_left:
+                    self.act_left[m] = "its input is not the output of a planned layer (no integer source)"
+            names = dict((m, name) for name, m in model.named_modules())
+            model.__dict__["_fq_resident_act"] = (dict((names.get(m, "?"), why) for m, why in self.act_left.items()),
+                                                  tuple(names.get(m, "?") for m in self.revoked))
 
 
-def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False):
+def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False, activations=False):
     """One forward of `model` in eval mode under the tracer: (tracer, the outputs of that forward)."""
     from .new_quantity_op import NewConv2d, NewLinear, NewAdd
     from .fabu_layer import Concat, Slice
@@ -1106,7 +1283,7 @@ def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False):
     tracer = _Tracer(avgpool)
     hooks = []
     for m in model.modules():
-        if isinstance(m, planned_types) or (concat and _upsample_factor(m) is not None):     # (any other nn.Upsample stays foreign code)
+        if isinstance(m, planned_types) or (concat and _upsample_factor(m) is not None) or (activations and _is_table_activation(m)):     # (any other nn.Upsample stays foreign code)
             hooks.append(m.register_forward_pre_hook(tracer.pre))
             hooks.append(m.register_forward_hook(tracer.post))
         elif concat and isinstance(m, Concat):
@@ -1127,7 +1304,7 @@ def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False):
 
 
 def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False, grouped=False, relu6=False,
-           flatten=False, shuffle=False):
+           flatten=False, shuffle=False, activations=False):
     """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
     on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
     nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
@@ -1140,25 +1317,35 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
     `avgpool=True` also plans a windowed nn.AvgPool2d between an int8 activation and convolutions (_plan_avgpool_window);
     `relu6=True` also fuses an nn.ReLU6 behind a NewConv2d, as an nn.ReLU is fused (_Planning.takes_relu6);
     `flatten=True` (with `concat=True`; ValueError without) runs nested Concats as one launch (_Planning.defer_concats);
-    `shuffle=True` also plans nn.ChannelShuffle and the Slice marker on the int8 integers (_Planning._shuffle_format)."""
+    `shuffle=True` also plans nn.ChannelShuffle and the Slice marker on the int8 integers (_Planning._shuffle_format);
+    `activations=True` also plans elementwise activations that are no clamp (nn.LeakyReLU, nn.Hardswish, nn.SiLU, ...) as a
+    256-entry table between integer layers (_Planning._act_format).  The tables are built here: changing an nn.PReLU weight
+    afterwards needs a new enable()."""
     from .new_quantity_op import QUANTIZE_BIT
     if flatten and not concat:
         raise ValueError("resident.enable(flatten=True) needs concat=True: only planned Concats are flattened")
     _clear(model)
     if QUANTIZE_BIT != 8:
         raise _native.FqError("resident activations are defined for QUANTIZE_BIT = 8")
-    tracer, traced_out = _trace(model, example_input, concat, avgpool, relu6, shuffle)
-    planning = _Planning(tracer, depthwise, concat, avgpool, grouped, relu6, flatten, shuffle)
-    planning.plan_formats()
-    planning.plan_outputs()
-    planning.defer_convs()
-    planning.fuse_block_tails()
-    planning.fuse_projections()
-    if concat:
-        planning.defer_upsamples()
-    if flatten:
-        planning.defer_concats()
-    planning.hook_global_pools()
+    tracer, traced_out = _trace(model, example_input, concat, avgpool, relu6, shuffle, activations)
+    names = dict((m, name) for name, m in model.named_modules()) if activations else None
+    revoked = {}
+    while True:
+        planning = _Planning(tracer, depthwise, concat, avgpool, grouped, relu6, flatten, shuffle, activations, revoked, names)
+        planning.plan_formats()
+        planning.plan_outputs()
+        planning.defer_convs()
+        planning.fuse_block_tails()
+        planning.fuse_projections()
+        if concat:
+            planning.defer_upsamples()
+        if flatten:
+            planning.defer_concats()
+        planning.hook_global_pools()
+        bad = planning.verify_lossy() if activations else {}
+        if not bad:
+            break
+        revoked.update(bad)                                 # (each round takes at least one activation out: it ends)
     planning.install(model)
     if verify:
         with torch.no_grad():
@@ -1175,7 +1362,11 @@ class _Description(dict):
     """describe()'s {module name: Plan}.  After enable(relu6=True) it also says what became of the nn.ReLU6 modules:
     `fused_relu6s`, how many a producer fused, and `relu6_left`, {module name: why} for each one that stays torch's.  After
     enable(flatten=True) `flattened_concats` names the Concats that launch nothing of their own.  After enable(shuffle=True)
-    `shuffle_left` is {module name: why} for every hooked nn.ChannelShuffle / Slice that stays torch's."""
+    `shuffle_left` is {module name: why} for every hooked nn.ChannelShuffle / Slice that stays torch's.  After
+    enable(activations=True) `activations_left` is {module name: why} for every hooked elementwise activation that stays torch's,
+    and `activations_revoked` names those among them that a first plan had accepted and the lossy-value verification took back."""
+    activations_left = {}
+    activations_revoked = ()
     fused_relu6s = 0
     relu6_left = {}
     shuffle_left = {}
@@ -1187,6 +1378,7 @@ def describe(model):
     d = _Description((name, m.__dict__["_resident"]) for name, m in model.named_modules() if "_resident" in m.__dict__)
     d.fused_relu6s, d.relu6_left = model.__dict__.get("_fq_resident_relu6", (0, {}))
     d.shuffle_left = model.__dict__.get("_fq_resident_shuffle", {})
+    d.activations_left, d.activations_revoked = model.__dict__.get("_fq_resident_act", ({}, ()))
     d.flattened_concats = tuple(name for name, m in model.named_modules()
                                 if type(m).__name__ == "Concat" and name in d and d[name].defer)
     return d
