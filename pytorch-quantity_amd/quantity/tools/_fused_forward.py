@@ -21,8 +21,6 @@ An out-of-place nn.ReLU6 takes the two conv -> ReLU rows as well when Quantity.f
 
 Every fusion falls back to the unfused form of the same arithmetic; none changes a table (tests/test_gpu_conv_add_fusion.py,
 tests/test_gpu_float_forward_kernels.py, tests/test_gpu_r50_tables.py)."""
-import weakref
-
 import torch
 
 from common.quantity import _native, _float_conv
@@ -316,12 +314,13 @@ class _FusedForward(object):
             ctl.eager.note(conv_key, t3)                        # (what its own hook left out: the tensor exists only now)
         if pair:
             # (the shortcut is the ReLU output another tail of this forward wrote?  Then it is max(that sum, 0) and pass 2 can
-            #  re-make it from that sum's own pair instead of the cache keeping it: src = that sum's key)
-            src = ctl.sum_relu.get(id(other))
-            ctl.pairs[key] = (conv_key, other, other._version, src[1] if src is not None and src[0]() is other else None)
+            #  re-make it from that sum's own pair instead of the cache keeping it: src = that sum's key -- unless the model has
+            #  written to it since (`z = relu(...); z.mul_(g)`): what the add saw is then no longer max(that sum, 0), the shortcut
+            #  stays a kept tensor and takes the single pair's version check)
+            ctl.pairs[key] = (conv_key, other, other._version, ctl.chain_src(other))
             ctl.pair_sums += 1
         if key is not None:
-            ctl.sum_relu[id(r)] = (weakref.ref(r), key)
+            ctl.note_tail_relu(r, key)
         ctl.fuse_verified.add(m)
         ctl.relu_ready = (output, r, relu, output._version)
         ctl.fused_relus.add(relu)

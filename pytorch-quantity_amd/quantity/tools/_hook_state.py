@@ -2,6 +2,7 @@
 during one calibration: the statistics gatherer of a forward (_EagerStats), the proof that a tensor may stay un-materialised
 (_DeferralProbe) and the shared state itself (_HookState).  No reference counterpart: the reference's hook copies every output
 to the host (pytorch_quantizer.py:513) and needs none of it."""
+import weakref
 from collections import OrderedDict
 
 import torch
@@ -61,6 +62,10 @@ class _EagerStats(object):
     def modified(self):
         """True if any tensor captured during this forward has been written to since (an in-place consumer)."""
         return any(t._version != v for (_k, t, v) in self.seen)
+
+    def written(self):
+        """[(key, tensor)] of the tensors captured during this forward that have been written to since."""
+        return [(k, t) for (k, t, v) in self.seen if t._version != v]
 
 
 class _DeferralProbe(object):
@@ -195,7 +200,7 @@ class _HookState(object):
     __slots__ = ("stop_after", "events", "eager", "fuse_bias", "fuse_collector", "fuse_off", "fuse_verified", "fuse_warm",
                  "relu_after", "relu_ready", "last_out", "fused_relus", "fuse_stat", "hist_fused", "keep_feats", "keep_names",
                  "own_plain", "own_conv1x1", "deferred", "defer_ok", "deferred_adds", "deferred_hists", "poison", "relu_only_ok", "skipped_outputs",
-                 "pair_ok", "pairs", "pair_sums", "sum_relu")
+                 "pair_ok", "pairs", "pair_sums", "sum_relu", "pairs_chained")
 
     def __init__(self):
         self.stop_after = None          # ordinal of the last module pass 2 needs (the hook raises _StopForward there)
@@ -228,5 +233,21 @@ class _HookState(object):
         self.pairs = {}                 # THIS forward: key of a sum that was not written -> (key of conv3's output, the shortcut
         #                                 tensor, its version): pass 2 histograms the pair (fq_hist2048_pair_seg)
         self.pair_sums = 0              # sums pass 1 did not write because pass 2 histograms (conv3 output, shortcut) instead
-        self.sum_relu = {}              # THIS forward: id(r) -> (weak reference to r, key of the sum): the ReLU outputs the one-kernel
-        #                                 tails wrote -- a pair whose shortcut is one of them can re-make it in pass 2
+        self.sum_relu = {}              # THIS forward: id(r) -> (weak reference to r, key of the sum, r's version): the ReLU outputs
+        #                                 the one-kernel tails wrote -- a pair whose shortcut is one of them can re-make it in pass 2
+        self.pairs_chained = 0          # pairs the cache holds WITHOUT their shortcut: pass 2 re-makes it from the pair in front
+
+    def note_tail_relu(self, r, key):
+        """A one-kernel tail has just written r = max(the sum `key`, 0)."""
+        self.sum_relu[id(r)] = (weakref.ref(r), key, r._version)
+
+    def chain_src(self, other):
+        """The key of the sum whose ReLU output the shortcut `other` is -- that very tensor object, not written to since the tail
+        wrote it -- or None: pass 2 re-makes such a shortcut as max(that sum, 0) instead of reading a kept tensor
+        (fq_hist2048_chain_seg), which is only the tensor the add saw while nobody has touched it.  A view is another object; an
+        id that a later tensor took over from a dead one fails the weak reference; a write in place -- through the tensor or
+        through any view of it -- moves the version counter."""
+        e = self.sum_relu.get(id(other))
+        if e is None or e[0]() is not other or other._version != e[2]:
+            return None
+        return e[1]

@@ -412,9 +412,36 @@ class Quantity(_FusedForward, _FileInputs):
             chain_len[n] = chain_len[src] + 1 if chained else 1
             if chained:
                 continued.add(src)
+                self._hook_ctl.pairs_chained += 1
             entry[("pair", n)] = (conv_key, named_feats[conv_key], None if chained else other, version, y_kept, src if chained else None)
             nbytes += hold(named_feats[conv_key]) + (0 if chained else hold(other))
         return entry, nbytes
+
+    @staticmethod
+    def _kept_intact(entry, eager):
+        """Refuse a cache entry one of whose hooked tensors was written to in place after its hook ran.  The probe forward has
+        shown that this model does no such thing (else nothing is cached at all), but a model may start to in a later forward, and
+        a statistic folded into the tensor's producer is taken before the write: nothing else would notice, and pass 2 would
+        histogram the overwritten tensor where the reference's hook saw the module's result.  `eager.seen` holds the version
+        counters of the whole forward whenever something is cached.  Not this check's business: a tensor the entry does not hold
+        (a sum left to its pair was never written, and nothing reads it again), and the shortcut of a pair the entry holds, whose
+        version _add_with_pairs compares where pass 2 reads it."""
+        written = eager.written() if eager is not None else None
+        if not written:                                    # (every forward of an ordinary model: one look at each counter)
+            return
+        held, at_use = set(), set()
+        for k, v in entry.items():
+            if isinstance(k, tuple):
+                held.add(v[1].data_ptr())
+                if v[2] is not None:
+                    at_use.add(v[2].data_ptr())
+            else:
+                held.add(v.data_ptr())
+        late = [k for k, t in written if t.data_ptr() in held and t.data_ptr() not in at_use]
+        if late:
+            raise RuntimeError("a hooked activation was modified in place after its statistics were taken (%s), in a forward whose "
+                               "tensors are kept for pass 2 -- the probe forward of this model had shown no such write; "
+                               "set FQ_ACT_CACHE_GB=0" % ", ".join(late))
 
     def _add_with_pairs(self, collector):
         """collector.add_to_distributions for dicts that may hold pairs (see _cache_entry): the pairs go through
@@ -725,7 +752,7 @@ class Quantity(_FusedForward, _FileInputs):
                 ctl.keep_names = None if len(cached) < plan["whole_batches"] else set()
             else:
                 ctl.keep_names = plan["keep"]
-            self._forward_with_stats(item, collector.refresh_max_val, named_feats)
+            eager = self._forward_with_stats(item, collector.refresh_max_val, named_feats)
             if os.environ.get("FQ_DEBUG_STEP_TIMES"):
                 self._sync()
                 step_ms.append(round((time.perf_counter() - ts) * 1e3, 2))
@@ -742,10 +769,12 @@ class Quantity(_FusedForward, _FileInputs):
             if plan["kind"] == "A":
                 if len(cached) < plan["whole_batches"] and used + need_all <= budget:
                     cached[i], nbytes = self._cache_entry(named_feats, None)
+                    self._kept_intact(cached[i], eager)
                     cached_ids.add(i)
                     used += nbytes
             else:
                 cached[i], nbytes = self._cache_entry(named_feats, plan["keep"])
+                self._kept_intact(cached[i], eager)
                 used += nbytes
         ctl.fuse_collector = None
         self._join_stat_stream()
@@ -855,7 +884,7 @@ class Quantity(_FusedForward, _FileInputs):
                         "own_conv1x1_launches": ctl.own_conv1x1,
                         "conv_add_chains_proven": len(ctl.defer_ok), "conv_add_launches": ctl.deferred_adds,
                         "conv_add_hist_launches": ctl.deferred_hists,
-                        "sums_left_to_pass2_pairs": ctl.pair_sums,
+                        "sums_left_to_pass2_pairs": ctl.pair_sums, "pairs_chained": ctl.pairs_chained,
                         "relu_only_chains_proven": len(ctl.relu_only_ok), "launches_without_own_output": ctl.skipped_outputs,
                         "chains_refused_for_keepers": dict(getattr(self, "deferral_refused", None) or {}),
                         "stats_group_bytes": self._stats_limit,

@@ -2,72 +2,14 @@
 behind it as ONE kernel (Quantity.fuse_conv_add, fq_conv1x1_add_f32): which chains are taken is PROVEN per model by the poison
 probe (tools.pytorch_quantizer._DeferralProbe), the tables do not depend on it, and whether the two intermediate tensors reach
 HBM follows what pass 2's cache wants.  Reference: the forward at pytorch_quantizer.py:288-296 through fabu_layer.py:5-11."""
-import os
-
 import pytest
 import torch
 
 import cases
+from calib_inplace_nets import _block_net, _calibrate
 from workdir_util import product_workdir
 
 pytestmark = pytest.mark.gpu
-
-
-def _block_net(variant="plain", hw=64):
-    """stem -> 2 x [1x1 -> ReLU -> 3x3 -> ReLU -> 1x1 (128 channels)] + shortcut -> Eltwise -> ReLU -> pool -> fc.
-    variant "peek": block 1's convolution output is ALSO read by something else before its Eltwise;
-    variant "inplace_relu": the ReLU behind the Eltwise works in place."""
-    from torch import nn
-    from common.quantity import Eltwise, View
-
-    class Block(nn.Module):
-        def __init__(self, cin, mid, cout, stride, peek):
-            super().__init__()
-            self.c1, self.r1 = nn.Conv2d(cin, mid, 1), nn.ReLU()
-            self.c2, self.r2 = nn.Conv2d(mid, mid, 3, stride=stride, padding=1), nn.ReLU()
-            self.c3 = nn.Conv2d(mid, cout, 1)
-            self.down = nn.Conv2d(cin, cout, 1, stride=stride) if (stride != 1 or cin != cout) else None
-            self.add = Eltwise()
-            self.r3 = nn.ReLU(variant == "inplace_relu")
-            self.peek = (nn.ReLU(), Eltwise()) if peek else None
-            if peek:
-                self.peek_relu, self.peek_add = self.peek
-
-        def forward(self, x):
-            y = self.c3(self.r2(self.c2(self.r1(self.c1(x)))))
-            side = self.peek_relu(y) if self.peek else None                    # a second reader of the convolution's output
-            z = self.r3(self.add(y, x if self.down is None else self.down(x)))
-            return z if side is None else self.peek_add(z, side)
-
-    class Net(nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.stem, self.relu0 = nn.Conv2d(3, 32, 3, padding=1), nn.ReLU()
-            self.b1 = Block(32, 16, 128, 2, peek=False)
-            self.b2 = Block(128, 32, 128, 1, peek=variant == "peek")
-            self.pool, self.view, self.fc = nn.AvgPool2d(hw // 2), View(), nn.Linear(128, 10)
-
-        def forward(self, x):
-            return self.fc(self.view(self.pool(self.b2(self.b1(self.relu0(self.stem(x)))))))
-    return Net()
-
-
-def _calibrate(model, fuse, cache_gb=None, plan="", batches=5, monkeypatch=None, hw=64, skip=None, pair=None, chain=None):
-    from tools import Quantity
-    if monkeypatch is not None and cache_gb is not None:
-        monkeypatch.setenv("FQ_ACT_CACHE_GB", cache_gb)
-        monkeypatch.setenv("FQ_CACHE_PLAN", plan)
-    with product_workdir(input_shape="1,3,%d,%d" % (hw, hw), device="gpu", max_cali_img_num=batches - 1) as tmp:
-        q = Quantity(model)
-        q.fuse_conv_add = fuse
-        q.skip_unread_outputs = fuse if skip is None else skip
-        if pair is not None:
-            q.pair_hist = pair
-        if chain is not None:
-            q.pair_chain = chain
-        bits = q.activation_quantize(cases.calib_batches(batches, (8, 3, hw, hw), seed=91))
-        table = open(os.path.join(tmp, "test", "workdir", "feat.table")).read()
-        return dict(bits), table, dict(q._collector.max_vals), q._collector.hist_device.clone(), dict(q.timings)
 
 
 @pytest.mark.parametrize("cache_gb,plan", [("0", ""), ("1", "A"), ("0.07", "A"), ("1", "B"), ("0.05", "B")])

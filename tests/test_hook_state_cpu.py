@@ -1,6 +1,7 @@
 """Host logic of tools/_hook_state.py on CPU tensors (no kernel involved): the bookkeeping of the poison probe that decides
 whether a convolution's output may stay un-materialised (Quantity.fuse_conv_add / skip_unread_outputs), and the statistics
-gatherer's in-place check.  The GPU behaviour built on it is tests/test_gpu_conv_add_fusion.py."""
+gatherer's in-place check, which ReLU output may be a chain link (note_tail_relu / chain_src) and what may go into pass 2's
+cache (Quantity._kept_intact).  The GPU behaviour built on it is tests/test_gpu_conv_add_fusion.py and tests/test_gpu_calib_inplace.py."""
 import pytest
 import torch
 
@@ -106,3 +107,88 @@ def test_eager_stats_groups_flushes_and_notices_in_place_writes():
     e.retain = False
     e.note("x", a)
     assert e.seen == []                                    # nothing held when no cache is wanted
+
+
+def test_eager_stats_flush_looks_at_pending_tensors_only():
+    """The grouped launch refuses a PENDING tensor whose version moved since its hook; a tensor whose producer already took its
+    statistic (note) is not its business -- `written()` names it for whoever keeps the tensor for pass 2."""
+    seen = []
+    e = _EagerStats(lambda d: seen.append(sorted(d)), _AFTER_FORWARD)
+    pending, noted = torch.zeros(4), torch.ones(4)
+    e.add("pending", pending)
+    e.note("noted", noted)
+    noted.mul_(0.5)                                        # after the producer's statistic: the launch does not read it
+    assert e.modified() and [k for k, _t in e.written()] == ["noted"]
+    e.flush()
+    assert seen == [["pending"]]
+    e = _EagerStats(lambda d: seen.append(sorted(d)), _AFTER_FORWARD)
+    e.add("pending", pending)
+    e.note("noted", noted)
+    pending[:2].add_(1.0)                                  # through a view: the same version counter
+    assert [k for k, _t in e.written()] == ["pending"]
+    with pytest.raises(RuntimeError, match="modified in place before its statistics were taken"):
+        e.flush()
+    assert seen == [["pending"]]                           # nothing was launched on the overwritten tensor
+    e = _EagerStats(lambda d: seen.append(sorted(d)), 0)   # limit 0: the launch already ran from inside the hook
+    e.add("pending", pending)
+    pending.add_(1.0)
+    e.flush()
+    assert seen == [["pending"], ["pending"]]
+
+
+def test_a_chained_shortcut_is_the_untouched_relu_output_object():
+    """_HookState.note_tail_relu / chain_src: pass 2 re-makes a shortcut as max(the sum in front, 0) only for the very tensor the
+    one-kernel tail wrote, and only while nobody has written to it."""
+    st = _HookState()
+    r = torch.arange(-3.0, 3.0).relu()
+    assert st.chain_src(r) is None                         # not a tail's ReLU output at all
+    st.note_tail_relu(r, "Eltwise_10")
+    assert st.chain_src(r) == "Eltwise_10" and st.chain_src(r) == "Eltwise_10"      # the same object, untouched
+    assert st.chain_src(r[:]) is None and st.chain_src(r.detach()) is None          # a view / an alias is another object
+    assert st.chain_src(r.clone()) is None
+    assert st.chain_src(r) == "Eltwise_10"                 # (looking through a view wrote nothing)
+    r.mul_(2)
+    assert st.chain_src(r) is None                         # written to: no longer max(the sum, 0)
+    # a write through a view moves the same counter
+    r2 = torch.ones(4)
+    st.note_tail_relu(r2, "Eltwise_20")
+    r2[:].mul_(0.5)
+    assert st.chain_src(r2) is None
+    # an id that a later tensor took over from a dead one
+    r3 = torch.ones(4)
+    st.note_tail_relu(r3, "Eltwise_30")
+    key = id(r3)
+    del r3
+    imposter = torch.ones(4)
+    st.sum_relu[id(imposter)] = st.sum_relu.pop(key)       # (what a recycled id amounts to: the entry is found, its tensor is gone)
+    assert st.sum_relu[id(imposter)][0]() is None and st.chain_src(imposter) is None
+    # ... and a forward starts from nothing (the calibration loop replaces the dict)
+    st.sum_relu = {}
+    r4 = torch.ones(2)
+    assert st.chain_src(r4) is None and st.pairs_chained == 0
+
+
+def test_a_cache_entry_with_a_late_write_is_refused_except_for_a_pairs_shortcut():
+    """Quantity._kept_intact: what pass 1 puts into pass 2's cache must still be what the hooks saw; the shortcut of a pair the
+    entry holds is compared where pass 2 reads it (_add_with_pairs) and is not this check's business."""
+    from tools.pytorch_quantizer import Quantity
+    e = _EagerStats(lambda d: None, _AFTER_FORWARD)
+    y, down, other = torch.ones(4), torch.ones(4), torch.ones(4)
+    for k, t in (("Conv2d_8", y), ("Conv2d_9", down), ("Conv2d_3", other)):
+        e.note(k, t.detach())                              # (the hooks keep detach() aliases: the same version counter)
+    entry = {"Conv2d_3": other, "Conv2d_8": y, "Conv2d_9": down,
+             ("pair", "Eltwise_10"): ("Conv2d_8", y, down, down._version, True, None)}
+    Quantity._kept_intact(entry, e)
+    Quantity._kept_intact(entry, None)                     # (an engine that takes its statistics after the forward: no counters)
+    unwritten_sum = torch.empty(4)
+    e.note("Eltwise_10", unwritten_sum.detach())
+    unwritten_sum.mul_(0.5)                                # hooked, but not in the entry (its pair is): nothing reads it again
+    Quantity._kept_intact(entry, e)
+    down.add_(1.0)
+    Quantity._kept_intact(entry, e)                        # the pair's shortcut: refused in pass 2, by name
+    plain = dict((k, v) for k, v in entry.items() if not isinstance(k, tuple))
+    with pytest.raises(RuntimeError, match=r"modified in place after its statistics were taken \(Conv2d_9\)"):
+        Quantity._kept_intact(plain, e)                    # ... the same tensor kept without its pair has no other check
+    y[:1].mul_(0.5)
+    with pytest.raises(RuntimeError, match=r"modified in place after its statistics were taken \(Conv2d_8\)"):
+        Quantity._kept_intact(entry, e)
