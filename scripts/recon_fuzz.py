@@ -4,15 +4,19 @@ scripts/model_fuzz.py): calibrate, rewrite, rebuild as ReconModel, then the logi
 form) against the logits of the resident plan (int8 / int16 hand-offs, fused ReLUs, conv + NewAdd in one kernel, block tails, pools
 on integers), eagerly and as one HIP graph: bit for bit.  The planner decides per edge who may hand over integers; a wrong decision
 on a graph nobody wrote a test for shows here.
-`relu6`: about half of the nn.ReLU modules become nn.ReLU6 (model_fuzz.with_relu6) and the plan is made with every opt-in argument on
-(depthwise, concat, avgpool, grouped, relu6) -- everything on against the fp32 module boundaries.
+`relu6`: about half of the nn.ReLU modules become nn.ReLU6 (model_fuzz.with_relu6) and the plan is made with the five switches that
+generator's vocabulary can reach (EVERYTHING: depthwise, concat, avgpool, grouped, relu6; it has no nested Concat, no Slice or
+nn.ChannelShuffle and no table activation, so flatten, shuffle and activations would plan nothing there).
+`mixed`: the generator of the mixed-graph tests (tests/mixed_nets.py: RandomMixedNet) -- dense, depthwise and grouped convolutions
+behind nn.ReLU, nn.ReLU6 and table activations, residual steps, two-operand and nested Concats with upsampled leaves, ShuffleNet
+units, windowed average pools, and what the planner has to leave alone -- planned with all eight switches on (ALL_SWITCHES).
 `shuffle`: another generator (tests/shuffle_nets.py: RandomShuffleNet) -- a stem and one to four random steps with Slice markers and
 nn.ChannelShuffle modules: stride-1 units cut anywhere, stride-2 units, a shuffle or a slice alone, overlapping slices joined by a
 Concat, a slice of a slice of a shuffle, group counts over every divisor -- planned with depthwise, concat, flatten and shuffle on.
 `act`: another generator (tests/activation_nets.py: RandomActNet) -- random listed activations (nn.LeakyReLU, nn.Hardswish, nn.SiLU,
 ...) behind random convolutions, with a max-pool, a Slice or a Concat of two Slices behind some of them -- planned with concat,
 shuffle and activations on.
-usage: recon_fuzz.py [models=40] [seed=1] [odd] [share] [bn] [big] [relu6] [shuffle] [act]"""
+usage: recon_fuzz.py [models=40] [seed=1] [odd] [share] [bn] [big] [relu6] [shuffle] [act] [mixed]"""
 import importlib.util, os, random, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,9 +32,14 @@ from workdir_util import product_workdir
 EVERYTHING = dict(depthwise=True, concat=True, avgpool=True, grouped=True, relu6=True)
 SHUFFLE = dict(depthwise=True, concat=True, flatten=True, shuffle=True)
 ACT = dict(concat=True, shuffle=True, activations=True)
+ALL_SWITCHES = dict(depthwise=True, concat=True, avgpool=True, grouped=True, relu6=True, flatten=True, shuffle=True, activations=True)
 
 
-def build(i, seed, odd=False, share=False, bn=False, relu6=False, shuffle=False, act=False):
+def build(i, seed, odd=False, share=False, bn=False, relu6=False, shuffle=False, act=False, mixed=False):
+    if mixed:
+        import mixed_nets
+        model = mixed_nets.float_model(i, seed).cuda()
+        return model, model.size, model.batch
     if act:
         import activation_nets
         model = activation_nets.RandomActNet(i, seed).cuda().eval()
@@ -61,20 +70,26 @@ def recon_of(model, twin, data):
         sys.stdout = out
 
 
-def run(n, seed, log=print, odd=False, share=False, bn=False, big=False, variants=None, relu6=False, shuffle=False, act=False):
+def run(n, seed, log=print, odd=False, share=False, bn=False, big=False, variants=None, relu6=False, shuffle=False, act=False,
+        mixed=False):
     bad, seen = 0, {}
     variants = variants if variants is not None else {}
     for i in range(n):
-        model, size, bs = build(i, seed, odd, share, bn, relu6, shuffle, act)
+        model, size, bs = build(i, seed, odd, share, bn, relu6, shuffle, act, mixed)
         data = [(torch.randn(bs, model.cin, size, size, device="cuda"), torch.zeros(bs, dtype=torch.long)) for _ in range(2)]
         out = sys.stdout
         try:
             with product_workdir(input_shape="1,%d,%d,%d" % (model.cin, size, size), device="gpu", max_cali_img_num=1):
-                net = recon_of(model, build(i, seed, odd, share, bn, relu6, shuffle, act)[0], data)
+                net = recon_of(model, build(i, seed, odd, share, bn, relu6, shuffle, act, mixed)[0], data)
                 x = data[0][0]
                 with torch.no_grad():
                     plain = net(x)
-                    summary = resident.enable(net, x, **(ACT if act else SHUFFLE if shuffle else EVERYTHING if relu6 else {}))
+                    summary = resident.enable(net, x, **(ALL_SWITCHES if mixed else ACT if act else SHUFFLE if shuffle else EVERYTHING if relu6 else {}))
+                    if mixed:
+                        plans = resident.describe(net)
+                        for key, left in (("acts_left", plans.activations_left), ("shuffles_left", plans.shuffle_left),
+                                          ("relu6s_left", plans.relu6_left), ("acts_revoked", plans.activations_revoked)):
+                            seen[key] = seen.get(key, 0) + len(left)
                     if act:
                         seen["act_modules"] = seen.get("act_modules", 0) + sum(1 for m in net.modules() if resident._is_table_activation(m))
                         seen["acts_left"] = seen.get("acts_left", 0) + len(resident.describe(net).activations_left)
@@ -141,9 +156,9 @@ if __name__ == "__main__":
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     odd, share, bn, big = "odd" in sys.argv[3:], "share" in sys.argv[3:], "bn" in sys.argv[3:], "big" in sys.argv[3:]
-    relu6, shuffle, act = "relu6" in sys.argv[3:], "shuffle" in sys.argv[3:], "act" in sys.argv[3:]
+    relu6, shuffle, act, mixed = "relu6" in sys.argv[3:], "shuffle" in sys.argv[3:], "act" in sys.argv[3:], "mixed" in sys.argv[3:]
     variants = {}
-    bad, seen = run(n, seed, odd=odd, share=share, bn=bn, big=big, variants=variants, relu6=relu6, shuffle=shuffle, act=act)
+    bad, seen = run(n, seed, odd=odd, share=share, bn=bn, big=big, variants=variants, relu6=relu6, shuffle=shuffle, act=act, mixed=mixed)
     if big:
         print("integer kernels at 256 images:", dict(sorted(variants.items())))
-    print("recon_fuzz%s: %d random models (seed %d), %d with a finding; plans in all: %s" % ((" odd" if odd else "") + (" share" if share else "") + (" bn" if bn else "") + (" relu6" if relu6 else "") + (" shuffle" if shuffle else "") + (" act" if act else ""), n, seed, bad, seen))
+    print("recon_fuzz%s: %d random models (seed %d), %d with a finding; plans in all: %s" % ((" odd" if odd else "") + (" share" if share else "") + (" bn" if bn else "") + (" relu6" if relu6 else "") + (" shuffle" if shuffle else "") + (" act" if act else "") + (" mixed" if mixed else ""), n, seed, bad, seen))

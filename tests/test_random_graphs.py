@@ -113,9 +113,13 @@ def test_random_graphs_gpu_match_reference(g11):
 @pytest.mark.gpu
 def test_random_graphs_reconmodel_logits_equal_the_reference(g11, oracle, golden_dir):
     """G4's check on graphs that are not ResNets: the reference's ReconModel logits (CPU, fixed input) of every graph it accepts,
-    against the integer-simulation model on the HIP kernels -- with fp32 module boundaries and with the resident integer plan --
-    bit for bit.  The tables the models are built from come from the oracle-backed CPU calibration, which the CPU test above pins to
-    the reference's byte for byte."""
+    against the integer-simulation model on the HIP kernels -- with fp32 module boundaries, with the resident integer plan and with
+    the plan made with all eight opt-in switches on -- bit for bit.  The tables the models are built from come from the oracle-backed
+    CPU calibration, which the CPU test above pins to the reference's byte for byte.  Over the family the second plan must have taken a
+    depthwise layer and a Concat, so that it cannot agree by planning nothing new (on the oracle-backed doubles it takes 2 and 7 on the
+    ten `odd` graphs alone).  No upsampling is asked for: none of the 46 recorded graphs drew one -- the generator makes one only
+    in a `pool` step of an `odd` graph on a plane of at most 8 pixels -- so the family cannot give that; the mixed graphs of
+    tests/test_gpu_mixed_fuzz.py and golden G21 do."""
     import numpy as np
     import torch
     from engine_doubles import OracleCollector, OracleQuantizer
@@ -127,7 +131,9 @@ def test_random_graphs_reconmodel_logits_equal_the_reference(g11, oracle, golden
         quantizer_cls = OracleQuantizer
 
     logits = np.load(os.path.join(G11_DIR, "g11_random_recon.npz"))
+    everything = dict(depthwise=True, concat=True, avgpool=True, grouped=True, relu6=True, flatten=True, shuffle=True, activations=True)
     checked = planned = 0
+    taken = {"resident_depthwise": 0, "resident_concats": 0}
     for tag in _tags():
         ref = g11[tag]
         if "reference_error" in ref:
@@ -151,6 +157,11 @@ def test_random_graphs_reconmodel_logits_equal_the_reference(g11, oracle, golden
                 np.testing.assert_array_equal(net(x).cpu().numpy(), want, err_msg=tag)
                 summary = resident.enable(net, x)
                 np.testing.assert_array_equal(net(x).cpu().numpy(), want, err_msg=tag + " (resident)")
+                wide = resident.enable(net, x, **everything)
+                np.testing.assert_array_equal(net(x).cpu().numpy(), want, err_msg=tag + " (resident, every switch on)")
             checked += 1
             planned += summary["resident_convs"]
+            for key in taken:
+                taken[key] += wide[key]
     assert checked >= 20 and planned > 150, (checked, planned)
+    assert all(v >= 1 for v in taken.values()), taken
