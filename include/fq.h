@@ -884,6 +884,21 @@ int fq_avgpool_i8_nhwc_supported(int kh, int kw, int sh, int sw, int ph, int pw,
 int fq_avgpool_i8_nhwc(const int8_t* x, int8_t* y, int N, int H, int W, int C, int Cpad, int kh, int kw, int sh, int sw,
                        int ph, int pw, int count_include_pad, int shift, int relu, fq_stream_t stream);
 
+/* The same pool over the exact int16 NHWC sum of a resident NewAdd (the wide output of fq_add_resident,
+ * fq_conv2d_i8_add_resident or fq_block_tail*_i8, value x * 2^-g, g <= 8): the ResNet-D shortcut AvgPool2d(2, 2) -> 1x1
+ * convolution reading ReLU(sum).  The rule is fq_avgpool_i8_nhwc's, word for word -- S, D, ONE fp32 division, 2^shift with
+ * shift = b - g, rint half to even, ReLU, clamp -- and stays the reference's chain for ANY int16 source:
+ * |S| <= 64 * 32768 = 2^21 < 2^24, so every partial sum of torch's fp32 accumulation and the conversion (float)S are exact.
+ * x: int16 [N][H][W][Cpad]; y: int8 [N][P][Q][Cpad], floor-mode P and Q; Cpad % 16 == 0, 1 <= C <= Cpad, both 16-byte aligned;
+ *   y[..][c] = 0 for c in [C, Cpad) whatever the source's padding channels hold.  Only aligned 16-byte loads inside
+ *   [x, x + 2*N*H*W*Cpad) are issued.
+ * Return codes: fq_avgpool_i8_nhwc's list; FQ_ERR_UNSUPPORTED for kh*kw > 64, |shift| > 8, or a source (2*N*H*W*Cpad bytes) or an
+ *   output of 2^31 - 1 bytes or more.  N == 0 is FQ_OK.
+ * fq_avgpool_i16_nhwc_supported: 1 when window, stride, padding and shift alone are taken (host arithmetic, no GPU needed). */
+int fq_avgpool_i16_nhwc_supported(int kh, int kw, int sh, int sw, int ph, int pw, int shift);
+int fq_avgpool_i16_nhwc(const int16_t* x, int8_t* y, int N, int H, int W, int C, int Cpad, int kh, int kw, int sh, int sw,
+                        int ph, int pw, int count_include_pad, int shift, int relu, fq_stream_t stream);
+
 /* ---- input files ------------------------------------------------------------------------------- */
 
 /* HOST helper for PRE_PROCESS.IMG = 2 (pytorch_quantizer.py:276-280: np.load of one CHW fp32 image per calibration item):

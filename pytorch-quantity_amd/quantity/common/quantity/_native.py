@@ -266,6 +266,10 @@ def lib():
     L.fq_avgpool_i8_nhwc_supported.argtypes = [ci] * 7
     L.fq_avgpool_i8_nhwc.restype = ci
     L.fq_avgpool_i8_nhwc.argtypes = [vp, vp] + [ci] * 14 + [vp]
+    L.fq_avgpool_i16_nhwc_supported.restype = ci
+    L.fq_avgpool_i16_nhwc_supported.argtypes = [ci] * 7
+    L.fq_avgpool_i16_nhwc.restype = ci
+    L.fq_avgpool_i16_nhwc.argtypes = [vp, vp] + [ci] * 14 + [vp]
     L.fq_add_resident.restype = ci
     L.fq_add_resident.argtypes = [vp, ci, ci, vp, ci, ci, vp, ci, vp, ci, ci, sz, vp]
     L.fq_dequant_nhwc_to_nchw.restype = ci
@@ -1663,6 +1667,36 @@ def avgpool_i8_nhwc(q, channels, kernel, stride, padding, count_include_pad, shi
     _check(lib().fq_avgpool_i8_nhwc(q.data_ptr(), out.data_ptr(), N, H, W, int(channels), cpad, int(kernel[0]), int(kernel[1]),
                                     int(stride[0]), int(stride[1]), int(padding[0]), int(padding[1]), 1 if count_include_pad else 0,
                                     int(shift), 1 if relu else 0, _stream(out)), "fq_avgpool_i8_nhwc")
+    return out
+
+
+def avgpool_i16_supported(kernel, stride, padding, shift):
+    """True when fq_avgpool_i16_nhwc takes this window, stride, padding and shift = consumer bit - grid of the sum (include/fq.h):
+    2 * padding <= kernel, at most 64 taps, |shift| <= 8.  Pure host arithmetic (no GPU needed)."""
+    return bool(lib().fq_avgpool_i16_nhwc_supported(int(kernel[0]), int(kernel[1]), int(stride[0]), int(stride[1]), int(padding[0]),
+                                                    int(padding[1]), int(shift)))
+
+
+def avgpool_i16_nhwc(q16, channels, kernel, stride, padding, count_include_pad, shift, relu, out=None):
+    """fq_avgpool_i16_nhwc: nn.AvgPool2d (floor mode) on the exact int16 sum [N, H, W, Cpad] of a NewAdd with `channels` real
+    channels, re-quantised by 2^shift for the convolution behind it, max(., 0) applied when relu -> int8 [N, P, Q, Cpad], padding
+    channels zero.  `out`: write there instead (that shape, dense, 16-byte aligned).  Launches on the current stream and does
+    not synchronise."""
+    _need_cuda(q16, torch.int16, "fq_avgpool_i16_nhwc")
+    assert q16.dim() == 4 and q16.is_contiguous()
+    N, H, W, cpad = (int(v) for v in q16.shape)
+    P = (H + 2 * int(padding[0]) - int(kernel[0])) // int(stride[0]) + 1
+    Q = (W + 2 * int(padding[1]) - int(kernel[1])) // int(stride[1]) + 1
+    if P < 1 or Q < 1:
+        raise FqError("fq_avgpool_i16_nhwc: the window %s does not fit the padded %d x %d plane" % (tuple(kernel), H, W))
+    if out is None:
+        out = torch.empty(N, P, Q, cpad, dtype=torch.int8, device=q16.device)
+    else:
+        _need_cuda(out, torch.int8, "fq_avgpool_i16_nhwc")
+        assert tuple(out.shape) == (N, P, Q, cpad) and out.is_contiguous()
+    _check(lib().fq_avgpool_i16_nhwc(q16.data_ptr(), out.data_ptr(), N, H, W, int(channels), cpad, int(kernel[0]), int(kernel[1]),
+                                     int(stride[0]), int(stride[1]), int(padding[0]), int(padding[1]), 1 if count_include_pad else 0,
+                                     int(shift), 1 if relu else 0, _stream(out)), "fq_avgpool_i16_nhwc")
     return out
 
 

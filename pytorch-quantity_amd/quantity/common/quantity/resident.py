@@ -318,22 +318,29 @@ class _AvgPoolResident(_InstanceForward):
 
 class _AvgPoolWindowResident(_InstanceForward):
     """Instance-level forward of a windowed nn.AvgPool2d between an int8 activation and the convolution(s) behind it
-    (enable(avgpool=True)): DeQuantity -> pool -> ReLU -> the consumers' Quantity in one kernel (fq_avgpool_i8_nhwc).  The result
-    has no exact integer form: the handle carries the narrow payload only, and anything but a NewConv2d at that bit that touches it
-    raises (QHandle.to_f32)."""
+    (enable(avgpool=True)): DeQuantity -> pool -> ReLU -> the consumers' Quantity in one kernel (fq_avgpool_i8_nhwc).  With
+    enable(avgpool=True, sums=True) the source may be the exact int16 sum of a NewAdd on the planned grid: that payload goes to
+    fq_avgpool_i16_nhwc, the same rule with int32 window sums; a ReLU between sum and pool is the add's fused one
+    (h.relu_done), one behind the pool is plan.relu.  The result has no exact integer form: the handle carries the narrow payload
+    only, and anything but a NewConv2d at that bit that touches it raises (QHandle.to_f32).  Every run-time miss falls back to the
+    module's own forward on the fp32 form."""
 
     def __call__(self, x):
         m = self.module
         plan = m.__dict__.get("_resident")
         h = resident_of(x)
         if (plan is None or plan.narrow_bit is None or plan.grid is None or h is None or h.exact is None or h.lossy
-                or h.exact.dtype != torch.int8 or h.exact.dim() != 4 or h.grid != plan.grid or not _avgpool_window_ok(m)):
+                or h.exact.dtype not in (torch.int8, torch.int16) or h.exact.dim() != 4 or h.grid != plan.grid
+                or not _avgpool_window_ok(m)):
             return type(m).forward(m, as_f32(x))
         k, st, pd = _pool_geometry(m)
         hh, ww = int(h.exact.shape[1]), int(h.exact.shape[2])
-        if (not _native.avgpool_supported(k, st, pd, plan.narrow_bit - h.grid) or hh + 2 * pd[0] < k[0] or ww + 2 * pd[1] < k[1]):
+        wide = h.exact.dtype == torch.int16                 # a NewAdd's exact sum (planned with sums=True)
+        supported, launch = ((_native.avgpool_i16_supported, _native.avgpool_i16_nhwc) if wide else
+                             (_native.avgpool_supported, _native.avgpool_i8_nhwc))
+        if (not supported(k, st, pd, plan.narrow_bit - h.grid) or hh + 2 * pd[0] < k[0] or ww + 2 * pd[1] < k[1]):
             return type(m).forward(m, as_f32(x))
-        y = _native.avgpool_i8_nhwc(h.exact, h.shape[1], k, st, pd, m.count_include_pad, plan.narrow_bit - h.grid, plan.relu)
+        y = launch(h.exact, h.shape[1], k, st, pd, m.count_include_pad, plan.narrow_bit - h.grid, plan.relu)
         return QHandle.wide_narrow(h.shape[1], None, None, y, plan.narrow_bit, plan.relu or h.relu_done)
 
 
@@ -640,6 +647,7 @@ def _clear(model):
     model.__dict__.pop("_fq_resident_relu6", None)
     model.__dict__.pop("_fq_resident_shuffle", None)
     model.__dict__.pop("_fq_resident_act", None)
+    model.__dict__.pop("_fq_resident_avgpool", None)
 
 
 def disable(model):
@@ -665,7 +673,7 @@ class _Planning(object):
     nothing on the model until install() writes the plans and the instance-level forwards to the modules."""
 
     def __init__(self, tracer, depthwise, concat, avgpool, grouped, relu6=False, flatten=False, shuffle=False, activations=False,
-                 revoked=None, names=None):
+                 revoked=None, names=None, sums=False):
         from .new_quantity_op import NewConv2d, NewAdd
         from .fabu_layer import Concat
         self.conv_type, self.concat_type = NewConv2d, Concat
@@ -692,6 +700,9 @@ class _Planning(object):
         self.add_resident = set()        # NewAdd modules whose operands arrive as integers
         self.int8_resident = set()       # nn.MaxPool2d, Concat, nearest-upsampling, nn.ChannelShuffle and Slice modules that run on the int8 integers
         self.avg_resident = {}           # windowed nn.AvgPool2d that runs on fq_avgpool_i8_nhwc -> (source grid g, consumer bit b)
+        self.sums = bool(sums)           # (avgpool=True, sums=True) a windowed pool may read a NewAdd's exact int16 sum
+        self.avg_sum = set()             # ... the pools of avg_resident that do (fq_avgpool_i16_nhwc)
+        self.avgpool_left = {}           # (sums=True) hooked windowed nn.AvgPool2d that stays torch's -> why
         self.plans = {}                  # producer module -> Plan
         self.forwards = []               # (module, its instance-level forward)
         self.summary = {"resident_convs": 0, "resident_adds": 0, "resident_pools": 0, "fused_relus": 0, "fp32_outputs": 0,
@@ -704,6 +715,8 @@ class _Planning(object):
             self.summary["flattened_concats"] = 0
         if avgpool:
             self.summary["resident_avgpools"] = 0
+        if sums:
+            self.summary["resident_sum_avgpools"] = 0
         if grouped:
             self.summary["resident_grouped"] = 0
         if relu6:
@@ -843,19 +856,60 @@ class _Planning(object):
         add, max-pool, upsampling or second pool takes it as an operand, it is handed to those convolutions only.  Left in fp32
         form (out of scope): a NewAdd sum (int16) as the source, consumers that are not all convolutions at one bit, ceil_mode,
         divisor_override, windows above 64 taps, |bit - grid| > 8, a pool called twice; F.avg_pool2d and nn.AdaptiveAvgPool2d stay
-        foreign.  The whole-plane pool in front of the head is served as before.  The summary then gains `resident_avgpools`."""
+        foreign.  The whole-plane pool in front of the head is served as before.  The summary then gains `resident_avgpools`.
+        `avgpool=True, sums=True` lifts the first exclusion: a source whose format is (2, g), the exact int16 sum of a resident
+        NewAdd -- the ResNet-D shortcut, AvgPool2d(2, 2) -> 1x1 convolution reading ReLU(sum) -- is taken under the same
+        conditions and runs on fq_avgpool_i16_nhwc (the same rule; |S| <= 64 * 32768 < 2^24 keeps it exact).  The add then
+        counts the pool as a reader of its exact integers (_readers) and writes no fp32 for it.  The pool's value still gets no
+        entry in fmt.  A pool over a sum whose window happens to be the whole plane -- the last shortcut of a ResNet-D at a small
+        input -- is planned the same way where its readers are convolutions (int8 out of one kernel instead of fp32 out of
+        fq_avgpool_global_nhwc and a re-quantisation); where they are not (the head's pool in front of View) it keeps the
+        whole-plane path.  The summary gains `resident_sum_avgpools`, and describe().avgpool_left names every hooked windowed
+        pool that stays torch's with its reason."""
         m = v.producer
-        f = self._int8_source(v)
-        if (self.avg_can_read(m) or f is None or not _avgpool_window_ok(m) or e.foreign or not e.consumers
-                or not all(self.conv_can_read(c) for (c, _pos) in e.consumers)):
+        if self.avg_can_read(m):                            # the whole-plane pool: _AvgPoolResident ...
+            f = self.fmt.get(id(v.src))
+            if self.sums and f is not None and f[0] == 2:   # ... unless it reads a sum and convolutions read it
+                self._avgpool_window_declined(v, e)
             return
+        why = self._avgpool_window_declined(v, e)
+        if why is not None and self.sums:
+            self.avgpool_left[m] = why
+
+    def _avgpool_window_declined(self, v, e):
+        """None when the windowed pool is planned (avg_resident), else why not."""
+        m = v.producer
+        f = self.fmt.get(id(v.src))
+        if not self.once(m):
+            return "the module was called more than once"
+        if f is None:
+            return "its source has no integer form in this plan (fp32 form)"
+        if f[0] != 1 and not (self.sums and f[0] == 2):
+            return "its source is a NewAdd sum (int16): needs sums=True (fp32 form)"
+        if m.ceil_mode:
+            return "ceil_mode=True: only floor-mode pools are taken (fp32 form)"
+        if not _avgpool_window_ok(m):
+            return "divisor_override is set (fp32 form)"
+        if e.foreign:
+            return "read as fp32 by code outside the plan, or it is a model output"
+        if not e.consumers:
+            return "nothing reads it"
+        for (c, _pos) in e.consumers:
+            if not self.conv_can_read(c):
+                return "read as fp32 by %s: only integer convolutions read a pooled value" % self._name(c)
         bits = set(c.input_bit for (c, _pos) in e.consumers)
         if len(bits) != 1:
-            return
+            return "its readers quantise at different bits %s" % sorted(bits)
         b = bits.pop()
         k, st, pd = _pool_geometry(m)
-        if min(st) >= 1 and _native.avgpool_supported(k, st, pd, b - f[1]):
-            self.avg_resident[m] = (f[1], b)
+        supported = _native.avgpool_i16_supported if f[0] == 2 else _native.avgpool_supported
+        if min(st) < 1 or not supported(k, st, pd, b - f[1]):
+            return ("window %dx%d, stride %s, padding %s, shift = bit %d - grid %d = %d: not taken by the kernel (at most 64 taps, "
+                    "|shift| <= 8, 2 * padding <= kernel)" % (k[0], k[1], st, pd, b, f[1], b - f[1]))
+        self.avg_resident[m] = (f[1], b)
+        if f[0] == 2:
+            self.avg_sum.add(m)
+        return None
 
     def _integer_operands(self, m):
         """(value, value, format, format) of the two operands of a NewAdd / Concat called once, if both are integers; or None."""
@@ -1045,6 +1099,8 @@ class _Planning(object):
                     plan.grid, plan.narrow_bit = self.avg_resident[v.producer]
                     self._take(v.producer, plan, relu_mod, _AvgPoolWindowResident)
                     self.summary["resident_avgpools"] += 1
+                    if v.producer in self.avg_sum:
+                        self.summary["resident_sum_avgpools"] += 1
             elif id(e) in self.fmt:                         # (anything else stays a plain fp32 producer)
                 self._plan_output(v, e, relu_mod)
 
@@ -1068,8 +1124,8 @@ class _Planning(object):
         for (c, _pos) in e.consumers:
             if self.conv_can_read(c):
                 bits.append(c.input_bit)
-            elif c in self.add_resident or self.avg_can_read(c):
-                exact += 1
+            elif c in self.add_resident or self.avg_can_read(c) or (v.kind == "add" and c in self.avg_sum):
+                exact += 1                                  # (a windowed pool over the sum reads the exact int16, as the whole-plane pool does)
             elif (c in self.int8_resident or c in self.avg_resident) and v.kind != "add":
                 int8 += 1                                   # int8 max-pool / Concat / nearest upsampling / windowed average pool
             else:
@@ -1242,7 +1298,7 @@ class _Planning(object):
 
     def hook_global_pools(self):
         for m in self.tracer.avgpool_shapes:
-            if self.avg_can_read(m):
+            if self.avg_can_read(m) and m not in self.avg_resident:
                 self.forwards.append((m, _AvgPoolResident(m)))
                 self.summary["resident_pools"] += 1
 
@@ -1263,6 +1319,13 @@ class _Planning(object):
                     self.shuffle_left[m] = "its input is not the output of a planned layer"
             names = dict((m, name) for name, m in model.named_modules())
             model.__dict__["_fq_resident_shuffle"] = dict((names.get(m, "?"), why) for m, why in self.shuffle_left.items())
+        if self.sums:
+            for m in self.tracer.calls:                     # (every hooked module that ran, a pool behind foreign code included)
+                if (isinstance(m, nn.AvgPool2d) and m not in self.plans and m not in self.avgpool_left
+                        and not self.avg_can_read(m)):
+                    self.avgpool_left[m] = "its input is not the output of a planned layer (no integer source)"
+            names = dict((m, name) for name, m in model.named_modules())
+            model.__dict__["_fq_resident_avgpool"] = dict((names.get(m, "?"), why) for m, why in self.avgpool_left.items())
         if self.activations:
             for m, (g, b) in self.act_grids.items():
                 self.plans[m].table = _native.build_act_table(m, g, b)
@@ -1304,7 +1367,7 @@ def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False, ac
 
 
 def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False, grouped=False, relu6=False,
-           flatten=False, shuffle=False, activations=False):
+           flatten=False, shuffle=False, activations=False, sums=False):
     """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
     on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
     nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
@@ -1320,18 +1383,23 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
     `shuffle=True` also plans nn.ChannelShuffle and the Slice marker on the int8 integers (_Planning._shuffle_format);
     `activations=True` also plans elementwise activations that are no clamp (nn.LeakyReLU, nn.Hardswish, nn.SiLU, ...) as a
     256-entry table between integer layers (_Planning._act_format).  The tables are built here: changing an nn.PReLU weight
-    afterwards needs a new enable()."""
+    afterwards needs a new enable();
+    `sums=True` (with `avgpool=True`; ValueError without) lets such a windowed pool read the exact int16 sum of a NewAdd -- the
+    ResNet-D shortcut -- on fq_avgpool_i16_nhwc (_plan_avgpool_window)."""
     from .new_quantity_op import QUANTIZE_BIT
     if flatten and not concat:
         raise ValueError("resident.enable(flatten=True) needs concat=True: only planned Concats are flattened")
+    if sums and not avgpool:
+        raise ValueError("resident.enable(sums=True) needs avgpool=True: only planned windowed pools read a NewAdd sum")
     _clear(model)
     if QUANTIZE_BIT != 8:
         raise _native.FqError("resident activations are defined for QUANTIZE_BIT = 8")
     tracer, traced_out = _trace(model, example_input, concat, avgpool, relu6, shuffle, activations)
-    names = dict((m, name) for name, m in model.named_modules()) if activations else None
+    names = dict((m, name) for name, m in model.named_modules()) if activations or sums else None
     revoked = {}
     while True:
-        planning = _Planning(tracer, depthwise, concat, avgpool, grouped, relu6, flatten, shuffle, activations, revoked, names)
+        planning = _Planning(tracer, depthwise, concat, avgpool, grouped, relu6, flatten, shuffle, activations, revoked, names,
+                             sums)
         planning.plan_formats()
         planning.plan_outputs()
         planning.defer_convs()
@@ -1364,8 +1432,11 @@ class _Description(dict):
     enable(flatten=True) `flattened_concats` names the Concats that launch nothing of their own.  After enable(shuffle=True)
     `shuffle_left` is {module name: why} for every hooked nn.ChannelShuffle / Slice that stays torch's.  After
     enable(activations=True) `activations_left` is {module name: why} for every hooked elementwise activation that stays torch's,
-    and `activations_revoked` names those among them that a first plan had accepted and the lossy-value verification took back."""
+    and `activations_revoked` names those among them that a first plan had accepted and the lossy-value verification took back.
+    After enable(avgpool=True, sums=True) `avgpool_left` is {module name: why} for every hooked windowed nn.AvgPool2d that stays
+    torch's."""
     activations_left = {}
+    avgpool_left = {}
     activations_revoked = ()
     fused_relu6s = 0
     relu6_left = {}
@@ -1379,6 +1450,7 @@ def describe(model):
     d.fused_relu6s, d.relu6_left = model.__dict__.get("_fq_resident_relu6", (0, {}))
     d.shuffle_left = model.__dict__.get("_fq_resident_shuffle", {})
     d.activations_left, d.activations_revoked = model.__dict__.get("_fq_resident_act", ({}, ()))
+    d.avgpool_left = model.__dict__.get("_fq_resident_avgpool", {})
     d.flattened_concats = tuple(name for name, m in model.named_modules()
                                 if type(m).__name__ == "Concat" and name in d and d[name].defer)
     return d
