@@ -843,6 +843,21 @@ int fq_block_tail_proj_i8(const int8_t* x_nhwc, const int8_t* w3_krsc, const flo
 int fq_add_resident(const void* x, int x_bytes, int gx, const void* y, int y_bytes, int gy, int16_t* wide,
                     int g_wide, int8_t* narrow, int ib, int relu, size_t n, fq_stream_t stream);
 
+/* The same add with its second operand read through a nearest upsampling by `up` (2 or 4), which is never materialised: the FPN
+ * top-down step Eltwise(lateral, up(top)).  x and both outputs are [N][H][W][Cpad], y is [N][H / up][W / up][Cpad]; each is int8
+ * or int16 as in fq_add_resident (y_bytes = 2: the exact sum of the add one level up).  Per element
+ *   out[n][h][w][c] = fq_add_resident's expression of (x[n][h][w][c], y[n][h / up][w / up][c])
+ * with the same parameters and the same arithmetic (nearest upsampling repeats values; addition commutes exactly, so callers put
+ * whichever operand is upsampled in y).  wide / narrow may be NULL (not both).
+ * Cpad % 16 == 0, H % up == 0 and W % up == 0, all four pointers 16-byte aligned: FQ_ERR_INVALID_ARG otherwise, as for x_bytes or
+ *   y_bytes outside {1, 2}, a negative size, no output, a null operand, or a grid or bit outside [-16, 16].  FQ_ERR_UNSUPPORTED for
+ *   any other `up`, and where fq_add_resident returns it (g_wide != max(0, gx, gy) or > 8).  Nothing is launched on an error.
+ *   N, H, W or Cpad == 0 is FQ_OK.  Offsets are computed in size_t: no size limit below the address space.
+ * fq_add_up_resident_supported: 1 when the factor and the shape alone are taken (host arithmetic, no GPU needed). */
+int fq_add_up_resident(const void* x, int x_bytes, int gx, const void* y, int y_bytes, int gy, int up, int16_t* wide,
+                       int g_wide, int8_t* narrow, int ib, int relu, int N, int H, int W, int Cpad, fq_stream_t stream);
+int fq_add_up_resident_supported(int up, int H, int W, int Cpad);
+
 /* Leaving the resident domain (DeQuantity, :66-68, fused with the layout change):
  *   y[n][c][hw] = q[n][hw][c] * 2^-g,   q: int8 / int16 (q_bytes 1 / 2) NHWC [N][HW][Cpad], y: fp32 NCHW. */
 int fq_dequant_nhwc_to_nchw(const void* q_nhwc, int q_bytes, int g, float* y_nchw, int N, int C, int HW,

@@ -272,6 +272,10 @@ def lib():
     L.fq_avgpool_i16_nhwc.argtypes = [vp, vp] + [ci] * 14 + [vp]
     L.fq_add_resident.restype = ci
     L.fq_add_resident.argtypes = [vp, ci, ci, vp, ci, ci, vp, ci, vp, ci, ci, sz, vp]
+    L.fq_add_up_resident.restype = ci
+    L.fq_add_up_resident.argtypes = [vp, ci, ci, vp, ci, ci, ci, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp]
+    L.fq_add_up_resident_supported.restype = ci
+    L.fq_add_up_resident_supported.argtypes = [ci] * 4
     L.fq_dequant_nhwc_to_nchw.restype = ci
     L.fq_dequant_nhwc_to_nchw.argtypes = [vp, ci, ci, vp, ci, ci, ci, ci, vp]
     L.fq_maxpool_i8_nhwc.restype = ci
@@ -1464,6 +1468,31 @@ def add_resident(x, gx, y, gy, want_wide, g_wide, want_narrow, ib, relu):
     _check(lib().fq_add_resident(x.data_ptr(), _INT_BYTES[x.dtype], int(gx), y.data_ptr(), _INT_BYTES[y.dtype], int(gy),
                                  _ptr(wide), int(g_wide), _ptr(narrow), int(ib), 1 if relu else 0, x.numel(),
                                  _stream(x)), "fq_add_resident")
+    return wide, narrow
+
+
+def add_up_supported(up, H, W, cpad):
+    """True when fq_add_up_resident takes an [*, H, W, cpad] output whose second operand is upsampled by `up` (include/fq.h):
+    up in {2, 4}, H and W multiples of it, cpad a positive multiple of 16.  Host arithmetic, no GPU needed."""
+    return bool(lib().fq_add_up_resident_supported(int(up), int(H), int(W), int(cpad)))
+
+
+def add_up_resident(x, gx, y, gy, up, want_wide, g_wide, want_narrow, ib, relu):
+    """fq_add_up_resident: the resident add of x [N, H, W, Cpad] and the nearest upsampling by `up` of y [N, H / up, W / up, Cpad]
+    (int8 / int16 NHWC each), the upsampled tensor never written: returns (wide int16 or None, narrow int8 or None) as
+    add_resident does."""
+    for t in (x, y):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype not in _INT_BYTES:
+            raise FqError("fq_add_up_resident: expected int8 / int16 torch.cuda tensors")
+    up = int(up)
+    if x.dim() != 4 or y.dim() != 4 or tuple(x.shape) != (y.shape[0], y.shape[1] * up, y.shape[2] * up, y.shape[3]):
+        raise FqError("fq_add_up_resident: %s is not %s upsampled by %d" % (tuple(x.shape), tuple(y.shape), up))
+    assert x.is_contiguous() and y.is_contiguous() and (want_wide or want_narrow)
+    wide, narrow = _wide_narrow(x.shape, x.device, want_wide, want_narrow)
+    N, H, W, cpad = (int(v) for v in x.shape)
+    _check(lib().fq_add_up_resident(x.data_ptr(), _INT_BYTES[x.dtype], int(gx), y.data_ptr(), _INT_BYTES[y.dtype], int(gy), up,
+                                    _ptr(wide), int(g_wide), _ptr(narrow), int(ib), 1 if relu else 0, N, H, W, cpad,
+                                    _stream(x)), "fq_add_up_resident")
     return wide, narrow
 
 

@@ -21,7 +21,7 @@ import torch
 from torch import nn
 
 from . import _native, _float_conv
-from .resident import QHandle, DeferredConv, resident_of, as_f32, block_tail_enabled, _emit
+from .resident import QHandle, DeferredConv, DeferredUpsample, resident_of, as_f32, block_tail_enabled, _emit
 
 QUANTIZE_BIT = 8
 
@@ -449,6 +449,10 @@ class NewAdd(nn.Module):
     def forward(self, x, y):
         plan = self.__dict__.get("_resident")             # set by common.quantity.resident.enable()
         if plan is not None and plan.resident_add and self.Sp.bitwidth == 8:
+            if type(x) is DeferredUpsample or type(y) is DeferredUpsample:
+                out = _newadd_upsampled_operand(plan, x, y)     # (resident.enable(topdown=True))
+                if out is not None:
+                    return out
             fused = self._fused_conv_add(plan, x, y)
             if fused is not None:
                 return fused
@@ -465,6 +469,29 @@ class NewAdd(nn.Module):
             out = torch.relu_(out)                        # the ReLU module after this add passes through
             out._fq_relu_done = True
         return out
+
+
+def _newadd_upsampled_operand(plan, x, y):
+    """The add of a resident activation and a DeferredUpsample (resident.enable(concat=True, topdown=True)): one launch of
+    fq_add_up_resident reads the coarse tensor -- int8, or the int16 sum of the add one level up -- at (h / s, w / s); the
+    upsampled tensor is never written.  The factor comes from the operand.  None on any miss -- both operands upsampled, an
+    operand materialised already, no exact payload, a `lossy` operand, a shape or plan grid that disagrees --: the caller goes on
+    with the values (DeferredUpsample.materialise)."""
+    if type(x) is DeferredUpsample and type(y) is DeferredUpsample:
+        return None
+    d, other = (x, y) if type(x) is DeferredUpsample else (y, x)
+    hc, ho = d.handle, resident_of(other)
+    if (d._out is not None or ho is None or ho.exact is None or hc.exact is None or ho.lossy or hc.lossy or ho.exact.dim() != 4
+            or hc.exact.dim() != 4 or max(0, ho.grid, hc.grid) != plan.grid):
+        return None
+    n, h, w, cpad = (int(v) for v in hc.exact.shape)
+    if (tuple(ho.exact.shape) != (n, h * d.s, w * d.s, cpad) or ho.shape[1] != hc.shape[1]
+            or not _native.add_up_supported(d.s, h * d.s, w * d.s, cpad)):
+        return None
+    want_wide, want_narrow = plan.sum_outputs()
+    wide, narrow = _native.add_up_resident(ho.exact, ho.grid, hc.exact, hc.grid, d.s, want_wide, plan.grid, want_narrow,
+                                           plan.narrow_bit if want_narrow else 0, plan.relu)
+    return _emit(plan, QHandle(ho.shape, wide, plan.grid, narrow, plan.narrow_bit, plan.relu))
 
 
 _BT_ALONE_MAX_C = int(os.environ.get("FQ_BT_ALONE_MAX_C", "64"))     # conv3 + NewAdd WITHOUT a next conv1 on fq_block_tail_i8 up to this width

@@ -104,21 +104,31 @@ class DeferredConv(object):
 class DeferredUpsample(object):
     """A nearest upsampling whose only consumer is a resident Concat (enable(concat=True)): nothing has been launched, the
     Concat reads the small tensor with the factor as its operand's `up` (fq_concat_i8_nhwc), so the s*s times larger tensor is
-    neither written nor read back.  Anything else that touches it materialises the upsampled activation."""
-    __slots__ = ("handle", "s", "_out")
+    neither written nor read back.  Anything else that touches it materialises the upsampled activation.
+    With enable(concat=True, topdown=True) the consumers are resident NewAdds (fq_add_up_resident) and the coarse handle's exact
+    payload may be the int16 sum of another add.  No integer kernel upsamples int16: materialise() then returns the fp32 tensor
+    that `module`'s own forward makes of the de-quantised coarse tensor (the values the reference computes), and resident_of()
+    reports no integer form."""
+    __slots__ = ("handle", "s", "_out", "module")
 
-    def __init__(self, handle, s):
-        self.handle, self.s, self._out = handle, int(s), None
+    def __init__(self, handle, s, module=None):
+        self.handle, self.s, self._out, self.module = handle, int(s), None, module
 
     def materialise(self):
         if self._out is None:
             h = self.handle
-            y = _native.concat_i8_nhwc([(h.exact, h.shape[1], self.s)], False)
-            self._out = _moved(QHandle.int8(y, h.shape[1], h.grid, h.relu_done), h)
+            if h.exact is not None and h.exact.dtype == torch.int16:
+                self._out = type(self.module).forward(self.module, h.to_f32())
+                if h.relu_done:
+                    self._out._fq_relu_done = True
+            else:
+                y = _native.concat_i8_nhwc([(h.exact, h.shape[1], self.s)], False)
+                self._out = _moved(QHandle.int8(y, h.shape[1], h.grid, h.relu_done), h)
         return self._out
 
     def to_f32(self):
-        return self.materialise().to_f32()
+        out = self.materialise()
+        return out.to_f32() if type(out) is QHandle else out
 
 
 MAX_CONCAT_LEAVES = _native.CONCAT_N_MAX_SRC       # sources of one fq_concat_n_i8_nhwc launch
@@ -189,7 +199,8 @@ def resident_of(x):
     if type(x) is QHandle:
         return x
     if type(x) in (DeferredConv, DeferredUpsample, DeferredConcat):
-        return x.materialise()
+        out = x.materialise()
+        return out if type(out) is QHandle else None         # (an upsampled int16 sum has the fp32 form only)
     h = getattr(x, "_fq_resident", None)
     if h is not None and getattr(x, "_fq_resident_version", None) != x._version:
         return None                                          # written to since its producer attached the integers
@@ -219,7 +230,7 @@ class Plan(object):
         self.narrow_to_hbm = True    # NewAdd with fuse_next: somebody besides that convolution reads the int8 re-quantisation
         self.fuse_proj = False       # NewAdd with fuse_arg: the OTHER operand is a deferred 1x1 projection that the kernel computes too
         self.depthwise = False       # NewConv2d: a depthwise layer taken by enable(depthwise=True); runs on fq_dwconv2d_i8_resident
-        self.up = None               # nearest upsampling taken by enable(concat=True): its factor (with `defer`: the Concat applies it)
+        self.up = None               # nearest upsampling taken by enable(concat=True): its factor (with `defer`: the Concat applies it -- or, with topdown=True, the NewAdd)
         self.grouped = False         # NewConv2d: a grouped layer taken by enable(grouped=True); runs on fq_gconv2d_i8_resident
         self.clip = False            # NewConv2d with `relu`: the fused activation is an nn.ReLU6 (enable(relu6=True)): clipped at 6
         self.perm = None             # nn.ChannelShuffle / Slice taken by enable(shuffle=True): (c_off, C, groups) of fq_shuffle_i8_nhwc
@@ -466,6 +477,22 @@ class _UpsampleResident(_InstanceForward):
         return _emit(plan, _moved(QHandle.int8(y, h.shape[1], h.grid, plan.relu or h.relu_done), h))
 
 
+class _UpsampleTopDown(_InstanceForward):
+    """Instance-level forward of a nearest upsampling whose readers are resident NewAdds (enable(concat=True, topdown=True)):
+    nothing runs here.  The coarse handle -- int8, or the exact int16 sum of the add one level up -- goes to the add as a
+    DeferredUpsample, and the add reads it at (h / s, w / s) (fq_add_up_resident).  A run-time miss -- no integer payload on the
+    planned grid -- runs the module's own forward on the fp32 form."""
+
+    def __call__(self, x):
+        m = self.module
+        plan = m.__dict__.get("_resident")
+        h = resident_of(x)
+        if (plan is None or plan.up is None or not plan.defer or plan.up != _upsample_factor(m) or h is None or h.exact is None
+                or h.exact.dtype not in (torch.int8, torch.int16) or h.exact.dim() != 4 or h.grid != plan.narrow_bit):
+            return type(m).forward(m, as_f32(x))
+        return DeferredUpsample(h, plan.up, m)
+
+
 class _ConcatResident(_InstanceForward):
     """Instance-level forward of a Concat marker whose operands are int8 NHWC on one grid: concatenating the integers is
     concatenating the values (fq_concat_i8_nhwc, the nn.ReLU behind it fused).  An operand that arrives as a DeferredUpsample is
@@ -648,6 +675,7 @@ def _clear(model):
     model.__dict__.pop("_fq_resident_shuffle", None)
     model.__dict__.pop("_fq_resident_act", None)
     model.__dict__.pop("_fq_resident_avgpool", None)
+    model.__dict__.pop("_fq_resident_topdown", None)
 
 
 def disable(model):
@@ -673,7 +701,7 @@ class _Planning(object):
     nothing on the model until install() writes the plans and the instance-level forwards to the modules."""
 
     def __init__(self, tracer, depthwise, concat, avgpool, grouped, relu6=False, flatten=False, shuffle=False, activations=False,
-                 revoked=None, names=None, sums=False):
+                 revoked=None, names=None, sums=False, topdown=False, revoked_up=None):
         from .new_quantity_op import NewConv2d, NewAdd
         from .fabu_layer import Concat
         self.conv_type, self.concat_type = NewConv2d, Concat
@@ -703,6 +731,11 @@ class _Planning(object):
         self.sums = bool(sums)           # (avgpool=True, sums=True) a windowed pool may read a NewAdd's exact int16 sum
         self.avg_sum = set()             # ... the pools of avg_resident that do (fq_avgpool_i16_nhwc)
         self.avgpool_left = {}           # (sums=True) hooked windowed nn.AvgPool2d that stays torch's -> why
+        self.topdown = bool(topdown)     # (concat=True, topdown=True) a NewAdd reads its upsampled operand at (h / s, w / s)
+        self.revoked_up = dict(revoked_up or {})    # ... upsampling that an earlier round planned so and verify_topdown() took back -> why
+        self.topdown_ups = {}            # ... planned upsampling -> (bytes, grid) of its source
+        self.topdown_adds = set()        # ... the NewAdd modules that take such an operand
+        self.topdown_left = {}           # ... hooked upsampling in front of a NewAdd that keeps its earlier plan -> why
         self.plans = {}                  # producer module -> Plan
         self.forwards = []               # (module, its instance-level forward)
         self.summary = {"resident_convs": 0, "resident_adds": 0, "resident_pools": 0, "fused_relus": 0, "fp32_outputs": 0,
@@ -725,6 +758,8 @@ class _Planning(object):
             self.summary["resident_shuffles"] = self.summary["resident_slices"] = 0
         if activations:
             self.summary["resident_activations"] = 0
+        if topdown:
+            self.summary["topdown_adds"] = self.summary["topdown_sum_sources"] = 0
 
     # ---- what a value is and what a module can do
 
@@ -828,6 +863,8 @@ class _Planning(object):
                 f = self._int8_source(v) if s is not None and len(v.shape) == 4 else None
                 if f is not None and not _native.concat_supported([v.shape[1]], [s]):
                     f = None
+                if self.topdown:
+                    f = self._topdown_format(v, relu_mod, f)
             elif v.kind == "avgpool":
                 self._plan_avgpool_window(v, e)             # (the value itself has no integer format)
             elif v.kind == "concat":
@@ -838,6 +875,9 @@ class _Planning(object):
                 f = self._act_format(v)
             else:
                 f = self._add_format(v)
+                ops = self.operands.get(m) or ()
+                if f is not None and any(o is not None and o.kind == "upsample" and o.producer in self.topdown_ups for o in ops):
+                    self.topdown_adds.add(m)
             if f is not None:
                 self.fmt[id(e)] = f
                 if v.kind != "contraction":
@@ -847,6 +887,83 @@ class _Planning(object):
         """The format of the value that a max-pool / upsampling / average pool called once reads, if that is int8."""
         f = self.fmt.get(id(v.src))
         return f if f is not None and f[0] == 1 and self.once(v.producer) else None
+
+    def _topdown_format(self, v, relu_mod, f_off):
+        """`concat=True, topdown=True` plans a nearest upsampling by 2 or 4 whose readers are NewAdds -- the FPN top-down step
+        Eltwise(lateral, up(top)) -- as an operand of those adds: the module launches nothing (Plan.up = s, Plan.defer = True,
+        integers only), each add reads the coarse tensor at (h / s, w / s) (fq_add_up_resident) and the upsampled tensor is never
+        written.  The source may be an int8 activation (format (1, g)) or the exact int16 sum of a resident NewAdd ((2, g), with
+        that add's fused ReLU, if any): nearest upsampling repeats values, so the add's arithmetic is unchanged.  The sum in front
+        counts the upsampling as a reader of its exact integers (_readers) and writes no fp32 for it.  Taken when the module is
+        called once, every reader is a NewAdd called once and no ReLU sits between the upsampling and the add; verify_topdown()
+        then checks the adds.  Returns the format of the upsampled value: the source's when planned, else `f_off`, what the plan
+        without the switch gives it, with the reason in topdown_left (describe().topdown_left) where a NewAdd reads it or it
+        reads a sum.  Left as they were: `size=` forms, other factors and modes (foreign code: not hooked), a module called
+        twice, any reader besides NewAdds, a ReLU behind the upsampling, both operands of an add upsampled, planes the factor
+        does not divide.  The summary gains `topdown_adds` and `topdown_sum_sources`."""
+        m = v.producer
+        src = self.fmt.get(id(v.src))
+        root = v.src.src if v.src.kind == "relu" and v.src.src is not None else v.src
+        adds = [c for (c, _pos) in v.consumers if self.tracer._kind(c) == "add"]
+        behind = self.relu_value.get(id(v))                 # the value of a ReLU that reads the upsampling, if there is one
+        relu_adds = [c for (c, _pos) in behind.consumers if self.tracer._kind(c) == "add"] if behind is not None else []
+        over_sum = src is not None and src[0] == 2
+        if not adds and not relu_adds and not over_sum:
+            return f_off                                    # an upsampling in front of a Concat or a convolution: not this switch's
+        s = _upsample_factor(m)
+        why = None
+        if not self.once(m):
+            why = "the module was called more than once"
+        elif src is None:
+            why = "its source has no integer form in this plan (fp32 form)"
+        elif over_sum and root.kind != "add":
+            why = "its source is int16 but no NewAdd sum (fp32 form)"
+        elif len(v.shape) != 4:
+            why = "its input is not 4-D"
+        elif relu_mod is not None or relu_adds:
+            why = "a ReLU sits between the upsampling and the add"
+        elif v.foreign or len(adds) != len(v.consumers) or not adds:
+            others = [self._name(c) for (c, _pos) in v.consumers if self.tracer._kind(c) != "add"]
+            why = "read by %s besides the NewAdd: every reader must be a NewAdd%s" % (
+                ", ".join(others) if others else "code outside the plan", " (a sum has no upsampled integer form: fp32 form)" if over_sum else "")
+        elif not all(self.once(c) for c in adds):
+            why = "a NewAdd that reads it was called more than once"
+        elif not _native.add_up_supported(s, v.shape[2], v.shape[3], _native.pad16(v.shape[1])):
+            why = "the %dx%d plane is not divisible by the factor %d" % (v.shape[2], v.shape[3], s)
+        elif m in self.revoked_up:
+            why = self.revoked_up[m]
+        if why is None:
+            self.topdown_ups[m] = src
+            return src
+        self.topdown_left[m] = why
+        return f_off
+
+    def verify_topdown(self):
+        """{upsampling: why} for every one planned by _topdown_format whose adds, after all passes, cannot take it: an add that
+        is not resident (its other operand has no integer form, or the grid does not fit int16), or one whose operands are both
+        upsampled.  enable() plans again without them, as it does for verify_lossy()."""
+        bad = {}
+        for v in self.tracer.produced:
+            m = v.producer
+            if v.kind != "upsample" or m not in self.topdown_ups:
+                continue
+            for (c, pos) in v.consumers:
+                ops = self.operands.get(c)
+                other = ops[1 - pos] if ops is not None and pos < 2 else None
+                if c not in self.add_resident or c not in self.plans or not self.plans[c].resident_add or other is None:
+                    bad[m] = "the NewAdd %s that reads it is not resident (its other operand has no integer form)" % self._name(c)
+                elif other.kind == "upsample" and (other.producer in self.topdown_ups or other is v):
+                    bad[m] = "both operands of the NewAdd %s are upsampled" % self._name(c)
+                elif other.shape is None or tuple(other.shape) != tuple(v.shape):
+                    bad[m] = "the operands of the NewAdd %s differ in shape" % self._name(c)
+        return bad
+
+    def count_topdown(self):
+        for v in self.tracer.produced:
+            if v.kind == "add" and v.producer in self.topdown_adds and v.producer in self.plans:
+                self.summary["topdown_adds"] += 1
+                ups = [o.producer for o in self.operands[v.producer] if o.kind == "upsample" and o.producer in self.topdown_ups]
+                self.summary["topdown_sum_sources"] += sum(1 for u in ups if self.topdown_ups[u][0] == 2)
 
     def _plan_avgpool_window(self, v, e):
         """`avgpool=True` plans a windowed nn.AvgPool2d (the pool branch of an Inception block, the 2x2 pool of a transition) that
@@ -1124,8 +1241,10 @@ class _Planning(object):
         for (c, _pos) in e.consumers:
             if self.conv_can_read(c):
                 bits.append(c.input_bit)
-            elif c in self.add_resident or self.avg_can_read(c) or (v.kind == "add" and c in self.avg_sum):
-                exact += 1                                  # (a windowed pool over the sum reads the exact int16, as the whole-plane pool does)
+            elif (c in self.add_resident or self.avg_can_read(c) or (v.kind == "add" and c in self.avg_sum)
+                  or (v.kind == "add" and c in self.topdown_ups)):
+                exact += 1                                  # (a windowed pool over the sum reads the exact int16, as the whole-plane pool does;
+                                                            #  so does an upsampling in front of a NewAdd, topdown=True)
             elif (c in self.int8_resident or c in self.avg_resident) and v.kind != "add":
                 int8 += 1                                   # int8 max-pool / Concat / nearest upsampling / windowed average pool
             else:
@@ -1158,11 +1277,14 @@ class _Planning(object):
             self.summary["resident_grouped"] += 1
         if v.kind == "upsample":
             plan.up = _upsample_factor(m)
+        forward = _FORWARD.get(v.kind)
+        if v.kind == "upsample" and m in self.topdown_ups:  # (nothing is launched: the adds behind it read the coarse tensor)
+            plan.defer, plan.emit_int, plan.emit_f32, forward = True, True, False, _UpsampleTopDown
         if v.kind in ("shuffle", "slice"):
             plan.perm = self.perm[m]
         if v.kind == "act":
             plan.grid = self.act_grids[m][0]
-        self._take(m, plan, relu_mod, _FORWARD.get(v.kind))
+        self._take(m, plan, relu_mod, forward)
         self.summary[_COUNTER[v.kind]] += 1
 
     # ---- fusion passes (in this order: fuse_projections reads the fuse_next that fuse_block_tails sets)
@@ -1171,6 +1293,8 @@ class _Planning(object):
         """A convolution whose value goes to one resident add and nowhere else is run BY that add (DeferredConv)."""
         self.summary["fused_conv_adds"] = 0
         for add_mod, add_plan, ops, _va in self.resident_adds():
+            if add_mod in self.topdown_adds:                # (its other operand stays a handle: the lateral convolution launches itself)
+                continue
             for pos in (0, 1):
                 v = ops[pos]
                 plan = self.plans.get(v.producer) if isinstance(v.producer, self.conv_type) else None
@@ -1244,7 +1368,8 @@ class _Planning(object):
         self.summary["fused_upsamples"] = 0
         for v in self.tracer.produced:
             plan = self.plans.get(v.producer)
-            if v.kind != "upsample" or plan is None or plan.up is None or plan.relu or plan.emit_f32 or v.foreign:
+            if (v.kind != "upsample" or plan is None or plan.up is None or plan.relu or plan.emit_f32 or v.foreign
+                    or v.producer in self.topdown_ups):
                 continue
             if (len(v.consumers) != 1 or v.consumers[0][0] not in self.int8_resident
                     or not isinstance(v.consumers[0][0], self.concat_type)):
@@ -1326,6 +1451,13 @@ class _Planning(object):
                     self.avgpool_left[m] = "its input is not the output of a planned layer (no integer source)"
             names = dict((m, name) for name, m in model.named_modules())
             model.__dict__["_fq_resident_avgpool"] = dict((names.get(m, "?"), why) for m, why in self.avgpool_left.items())
+        if self.topdown:
+            for m in model.modules():                       # (what _trace did not hook: foreign code, named all the same)
+                if isinstance(m, nn.Upsample) and _upsample_factor(m) is None:
+                    self.topdown_left[m] = ("no nearest upsampling by one integer scale_factor of 2 or 4 (a `size=` form, another "
+                                            "factor or another mode): foreign code")
+            names = dict((m, name) for name, m in model.named_modules())
+            model.__dict__["_fq_resident_topdown"] = dict((names.get(m, "?"), why) for m, why in self.topdown_left.items())
         if self.activations:
             for m, (g, b) in self.act_grids.items():
                 self.plans[m].table = _native.build_act_table(m, g, b)
@@ -1367,7 +1499,7 @@ def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False, ac
 
 
 def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False, grouped=False, relu6=False,
-           flatten=False, shuffle=False, activations=False, sums=False):
+           flatten=False, shuffle=False, activations=False, sums=False, topdown=False):
     """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
     on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
     nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
@@ -1385,21 +1517,26 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
     256-entry table between integer layers (_Planning._act_format).  The tables are built here: changing an nn.PReLU weight
     afterwards needs a new enable();
     `sums=True` (with `avgpool=True`; ValueError without) lets such a windowed pool read the exact int16 sum of a NewAdd -- the
-    ResNet-D shortcut -- on fq_avgpool_i16_nhwc (_plan_avgpool_window)."""
+    ResNet-D shortcut -- on fq_avgpool_i16_nhwc (_plan_avgpool_window);
+    `topdown=True` (with `concat=True`; ValueError without) lets a NewAdd read an operand through a nearest upsampling by 2 or 4
+    -- the FPN top-down step, over an int8 activation or the int16 sum of the add above -- on fq_add_up_resident, the upsampled
+    tensor never written (_Planning._topdown_format)."""
     from .new_quantity_op import QUANTIZE_BIT
     if flatten and not concat:
         raise ValueError("resident.enable(flatten=True) needs concat=True: only planned Concats are flattened")
     if sums and not avgpool:
         raise ValueError("resident.enable(sums=True) needs avgpool=True: only planned windowed pools read a NewAdd sum")
+    if topdown and not concat:
+        raise ValueError("resident.enable(topdown=True) needs concat=True: the upsampling is hooked by that switch")
     _clear(model)
     if QUANTIZE_BIT != 8:
         raise _native.FqError("resident activations are defined for QUANTIZE_BIT = 8")
     tracer, traced_out = _trace(model, example_input, concat, avgpool, relu6, shuffle, activations)
-    names = dict((m, name) for name, m in model.named_modules()) if activations or sums else None
-    revoked = {}
+    names = dict((m, name) for name, m in model.named_modules()) if activations or sums or topdown else None
+    revoked, revoked_up = {}, {}
     while True:
         planning = _Planning(tracer, depthwise, concat, avgpool, grouped, relu6, flatten, shuffle, activations, revoked, names,
-                             sums)
+                             sums, topdown, revoked_up)
         planning.plan_formats()
         planning.plan_outputs()
         planning.defer_convs()
@@ -1411,9 +1548,13 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
             planning.defer_concats()
         planning.hook_global_pools()
         bad = planning.verify_lossy() if activations else {}
-        if not bad:
+        bad_up = planning.verify_topdown() if topdown else {}
+        if not bad and not bad_up:
             break
         revoked.update(bad)                                 # (each round takes at least one activation out: it ends)
+        revoked_up.update(bad_up)                           # (... or one upsampling)
+    if topdown:
+        planning.count_topdown()
     planning.install(model)
     if verify:
         with torch.no_grad():
@@ -1434,9 +1575,11 @@ class _Description(dict):
     enable(activations=True) `activations_left` is {module name: why} for every hooked elementwise activation that stays torch's,
     and `activations_revoked` names those among them that a first plan had accepted and the lossy-value verification took back.
     After enable(avgpool=True, sums=True) `avgpool_left` is {module name: why} for every hooked windowed nn.AvgPool2d that stays
-    torch's."""
+    torch's.  After enable(concat=True, topdown=True) `topdown_left` is {module name: why} for every nearest upsampling in front
+    of a NewAdd (or over a sum) that keeps the plan it had without the switch, and for every nn.Upsample that is foreign code."""
     activations_left = {}
     avgpool_left = {}
+    topdown_left = {}
     activations_revoked = ()
     fused_relu6s = 0
     relu6_left = {}
@@ -1451,6 +1594,7 @@ def describe(model):
     d.shuffle_left = model.__dict__.get("_fq_resident_shuffle", {})
     d.activations_left, d.activations_revoked = model.__dict__.get("_fq_resident_act", ({}, ()))
     d.avgpool_left = model.__dict__.get("_fq_resident_avgpool", {})
+    d.topdown_left = model.__dict__.get("_fq_resident_topdown", {})
     d.flattened_concats = tuple(name for name, m in model.named_modules()
                                 if type(m).__name__ == "Concat" and name in d and d[name].defer)
     return d
