@@ -914,6 +914,33 @@ int fq_avgpool_i16_nhwc_supported(int kh, int kw, int sh, int sw, int ph, int pw
 int fq_avgpool_i16_nhwc(const int16_t* x, int8_t* y, int N, int H, int W, int C, int Cpad, int kh, int kw, int sh, int sw,
                         int ph, int pw, int count_include_pad, int shift, int relu, fq_stream_t stream);
 
+/* nn.Upsample(scale_factor=up, mode="bilinear", align_corners=False), up 2 or 4, on a resident int8 NHWC activation, re-quantised
+ * for the convolutions behind it.  The reference's chain is DeQuantity(g) -> bilinear interpolation -> optional nn.ReLU ->
+ * Quantity(b).  With D = 2*up, output row o reads
+ *   t = max(2*o + 1 - up, 0);  i0 = t div D;  l1 = t mod D;  l0 = D - l1;  i1 = min(i0 + 1, H - 1)
+ * (rows i0, i1 with weights l0 / D, l1 / D), columns by the same rule with W.  Per output element and channel
+ *   S = sum over the 2 x 2 taps of ly * lx * x[n][iy][ix][c]      (integer; |S| <= 128 * D^2: 2048 for up 2, 8192 for up 4)
+ *   e = shift - 2*log2(D)                                           shift = b - g; 2*log2(D) is 4 for up 2, 6 for up 4
+ *   r = S * 2^e rounded half to even                                an exact left shift when e >= 0
+ *   y = clamp(relu ? max(r, 0) : r, -128, 127)
+ * ONE integer rounding and no fp32 step, unlike fq_avgpool_i8_nhwc: the weights are odd multiples of 1 / D and the source is
+ * q * 2^-g, so every product and partial sum of torch's fp32 kernel is a dyadic number of at most 8 + 6 significant bits -- exact in
+ * any evaluation order -- and Quantity's rint of the exact value is the rounding above.  (The pool's divisor is no power of two:
+ * its quotient is rounded to fp32 first, which is why that rule has two roundings and this one has one.)  align_corners=True
+ * has weights that are no dyadic numbers and is not this function.
+ * x: int8 [N][H][W][Cpad]; y: int8 [N][up*H][up*W][Cpad]; Cpad % 16 == 0, 1 <= C <= Cpad, both 16-byte aligned, y must not
+ *   overlap x; y[..][c] = 0 for c in [C, Cpad) whatever the source's padding channels hold (the contract of the other int8 NHWC
+ *   entry points).  Only aligned 16-byte loads inside [x, x + N*H*W*Cpad) are issued.  The result is Quantity_b(up(x)), not up(x):
+ *   it stands for the value only where every reader applies Quantity_b next (the lossy-value rule of fq_act_lut_i8_nhwc).
+ * Return codes: FQ_ERR_INVALID_ARG for a null or misaligned pointer with N > 0, overlapping x and y, a non-positive size (N < 0),
+ *   C > Cpad or Cpad % 16 != 0; FQ_ERR_UNSUPPORTED -- callers keep the fp32 form -- for up outside {2, 4}, |shift| > 8, or an output
+ *   of 2^31 - 1 bytes or more (32-bit byte offsets).  N == 0 is FQ_OK.  All decided on the host before anything is launched; no
+ *   global state, no environment variable.
+ * fq_upsample_bilinear_i8_nhwc_supported: 1 when factor and shift alone are taken (host arithmetic, no GPU needed). */
+int fq_upsample_bilinear_i8_nhwc_supported(int up, int shift /* b - g */);
+int fq_upsample_bilinear_i8_nhwc(const int8_t* x, int8_t* y, int N, int H, int W, int C, int Cpad, int up, int shift, int relu,
+                                 fq_stream_t stream);
+
 /* ---- input files ------------------------------------------------------------------------------- */
 
 /* HOST helper for PRE_PROCESS.IMG = 2 (pytorch_quantizer.py:276-280: np.load of one CHW fp32 image per calibration item):

@@ -270,6 +270,10 @@ def lib():
     L.fq_avgpool_i16_nhwc_supported.argtypes = [ci] * 7
     L.fq_avgpool_i16_nhwc.restype = ci
     L.fq_avgpool_i16_nhwc.argtypes = [vp, vp] + [ci] * 14 + [vp]
+    L.fq_upsample_bilinear_i8_nhwc_supported.restype = ci
+    L.fq_upsample_bilinear_i8_nhwc_supported.argtypes = [ci] * 2
+    L.fq_upsample_bilinear_i8_nhwc.restype = ci
+    L.fq_upsample_bilinear_i8_nhwc.argtypes = [vp, vp] + [ci] * 8 + [vp]
     L.fq_add_resident.restype = ci
     L.fq_add_resident.argtypes = [vp, ci, ci, vp, ci, ci, vp, ci, vp, ci, ci, sz, vp]
     L.fq_add_up_resident.restype = ci
@@ -1696,6 +1700,31 @@ def avgpool_i8_nhwc(q, channels, kernel, stride, padding, count_include_pad, shi
     _check(lib().fq_avgpool_i8_nhwc(q.data_ptr(), out.data_ptr(), N, H, W, int(channels), cpad, int(kernel[0]), int(kernel[1]),
                                     int(stride[0]), int(stride[1]), int(padding[0]), int(padding[1]), 1 if count_include_pad else 0,
                                     int(shift), 1 if relu else 0, _stream(out)), "fq_avgpool_i8_nhwc")
+    return out
+
+
+def upsample_bilinear_supported(up, shift):
+    """True when fq_upsample_bilinear_i8_nhwc takes this factor and shift = consumer bit - source grid (include/fq.h): up 2 or 4,
+    |shift| <= 8.  Pure host arithmetic (no GPU needed); an output of 2^31 - 1 bytes or more is refused by the entry point itself."""
+    return bool(lib().fq_upsample_bilinear_i8_nhwc_supported(int(up), int(shift)))
+
+
+def upsample_bilinear_i8_nhwc(q, channels, up, shift, relu, out=None):
+    """fq_upsample_bilinear_i8_nhwc: nn.Upsample(scale_factor=up, mode="bilinear", align_corners=False) on int8 [N, H, W, Cpad]
+    with `channels` real channels, re-quantised by 2^shift for the convolutions behind it, max(., 0) applied when relu ->
+    int8 [N, up H, up W, Cpad], padding channels zero.  `out`: write there instead (that shape, dense, 16-byte aligned, not q).
+    Launches on the current stream and does not synchronise."""
+    _need_cuda(q, torch.int8, "fq_upsample_bilinear_i8_nhwc")
+    assert q.dim() == 4 and q.is_contiguous()
+    N, H, W, cpad = (int(v) for v in q.shape)
+    up = int(up)
+    if out is None:
+        out = torch.empty(N, up * H, up * W, cpad, dtype=torch.int8, device=q.device)
+    else:
+        _need_cuda(out, torch.int8, "fq_upsample_bilinear_i8_nhwc")
+        assert tuple(out.shape) == (N, up * H, up * W, cpad) and out.is_contiguous()
+    _check(lib().fq_upsample_bilinear_i8_nhwc(q.data_ptr(), out.data_ptr(), N, H, W, int(channels), cpad, up, int(shift),
+                                              1 if relu else 0, _stream(out)), "fq_upsample_bilinear_i8_nhwc")
     return out
 
 

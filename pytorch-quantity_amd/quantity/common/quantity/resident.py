@@ -222,7 +222,7 @@ class Plan(object):
         self.emit_int = False        # some consumer reads the integer form
         self.narrow_bit = None       # NewAdd: Quantity bit of the conv consumers (None: no narrow output)
         self.want_wide = False       # NewAdd: exact int16 sum needed (next add, or fp32 via dequant)
-        self.grid = None             # NewAdd: grid of the exact sum; windowed nn.AvgPool2d (enable(avgpool=True)): grid of its source
+        self.grid = None             # NewAdd: grid of the exact sum; windowed nn.AvgPool2d (enable(avgpool=True)) and bilinear upsampling (enable(bilinear=True)): grid of its source
         self.resident_add = False    # NewAdd: operands arrive as integers
         self.defer = False           # NewConv2d: only consumer is a resident NewAdd, which runs this conv itself
         self.fuse_arg = None         # NewAdd: operand position (0 / 1) that arrives as a DeferredConv
@@ -230,7 +230,7 @@ class Plan(object):
         self.narrow_to_hbm = True    # NewAdd with fuse_next: somebody besides that convolution reads the int8 re-quantisation
         self.fuse_proj = False       # NewAdd with fuse_arg: the OTHER operand is a deferred 1x1 projection that the kernel computes too
         self.depthwise = False       # NewConv2d: a depthwise layer taken by enable(depthwise=True); runs on fq_dwconv2d_i8_resident
-        self.up = None               # nearest upsampling taken by enable(concat=True): its factor (with `defer`: the Concat applies it -- or, with topdown=True, the NewAdd)
+        self.up = None               # nearest upsampling taken by enable(concat=True): its factor (with `defer`: the Concat applies it -- or, with topdown=True, the NewAdd); bilinear upsampling taken by enable(bilinear=True): its factor, from grid `grid` to bit `narrow_bit`
         self.grouped = False         # NewConv2d: a grouped layer taken by enable(grouped=True); runs on fq_gconv2d_i8_resident
         self.clip = False            # NewConv2d with `relu`: the fused activation is an nn.ReLU6 (enable(relu6=True)): clipped at 6
         self.perm = None             # nn.ChannelShuffle / Slice taken by enable(shuffle=True): (c_off, C, groups) of fq_shuffle_i8_nhwc
@@ -444,6 +444,33 @@ def _upsample_factor(m):
     return int(sf) if float(sf) in (2.0, 4.0) else None
 
 
+def _bilinear_factor(m):
+    """2 or 4 for an nn.Upsample that fq_upsample_bilinear_i8_nhwc can stand for: mode "bilinear", align_corners false, no `size`,
+    one integer scale factor for both axes; None for anything else (_bilinear_form_left says which)."""
+    return None if _bilinear_form_left(m) is not None else int(_scale_factor(m))
+
+
+def _scale_factor(m):
+    sf = m.scale_factor
+    if isinstance(sf, (tuple, list)):
+        return sf[0] if len(sf) == 2 and sf[0] == sf[1] else None
+    return sf
+
+
+def _bilinear_form_left(m):
+    """Why a bilinear-mode nn.Upsample is no module of enable(bilinear=True) by its own arguments, or None."""
+    if not isinstance(m, nn.Upsample) or m.mode != "bilinear":
+        return "no bilinear-mode nn.Upsample"
+    if m.align_corners:
+        return "align_corners=True: its weights are no dyadic numbers, the integer rule is not exact (fp32 form)"
+    if m.size is not None or m.scale_factor is None:
+        return "the `size=` form: only an integer scale_factor is taken (fp32 form)"
+    sf = _scale_factor(m)
+    if sf is None or float(sf) not in (2.0, 4.0):
+        return "scale_factor %r: only one integer factor of 2 or 4 for both axes is taken (fp32 form)" % (m.scale_factor,)
+    return None
+
+
 def _emit(plan, out, t=None):
     """A finished integer activation as its consumers want it: the handle, or the fp32 tensor (carrying the handle where
     somebody reads the integers too).  The only copy of this hand-off: every integer producer ends here.  plan None: a layer
@@ -475,6 +502,27 @@ class _UpsampleResident(_InstanceForward):
             return DeferredUpsample(h, plan.up)
         y = _native.concat_i8_nhwc([(h.exact, h.shape[1], plan.up)], plan.relu)
         return _emit(plan, _moved(QHandle.int8(y, h.shape[1], h.grid, plan.relu or h.relu_done), h))
+
+
+class _BilinearResident(_InstanceForward):
+    """Instance-level forward of a bilinear upsampling between an int8 activation and the convolutions behind it
+    (enable(concat=True, bilinear=True)): DeQuantity -> interpolation -> ReLU -> the consumers' Quantity in one kernel
+    (fq_upsample_bilinear_i8_nhwc).  The handle is marked `lossy`: it stands for Quantity_b(up(x)), not for up(x).  Whenever a
+    run-time condition fails -- no plan, no int8 exact payload, another grid than the planned one, a lossy source, a factor or shift
+    the kernel does not take -- the module's own forward runs on the fp32 form."""
+
+    def __call__(self, x):
+        m = self.module
+        plan = m.__dict__.get("_resident")
+        h = resident_of(x)
+        if (plan is None or plan.up is None or plan.grid is None or plan.narrow_bit is None or plan.up != _bilinear_factor(m)
+                or h is None or h.exact is None or h.lossy or h.exact.dtype != torch.int8 or h.exact.dim() != 4
+                or h.grid != plan.grid or not _native.upsample_bilinear_supported(plan.up, plan.narrow_bit - h.grid)):
+            return type(m).forward(m, as_f32(x))
+        y = _native.upsample_bilinear_i8_nhwc(h.exact, h.shape[1], plan.up, plan.narrow_bit - h.grid, plan.relu)
+        out = QHandle.int8(y, h.shape[1], plan.narrow_bit, plan.relu or h.relu_done)
+        out.lossy = True
+        return _emit(plan, out)
 
 
 class _UpsampleTopDown(_InstanceForward):
@@ -576,6 +624,7 @@ class _Tracer(TorchFunctionMode):
         self.relu6_seen = []             # (enable(relu6=True)) every hooked nn.ReLU6 module, in execution order
         self.act_seen = []               # (enable(activations=True)) every hooked table activation, in execution order
         self.act_inplace = set()         # ... those that returned their own input tensor
+        self.bilinear_seen = []          # (enable(bilinear=True)) every hooked bilinear-mode nn.Upsample, in execution order
         self.values = {}             # id(tensor) -> _Value
         self.keep = []               # keeps traced tensors alive so ids are not reused
         self.depth = 0
@@ -601,6 +650,8 @@ class _Tracer(TorchFunctionMode):
             self.shuffle_seen.append(module)
         if _is_table_activation(module) and module not in self.act_seen:
             self.act_seen.append(module)
+        if isinstance(module, nn.Upsample) and module.mode == "bilinear" and module not in self.bilinear_seen:
+            self.bilinear_seen.append(module)
         for pos, a in enumerate(args):
             v = self.values.get(id(a)) if isinstance(a, torch.Tensor) else None
             if v is not None:
@@ -626,8 +677,8 @@ class _Tracer(TorchFunctionMode):
             return "maxpool"
         if isinstance(module, nn.AvgPool2d):
             return "avgpool"
-        if isinstance(module, nn.Upsample):                 # (hooked only with enable(concat=True))
-            return "upsample"
+        if isinstance(module, nn.Upsample):                 # (hooked only with enable(concat=True); bilinear mode: with bilinear=True)
+            return "bilinear" if module.mode == "bilinear" else "upsample"
         if isinstance(module, nn.ChannelShuffle):           # (hooked only with enable(shuffle=True))
             return "shuffle"
         if _is_table_activation(module):                    # (hooked only with enable(activations=True))
@@ -643,7 +694,7 @@ class _Tracer(TorchFunctionMode):
         src = None
         if kind == "act" and args and output is args[0]:
             self.act_inplace.add(module)
-        if kind in ("relu", "maxpool", "avgpool", "upsample", "shuffle", "slice", "act"):     # a value of these kinds exists only behind a traced value
+        if kind in ("relu", "maxpool", "avgpool", "upsample", "bilinear", "shuffle", "slice", "act"):     # a value of these kinds exists only behind a traced value
             if kind == "avgpool" and not self.avgpool:
                 return                                      # its output is an ordinary fp32 tensor
             src = self.values.get(id(args[0])) if args and isinstance(args[0], torch.Tensor) else None
@@ -676,6 +727,7 @@ def _clear(model):
     model.__dict__.pop("_fq_resident_act", None)
     model.__dict__.pop("_fq_resident_avgpool", None)
     model.__dict__.pop("_fq_resident_topdown", None)
+    model.__dict__.pop("_fq_resident_bilinear", None)
 
 
 def disable(model):
@@ -690,10 +742,11 @@ def is_enabled(model):
 
 _COUNTER = {"contraction": "resident_convs", "add": "resident_adds", "maxpool": "resident_pools", "concat": "resident_concats",
             "upsample": "resident_upsamples", "shuffle": "resident_shuffles", "slice": "resident_slices",
-            "act": "resident_activations"}
+            "act": "resident_activations", "bilinear": "resident_bilinears"}
 _FORWARD = {"maxpool": _MaxPoolResident, "concat": _ConcatResident, "upsample": _UpsampleResident, "shuffle": _ShuffleResident,
-            "slice": _SliceResident, "act": _ActTableResident}
+            "slice": _SliceResident, "act": _ActTableResident, "bilinear": _BilinearResident}
 _MOVES = ("maxpool", "concat", "upsample", "shuffle", "slice")       # what Quantity_b commutes with: data movement and max
+#                                                                      (not "bilinear": Quantity_b does not commute with interpolation)
 
 
 class _Planning(object):
@@ -701,7 +754,7 @@ class _Planning(object):
     nothing on the model until install() writes the plans and the instance-level forwards to the modules."""
 
     def __init__(self, tracer, depthwise, concat, avgpool, grouped, relu6=False, flatten=False, shuffle=False, activations=False,
-                 revoked=None, names=None, sums=False, topdown=False, revoked_up=None):
+                 revoked=None, names=None, sums=False, topdown=False, revoked_up=None, bilinear=False, revoked_bil=None):
         from .new_quantity_op import NewConv2d, NewAdd
         from .fabu_layer import Concat
         self.conv_type, self.concat_type = NewConv2d, Concat
@@ -736,6 +789,10 @@ class _Planning(object):
         self.topdown_ups = {}            # ... planned upsampling -> (bytes, grid) of its source
         self.topdown_adds = set()        # ... the NewAdd modules that take such an operand
         self.topdown_left = {}           # ... hooked upsampling in front of a NewAdd that keeps its earlier plan -> why
+        self.bilinear = bool(bilinear)   # (concat=True, bilinear=True) bilinear upsampling by 2 or 4 on fq_upsample_bilinear_i8_nhwc
+        self.revoked_bil = dict(revoked_bil or {})  # ... module that an earlier round planned and verify_lossy_bilinear() took back -> why
+        self.bil_grids = {}              # ... planned bilinear upsampling -> (source grid g, consumer bit b)
+        self.bil_left = {}               # ... hooked bilinear-mode nn.Upsample that stays torch's -> why
         self.plans = {}                  # producer module -> Plan
         self.forwards = []               # (module, its instance-level forward)
         self.summary = {"resident_convs": 0, "resident_adds": 0, "resident_pools": 0, "fused_relus": 0, "fp32_outputs": 0,
@@ -760,6 +817,8 @@ class _Planning(object):
             self.summary["resident_activations"] = 0
         if topdown:
             self.summary["topdown_adds"] = self.summary["topdown_sum_sources"] = 0
+        if bilinear:
+            self.summary["resident_bilinears"] = 0
 
     # ---- what a value is and what a module can do
 
@@ -865,6 +924,8 @@ class _Planning(object):
                     f = None
                 if self.topdown:
                     f = self._topdown_format(v, relu_mod, f)
+            elif v.kind == "bilinear":
+                f = self._bilinear_format(v)
             elif v.kind == "avgpool":
                 self._plan_avgpool_window(v, e)             # (the value itself has no integer format)
             elif v.kind == "concat":
@@ -1139,6 +1200,79 @@ class _Planning(object):
         self.act_left[m] = why
         return None
 
+    def _bilinear_format(self, v):
+        """`concat=True, bilinear=True` plans nn.Upsample(scale_factor=2 or 4, mode="bilinear", align_corners=False) -- the decoder
+        step of a U-Net, DeepLabV3+ or BiSeNet -- on fq_upsample_bilinear_i8_nhwc: between an int8 activation q on grid g and
+        convolutions that quantise at bit b the chain DeQuantity_g -> interpolation -> (ReLU) -> Quantity_b is a closed integer
+        function (weights are odd multiples of 1 / (2 up): one rounding of S * 2^(b - g) / (2 up)^2, include/fq.h).  Its output is
+        Quantity_b(up(x)), not up(x): the lossy-value rule of _act_format applies word for word -- planned as an int8 value on grid
+        b only where every transitive reader through _MOVES is an integer convolution with input_bit == b (_lossy_walk), taken
+        back by verify_lossy_bilinear() where a later pass left one of those readers in fp32 form.  The kind is NOT one of _MOVES:
+        Quantity_b does not commute with interpolation, so a table activation (or another bilinear upsampling) in front of one
+        is left by _lossy_walk.  An nn.ReLU directly behind the module is the kernel's `relu` flag (effective, _take).  Left to
+        torch, each named with its reason by describe().bilinear_left: align_corners=True, the `size=` form, another or a
+        non-integer factor, a module called twice, a NewAdd sum (int16) as the source, a lossy source, a source without an integer
+        form, readers at two bits, any fp32 reader (a NewAdd, an average pool, a table activation, a model output, foreign code),
+        |b - g| > 8.  The summary then gains `resident_bilinears`."""
+        m = v.producer
+        src = self.fmt.get(id(v.src))
+        why = _bilinear_form_left(m)
+        if why is not None:
+            pass
+        elif not self.once(m):
+            why = "the module was called more than once"
+        elif v.src.shape is None or len(v.src.shape) != 4:
+            why = "its input is not 4-D"
+        elif self._lossy_origin(v.src) is not None:
+            why = ("its source is the lossy value of %s: Quantity_b does not commute with interpolation, so that module stays torch's "
+                   "and this one reads fp32" % self._name(self._lossy_origin(v.src)))
+        elif src is None:
+            why = "its source has no integer form in this plan (fp32 form)"
+        elif src[0] != 1:
+            why = "its source is a NewAdd sum (int16): only int8 activations are interpolated (fp32 form)"
+        elif m in self.revoked_bil:
+            why = self.revoked_bil[m]
+        else:
+            bits, why = self._lossy_walk(v)
+            if why is None and len(bits) != 1:
+                why = "its readers quantise at different bits %s" % sorted(bits)
+            if why is None:
+                b = bits.pop()
+                if not _native.upsample_bilinear_supported(_bilinear_factor(m), b - src[1]):
+                    why = "|b - g| = |%d - %d| > 8: not taken by the kernel (fp32 form)" % (b, src[1])
+                else:
+                    self.bil_grids[m] = (src[1], b)
+                    return (1, b)
+        self.bil_left[m] = why
+        return None
+
+    def _lossy_origin(self, v, depth=0):
+        """The table activation or bilinear upsampling whose (would-be) lossy value reaches v through ReLUs and _MOVES, or None.
+        Decided on the trace alone."""
+        if v is None or depth > 64:
+            return None
+        if v.kind in ("act", "bilinear"):
+            return v.producer
+        if v.kind == "concat":
+            for o in self.operands.get(v.producer) or ():
+                found = self._lossy_origin(o, depth + 1)
+                if found is not None:
+                    return found
+            return None
+        if v.kind == "relu" or v.kind in _MOVES:
+            return self._lossy_origin(v.src, depth + 1)
+        return None
+
+    def verify_lossy_bilinear(self):
+        """verify_lossy() for the planned bilinear upsamplings: {module: why} for every one whose value, after all passes, somebody
+        would read in fp32 form.  enable() plans again without them."""
+        bad = {}
+        for m, (_g, b) in self.bil_grids.items():
+            why = self._lossy_violation(self.value_of[m], b)
+            if why is not None:
+                bad[m] = "revoked by the lossy rule: " + why
+        return bad
+
     def _lossy_walk(self, v):
         """({input bits of the convolutions that read v, directly or through _MOVES}, None), or (_, why not): the first reader
         that would see the value in fp32 form.  Decided on the trace alone, before the movement modules are planned."""
@@ -1159,7 +1293,8 @@ class _Planning(object):
                     return bits, why
                 bits |= more
                 continue
-            what = {"add": "the NewAdd", "avgpool": "the average pool", "act": "the table activation", "relu": "the ReLU"}.get(
+            what = {"add": "the NewAdd", "avgpool": "the average pool", "act": "the table activation", "relu": "the ReLU",
+                    "bilinear": "the bilinear upsampling"}.get(
                 self.tracer._kind(c) if not isinstance(c, nn.AvgPool2d) else "avgpool", "the module")
             return bits, "read as fp32 by %s %s" % (what, self._name(c))
         return bits, None
@@ -1284,6 +1419,8 @@ class _Planning(object):
             plan.perm = self.perm[m]
         if v.kind == "act":
             plan.grid = self.act_grids[m][0]
+        if v.kind == "bilinear":
+            plan.up, plan.grid = _bilinear_factor(m), self.bil_grids[m][0]
         self._take(m, plan, relu_mod, forward)
         self.summary[_COUNTER[v.kind]] += 1
 
@@ -1453,11 +1590,17 @@ class _Planning(object):
             model.__dict__["_fq_resident_avgpool"] = dict((names.get(m, "?"), why) for m, why in self.avgpool_left.items())
         if self.topdown:
             for m in model.modules():                       # (what _trace did not hook: foreign code, named all the same)
-                if isinstance(m, nn.Upsample) and _upsample_factor(m) is None:
+                if isinstance(m, nn.Upsample) and _upsample_factor(m) is None and m not in self.bil_grids:
                     self.topdown_left[m] = ("no nearest upsampling by one integer scale_factor of 2 or 4 (a `size=` form, another "
                                             "factor or another mode): foreign code")
             names = dict((m, name) for name, m in model.named_modules())
             model.__dict__["_fq_resident_topdown"] = dict((names.get(m, "?"), why) for m, why in self.topdown_left.items())
+        if self.bilinear:
+            for m in self.tracer.bilinear_seen:
+                if m not in self.plans and m not in self.bil_left:
+                    self.bil_left[m] = _bilinear_form_left(m) or "its input is not the output of a planned layer (no integer source)"
+            names = dict((m, name) for name, m in model.named_modules())
+            model.__dict__["_fq_resident_bilinear"] = dict((names.get(m, "?"), why) for m, why in self.bil_left.items())
         if self.activations:
             for m, (g, b) in self.act_grids.items():
                 self.plans[m].table = _native.build_act_table(m, g, b)
@@ -1469,7 +1612,7 @@ class _Planning(object):
                                                   tuple(names.get(m, "?") for m in self.revoked))
 
 
-def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False, activations=False):
+def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False, activations=False, bilinear=False):
     """One forward of `model` in eval mode under the tracer: (tracer, the outputs of that forward)."""
     from .new_quantity_op import NewConv2d, NewLinear, NewAdd
     from .fabu_layer import Concat, Slice
@@ -1478,7 +1621,8 @@ def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False, ac
     tracer = _Tracer(avgpool)
     hooks = []
     for m in model.modules():
-        if isinstance(m, planned_types) or (concat and _upsample_factor(m) is not None) or (activations and _is_table_activation(m)):     # (any other nn.Upsample stays foreign code)
+        if (isinstance(m, planned_types) or (concat and _upsample_factor(m) is not None) or (activations and _is_table_activation(m))
+                or (bilinear and isinstance(m, nn.Upsample) and m.mode == "bilinear")):     # (any other nn.Upsample stays foreign code)
             hooks.append(m.register_forward_pre_hook(tracer.pre))
             hooks.append(m.register_forward_hook(tracer.post))
         elif concat and isinstance(m, Concat):
@@ -1499,7 +1643,7 @@ def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False, ac
 
 
 def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False, grouped=False, relu6=False,
-           flatten=False, shuffle=False, activations=False, sums=False, topdown=False):
+           flatten=False, shuffle=False, activations=False, sums=False, topdown=False, bilinear=False):
     """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
     on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
     nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
@@ -1520,7 +1664,10 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
     ResNet-D shortcut -- on fq_avgpool_i16_nhwc (_plan_avgpool_window);
     `topdown=True` (with `concat=True`; ValueError without) lets a NewAdd read an operand through a nearest upsampling by 2 or 4
     -- the FPN top-down step, over an int8 activation or the int16 sum of the add above -- on fq_add_up_resident, the upsampled
-    tensor never written (_Planning._topdown_format)."""
+    tensor never written (_Planning._topdown_format);
+    `bilinear=True` (with `concat=True`; ValueError without) also plans nn.Upsample(scale_factor=2 or 4, mode="bilinear",
+    align_corners=False) between an int8 activation and convolutions at one bit -- the decoder step of a U-Net -- on
+    fq_upsample_bilinear_i8_nhwc, a lossy value like a table activation's (_Planning._bilinear_format)."""
     from .new_quantity_op import QUANTIZE_BIT
     if flatten and not concat:
         raise ValueError("resident.enable(flatten=True) needs concat=True: only planned Concats are flattened")
@@ -1528,15 +1675,17 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
         raise ValueError("resident.enable(sums=True) needs avgpool=True: only planned windowed pools read a NewAdd sum")
     if topdown and not concat:
         raise ValueError("resident.enable(topdown=True) needs concat=True: the upsampling is hooked by that switch")
+    if bilinear and not concat:
+        raise ValueError("resident.enable(bilinear=True) needs concat=True: the Concat behind a decoder's upsampling is planned by that switch")
     _clear(model)
     if QUANTIZE_BIT != 8:
         raise _native.FqError("resident activations are defined for QUANTIZE_BIT = 8")
-    tracer, traced_out = _trace(model, example_input, concat, avgpool, relu6, shuffle, activations)
-    names = dict((m, name) for name, m in model.named_modules()) if activations or sums or topdown else None
-    revoked, revoked_up = {}, {}
+    tracer, traced_out = _trace(model, example_input, concat, avgpool, relu6, shuffle, activations, bilinear)
+    names = dict((m, name) for name, m in model.named_modules()) if activations or sums or topdown or bilinear else None
+    revoked, revoked_up, revoked_bil = {}, {}, {}
     while True:
         planning = _Planning(tracer, depthwise, concat, avgpool, grouped, relu6, flatten, shuffle, activations, revoked, names,
-                             sums, topdown, revoked_up)
+                             sums, topdown, revoked_up, bilinear, revoked_bil)
         planning.plan_formats()
         planning.plan_outputs()
         planning.defer_convs()
@@ -1549,8 +1698,10 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
         planning.hook_global_pools()
         bad = planning.verify_lossy() if activations else {}
         bad_up = planning.verify_topdown() if topdown else {}
-        if not bad and not bad_up:
+        bad_bil = planning.verify_lossy_bilinear() if bilinear else {}
+        if not bad and not bad_up and not bad_bil:
             break
+        revoked_bil.update(bad_bil)                         # (... or one bilinear upsampling)
         revoked.update(bad)                                 # (each round takes at least one activation out: it ends)
         revoked_up.update(bad_up)                           # (... or one upsampling)
     if topdown:
@@ -1576,8 +1727,11 @@ class _Description(dict):
     and `activations_revoked` names those among them that a first plan had accepted and the lossy-value verification took back.
     After enable(avgpool=True, sums=True) `avgpool_left` is {module name: why} for every hooked windowed nn.AvgPool2d that stays
     torch's.  After enable(concat=True, topdown=True) `topdown_left` is {module name: why} for every nearest upsampling in front
-    of a NewAdd (or over a sum) that keeps the plan it had without the switch, and for every nn.Upsample that is foreign code."""
+    of a NewAdd (or over a sum) that keeps the plan it had without the switch, and for every nn.Upsample that is foreign code.
+    After enable(concat=True, bilinear=True) `bilinear_left` is {module name: why} for every hooked bilinear-mode nn.Upsample that
+    stays torch's."""
     activations_left = {}
+    bilinear_left = {}
     avgpool_left = {}
     topdown_left = {}
     activations_revoked = ()
@@ -1595,6 +1749,7 @@ def describe(model):
     d.activations_left, d.activations_revoked = model.__dict__.get("_fq_resident_act", ({}, ()))
     d.avgpool_left = model.__dict__.get("_fq_resident_avgpool", {})
     d.topdown_left = model.__dict__.get("_fq_resident_topdown", {})
+    d.bilinear_left = model.__dict__.get("_fq_resident_bilinear", {})
     d.flattened_concats = tuple(name for name, m in model.named_modules()
                                 if type(m).__name__ == "Concat" and name in d and d[name].defer)
     return d
