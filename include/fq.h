@@ -753,6 +753,32 @@ int fq_concat_n_i8_nhwc_supported(const int* C, const int* up, int nsrc);
 int fq_concat_n_i8_nhwc(const fq_cat_src_n* srcs, int nsrc, int8_t* out, int Cpad_out, int N, int H, int W,
                         fq_stream_t stream);
 
+/* The concatenation that RE-QUANTISES: up to FQ_CONCAT_N_MAX_SRC sources, each on its own grid g_i, joined into one int8 tensor at
+ * the bit b at which every reader quantises.  The reference never re-quantises a Concat: its fp32 chain is DeQuantity_g_i ->
+ * (nearest upsampling) -> torch.cat -> (nn.ReLU) -> Quantity_b of the convolutions behind it, every scale a power of two and every
+ * value below 2^16 in magnitude, so nothing is rounded in front of Quantity's rint and the chain is ONE integer function with one
+ * rounding per element.  A source is an int8 activation (bytes == 1) or the exact int16 sum of a resident NewAdd (bytes == 2).
+ * With base_i = C_0 + ... + C_{i-1}, shift_i = b - g_i and v = src_i[n][h / up_i][w / up_i][c - base_i]:
+ *   r = rint(v * 2^shift_i)                                      round half to even; an exact left shift for shift_i >= 0
+ *   out[n][h][w][c] = clamp(relu_i ? max(r, 0) : r, -128, 127)   for base_i <= c < base_i + C_i
+ *                   = 0                                          for sum C <= c < Cpad_out, whatever the sources' padding holds
+ * The rule holds for EVERY int8 and EVERY int16 value: the rounding never adds to v itself (quotient and dropped bits are rounded
+ * apart), so nothing wraps for |v| near 2^15.  The result is Quantity_b(cat(...)), not cat(...): it stands for the value only
+ * where every reader applies Quantity_b next (the lossy-value rule of fq_act_lut_i8_nhwc and fq_upsample_bilinear_i8_nhwc).
+ * Source i: [N][H / up_i][W / up_i][Cpad_i] elements of bytes_i bytes, 16-byte aligned, Cpad_i % 16 == 0, 1 <= C_i <= Cpad_i,
+ *   up_i in {1, 2, 4} with H % up_i == 0 and W % up_i == 0, shift_i in [-8, 8], relu_i in {0, 1}.
+ * out: int8 [N][H][W][Cpad_out], 16-byte aligned, Cpad_out == pad16(sum C); it must not overlap a source.  Only aligned loads
+ *   are issued and no byte outside [q_i, q_i + N (H / up_i) (W / up_i) Cpad_i bytes_i) is read.
+ * Return codes: fq_concat_n_i8_nhwc's, and FQ_ERR_INVALID_ARG for bytes_i outside {1, 2} and for the call with nothing to do
+ *   (nsrc == 1, bytes == 1, up == 1, relu == 0, shift == 0: a copy); FQ_ERR_UNSUPPORTED for |shift_i| > 8 and for an output or a
+ *   source of 2^31 - 1 bytes or more.  The scalar arguments are judged before the pointers.  N == 0 is FQ_OK without a launch.
+ *   Everything is decided on the host before anything is launched; no global state, no environment variable.
+ * fq_concat_rq_i8_nhwc_supported: 1 when channel counts, factors, element sizes and shifts alone are taken (host arithmetic). */
+typedef struct fq_cat_src_rq { const void* q; int bytes; int C; int Cpad; int up; int relu; int shift; } fq_cat_src_rq;
+int fq_concat_rq_i8_nhwc_supported(const int* C, const int* up, const int* bytes, const int* shift, int nsrc);
+int fq_concat_rq_i8_nhwc(const fq_cat_src_rq* srcs, int nsrc, int8_t* out, int Cpad_out, int N, int H, int W,
+                         fq_stream_t stream);
+
 /* Channel shuffle (nn.ChannelShuffle, torch.channel_shuffle) and channel slice (the Slice marker layer, x[:, a:b]) of a resident
  * int8 NHWC activation, one kernel for both: permuting the integers is permuting the values q * 2^-g, as for the Concat above.
  *   y[n][h][w][j] = x[n][h][w][c_off + (j mod groups) * (C / groups) + floor(j / groups)]    for 0 <= j < C

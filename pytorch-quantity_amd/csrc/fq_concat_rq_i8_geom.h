@@ -1,0 +1,206 @@
+// fq_concat_rq_i8_geom.h -- the lane -> (sources, offsets, masks, loads) arithmetic, the re-quantisation and the host guards of the
+// re-quantising int8 NHWC concatenation (fq_concat_rq_i8.hip), kept apart from the kernel so that the same functions compile as
+// host code: scripts/concat_rq_geom_check.cpp walks them over the shapes the GPU tests and the models run and asserts that every
+// load lies inside its source and is aligned, that every output chunk is written exactly once, that the re-quantisation is
+// v * 2^shift rounded half to even for every int8 and int16 value, and that the guards answer what include/fq.h says.
+//
+// The output is fq_concat_i8_geom.h's: [N][H][W][Cpad_out] bytes, a CHUNK is 16 consecutive channels of one pixel (one dwordx4
+// store), chunk k holds output channels [16k, 16k + 16), source i owns [base_i, base_i + C_i).  A source stores ELEMENTS of 1 or 2
+// bytes: everything below counts channels, and a byte offset is the channel offset times the source's `bytes`.  Relative to the
+// source's pixel row the chunk starts at channel s = 16k - base_i.  A lane keeps k for its whole life, so everything except the
+// pixel is per-lane constant.
+#pragma once
+
+#include "fq_concat_i8_geom.h"         // kCatBlock, kCatMaxBlocks, cat_dword_mask
+
+namespace fq {
+
+constexpr int kCrqMaxSrc = 8;                    // FQ_CONCAT_N_MAX_SRC
+constexpr int kCrqMaxShift = 8;                  // |b - g|
+constexpr long kCrqMaxBytes = 0x7ffffffeL;       // the output and every source: below 2^31 - 1 bytes
+
+struct CrqSrcGeom {
+    int C, Cpad;                       // real / stored channels of the source
+    int lu;                            // log2 of the nearest-upsampling factor (0, 1, 2)
+    int base;                          // first output channel of the source
+    int wide;                          // 1: int16 elements, 0: int8
+};
+
+// r = v * 2^shift rounded half to even, then the ReLU and the clamp to int8, as shift amounts and masks (crq_requant)
+struct CrqRound {
+    int rsh, lsh;                      // shift < 0: rsh = -shift; shift > 0: lsh = shift
+    int mask;                          // 2^rsh - 1: the bits the right shift drops
+    int bias;                          // 2^(rsh - 1) - 1 (0 for rsh == 0)
+    int odd;                           // 1 where rsh > 0: the bit of the quotient that decides a tie
+    int lo;                            // 0 with the ReLU, else -128
+};
+
+struct CrqGeom {
+    int nsrc;
+    CrqSrcGeom s[kCrqMaxSrc];          // entries at and behind nsrc: C = 0 (nothing of them lies in any chunk)
+    CrqRound r[kCrqMaxSrc];
+    int N, H, W;                       // OUTPUT plane; source i is [N][H >> lu][W >> lu][Cpad]
+    int Cpad_out, CH;                  // CH = Cpad_out / 16
+    unsigned npix;                     // N * H * W
+};
+
+FQ_CAT_HD CrqRound crq_round(int shift, int relu) {
+    CrqRound r;
+    r.rsh = shift < 0 ? -shift : 0;
+    r.lsh = shift > 0 ? shift : 0;
+    r.mask = (1 << r.rsh) - 1;
+    r.bias = r.rsh > 0 ? (1 << (r.rsh - 1)) - 1 : 0;
+    r.odd = r.rsh > 0 ? 1 : 0;
+    r.lo = relu ? 0 : -128;
+    return r;
+}
+
+// The rule on one int8 or int16 value, in plain integers; the kernel does the same steps on packed int16, so every intermediate
+// has to fit int16 for EVERY int16 v (the walker asserts it through `fits`):
+//   q = v >> rsh (floor), rem = v & mask;  rem + bias + 1 <= 255 + 127 + 1;  q + 1 <= 2^14 + 1 for rsh >= 1 -- the rounding addend
+//   never meets v itself, so nothing wraps at |v| near 2^15; for rsh == 0 the addend is 0 and q = v;
+//   half to even: the dropped bits plus 2^(rsh-1) - 1 plus the quotient's lowest bit carry into bit rsh exactly when the value
+//   rounds up;
+//   the clamp to [lo, 127] BEFORE the left shift (monotone, so the result is unchanged) keeps 127 * 2^8 = 32512 inside int16,
+//   the clamp after it is the rule's own.
+FQ_CAT_HD bool crq_fits16(int x) { return x >= -32768 && x <= 32767; }
+
+FQ_CAT_HD int crq_requant(int v, const CrqRound& r, bool* fits = nullptr) {
+    const int q = v >> r.rsh;
+    const int a = (v & r.mask) + r.bias + (q & r.odd);
+    int x = q + (a >> r.rsh);
+    bool ok = crq_fits16(a) && crq_fits16(x);
+    x = x < r.lo ? r.lo : (x > 127 ? 127 : x);
+    x = x * (1 << r.lsh);
+    ok = ok && crq_fits16(x);
+    if (fits) *fits = ok;
+    return x < r.lo ? r.lo : (x > 127 ? 127 : x);
+}
+
+FQ_CAT_HD int crq_log2_up(int up) { return up == 1 ? 0 : (up == 2 ? 1 : (up == 4 ? 2 : -1)); }
+
+// what fq_concat_rq_i8_nhwc_supported answers: channel counts, factors, element sizes and shifts alone
+FQ_CAT_HD bool crq_supported(const int* C, const int* up, const int* bytes, const int* shift, int nsrc) {
+    if (!C || !up || !bytes || !shift || nsrc < 1 || nsrc > kCrqMaxSrc) return false;
+    long sum = 0;
+    for (int i = 0; i < nsrc; ++i) {
+        if (C[i] < 1 || C[i] > 65536 || crq_log2_up(up[i]) < 0 || (bytes[i] != 1 && bytes[i] != 2)) return false;
+        if (shift[i] < -kCrqMaxShift || shift[i] > kCrqMaxShift) return false;
+        sum += C[i];
+    }
+    return sum <= 65536;                                   // the chunks of one pixel fit the smallest launch
+}
+
+// a * b * c * d > limit, each factor positive and below 2^31, without leaving long
+FQ_CAT_HD bool crq_over(long a, long b, long c, long d, long limit) {
+    long n = a;
+    if (n > limit) return true;
+    n *= b;
+    if (n > limit) return true;
+    n *= c;
+    if (n > limit) return true;
+    n *= d;
+    return n > limit;
+}
+
+// Status of everything but the pointers: 0 fine, -1 FQ_ERR_INVALID_ARG, -4 FQ_ERR_UNSUPPORTED, in fq_concat_n_i8_nhwc's order.
+// N == 0 is fine whatever the other sizes are (nothing is launched, no size is looked at).
+FQ_CAT_HD int crq_args(const int* bytes, const int* C, const int* Cpad, const int* up, const int* relu, const int* shift, int nsrc,
+                       int Cpad_out, int N, int H, int W) {
+    if (nsrc < 1 || N < 0 || H <= 0 || W <= 0) return -1;
+    if (nsrc > kCrqMaxSrc) return -4;
+    long sum = 0;
+    for (int i = 0; i < nsrc; ++i) {
+        if (C[i] < 1 || up[i] < 1 || Cpad[i] < C[i] || (relu[i] != 0 && relu[i] != 1) || (bytes[i] != 1 && bytes[i] != 2)) return -1;
+        sum += C[i];
+    }
+    if (!crq_supported(C, up, bytes, shift, nsrc)) return -4;
+    for (int i = 0; i < nsrc; ++i)
+        if (Cpad[i] % 16 || H % up[i] || W % up[i]) return -4;
+    if (Cpad_out != (int)((sum + 15) / 16 * 16)) return -1;
+    if (nsrc == 1 && bytes[0] == 1 && up[0] == 1 && !relu[0] && shift[0] == 0) return -1;      // nothing to do
+    if (N == 0) return 0;
+    if (crq_over(N, H, W, Cpad_out, kCrqMaxBytes)) return -4;
+    for (int i = 0; i < nsrc; ++i)
+        if (crq_over(N, H / up[i], W / up[i], (long)Cpad[i] * bytes[i], kCrqMaxBytes)) return -4;
+    return 0;
+}
+
+FQ_CAT_HD CrqGeom crq_geom(const int* bytes, const int* C, const int* Cpad, const int* up, const int* relu, const int* shift, int nsrc,
+                           int Cpad_out, int N, int H, int W) {
+    CrqGeom g;
+    g.nsrc = nsrc;
+    int base = 0;
+    for (int i = 0; i < kCrqMaxSrc; ++i) {
+        const bool have = i < nsrc;
+        g.s[i].C = have ? C[i] : 0;
+        g.s[i].Cpad = have ? Cpad[i] : 16;
+        g.s[i].lu = have ? crq_log2_up(up[i]) : 0;
+        g.s[i].base = base;
+        g.s[i].wide = have && bytes[i] == 2 ? 1 : 0;
+        g.r[i] = crq_round(have ? shift[i] : 0, have ? relu[i] : 0);
+        base += g.s[i].C;
+    }
+    g.N = N; g.H = H; g.W = W; g.Cpad_out = Cpad_out; g.CH = Cpad_out / 16;
+    g.npix = (unsigned)((long)N * H * W);
+    return g;
+}
+
+// What source i contributes to the chunk k of every pixel.
+struct CrqPart {
+    int use;                           // 0: nothing of this source lies in the chunk
+    int s;                             // channel of the source's pixel row at the chunk's channel 0 (may be negative)
+    int lo, hi;                        // channels [lo, hi) of the chunk come from this source
+    int whole16;                       // the 16 elements at row + s are the chunk (s % 16 == 0, lo == 0; hi < 16 only masks the tail)
+    // the general family: the chunk's elements start at byte s * bytes of the row; a = that rounded down to a dword, sh = the rest
+    // (int8: 0 .. 3, int16: 0 or 2); dword t of the elements = alignbyte(d[t + 1], d[t], sh), t < 4 (int8) or t < 8 (int16)
+    int a, sh;
+    unsigned ld;                       // bit t: the dword at row + a + 4t holds a wanted byte and is loaded (t = 0 .. 4, or 0 .. 8)
+};
+
+FQ_CAT_HD CrqPart crq_part(const CrqGeom& g, int k, int i) {
+    CrqPart p;
+    const int C = g.s[i].C, eb = g.s[i].wide ? 2 : 1;
+    p.s = 16 * k - g.s[i].base;
+    p.lo = p.s < 0 ? -p.s : 0;
+    p.hi = C - p.s < 16 ? C - p.s : 16;
+    p.use = i < g.nsrc && p.lo < p.hi;
+    p.a = (p.s * eb) & ~3;
+    p.sh = (p.s * eb) & 3;
+    p.ld = 0u;
+    p.whole16 = 0;
+    if (!p.use) return p;
+    for (int t = 0; t < 4 * eb + 1; ++t) {
+        const int o = p.a + 4 * t;                          // wanted bytes of the row: [(s + lo) eb, (s + hi) eb), inside [0, C eb)
+        if (o < (p.s + p.hi) * eb && o + 4 > (p.s + p.lo) * eb) p.ld |= 1u << t;
+    }
+    p.whole16 = p.lo == 0 && (p.s & 15) == 0;
+    return p;
+}
+
+// pixel index of a source upsampled by 2^lu under the output pixel (n, h, w)
+FQ_CAT_HD unsigned crq_src_pix(const CrqGeom& g, int lu, unsigned n, unsigned h, unsigned w) {
+    return (n * ((unsigned)g.H >> lu) + (h >> lu)) * ((unsigned)g.W >> lu) + (w >> lu);
+}
+
+// every base_i % 16 == 0: each chunk is 16 elements of exactly one source at a 16-element-aligned offset (the aligned family)
+FQ_CAT_HD bool crq_aligned(const CrqGeom& g) {
+    bool a = true;
+    for (int i = 0; i < kCrqMaxSrc; ++i) a = a && (i >= g.nsrc || (g.s[i].base & 15) == 0);
+    return a;
+}
+
+FQ_CAT_HD bool crq_upsampled(const CrqGeom& g) {
+    bool u = false;
+    for (int i = 0; i < kCrqMaxSrc; ++i) u = u || g.s[i].lu > 0;
+    return u;
+}
+
+// The launch is fq_concat_i8's: lane gid owns chunk k = gid % CH of the pixels gid / CH, + stride, + 2 stride, ... with
+// stride = threads / CH; lanes whose first pixel is >= stride do nothing.
+FQ_CAT_HD long crq_blocks(const CrqGeom& g) {
+    long b = ((long)g.npix * g.CH + kCatBlock - 1) / kCatBlock;
+    return b > kCatMaxBlocks ? kCatMaxBlocks : b;
+}
+
+}  // namespace fq

@@ -49,6 +49,11 @@ class _CatSrcN(ctypes.Structure):
                 ("relu", ctypes.c_int32)]
 
 
+class _CatSrcRq(ctypes.Structure):
+    _fields_ = [("q", ctypes.c_void_p), ("bytes", ctypes.c_int32), ("C", ctypes.c_int32), ("Cpad", ctypes.c_int32),
+                ("up", ctypes.c_int32), ("relu", ctypes.c_int32), ("shift", ctypes.c_int32)]
+
+
 CONCAT_N_MAX_SRC = 8         # FQ_CONCAT_N_MAX_SRC
 
 
@@ -254,6 +259,10 @@ def lib():
     L.fq_concat_n_i8_nhwc_supported.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci), ci]
     L.fq_concat_n_i8_nhwc.restype = ci
     L.fq_concat_n_i8_nhwc.argtypes = [ctypes.POINTER(_CatSrcN), ci, vp, ci, ci, ci, ci, vp]
+    L.fq_concat_rq_i8_nhwc_supported.restype = ci
+    L.fq_concat_rq_i8_nhwc_supported.argtypes = [ctypes.POINTER(ci)] * 4 + [ci]
+    L.fq_concat_rq_i8_nhwc.restype = ci
+    L.fq_concat_rq_i8_nhwc.argtypes = [ctypes.POINTER(_CatSrcRq), ci, vp, ci, ci, ci, ci, vp]
     L.fq_shuffle_i8_nhwc_supported.restype = ci
     L.fq_shuffle_i8_nhwc_supported.argtypes = [ci] * 4
     L.fq_shuffle_i8_nhwc.restype = ci
@@ -1596,6 +1605,55 @@ def concat_n_i8_nhwc(srcs, out=None):
     `out`: write there instead (that shape, dense, 16-byte aligned).  Launches on the current stream and does not synchronise."""
     arr, n, out, cpad, N, H, W = _concat_operands("fq_concat_n_i8_nhwc", _CatSrcN, [(q, C, up, bool(relu)) for q, C, up, relu in srcs], out)
     _check(lib().fq_concat_n_i8_nhwc(arr, n, out.data_ptr(), cpad, N, H, W, _stream(out)), "fq_concat_n_i8_nhwc")
+    return out
+
+
+def concat_rq_supported(Cs, ups, nbytes, shifts):
+    """True when fq_concat_rq_i8_nhwc takes sources of these channel counts, nearest-upsampling factors, element sizes (1: int8,
+    2: int16) and shifts = consumer bit - source grid (include/fq.h): one to eight sources, every C >= 1, every factor 1, 2 or 4,
+    every |shift| <= 8, at most 65536 channels in all.  Pure host arithmetic (no GPU needed)."""
+    n = len(Cs)
+    if n < 1 or len(ups) != n or len(nbytes) != n or len(shifts) != n:
+        return False
+    ci = ctypes.c_int * n
+    return bool(lib().fq_concat_rq_i8_nhwc_supported(ci(*[int(c) for c in Cs]), ci(*[int(u) for u in ups]),
+                                                     ci(*[int(b) for b in nbytes]), ci(*[int(s) for s in shifts]), n))
+
+
+def concat_rq_i8_nhwc(srcs, out=None):
+    """fq_concat_rq_i8_nhwc.  srcs = [(q, C, up, relu, shift), ...]: one to eight int8 or int16 [N, H / up, W / up, Cpad] tensors,
+    each on its own grid, with C real channels; `up` the nearest-upsampling factor of that operand, `relu` whether max(., 0) is
+    applied to ITS elements and `shift` = consumer bit - its grid.  Returns int8 [N, H, W, pad16(sum C)]: every element
+    re-quantised to the consumers' bit (round half to even, clamped to int8), the operands one behind the other along the
+    channels, the padding channels zero.  `out`: write there instead (that shape, dense, 16-byte aligned).  Launches on the
+    current stream and does not synchronise."""
+    entry = "fq_concat_rq_i8_nhwc"
+    n = len(srcs)
+    arr = (_CatSrcRq * max(n, 1))()
+    plane, total = None, 0
+    for i, (q, C, up, relu, shift) in enumerate(srcs):
+        if q.dtype not in (torch.int8, torch.int16):
+            raise FqError("%s: an operand is %s, not int8 or int16" % (entry, q.dtype))
+        _need_cuda(q, q.dtype, entry)
+        assert q.dim() == 4 and q.is_contiguous()
+        here = (int(q.shape[0]), int(q.shape[1]) * int(up), int(q.shape[2]) * int(up))
+        if plane is None:
+            plane = here
+        elif here != plane:
+            raise FqError("%s: the operands give different output planes (%s, %s)" % (entry, plane, here))
+        arr[i].q, arr[i].bytes, arr[i].C, arr[i].Cpad = q.data_ptr(), q.element_size(), int(C), int(q.shape[3])
+        arr[i].up, arr[i].relu, arr[i].shift = int(up), 1 if relu else 0, int(shift)
+        total += int(C)
+    if plane is None:
+        raise FqError("%s: no operand" % entry)
+    N, H, W = plane
+    cpad = pad16(total)
+    if out is None:
+        out = torch.empty(N, H, W, cpad, dtype=torch.int8, device=srcs[0][0].device)
+    else:
+        _need_cuda(out, torch.int8, entry)
+        assert tuple(out.shape) == (N, H, W, cpad) and out.is_contiguous()
+    _check(lib().fq_concat_rq_i8_nhwc(arr, n, out.data_ptr(), cpad, N, H, W, _stream(out)), entry)
     return out
 
 

@@ -222,7 +222,7 @@ class Plan(object):
         self.emit_int = False        # some consumer reads the integer form
         self.narrow_bit = None       # NewAdd: Quantity bit of the conv consumers (None: no narrow output)
         self.want_wide = False       # NewAdd: exact int16 sum needed (next add, or fp32 via dequant)
-        self.grid = None             # NewAdd: grid of the exact sum; windowed nn.AvgPool2d (enable(avgpool=True)) and bilinear upsampling (enable(bilinear=True)): grid of its source
+        self.grid = None             # NewAdd: grid of the exact sum; windowed nn.AvgPool2d (enable(avgpool=True)) and bilinear upsampling (enable(bilinear=True)): grid of its source; re-quantising Concat (enable(requant=True)): the TUPLE of its operands' planned grids, which marks the plan as that kind (to bit `narrow_bit`)
         self.resident_add = False    # NewAdd: operands arrive as integers
         self.defer = False           # NewConv2d: only consumer is a resident NewAdd, which runs this conv itself
         self.fuse_arg = None         # NewAdd: operand position (0 / 1) that arrives as a DeferredConv
@@ -590,6 +590,50 @@ class _ConcatResident(_InstanceForward):
                                                all(r or h.relu_done for h, _up, r in leaves)), *[h for h, _up, _r in leaves]))
 
 
+class _ConcatRequant(_InstanceForward):
+    """Instance-level forward of a Concat marker that re-quantises (enable(concat=True, requant=True)): its operands lie on
+    their own grids -- int8 activations, directly or through a deferred nearest upsampling, or the exact int16 sum of a resident
+    NewAdd -- and every reader quantises at one bit b = plan.narrow_bit, so DeQuantity_g -> cat -> (ReLU) -> Quantity_b runs as one
+    kernel on the integers (fq_concat_rq_i8_nhwc), each source shifted by b - its handle's grid.  plan.grid holds the tuple of the
+    planned operand grids and marks the plan as this kind.  The handle is `lossy`: it stands for Quantity_b(cat(...)).  A lossy
+    operand (a table activation, a bilinear upsampling, another such Concat) is taken at bit b only: its integers are copied.
+    Every run-time miss -- no exact payload, a lossy operand at another bit, planes that differ, a geometry or shift the kernel
+    does not take -- runs the marker's own forward on the fp32 forms (which raises where an operand has none)."""
+
+    @staticmethod
+    def _sources(plan, dim, operands):
+        if plan is None or type(plan.grid) is not tuple or plan.narrow_bit is None or dim != 1:
+            return None
+        b, out = plan.narrow_bit, []
+        for t in operands:
+            if type(t) is DeferredUpsample and t._out is None and t.handle.exact is not None and t.handle.exact.dtype == torch.int8:
+                h, up = t.handle, t.s
+            else:
+                h, up = resident_of(t), 1
+            if (h is None or h.exact is None or h.exact.dim() != 4 or h.exact.dtype not in (torch.int8, torch.int16)
+                    or (h.lossy and (h.grid != b or h.exact.dtype != torch.int8))):
+                return None
+            out.append((h, up))
+        planes = set((h.exact.shape[0], h.exact.shape[1] * up, h.exact.shape[2] * up) for h, up in out)
+        if len(planes) != 1 or not _native.concat_rq_supported([h.shape[1] for h, _up in out], [up for _h, up in out],
+                                                               [h.exact.element_size() for h, _up in out],
+                                                               [b - h.grid for h, _up in out]):
+            return None
+        return out
+
+    def __call__(self, x, y, dim=1):
+        m = self.module
+        plan = m.__dict__.get("_resident")
+        srcs = self._sources(plan, dim, (x, y))
+        if srcs is None:
+            return type(m).forward(m, as_f32(x), as_f32(y), dim)
+        b = plan.narrow_bit
+        q = _native.concat_rq_i8_nhwc([(h.exact, h.shape[1], up, plan.relu, b - h.grid) for h, up in srcs])
+        out = QHandle.int8(q, sum(h.shape[1] for h, _up in srcs), b, plan.relu or all(h.relu_done for h, _up in srcs))
+        out.lossy = True
+        return _emit(plan, out)
+
+
 # ---- tracing -------------------------------------------------------------------------------------
 
 class _Value(object):
@@ -728,6 +772,7 @@ def _clear(model):
     model.__dict__.pop("_fq_resident_avgpool", None)
     model.__dict__.pop("_fq_resident_topdown", None)
     model.__dict__.pop("_fq_resident_bilinear", None)
+    model.__dict__.pop("_fq_resident_requant", None)
 
 
 def disable(model):
@@ -754,7 +799,8 @@ class _Planning(object):
     nothing on the model until install() writes the plans and the instance-level forwards to the modules."""
 
     def __init__(self, tracer, depthwise, concat, avgpool, grouped, relu6=False, flatten=False, shuffle=False, activations=False,
-                 revoked=None, names=None, sums=False, topdown=False, revoked_up=None, bilinear=False, revoked_bil=None):
+                 revoked=None, names=None, sums=False, topdown=False, revoked_up=None, bilinear=False, revoked_bil=None,
+                 requant=False, revoked_cat=None):
         from .new_quantity_op import NewConv2d, NewAdd
         from .fabu_layer import Concat
         self.conv_type, self.concat_type = NewConv2d, Concat
@@ -793,6 +839,10 @@ class _Planning(object):
         self.revoked_bil = dict(revoked_bil or {})  # ... module that an earlier round planned and verify_lossy_bilinear() took back -> why
         self.bil_grids = {}              # ... planned bilinear upsampling -> (source grid g, consumer bit b)
         self.bil_left = {}               # ... hooked bilinear-mode nn.Upsample that stays torch's -> why
+        self.requant = bool(requant)     # (concat=True, requant=True) a Concat re-quantises its operands on fq_concat_rq_i8_nhwc
+        self.revoked_cat = dict(revoked_cat or {})  # ... Concat that an earlier round planned so and verify_lossy_concat() took back -> why
+        self.rq_cats = {}                # ... planned re-quantising Concat -> (reader bit b, (format of operand 0, of operand 1))
+        self.rq_left = {}                # ... Concat that the plain rule does not fully serve and this one declines -> why
         self.plans = {}                  # producer module -> Plan
         self.forwards = []               # (module, its instance-level forward)
         self.summary = {"resident_convs": 0, "resident_adds": 0, "resident_pools": 0, "fused_relus": 0, "fp32_outputs": 0,
@@ -819,6 +869,8 @@ class _Planning(object):
             self.summary["topdown_adds"] = self.summary["topdown_sum_sources"] = 0
         if bilinear:
             self.summary["resident_bilinears"] = 0
+        if requant:
+            self.summary["requant_concats"] = self.summary["requant_sum_sources"] = 0
 
     # ---- what a value is and what a module can do
 
@@ -1105,6 +1157,15 @@ class _Planning(object):
         with a NewAdd sum (int16) as an operand or with operands on different grids, any dim but 1, more than two operands (nested
         Concats are flattened by defer_concats, `flatten=True`), the `size=` form and other factors of an upsampling; a bare torch.cat stays foreign, as a bare
         `+` does.  The summary then gains `resident_concats`, `resident_upsamples` and `fused_upsamples` (defer_upsamples)."""
+        plain = self._concat_plain(v)
+        if not self.requant:
+            return plain
+        f, why = self._concat_requant(v, plain)
+        if f is None and why is not None:
+            self.rq_left[v.producer] = why
+        return f if f is not None else plain
+
+    def _concat_plain(self, v):
         m = v.producer
         ops = self._integer_operands(m) if self.tracer.concat_ok.get(m) else None
         if ops is None:
@@ -1115,6 +1176,71 @@ class _Planning(object):
         if not _native.concat_supported([x.shape[1], y.shape[1]], [1, 1]):
             return None
         return fx
+
+    def _concat_requant(self, v, plain):
+        """`concat=True, requant=True` plans a Concat whose operands lie on grids g_i of their own and whose readers all quantise
+        at one bit b on fq_concat_rq_i8_nhwc: the reference never re-quantises a Concat, so its chain DeQuantity_g_i -> cat ->
+        (ReLU) -> Quantity_b is a closed integer function, r = rint(v * 2^(b - g_i)) clamped (include/fq.h).  An operand is an
+        int8 activation ((1, g_i), directly or through a planned nearest upsampling, which defer_upsamples folds in), the exact
+        int16 sum of a resident NewAdd ((2, g_i), with that add's fused ReLU; the add counts the Concat as a reader of its exact
+        integers, _readers), or a lossy int8 value -- a table activation, a bilinear upsampling, another such Concat -- at bit b
+        exactly.  The output is Quantity_b(cat(...)), a lossy value: planned with format (1, b) only where every transitive reader
+        through _MOVES is an integer convolution at b (_lossy_walk) and |b - g_i| <= 8; verify_lossy_concat() takes it back where
+        a later pass left a reader in fp32 form.  The plain rule keeps every Concat it fully serves (operands int8 on one grid g,
+        every convolution that reads it directly at g; a mover behind it takes its int8 as it is): this rule takes what that one
+        refuses, or plans but has to emit fp32 for.  Returns (format, None) when planned, (None, why) when declined --
+        describe().requant_left -- and (None, None) where the plain rule serves it."""
+        m = v.producer
+        direct = [c.input_bit for (c, _pos) in self.effective(v)[0].consumers if self.conv_can_read(c)]
+        if plain is not None and all(bit == plain[1] for bit in direct):
+            return None, None                               # (a mover behind it -- an outer Concat -- takes its int8 as it is)
+        bits, fp32_reader = self._lossy_walk(v)
+        ops = self.operands.get(m)
+        if not self.once(m):
+            return None, "the module was called more than once"
+        if not self.tracer.concat_ok.get(m):
+            return None, "dim != 1, or its operands are not two 4-D tensors"
+        if ops is None or ops[0] is None or ops[1] is None:
+            return None, "an operand is not the output of a planned layer (no integer source)"
+        if m in self.revoked_cat:
+            return None, self.revoked_cat[m]
+        if fp32_reader is not None:
+            return None, fp32_reader
+        if len(bits) != 1:
+            return None, "its readers quantise at different bits %s" % sorted(bits)
+        b = next(iter(bits))
+        fmts = []
+        for o in ops:
+            f = self.fmt.get(id(o))
+            if f is None:
+                src = self.fmt.get(id(o.src)) if o.kind == "upsample" and o.src is not None else None
+                if src is not None and src[0] == 2:
+                    return None, "an operand is an upsampled NewAdd sum: no integer kernel upsamples int16 (fp32 form)"
+                return None, "an operand has no integer form in this plan (fp32 form)"
+            root = o.src if o.kind == "relu" and o.src is not None else o
+            if f[0] == 2 and root.kind != "add":
+                return None, "an operand is int16 but no NewAdd sum (fp32 form)"
+            if o.shape is None or len(o.shape) != 4:
+                return None, "an operand is not 4-D"
+            # (a lossy operand -- a table activation, a bilinear upsampling, another such Concat -- sits at b: its own walk went
+            #  through this Concat to the same readers; the run-time path checks it all the same)
+            if abs(b - f[1]) > 8:
+                return None, "|b - g| = |%d - %d| > 8: not taken by the kernel (fp32 form)" % (b, f[1])
+            fmts.append(f)
+        if not _native.concat_rq_supported([o.shape[1] for o in ops], [1, 1], [f[0] for f in fmts], [b - f[1] for f in fmts]):
+            return None, "fq_concat_rq_i8_nhwc does not take operands of %s channels (unsupported geometry)" % [o.shape[1] for o in ops]
+        self.rq_cats[m] = (b, tuple(fmts))
+        return (1, b), None
+
+    def verify_lossy_concat(self):
+        """verify_lossy() for the planned re-quantising Concats: {module: why} for every one whose value, after all passes,
+        somebody would read in fp32 form.  enable() plans again without them: the Concat keeps the plain rule's plan."""
+        bad = {}
+        for m, (b, _fmts) in self.rq_cats.items():
+            why = self._lossy_violation(self.value_of[m], b)
+            if why is not None:
+                bad[m] = "revoked by the lossy rule: " + why
+        return bad
 
     def _shuffle_format(self, v):
         """`shuffle=True` plans nn.ChannelShuffle and the Slice marker (fabu_layer.Slice, x[:, start:stop]), both served by
@@ -1247,13 +1373,15 @@ class _Planning(object):
         return None
 
     def _lossy_origin(self, v, depth=0):
-        """The table activation or bilinear upsampling whose (would-be) lossy value reaches v through ReLUs and _MOVES, or None.
-        Decided on the trace alone."""
+        """The table activation, bilinear upsampling or (planned) re-quantising Concat whose (would-be) lossy value reaches v
+        through ReLUs and _MOVES, or None.  Decided on the trace and on what was planned in front of v."""
         if v is None or depth > 64:
             return None
         if v.kind in ("act", "bilinear"):
             return v.producer
         if v.kind == "concat":
+            if v.producer in self.rq_cats:                  # (a re-quantising Concat: its own value is Quantity_b(cat(...)))
+                return v.producer
             for o in self.operands.get(v.producer) or ():
                 found = self._lossy_origin(o, depth + 1)
                 if found is not None:
@@ -1377,9 +1505,10 @@ class _Planning(object):
             if self.conv_can_read(c):
                 bits.append(c.input_bit)
             elif (c in self.add_resident or self.avg_can_read(c) or (v.kind == "add" and c in self.avg_sum)
-                  or (v.kind == "add" and c in self.topdown_ups)):
+                  or (v.kind == "add" and c in self.topdown_ups) or (v.kind == "add" and c in self.rq_cats)):
                 exact += 1                                  # (a windowed pool over the sum reads the exact int16, as the whole-plane pool does;
-                                                            #  so does an upsampling in front of a NewAdd, topdown=True)
+                                                            #  so does an upsampling in front of a NewAdd, topdown=True, and a
+                                                            #  re-quantising Concat, requant=True)
             elif (c in self.int8_resident or c in self.avg_resident) and v.kind != "add":
                 int8 += 1                                   # int8 max-pool / Concat / nearest upsampling / windowed average pool
             else:
@@ -1421,6 +1550,11 @@ class _Planning(object):
             plan.grid = self.act_grids[m][0]
         if v.kind == "bilinear":
             plan.up, plan.grid = _bilinear_factor(m), self.bil_grids[m][0]
+        if v.kind == "concat" and m in self.rq_cats:        # (narrow_bit is the readers' bit b already: the value's format)
+            fmts = self.rq_cats[m][1]
+            plan.grid, forward = tuple(f[1] for f in fmts), _ConcatRequant
+            self.summary["requant_concats"] += 1
+            self.summary["requant_sum_sources"] += sum(1 for f in fmts if f[0] == 2)
         self._take(m, plan, relu_mod, forward)
         self.summary[_COUNTER[v.kind]] += 1
 
@@ -1545,12 +1679,14 @@ class _Planning(object):
             if v.kind != "concat" or plan is None or v.producer not in self.int8_resident:
                 continue
             leaves[id(v)] = count(v.producer)
+            if v.producer in self.rq_cats:                  # (a re-quantising Concat launches itself: its leaves are on other grids)
+                continue
             e = self.eff_of[id(v)][0]
             if v.foreign or e.foreign or plan.emit_f32 or len(e.consumers) != 1:
                 continue
             cat_mod, pos = e.consumers[0]
             if (not isinstance(cat_mod, self.concat_type) or cat_mod not in self.int8_resident or cat_mod not in self.plans
-                    or pos > 1):
+                    or pos > 1 or cat_mod in self.rq_cats):     # (... and takes an inner plain Concat as ONE int8 source)
                 continue
             ops = self.operands[cat_mod]
             if ops[pos] is not e or ops[1 - pos] is e or count(cat_mod, assume=v) > MAX_CONCAT_LEAVES:
@@ -1601,6 +1737,9 @@ class _Planning(object):
                     self.bil_left[m] = _bilinear_form_left(m) or "its input is not the output of a planned layer (no integer source)"
             names = dict((m, name) for name, m in model.named_modules())
             model.__dict__["_fq_resident_bilinear"] = dict((names.get(m, "?"), why) for m, why in self.bil_left.items())
+        if self.requant:
+            names = dict((m, name) for name, m in model.named_modules())
+            model.__dict__["_fq_resident_requant"] = dict((names.get(m, "?"), why) for m, why in self.rq_left.items())
         if self.activations:
             for m, (g, b) in self.act_grids.items():
                 self.plans[m].table = _native.build_act_table(m, g, b)
@@ -1643,7 +1782,7 @@ def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False, ac
 
 
 def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False, grouped=False, relu6=False,
-           flatten=False, shuffle=False, activations=False, sums=False, topdown=False, bilinear=False):
+           flatten=False, shuffle=False, activations=False, sums=False, topdown=False, bilinear=False, requant=False):
     """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
     on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
     nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
@@ -1667,7 +1806,11 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
     tensor never written (_Planning._topdown_format);
     `bilinear=True` (with `concat=True`; ValueError without) also plans nn.Upsample(scale_factor=2 or 4, mode="bilinear",
     align_corners=False) between an int8 activation and convolutions at one bit -- the decoder step of a U-Net -- on
-    fq_upsample_bilinear_i8_nhwc, a lossy value like a table activation's (_Planning._bilinear_format)."""
+    fq_upsample_bilinear_i8_nhwc, a lossy value like a table activation's (_Planning._bilinear_format);
+    `requant=True` (with `concat=True`; ValueError without) also plans a Concat whose operands lie on different grids, whose
+    readers quantise at another bit than its operands, or one of whose operands is the int16 sum of a NewAdd -- the skip of a
+    ResNet-encoder U-Net -- on fq_concat_rq_i8_nhwc, which re-quantises every source to the readers' bit: a lossy value too
+    (_Planning._concat_requant)."""
     from .new_quantity_op import QUANTIZE_BIT
     if flatten and not concat:
         raise ValueError("resident.enable(flatten=True) needs concat=True: only planned Concats are flattened")
@@ -1677,15 +1820,17 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
         raise ValueError("resident.enable(topdown=True) needs concat=True: the upsampling is hooked by that switch")
     if bilinear and not concat:
         raise ValueError("resident.enable(bilinear=True) needs concat=True: the Concat behind a decoder's upsampling is planned by that switch")
+    if requant and not concat:
+        raise ValueError("resident.enable(requant=True) needs concat=True: only a hooked Concat marker re-quantises")
     _clear(model)
     if QUANTIZE_BIT != 8:
         raise _native.FqError("resident activations are defined for QUANTIZE_BIT = 8")
     tracer, traced_out = _trace(model, example_input, concat, avgpool, relu6, shuffle, activations, bilinear)
-    names = dict((m, name) for name, m in model.named_modules()) if activations or sums or topdown or bilinear else None
-    revoked, revoked_up, revoked_bil = {}, {}, {}
+    names = dict((m, name) for name, m in model.named_modules()) if activations or sums or topdown or bilinear or requant else None
+    revoked, revoked_up, revoked_bil, revoked_cat = {}, {}, {}, {}
     while True:
         planning = _Planning(tracer, depthwise, concat, avgpool, grouped, relu6, flatten, shuffle, activations, revoked, names,
-                             sums, topdown, revoked_up, bilinear, revoked_bil)
+                             sums, topdown, revoked_up, bilinear, revoked_bil, requant, revoked_cat)
         planning.plan_formats()
         planning.plan_outputs()
         planning.defer_convs()
@@ -1699,8 +1844,10 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
         bad = planning.verify_lossy() if activations else {}
         bad_up = planning.verify_topdown() if topdown else {}
         bad_bil = planning.verify_lossy_bilinear() if bilinear else {}
-        if not bad and not bad_up and not bad_bil:
+        bad_cat = planning.verify_lossy_concat() if requant else {}
+        if not bad and not bad_up and not bad_bil and not bad_cat:
             break
+        revoked_cat.update(bad_cat)                         # (... or one re-quantising Concat)
         revoked_bil.update(bad_bil)                         # (... or one bilinear upsampling)
         revoked.update(bad)                                 # (each round takes at least one activation out: it ends)
         revoked_up.update(bad_up)                           # (... or one upsampling)
@@ -1729,9 +1876,11 @@ class _Description(dict):
     torch's.  After enable(concat=True, topdown=True) `topdown_left` is {module name: why} for every nearest upsampling in front
     of a NewAdd (or over a sum) that keeps the plan it had without the switch, and for every nn.Upsample that is foreign code.
     After enable(concat=True, bilinear=True) `bilinear_left` is {module name: why} for every hooked bilinear-mode nn.Upsample that
-    stays torch's."""
+    stays torch's.  After enable(concat=True, requant=True) `requant_left` is {module name: why} for every Concat that the plain
+    rule does not fully serve -- it has no integer plan, or emits fp32 for a reader -- and the re-quantising rule declines."""
     activations_left = {}
     bilinear_left = {}
+    requant_left = {}
     avgpool_left = {}
     topdown_left = {}
     activations_revoked = ()
@@ -1750,6 +1899,7 @@ def describe(model):
     d.avgpool_left = model.__dict__.get("_fq_resident_avgpool", {})
     d.topdown_left = model.__dict__.get("_fq_resident_topdown", {})
     d.bilinear_left = model.__dict__.get("_fq_resident_bilinear", {})
+    d.requant_left = model.__dict__.get("_fq_resident_requant", {})
     d.flattened_concats = tuple(name for name, m in model.named_modules()
                                 if type(m).__name__ == "Concat" and name in d and d[name].defer)
     return d
