@@ -801,6 +801,33 @@ int fq_shuffle_i8_nhwc_supported(int C_in, int c_off, int C, int groups);
 int fq_shuffle_i8_nhwc(const int8_t* x, int Cpad_in, int c_off, int8_t* y, int Cpad_out, int C, int groups, int N, int H, int W,
                        fq_stream_t stream);
 
+/* Pixel shuffle and unshuffle (nn.PixelShuffle(r), nn.PixelUnshuffle(r): depth-to-space, space-to-depth) of a resident int8 NHWC
+ * activation: a permutation of the integers is the same permutation of the values q * 2^-g, as for the shuffle above.
+ *   inverse == 0, nn.PixelShuffle(r):    x int8 [N][H][W][Cpad_in] with C r^2 real channels, Cpad_in == pad16(C r^2);
+ *                                         y int8 [N][H r][W r][Cpad_out], Cpad_out == pad16(C);
+ *                                         y[n][h r + i][w r + j][c] = x[n][h][w][c r^2 + i r + j]        for 0 <= c < C
+ *   inverse == 1, nn.PixelUnshuffle(r):  x int8 [N][H r][W r][Cpad_in] with C real channels, Cpad_in == pad16(C);
+ *                                         y int8 [N][H][W][Cpad_out], Cpad_out == pad16(C r^2);
+ *                                         y[n][h][w][c r^2 + i r + j] = x[n][h r + i][w r + j][c]
+ *   The padding channels of y are zero, whatever x's padding channels hold.  H, W are the LOW-resolution plane in both
+ *   directions, so no plane that does not divide can be passed.  r in {2, 3, 4}; C is BYTE granular (3, 17, 100: an RGB head).
+ * x, y: 16-byte aligned, not overlapping.  Only aligned loads are issued, no byte outside x's extent is read and none outside y's
+ *   is written; every store is a dwordx4.  r in {2, 4} with C % 16 == 0 runs a register-transpose kernel (r^2 dwordx4 loads,
+ *   v_perm_b32, r^2 dwordx4 stores per lane), everything else a kernel that gathers bytes from aligned dwords.
+ * Return codes, scalars judged before pointers: FQ_ERR_INVALID_ARG for N < 0, H < 1, W < 1, C < 1, inverse outside {0, 1}; then
+ *   FQ_ERR_UNSUPPORTED for r outside {2, 3, 4} and for C r^2 > 65536; then FQ_ERR_INVALID_ARG for a wrong Cpad_in or Cpad_out; then
+ *   FQ_ERR_UNSUPPORTED for a source or an output of 2^31 - 1 bytes or more (32-bit byte offsets): callers keep the fp32 form
+ *   there.  N == 0 is then FQ_OK without a launch; with N > 0 a null or misaligned pointer is FQ_ERR_INVALID_ARG.  Everything is
+ *   decided on the host before anything is launched; no global state, no environment variable.
+ * Not built: a NewAdd sum (int16) as the source, the permutation fused into the producing convolution's epilogue or the
+ *   consumer's loads, r > 4.
+ * fq_pixel_shuffle_i8_nhwc_supported: 1 when (C, r, inverse) is taken (host arithmetic, no GPU needed).
+ * fq_pixel_shuffle_i8_nhwc_family: a diagnostic for tests -- 0 not taken, 1 the register-transpose kernel, 2 the byte gather. */
+int fq_pixel_shuffle_i8_nhwc_supported(int C, int r, int inverse);
+int fq_pixel_shuffle_i8_nhwc_family(int C, int r, int inverse);
+int fq_pixel_shuffle_i8_nhwc(const int8_t* x, int Cpad_in, int8_t* y, int Cpad_out, int C, int r, int inverse, int N, int H, int W,
+                             fq_stream_t stream);
+
 /* An elementwise activation f between two integer layers (nn.LeakyReLU, nn.Hardswish, nn.SiLU, ...: anything that is no clamp) on
  * a resident int8 NHWC activation, as a table of 256 bytes.  Between a producer's int8 output q on grid g and a consumer's
  * Quantity(b), f is a function of 256 values: table256[q + 128] = Quantity_b(f(DeQuantity_g(q))), made once by the caller with

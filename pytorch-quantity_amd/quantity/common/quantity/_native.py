@@ -267,6 +267,12 @@ def lib():
     L.fq_shuffle_i8_nhwc_supported.argtypes = [ci] * 4
     L.fq_shuffle_i8_nhwc.restype = ci
     L.fq_shuffle_i8_nhwc.argtypes = [vp, ci, ci, vp] + [ci] * 6 + [vp]
+    L.fq_pixel_shuffle_i8_nhwc_supported.restype = ci
+    L.fq_pixel_shuffle_i8_nhwc_supported.argtypes = [ci] * 3
+    L.fq_pixel_shuffle_i8_nhwc_family.restype = ci
+    L.fq_pixel_shuffle_i8_nhwc_family.argtypes = [ci] * 3
+    L.fq_pixel_shuffle_i8_nhwc.restype = ci
+    L.fq_pixel_shuffle_i8_nhwc.argtypes = [vp, ci, vp] + [ci] * 7 + [vp]
     L.fq_act_lut_i8_nhwc_supported.restype = ci
     L.fq_act_lut_i8_nhwc_supported.argtypes = [ci]
     L.fq_act_lut_i8_nhwc.restype = ci
@@ -1730,6 +1736,43 @@ def build_act_table(module, grid, bit):
         q = torch.arange(-128, 128, dtype=torch.float32, device=device).reshape(1, 1, 16, 16)
         t = quantity(type(module).forward(module, dequantity(q, int(grid))).contiguous(), int(bit))
         return t.reshape(256).to(torch.int8)
+
+
+def pixel_shuffle_supported(C, r, inverse):
+    """True when fq_pixel_shuffle_i8_nhwc takes C shallow channels, factor r and this direction (include/fq.h): C >= 1, r in
+    {2, 3, 4}, inverse in {0, 1}, C * r * r <= 65536.  Pure host arithmetic (no GPU needed)."""
+    return bool(lib().fq_pixel_shuffle_i8_nhwc_supported(int(C), int(r), int(inverse)))
+
+
+def pixel_shuffle_family(C, r, inverse):
+    """Which kernel fq_pixel_shuffle_i8_nhwc runs for (C, r, inverse): 0 none, 1 the register transpose, 2 the byte gather."""
+    return int(lib().fq_pixel_shuffle_i8_nhwc_family(int(C), int(r), int(inverse)))
+
+
+def pixel_shuffle_i8_nhwc(x, C, r, inverse, out=None):
+    """fq_pixel_shuffle_i8_nhwc.  C: the channels of the SHALLOW tensor (nn.PixelShuffle's output, nn.PixelUnshuffle's input).
+    inverse == 0: x int8 [N, H, W, pad16(C r^2)] -> int8 [N, H r, W r, pad16(C)], y[n, h r + i, w r + j, c] = x[n, h, w, c r^2 + i r + j];
+    inverse == 1: x int8 [N, H r, W r, pad16(C)] -> int8 [N, H, W, pad16(C r^2)], the inverse map.  The padding channels are zero.
+    `out`: write there instead (that shape, dense, 16-byte aligned).  Launches on the current stream and does not synchronise."""
+    entry = "fq_pixel_shuffle_i8_nhwc"
+    _need_cuda(x, torch.int8, entry)
+    assert x.dim() == 4 and x.is_contiguous()
+    C, r, inverse = int(C), int(r), int(inverse)
+    N, Hx, Wx, cpad_in = (int(v) for v in x.shape)
+    want_in = pad16(C) if inverse else pad16(C * r * r)
+    if cpad_in != want_in:
+        raise FqError("%s: the source of %d channels, r = %d, inverse = %d is stored as %d, got %d" % (entry, C, r, inverse, want_in, cpad_in))
+    if inverse and (r < 1 or Hx % r or Wx % r):
+        raise FqError("%s: a %d x %d plane is not divisible by r = %d" % (entry, Hx, Wx, r))
+    H, W = (Hx // r, Wx // r) if inverse else (Hx, Wx)
+    shape = (N, H, W, pad16(C * r * r)) if inverse else (N, H * r, W * r, pad16(C))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int8, device=x.device)
+    else:
+        _need_cuda(out, torch.int8, entry)
+        assert tuple(out.shape) == shape and out.is_contiguous()
+    _check(lib().fq_pixel_shuffle_i8_nhwc(x.data_ptr(), cpad_in, out.data_ptr(), shape[3], C, r, inverse, N, H, W, _stream(out)), entry)
+    return out
 
 
 def avgpool_supported(kernel, stride, padding, shift):

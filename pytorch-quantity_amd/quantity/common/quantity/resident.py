@@ -230,10 +230,10 @@ class Plan(object):
         self.narrow_to_hbm = True    # NewAdd with fuse_next: somebody besides that convolution reads the int8 re-quantisation
         self.fuse_proj = False       # NewAdd with fuse_arg: the OTHER operand is a deferred 1x1 projection that the kernel computes too
         self.depthwise = False       # NewConv2d: a depthwise layer taken by enable(depthwise=True); runs on fq_dwconv2d_i8_resident
-        self.up = None               # nearest upsampling taken by enable(concat=True): its factor (with `defer`: the Concat applies it -- or, with topdown=True, the NewAdd); bilinear upsampling taken by enable(bilinear=True): its factor, from grid `grid` to bit `narrow_bit`
+        self.up = None               # nearest upsampling taken by enable(concat=True): its factor (with `defer`: the Concat applies it -- or, with topdown=True, the NewAdd); bilinear upsampling taken by enable(bilinear=True): its factor, from grid `grid` to bit `narrow_bit`; nn.PixelShuffle / nn.PixelUnshuffle taken by enable(pixelshuffle=True): its factor r (with `perm`)
         self.grouped = False         # NewConv2d: a grouped layer taken by enable(grouped=True); runs on fq_gconv2d_i8_resident
         self.clip = False            # NewConv2d with `relu`: the fused activation is an nn.ReLU6 (enable(relu6=True)): clipped at 6
-        self.perm = None             # nn.ChannelShuffle / Slice taken by enable(shuffle=True): (c_off, C, groups) of fq_shuffle_i8_nhwc
+        self.perm = None             # nn.ChannelShuffle / Slice taken by enable(shuffle=True): (c_off, C, groups) of fq_shuffle_i8_nhwc; nn.PixelShuffle / nn.PixelUnshuffle taken by enable(pixelshuffle=True): ("d2s", C) / ("s2d", C) of fq_pixel_shuffle_i8_nhwc, C the channels of the shallow tensor
         self.table = None            # elementwise activation taken by enable(activations=True): the 256 int8 of fq_act_lut_i8_nhwc, from grid `grid` to bit `narrow_bit`
 
     def __getstate__(self):
@@ -392,6 +392,50 @@ class _ShuffleResident(_InstanceForward):
 class _SliceResident(_ShuffleResident):
     """Instance-level forward of a Slice marker between integer layers (enable(shuffle=True)): channels [start, stop) of the int8
     NHWC integers as a tensor of their own, the padding channels zero (fq_shuffle_i8_nhwc with one group)."""
+
+
+PIXEL_FACTORS = (2, 3, 4)          # the factors fq_pixel_shuffle_i8_nhwc takes
+
+
+def _pixel_factor(m):
+    """The factor of an nn.PixelShuffle / nn.PixelUnshuffle as the module holds it (any object)."""
+    return m.upscale_factor if isinstance(m, nn.PixelShuffle) else m.downscale_factor
+
+
+def _pixel_geometry(m, shape):
+    """(r, ("d2s" | "s2d", C)) -- Plan.up and Plan.perm -- of fq_pixel_shuffle_i8_nhwc for an nn.PixelShuffle / nn.PixelUnshuffle that
+    reads a 4-D activation of `shape` (N, channels, height, width), C the channels of the shallow tensor; or None: a factor that is
+    no plain int of PIXEL_FACTORS, channels that r^2 does not divide (a shuffle), a plane that r does not divide (an unshuffle)."""
+    r = _pixel_factor(m)
+    if type(r) is not int or r not in PIXEL_FACTORS or len(shape) != 4:
+        return None
+    channels, hh, ww = int(shape[1]), int(shape[2]), int(shape[3])
+    if isinstance(m, nn.PixelShuffle):
+        return (r, ("d2s", channels // (r * r))) if channels % (r * r) == 0 and channels >= r * r else None
+    return (r, ("s2d", channels)) if hh % r == 0 and ww % r == 0 and hh >= r and ww >= r else None
+
+
+class _PixelShuffleResident(_InstanceForward):
+    """Instance-level forward of an nn.PixelShuffle / nn.PixelUnshuffle between integer layers (enable(pixelshuffle=True)):
+    permuting the int8 NHWC integers between depth and space is permuting the values (fq_pixel_shuffle_i8_nhwc).  The handle is
+    built as _ShuffleResident builds its own: the source's grid, lossy where the source is, the narrow form carried where it equals
+    the exact one.  An operand that arrives deferred is materialised first (resident_of).  Whenever a run-time condition fails --
+    no plan, no int8 exact payload, a factor, direction or width other than the planned one, a geometry the kernel refuses --
+    the module's own forward runs on the fp32 form."""
+
+    def __call__(self, x):
+        m = self.module
+        plan = m.__dict__.get("_resident")
+        h = resident_of(x)
+        geo = None
+        if plan is not None and h is not None and h.exact is not None and h.exact.dtype == torch.int8 and h.exact.dim() == 4:
+            geo = _pixel_geometry(m, (h.shape[0], h.shape[1], h.exact.shape[1], h.exact.shape[2]))
+        if geo is None or geo != (plan.up, plan.perm) or not _native.pixel_shuffle_supported(geo[1][1], geo[0], geo[1][0] == "s2d"):
+            return type(m).forward(m, as_f32(x))
+        r, (way, c) = geo
+        y = _native.pixel_shuffle_i8_nhwc(h.exact, c, r, way == "s2d")
+        narrow = y if (h.narrow is h.exact or h.bit == h.grid) else None
+        return _emit(plan, _moved(QHandle.wide_narrow(c if way == "d2s" else c * r * r, y, h.grid, narrow, h.grid, h.relu_done), h))
 
 
 ACTIVATION_TYPES = (nn.LeakyReLU, nn.PReLU, nn.Hardswish, nn.Hardsigmoid, nn.SiLU, nn.Sigmoid, nn.Tanh, nn.ELU, nn.Hardtanh, nn.Mish,
@@ -669,6 +713,7 @@ class _Tracer(TorchFunctionMode):
         self.act_seen = []               # (enable(activations=True)) every hooked table activation, in execution order
         self.act_inplace = set()         # ... those that returned their own input tensor
         self.bilinear_seen = []          # (enable(bilinear=True)) every hooked bilinear-mode nn.Upsample, in execution order
+        self.pixel_seen = []             # (enable(pixelshuffle=True)) every hooked nn.PixelShuffle / nn.PixelUnshuffle, in execution order
         self.values = {}             # id(tensor) -> _Value
         self.keep = []               # keeps traced tensors alive so ids are not reused
         self.depth = 0
@@ -696,6 +741,8 @@ class _Tracer(TorchFunctionMode):
             self.act_seen.append(module)
         if isinstance(module, nn.Upsample) and module.mode == "bilinear" and module not in self.bilinear_seen:
             self.bilinear_seen.append(module)
+        if isinstance(module, (nn.PixelShuffle, nn.PixelUnshuffle)) and module not in self.pixel_seen:
+            self.pixel_seen.append(module)
         for pos, a in enumerate(args):
             v = self.values.get(id(a)) if isinstance(a, torch.Tensor) else None
             if v is not None:
@@ -727,6 +774,8 @@ class _Tracer(TorchFunctionMode):
             return "shuffle"
         if _is_table_activation(module):                    # (hooked only with enable(activations=True))
             return "act"
+        if isinstance(module, (nn.PixelShuffle, nn.PixelUnshuffle)):     # (hooked only with enable(pixelshuffle=True))
+            return "pixelshuffle"
         name = type(module).__name__
         return {"Concat": "concat", "NewAdd": "add", "Slice": "slice"}.get(name, "contraction")     # (Concat, Slice: likewise)
 
@@ -738,7 +787,7 @@ class _Tracer(TorchFunctionMode):
         src = None
         if kind == "act" and args and output is args[0]:
             self.act_inplace.add(module)
-        if kind in ("relu", "maxpool", "avgpool", "upsample", "bilinear", "shuffle", "slice", "act"):     # a value of these kinds exists only behind a traced value
+        if kind in ("relu", "maxpool", "avgpool", "upsample", "bilinear", "shuffle", "slice", "act", "pixelshuffle"):     # a value of these kinds exists only behind a traced value
             if kind == "avgpool" and not self.avgpool:
                 return                                      # its output is an ordinary fp32 tensor
             src = self.values.get(id(args[0])) if args and isinstance(args[0], torch.Tensor) else None
@@ -773,6 +822,7 @@ def _clear(model):
     model.__dict__.pop("_fq_resident_topdown", None)
     model.__dict__.pop("_fq_resident_bilinear", None)
     model.__dict__.pop("_fq_resident_requant", None)
+    model.__dict__.pop("_fq_resident_pixelshuffle", None)
 
 
 def disable(model):
@@ -787,10 +837,10 @@ def is_enabled(model):
 
 _COUNTER = {"contraction": "resident_convs", "add": "resident_adds", "maxpool": "resident_pools", "concat": "resident_concats",
             "upsample": "resident_upsamples", "shuffle": "resident_shuffles", "slice": "resident_slices",
-            "act": "resident_activations", "bilinear": "resident_bilinears"}
+            "act": "resident_activations", "bilinear": "resident_bilinears", "pixelshuffle": "resident_pixelshuffles"}
 _FORWARD = {"maxpool": _MaxPoolResident, "concat": _ConcatResident, "upsample": _UpsampleResident, "shuffle": _ShuffleResident,
-            "slice": _SliceResident, "act": _ActTableResident, "bilinear": _BilinearResident}
-_MOVES = ("maxpool", "concat", "upsample", "shuffle", "slice")       # what Quantity_b commutes with: data movement and max
+            "slice": _SliceResident, "act": _ActTableResident, "bilinear": _BilinearResident, "pixelshuffle": _PixelShuffleResident}
+_MOVES = ("maxpool", "concat", "upsample", "shuffle", "slice", "pixelshuffle")       # what Quantity_b commutes with: data movement and max
 #                                                                      (not "bilinear": Quantity_b does not commute with interpolation)
 
 
@@ -800,7 +850,7 @@ class _Planning(object):
 
     def __init__(self, tracer, depthwise, concat, avgpool, grouped, relu6=False, flatten=False, shuffle=False, activations=False,
                  revoked=None, names=None, sums=False, topdown=False, revoked_up=None, bilinear=False, revoked_bil=None,
-                 requant=False, revoked_cat=None):
+                 requant=False, revoked_cat=None, pixelshuffle=False):
         from .new_quantity_op import NewConv2d, NewAdd
         from .fabu_layer import Concat
         self.conv_type, self.concat_type = NewConv2d, Concat
@@ -825,7 +875,7 @@ class _Planning(object):
                 if isinstance(m, (NewAdd, Concat)) and pos < 2:
                     self.operands.setdefault(m, [None, None])[pos] = v
         self.add_resident = set()        # NewAdd modules whose operands arrive as integers
-        self.int8_resident = set()       # nn.MaxPool2d, Concat, nearest-upsampling, nn.ChannelShuffle and Slice modules that run on the int8 integers
+        self.int8_resident = set()       # nn.MaxPool2d, Concat, nearest-upsampling, nn.ChannelShuffle, Slice and nn.PixelShuffle / nn.PixelUnshuffle modules that run on the int8 integers
         self.avg_resident = {}           # windowed nn.AvgPool2d that runs on fq_avgpool_i8_nhwc -> (source grid g, consumer bit b)
         self.sums = bool(sums)           # (avgpool=True, sums=True) a windowed pool may read a NewAdd's exact int16 sum
         self.avg_sum = set()             # ... the pools of avg_resident that do (fq_avgpool_i16_nhwc)
@@ -843,6 +893,9 @@ class _Planning(object):
         self.revoked_cat = dict(revoked_cat or {})  # ... Concat that an earlier round planned so and verify_lossy_concat() took back -> why
         self.rq_cats = {}                # ... planned re-quantising Concat -> (reader bit b, (format of operand 0, of operand 1))
         self.rq_left = {}                # ... Concat that the plain rule does not fully serve and this one declines -> why
+        self.pixelshuffle = bool(pixelshuffle)      # (pixelshuffle=True) nn.PixelShuffle / nn.PixelUnshuffle on fq_pixel_shuffle_i8_nhwc
+        self.pixel_geo = {}              # ... planned module -> (r, ("d2s" | "s2d", C))
+        self.pixel_left = {}             # ... hooked module that stays torch's -> why
         self.plans = {}                  # producer module -> Plan
         self.forwards = []               # (module, its instance-level forward)
         self.summary = {"resident_convs": 0, "resident_adds": 0, "resident_pools": 0, "fused_relus": 0, "fp32_outputs": 0,
@@ -871,6 +924,8 @@ class _Planning(object):
             self.summary["resident_bilinears"] = 0
         if requant:
             self.summary["requant_concats"] = self.summary["requant_sum_sources"] = 0
+        if pixelshuffle:
+            self.summary["resident_pixelshuffles"] = self.summary["resident_pixelunshuffles"] = 0
 
     # ---- what a value is and what a module can do
 
@@ -880,7 +935,7 @@ class _Planning(object):
 
     def effective(self, v):
         """(value the consumers see, fused ReLU / ReLU6 module or None)"""
-        if v.kind not in ("maxpool", "shuffle", "slice", "act") and not v.foreign and len(v.consumers) == 1 and isinstance(v.consumers[0][0], (nn.ReLU, nn.ReLU6)):
+        if v.kind not in ("maxpool", "shuffle", "slice", "act", "pixelshuffle") and not v.foreign and len(v.consumers) == 1 and isinstance(v.consumers[0][0], (nn.ReLU, nn.ReLU6)):
             act = v.consumers[0][0]
             after = self.relu_value.get(id(v))
             if after is not None and (isinstance(act, nn.ReLU) or self.takes_relu6(v)):
@@ -986,6 +1041,8 @@ class _Planning(object):
                 f = self._shuffle_format(v)
             elif v.kind == "act":
                 f = self._act_format(v)
+            elif v.kind == "pixelshuffle":
+                f = self._pixelshuffle_format(v)
             else:
                 f = self._add_format(v)
                 ops = self.operands.get(m) or ()
@@ -1279,6 +1336,44 @@ class _Planning(object):
         self.shuffle_left[m] = why
         return None
 
+    def _pixelshuffle_format(self, v):
+        """`pixelshuffle=True` plans nn.PixelShuffle(r) and nn.PixelUnshuffle(r) -- the upsampler of a sub-pixel super-resolution
+        network, the samplers of a restoration network, YOLOv2's passthrough -- on fq_pixel_shuffle_i8_nhwc: a module called once
+        that reads a 4-D int8 activation (format (1, g), lossy or not) moves the integers between depth and space and hands them on
+        the source's grid.  Both are pure permutations, so Quantity_b commutes with them: the kind is one of _MOVES and a lossy
+        value walks through it.  Its readers are whatever a channel shuffle's may be: convolutions (dense, depthwise, grouped), a
+        Concat (plain, flattened, re-quantising), a NewAdd, a max-pool, a windowed pool, a shuffle or slice, another pixel shuffle,
+        or fp32 code and model outputs through to_f32().  No ReLU is fused into it (effective): a ReLU directly behind one reads the
+        fp32 form; the common order, convolution + ReLU then pixel shuffle, fuses in the convolution as always.  Without the
+        argument both modules are foreign code and their source leaves as fp32.  Plan.up carries the factor, Plan.perm the
+        direction and the shallow tensor's channels.  Left to torch, each named with its reason by describe().pixelshuffle_left: a
+        NewAdd sum (int16) as the source, a source without an integer form, a module called twice, a non-4-D input, a factor
+        outside {2, 3, 4}, a geometry the kernel refuses; an F.pixel_shuffle call stays foreign, as a bare `+` does.  The summary
+        gains `resident_pixelshuffles` and `resident_pixelunshuffles`."""
+        m = v.producer
+        src = self.fmt.get(id(v.src))
+        why = None
+        r = _pixel_factor(m)
+        if not self.once(m):
+            why = "the module was called more than once"
+        elif v.src.shape is None or len(v.src.shape) != 4:
+            why = "its input is not 4-D"
+        elif src is None:
+            why = "its source has no integer form in this plan (fp32 form)"
+        elif src[0] != 1:
+            why = "its source is a NewAdd sum (int16): only int8 activations are permuted (fp32 form)"
+        elif type(r) is not int or r not in PIXEL_FACTORS:
+            why = "factor %r: only the factors 2, 3 and 4 are taken (fp32 form)" % (r,)
+        else:
+            geo = _pixel_geometry(m, v.src.shape)
+            if geo is None or not _native.pixel_shuffle_supported(geo[1][1], geo[0], geo[1][0] == "s2d"):
+                why = "fq_pixel_shuffle_i8_nhwc does not take r = %d on an input of shape %s (unsupported geometry)" % (r, tuple(v.src.shape))
+            else:
+                self.pixel_geo[m] = geo
+                return src
+        self.pixel_left[m] = why
+        return None
+
     def _name(self, m):
         return self.names.get(m) or type(m).__name__
 
@@ -1548,6 +1643,8 @@ class _Planning(object):
             plan.perm = self.perm[m]
         if v.kind == "act":
             plan.grid = self.act_grids[m][0]
+        if v.kind == "pixelshuffle":
+            plan.up, plan.perm = self.pixel_geo[m]
         if v.kind == "bilinear":
             plan.up, plan.grid = _bilinear_factor(m), self.bil_grids[m][0]
         if v.kind == "concat" and m in self.rq_cats:        # (narrow_bit is the readers' bit b already: the value's format)
@@ -1556,7 +1653,7 @@ class _Planning(object):
             self.summary["requant_concats"] += 1
             self.summary["requant_sum_sources"] += sum(1 for f in fmts if f[0] == 2)
         self._take(m, plan, relu_mod, forward)
-        self.summary[_COUNTER[v.kind]] += 1
+        self.summary["resident_pixelunshuffles" if isinstance(m, nn.PixelUnshuffle) else _COUNTER[v.kind]] += 1
 
     # ---- fusion passes (in this order: fuse_projections reads the fuse_next that fuse_block_tails sets)
 
@@ -1740,6 +1837,12 @@ class _Planning(object):
         if self.requant:
             names = dict((m, name) for name, m in model.named_modules())
             model.__dict__["_fq_resident_requant"] = dict((names.get(m, "?"), why) for m, why in self.rq_left.items())
+        if self.pixelshuffle:
+            for m in self.tracer.pixel_seen:
+                if m not in self.plans and m not in self.pixel_left:
+                    self.pixel_left[m] = "its input is not the output of a planned layer (no integer source)"
+            names = dict((m, name) for name, m in model.named_modules())
+            model.__dict__["_fq_resident_pixelshuffle"] = dict((names.get(m, "?"), why) for m, why in self.pixel_left.items())
         if self.activations:
             for m, (g, b) in self.act_grids.items():
                 self.plans[m].table = _native.build_act_table(m, g, b)
@@ -1751,12 +1854,13 @@ class _Planning(object):
                                                   tuple(names.get(m, "?") for m in self.revoked))
 
 
-def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False, activations=False, bilinear=False):
+def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False, activations=False, bilinear=False, pixelshuffle=False):
     """One forward of `model` in eval mode under the tracer: (tracer, the outputs of that forward)."""
     from .new_quantity_op import NewConv2d, NewLinear, NewAdd
     from .fabu_layer import Concat, Slice
     planned_types = (NewConv2d, NewLinear, NewAdd, nn.ReLU, nn.MaxPool2d, nn.AvgPool2d) + ((nn.ReLU6,) if relu6 else ()) \
-        + ((nn.ChannelShuffle, Slice) if shuffle else ())       # (without the switch both stay foreign code)
+        + ((nn.ChannelShuffle, Slice) if shuffle else ()) \
+        + ((nn.PixelShuffle, nn.PixelUnshuffle) if pixelshuffle else ())       # (without their switch these stay foreign code)
     tracer = _Tracer(avgpool)
     hooks = []
     for m in model.modules():
@@ -1782,7 +1886,8 @@ def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False, ac
 
 
 def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False, grouped=False, relu6=False,
-           flatten=False, shuffle=False, activations=False, sums=False, topdown=False, bilinear=False, requant=False):
+           flatten=False, shuffle=False, activations=False, sums=False, topdown=False, bilinear=False, requant=False,
+           pixelshuffle=False):
     """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
     on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
     nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
@@ -1810,7 +1915,9 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
     `requant=True` (with `concat=True`; ValueError without) also plans a Concat whose operands lie on different grids, whose
     readers quantise at another bit than its operands, or one of whose operands is the int16 sum of a NewAdd -- the skip of a
     ResNet-encoder U-Net -- on fq_concat_rq_i8_nhwc, which re-quantises every source to the readers' bit: a lossy value too
-    (_Planning._concat_requant)."""
+    (_Planning._concat_requant);
+    `pixelshuffle=True` also plans nn.PixelShuffle(r) and nn.PixelUnshuffle(r), r in {2, 3, 4}, on the int8 integers
+    (fq_pixel_shuffle_i8_nhwc; _Planning._pixelshuffle_format).  It needs no other switch."""
     from .new_quantity_op import QUANTIZE_BIT
     if flatten and not concat:
         raise ValueError("resident.enable(flatten=True) needs concat=True: only planned Concats are flattened")
@@ -1825,12 +1932,12 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
     _clear(model)
     if QUANTIZE_BIT != 8:
         raise _native.FqError("resident activations are defined for QUANTIZE_BIT = 8")
-    tracer, traced_out = _trace(model, example_input, concat, avgpool, relu6, shuffle, activations, bilinear)
+    tracer, traced_out = _trace(model, example_input, concat, avgpool, relu6, shuffle, activations, bilinear, pixelshuffle)
     names = dict((m, name) for name, m in model.named_modules()) if activations or sums or topdown or bilinear or requant else None
     revoked, revoked_up, revoked_bil, revoked_cat = {}, {}, {}, {}
     while True:
         planning = _Planning(tracer, depthwise, concat, avgpool, grouped, relu6, flatten, shuffle, activations, revoked, names,
-                             sums, topdown, revoked_up, bilinear, revoked_bil, requant, revoked_cat)
+                             sums, topdown, revoked_up, bilinear, revoked_bil, requant, revoked_cat, pixelshuffle)
         planning.plan_formats()
         planning.plan_outputs()
         planning.defer_convs()
@@ -1877,7 +1984,10 @@ class _Description(dict):
     of a NewAdd (or over a sum) that keeps the plan it had without the switch, and for every nn.Upsample that is foreign code.
     After enable(concat=True, bilinear=True) `bilinear_left` is {module name: why} for every hooked bilinear-mode nn.Upsample that
     stays torch's.  After enable(concat=True, requant=True) `requant_left` is {module name: why} for every Concat that the plain
-    rule does not fully serve -- it has no integer plan, or emits fp32 for a reader -- and the re-quantising rule declines."""
+    rule does not fully serve -- it has no integer plan, or emits fp32 for a reader -- and the re-quantising rule declines.  After
+    enable(pixelshuffle=True) `pixelshuffle_left` is {module name: why} for every hooked nn.PixelShuffle / nn.PixelUnshuffle that
+    stays torch's."""
+    pixelshuffle_left = {}
     activations_left = {}
     bilinear_left = {}
     requant_left = {}
@@ -1900,6 +2010,7 @@ def describe(model):
     d.topdown_left = model.__dict__.get("_fq_resident_topdown", {})
     d.bilinear_left = model.__dict__.get("_fq_resident_bilinear", {})
     d.requant_left = model.__dict__.get("_fq_resident_requant", {})
+    d.pixelshuffle_left = model.__dict__.get("_fq_resident_pixelshuffle", {})
     d.flattened_concats = tuple(name for name, m in model.named_modules()
                                 if type(m).__name__ == "Concat" and name in d and d[name].defer)
     return d
