@@ -20,6 +20,7 @@ The plan assumes a static dataflow (as a captured graph would).  Consumers stay 
 that unexpectedly receives fp32 quantises it as usual -- and a resident handle reaching code that
 is not part of the plan raises instead of computing garbage.
 """
+import collections
 import os
 
 import torch
@@ -174,6 +175,20 @@ def _moved(out, *sources):
     return out
 
 
+def _moved_handle(h, y, channels):
+    """The handle of y, the int8 integers of `h` moved or max-pooled into `channels` channels: on the source's grid, lossy where
+    the source is, the narrow form carried where it equals the exact one."""
+    narrow = y if (h.narrow is h.exact or h.bit == h.grid) else None
+    return _moved(QHandle.wide_narrow(channels, y, h.grid, narrow, h.grid, h.relu_done), h)
+
+
+def _lossy_int8(q, channels, bit, relu_done):
+    """The handle of q = Quantity_bit(f(...)), the output of a kernel that re-quantises for the convolutions behind it: lossy."""
+    out = QHandle.int8(q, channels, bit, relu_done)
+    out.lossy = True
+    return out
+
+
 def block_tail_enabled():
     """FQ_BLOCK_TAIL=0: keep conv3 + add and the next conv1 as two launches (A/B timing).  Read at every call."""
     return os.environ.get("FQ_BLOCK_TAIL", "1") != "0"
@@ -212,7 +227,26 @@ def as_f32(x):
 
 
 class Plan(object):
-    """What one producer emits.  Plain data (pickles with the module)."""
+    """What one producer emits.  Plain data (pickles with the module).  Three fields mean different things for different kinds of
+    producer (the fields stay as they are: Plan pickles with models):
+
+    field | producer (switch)                           | meaning
+    ------+---------------------------------------------+------------------------------------------------------------------------
+    grid  | NewAdd                                      | grid of the exact sum
+          | windowed nn.AvgPool2d (avgpool)             | grid of its source
+          | table activation (activations)              | grid of its source (the table maps it to bit `narrow_bit`)
+          | bilinear upsampling (bilinear)              | grid of its source
+          | re-quantising Concat (requant)              | the TUPLE of its operands' planned grids, which marks the plan as that
+          |                                             | kind (to bit `narrow_bit`)
+    up    | nearest upsampling (concat)                 | its factor (with `defer`: the Concat applies it -- or, with topdown, the
+          |                                             | NewAdd)
+          | bilinear upsampling (bilinear)              | its factor, from grid `grid` to bit `narrow_bit`
+          | nn.PixelShuffle / nn.PixelUnshuffle         | its factor r (with `perm`)
+          | (pixelshuffle)                              |
+    perm  | nn.ChannelShuffle / Slice (shuffle)         | (c_off, C, groups) of fq_shuffle_i8_nhwc
+          | nn.PixelShuffle / nn.PixelUnshuffle         | ("d2s", C) / ("s2d", C) of fq_pixel_shuffle_i8_nhwc, C the channels of
+          | (pixelshuffle)                              | the shallow tensor
+    """
     __slots__ = ("relu", "emit_f32", "emit_int", "narrow_bit", "want_wide", "grid", "resident_add", "defer", "fuse_arg",
                  "fuse_next", "narrow_to_hbm", "fuse_proj", "depthwise", "up", "grouped", "clip", "perm", "table")
 
@@ -222,7 +256,7 @@ class Plan(object):
         self.emit_int = False        # some consumer reads the integer form
         self.narrow_bit = None       # NewAdd: Quantity bit of the conv consumers (None: no narrow output)
         self.want_wide = False       # NewAdd: exact int16 sum needed (next add, or fp32 via dequant)
-        self.grid = None             # NewAdd: grid of the exact sum; windowed nn.AvgPool2d (enable(avgpool=True)) and bilinear upsampling (enable(bilinear=True)): grid of its source; re-quantising Concat (enable(requant=True)): the TUPLE of its operands' planned grids, which marks the plan as that kind (to bit `narrow_bit`)
+        self.grid = None             # a grid, by kind of producer: the table above
         self.resident_add = False    # NewAdd: operands arrive as integers
         self.defer = False           # NewConv2d: only consumer is a resident NewAdd, which runs this conv itself
         self.fuse_arg = None         # NewAdd: operand position (0 / 1) that arrives as a DeferredConv
@@ -230,10 +264,10 @@ class Plan(object):
         self.narrow_to_hbm = True    # NewAdd with fuse_next: somebody besides that convolution reads the int8 re-quantisation
         self.fuse_proj = False       # NewAdd with fuse_arg: the OTHER operand is a deferred 1x1 projection that the kernel computes too
         self.depthwise = False       # NewConv2d: a depthwise layer taken by enable(depthwise=True); runs on fq_dwconv2d_i8_resident
-        self.up = None               # nearest upsampling taken by enable(concat=True): its factor (with `defer`: the Concat applies it -- or, with topdown=True, the NewAdd); bilinear upsampling taken by enable(bilinear=True): its factor, from grid `grid` to bit `narrow_bit`; nn.PixelShuffle / nn.PixelUnshuffle taken by enable(pixelshuffle=True): its factor r (with `perm`)
+        self.up = None               # a factor, by kind of producer: the table above
         self.grouped = False         # NewConv2d: a grouped layer taken by enable(grouped=True); runs on fq_gconv2d_i8_resident
         self.clip = False            # NewConv2d with `relu`: the fused activation is an nn.ReLU6 (enable(relu6=True)): clipped at 6
-        self.perm = None             # nn.ChannelShuffle / Slice taken by enable(shuffle=True): (c_off, C, groups) of fq_shuffle_i8_nhwc; nn.PixelShuffle / nn.PixelUnshuffle taken by enable(pixelshuffle=True): ("d2s", C) / ("s2d", C) of fq_pixel_shuffle_i8_nhwc, C the channels of the shallow tensor
+        self.perm = None             # a permutation, by kind of producer: the table above
         self.table = None            # elementwise activation taken by enable(activations=True): the 256 int8 of fq_act_lut_i8_nhwc, from grid `grid` to bit `narrow_bit`
 
     def __getstate__(self):
@@ -275,6 +309,28 @@ class _ReluPassThrough(_InstanceForward):
         return type(self.module).forward(self.module, x)
 
 
+class _UnaryResident(_InstanceForward):
+    """Instance-level forward of a module with one operand that runs on the integers where it can.  The module needs its plan and
+    an operand with an exact 4-D payload of one of `dtypes` -- not a lossy one unless `lossy_source` --; an operand that arrives
+    deferred is materialised first (resident_of).  run() then returns what the module hands out, or None; on None, and on every
+    miss above, the module's own forward runs on the fp32 form."""
+    dtypes = (torch.int8,)           # payloads the kernel reads
+    lossy_source = True              # a lossy source is taken (pure data movement and max: Quantity_b commutes with them)
+
+    def __call__(self, x):
+        m = self.module
+        plan = m.__dict__.get("_resident")
+        h = resident_of(x)
+        out = None
+        if (plan is not None and h is not None and h.exact is not None and h.exact.dtype in self.dtypes and h.exact.dim() == 4
+                and (self.lossy_source or not h.lossy)):
+            out = self.run(m, plan, h)
+        return type(m).forward(m, as_f32(x)) if out is None else out
+
+    def run(self, m, plan, h):
+        raise NotImplementedError
+
+
 def _pair(v):
     return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
 
@@ -301,19 +357,14 @@ def _avgpool_is_global(m, h, w):
             and h * w * 32768 < (1 << 24))
 
 
-class _MaxPoolResident(_InstanceForward):
+class _MaxPoolResident(_UnaryResident):
     """Instance-level forward of an nn.MaxPool2d between integer layers: pooling the int8 NHWC integers is
     pooling the values (max commutes with the monotone scale q -> q * 2^-g)."""
 
-    def __call__(self, x):
-        m = self.module
-        plan = m.__dict__.get("_resident")
-        h = resident_of(x)
-        if plan is None or h is None or h.exact is None or h.exact.dtype != torch.int8 or not _maxpool_supported(m):
-            return type(m).forward(m, as_f32(x))
-        y = _native.maxpool_i8_nhwc(h.exact, *_pool_geometry(m))
-        narrow = y if (h.narrow is h.exact or h.bit == h.grid) else None
-        return _emit(plan, _moved(QHandle.wide_narrow(h.shape[1], y, h.grid, narrow, h.grid, h.relu_done), h))
+    def run(self, m, plan, h):
+        if not _maxpool_supported(m):
+            return None
+        return _emit(plan, _moved_handle(h, _native.maxpool_i8_nhwc(h.exact, *_pool_geometry(m)), h.shape[1]))
 
 
 class _AvgPoolResident(_InstanceForward):
@@ -327,7 +378,7 @@ class _AvgPoolResident(_InstanceForward):
         return type(m).forward(m, as_f32(x))
 
 
-class _AvgPoolWindowResident(_InstanceForward):
+class _AvgPoolWindowResident(_UnaryResident):
     """Instance-level forward of a windowed nn.AvgPool2d between an int8 activation and the convolution(s) behind it
     (enable(avgpool=True)): DeQuantity -> pool -> ReLU -> the consumers' Quantity in one kernel (fq_avgpool_i8_nhwc).  With
     enable(avgpool=True, sums=True) the source may be the exact int16 sum of a NewAdd on the planned grid: that payload goes to
@@ -336,21 +387,19 @@ class _AvgPoolWindowResident(_InstanceForward):
     only, and anything but a NewConv2d at that bit that touches it raises (QHandle.to_f32).  Every run-time miss falls back to the
     module's own forward on the fp32 form."""
 
-    def __call__(self, x):
-        m = self.module
-        plan = m.__dict__.get("_resident")
-        h = resident_of(x)
-        if (plan is None or plan.narrow_bit is None or plan.grid is None or h is None or h.exact is None or h.lossy
-                or h.exact.dtype not in (torch.int8, torch.int16) or h.exact.dim() != 4 or h.grid != plan.grid
-                or not _avgpool_window_ok(m)):
-            return type(m).forward(m, as_f32(x))
+    dtypes = (torch.int8, torch.int16)
+    lossy_source = False
+
+    def run(self, m, plan, h):
+        if plan.narrow_bit is None or plan.grid is None or h.grid != plan.grid or not _avgpool_window_ok(m):
+            return None
         k, st, pd = _pool_geometry(m)
         hh, ww = int(h.exact.shape[1]), int(h.exact.shape[2])
         wide = h.exact.dtype == torch.int16                 # a NewAdd's exact sum (planned with sums=True)
         supported, launch = ((_native.avgpool_i16_supported, _native.avgpool_i16_nhwc) if wide else
                              (_native.avgpool_supported, _native.avgpool_i8_nhwc))
         if (not supported(k, st, pd, plan.narrow_bit - h.grid) or hh + 2 * pd[0] < k[0] or ww + 2 * pd[1] < k[1]):
-            return type(m).forward(m, as_f32(x))
+            return None
         y = launch(h.exact, h.shape[1], k, st, pd, m.count_include_pad, plan.narrow_bit - h.grid, plan.relu)
         return QHandle.wide_narrow(h.shape[1], None, None, y, plan.narrow_bit, plan.relu or h.relu_done)
 
@@ -368,25 +417,17 @@ def _shuffle_geometry(m, channels):
     return (a, b - a, 1) if plain(a) and plain(b) and 0 <= a < b <= channels else None
 
 
-class _ShuffleResident(_InstanceForward):
+class _ShuffleResident(_UnaryResident):
     """Instance-level forward of an nn.ChannelShuffle between integer layers (enable(shuffle=True)): permuting the channels of
-    the int8 NHWC integers is permuting the values (fq_shuffle_i8_nhwc).  An operand that arrives deferred is materialised first
-    (resident_of).  Whenever a run-time condition fails -- no plan, no int8 exact payload, a geometry other than the planned
-    one -- the module's own forward runs on the fp32 form."""
+    the int8 NHWC integers is permuting the values (fq_shuffle_i8_nhwc).  Whenever a run-time condition fails -- no plan, no int8
+    exact payload, a geometry other than the planned one -- the module's own forward runs on the fp32 form."""
 
-    def __call__(self, x):
-        m = self.module
-        plan = m.__dict__.get("_resident")
-        h = resident_of(x)
-        geo = None
-        if plan is not None and h is not None and h.exact is not None and h.exact.dtype == torch.int8 and h.exact.dim() == 4:
-            geo = _shuffle_geometry(m, h.shape[1])
+    def run(self, m, plan, h):
+        geo = _shuffle_geometry(m, h.shape[1])
         if geo is None or geo != plan.perm or not _native.shuffle_supported(h.shape[1], *geo):
-            return type(m).forward(m, as_f32(x))
+            return None
         c_off, c, g = geo
-        y = _native.shuffle_i8_nhwc(h.exact, h.shape[1], c_off, c, g)
-        narrow = y if (h.narrow is h.exact or h.bit == h.grid) else None
-        return _emit(plan, _moved(QHandle.wide_narrow(c, y, h.grid, narrow, h.grid, h.relu_done), h))
+        return _emit(plan, _moved_handle(h, _native.shuffle_i8_nhwc(h.exact, h.shape[1], c_off, c, g), c))
 
 
 class _SliceResident(_ShuffleResident):
@@ -415,27 +456,20 @@ def _pixel_geometry(m, shape):
     return (r, ("s2d", channels)) if hh % r == 0 and ww % r == 0 and hh >= r and ww >= r else None
 
 
-class _PixelShuffleResident(_InstanceForward):
+class _PixelShuffleResident(_UnaryResident):
     """Instance-level forward of an nn.PixelShuffle / nn.PixelUnshuffle between integer layers (enable(pixelshuffle=True)):
     permuting the int8 NHWC integers between depth and space is permuting the values (fq_pixel_shuffle_i8_nhwc).  The handle is
-    built as _ShuffleResident builds its own: the source's grid, lossy where the source is, the narrow form carried where it equals
-    the exact one.  An operand that arrives deferred is materialised first (resident_of).  Whenever a run-time condition fails --
-    no plan, no int8 exact payload, a factor, direction or width other than the planned one, a geometry the kernel refuses --
-    the module's own forward runs on the fp32 form."""
+    built as _ShuffleResident builds its own (_moved_handle).  Whenever a run-time condition fails -- no plan, no int8 exact
+    payload, a factor, direction or width other than the planned one, a geometry the kernel refuses -- the module's own forward
+    runs on the fp32 form."""
 
-    def __call__(self, x):
-        m = self.module
-        plan = m.__dict__.get("_resident")
-        h = resident_of(x)
-        geo = None
-        if plan is not None and h is not None and h.exact is not None and h.exact.dtype == torch.int8 and h.exact.dim() == 4:
-            geo = _pixel_geometry(m, (h.shape[0], h.shape[1], h.exact.shape[1], h.exact.shape[2]))
+    def run(self, m, plan, h):
+        geo = _pixel_geometry(m, (h.shape[0], h.shape[1], h.exact.shape[1], h.exact.shape[2]))
         if geo is None or geo != (plan.up, plan.perm) or not _native.pixel_shuffle_supported(geo[1][1], geo[0], geo[1][0] == "s2d"):
-            return type(m).forward(m, as_f32(x))
+            return None
         r, (way, c) = geo
         y = _native.pixel_shuffle_i8_nhwc(h.exact, c, r, way == "s2d")
-        narrow = y if (h.narrow is h.exact or h.bit == h.grid) else None
-        return _emit(plan, _moved(QHandle.wide_narrow(c if way == "d2s" else c * r * r, y, h.grid, narrow, h.grid, h.relu_done), h))
+        return _emit(plan, _moved_handle(h, y, c if way == "d2s" else c * r * r))
 
 
 ACTIVATION_TYPES = (nn.LeakyReLU, nn.PReLU, nn.Hardswish, nn.Hardsigmoid, nn.SiLU, nn.Sigmoid, nn.Tanh, nn.ELU, nn.Hardtanh, nn.Mish,
@@ -448,23 +482,19 @@ def _is_table_activation(m):
     return isinstance(m, ACTIVATION_TYPES) and not isinstance(m, (nn.ReLU, nn.ReLU6))
 
 
-class _ActTableResident(_InstanceForward):
+class _ActTableResident(_UnaryResident):
     """Instance-level forward of an elementwise activation between integer layers (enable(activations=True)): the int8 NHWC
     integers on the planned grid go through the module's 256-entry table (fq_act_lut_i8_nhwc) and come out as the integers the
     convolutions behind it would quantise to.  The handle is marked `lossy`: it stands for Quantity_b(f(x)), not for f(x).
     Whenever a run-time condition fails -- no plan, no int8 exact payload, another grid than the planned one -- the module's own
     forward runs on the fp32 form."""
 
-    def __call__(self, x):
-        m = self.module
-        plan = m.__dict__.get("_resident")
-        h = resident_of(x)
-        if (plan is None or plan.table is None or h is None or h.exact is None or h.lossy or h.exact.dtype != torch.int8
-                or h.exact.dim() != 4 or h.grid != plan.grid or not _native.act_lut_supported(h.shape[1])):
-            return type(m).forward(m, as_f32(x))
-        out = QHandle.int8(_native.act_lut_i8_nhwc(h.exact, h.shape[1], plan.table), h.shape[1], plan.narrow_bit, False)
-        out.lossy = True
-        return _emit(plan, out)
+    lossy_source = False
+
+    def run(self, m, plan, h):
+        if plan.table is None or h.grid != plan.grid or not _native.act_lut_supported(h.shape[1]):
+            return None
+        return _emit(plan, _lossy_int8(_native.act_lut_i8_nhwc(h.exact, h.shape[1], plan.table), h.shape[1], plan.narrow_bit, False))
 
 
 def _pool_geometry(m):
@@ -531,57 +561,47 @@ def _emit(plan, out, t=None):
     return t
 
 
-class _UpsampleResident(_InstanceForward):
+class _UpsampleResident(_UnaryResident):
     """Instance-level forward of a nearest upsampling between integer layers: repeating the int8 NHWC integers is repeating the
     values.  With plan.defer nothing runs here: the resident Concat that consumes it reads the small tensor (DeferredUpsample)."""
 
-    def __call__(self, x):
-        m = self.module
-        plan = m.__dict__.get("_resident")
-        h = resident_of(x)
-        if (plan is None or plan.up is None or plan.up != _upsample_factor(m) or h is None or h.exact is None
-                or h.exact.dtype != torch.int8 or h.exact.dim() != 4 or h.grid != plan.narrow_bit):
-            return type(m).forward(m, as_f32(x))
+    def run(self, m, plan, h):
+        if plan.up is None or plan.up != _upsample_factor(m) or h.grid != plan.narrow_bit:
+            return None
         if plan.defer and not plan.relu:
             return DeferredUpsample(h, plan.up)
         y = _native.concat_i8_nhwc([(h.exact, h.shape[1], plan.up)], plan.relu)
         return _emit(plan, _moved(QHandle.int8(y, h.shape[1], h.grid, plan.relu or h.relu_done), h))
 
 
-class _BilinearResident(_InstanceForward):
+class _BilinearResident(_UnaryResident):
     """Instance-level forward of a bilinear upsampling between an int8 activation and the convolutions behind it
     (enable(concat=True, bilinear=True)): DeQuantity -> interpolation -> ReLU -> the consumers' Quantity in one kernel
     (fq_upsample_bilinear_i8_nhwc).  The handle is marked `lossy`: it stands for Quantity_b(up(x)), not for up(x).  Whenever a
     run-time condition fails -- no plan, no int8 exact payload, another grid than the planned one, a lossy source, a factor or shift
     the kernel does not take -- the module's own forward runs on the fp32 form."""
 
-    def __call__(self, x):
-        m = self.module
-        plan = m.__dict__.get("_resident")
-        h = resident_of(x)
-        if (plan is None or plan.up is None or plan.grid is None or plan.narrow_bit is None or plan.up != _bilinear_factor(m)
-                or h is None or h.exact is None or h.lossy or h.exact.dtype != torch.int8 or h.exact.dim() != 4
+    lossy_source = False
+
+    def run(self, m, plan, h):
+        if (plan.up is None or plan.grid is None or plan.narrow_bit is None or plan.up != _bilinear_factor(m)
                 or h.grid != plan.grid or not _native.upsample_bilinear_supported(plan.up, plan.narrow_bit - h.grid)):
-            return type(m).forward(m, as_f32(x))
+            return None
         y = _native.upsample_bilinear_i8_nhwc(h.exact, h.shape[1], plan.up, plan.narrow_bit - h.grid, plan.relu)
-        out = QHandle.int8(y, h.shape[1], plan.narrow_bit, plan.relu or h.relu_done)
-        out.lossy = True
-        return _emit(plan, out)
+        return _emit(plan, _lossy_int8(y, h.shape[1], plan.narrow_bit, plan.relu or h.relu_done))
 
 
-class _UpsampleTopDown(_InstanceForward):
+class _UpsampleTopDown(_UnaryResident):
     """Instance-level forward of a nearest upsampling whose readers are resident NewAdds (enable(concat=True, topdown=True)):
     nothing runs here.  The coarse handle -- int8, or the exact int16 sum of the add one level up -- goes to the add as a
     DeferredUpsample, and the add reads it at (h / s, w / s) (fq_add_up_resident).  A run-time miss -- no integer payload on the
     planned grid -- runs the module's own forward on the fp32 form."""
 
-    def __call__(self, x):
-        m = self.module
-        plan = m.__dict__.get("_resident")
-        h = resident_of(x)
-        if (plan is None or plan.up is None or not plan.defer or plan.up != _upsample_factor(m) or h is None or h.exact is None
-                or h.exact.dtype not in (torch.int8, torch.int16) or h.exact.dim() != 4 or h.grid != plan.narrow_bit):
-            return type(m).forward(m, as_f32(x))
+    dtypes = (torch.int8, torch.int16)
+
+    def run(self, m, plan, h):
+        if plan.up is None or not plan.defer or plan.up != _upsample_factor(m) or h.grid != plan.narrow_bit:
+            return None
         return DeferredUpsample(h, plan.up, m)
 
 
@@ -673,9 +693,7 @@ class _ConcatRequant(_InstanceForward):
             return type(m).forward(m, as_f32(x), as_f32(y), dim)
         b = plan.narrow_bit
         q = _native.concat_rq_i8_nhwc([(h.exact, h.shape[1], up, plan.relu, b - h.grid) for h, up in srcs])
-        out = QHandle.int8(q, sum(h.shape[1] for h, _up in srcs), b, plan.relu or all(h.relu_done for h, _up in srcs))
-        out.lossy = True
-        return _emit(plan, out)
+        return _emit(plan, _lossy_int8(q, sum(h.shape[1] for h, _up in srcs), b, plan.relu or all(h.relu_done for h, _up in srcs)))
 
 
 # ---- tracing -------------------------------------------------------------------------------------
@@ -708,12 +726,8 @@ class _Tracer(TorchFunctionMode):
     def __init__(self, avgpool=False):
         super(_Tracer, self).__init__()
         self.avgpool = bool(avgpool)     # enable(avgpool=True): an nn.AvgPool2d output is a traced value
-        self.shuffle_seen = []           # (enable(shuffle=True)) every hooked nn.ChannelShuffle / Slice module, in execution order
-        self.relu6_seen = []             # (enable(relu6=True)) every hooked nn.ReLU6 module, in execution order
-        self.act_seen = []               # (enable(activations=True)) every hooked table activation, in execution order
-        self.act_inplace = set()         # ... those that returned their own input tensor
-        self.bilinear_seen = []          # (enable(bilinear=True)) every hooked bilinear-mode nn.Upsample, in execution order
-        self.pixel_seen = []             # (enable(pixelshuffle=True)) every hooked nn.PixelShuffle / nn.PixelUnshuffle, in execution order
+        self.seen = collections.defaultdict(list)    # report attribute of _KINDS -> every hooked module that reports there, in execution order
+        self.inplace = set()             # hooked modules that returned their own input tensor
         self.values = {}             # id(tensor) -> _Value
         self.keep = []               # keeps traced tensors alive so ids are not reused
         self.depth = 0
@@ -733,16 +747,9 @@ class _Tracer(TorchFunctionMode):
     def pre(self, module, args):
         self.depth += 1
         self.calls[module] = self.calls.get(module, 0) + 1
-        if isinstance(module, nn.ReLU6) and module not in self.relu6_seen:
-            self.relu6_seen.append(module)
-        if self._kind(module) in ("shuffle", "slice") and module not in self.shuffle_seen:
-            self.shuffle_seen.append(module)
-        if _is_table_activation(module) and module not in self.act_seen:
-            self.act_seen.append(module)
-        if isinstance(module, nn.Upsample) and module.mode == "bilinear" and module not in self.bilinear_seen:
-            self.bilinear_seen.append(module)
-        if isinstance(module, (nn.PixelShuffle, nn.PixelUnshuffle)) and module not in self.pixel_seen:
-            self.pixel_seen.append(module)
+        report = _row(module).report
+        if report is not None and module not in self.seen[report]:
+            self.seen[report].append(module)
         for pos, a in enumerate(args):
             v = self.values.get(id(a)) if isinstance(a, torch.Tensor) else None
             if v is not None:
@@ -762,32 +769,18 @@ class _Tracer(TorchFunctionMode):
 
     @staticmethod
     def _kind(module):
-        if isinstance(module, (nn.ReLU, nn.ReLU6)):         # (nn.ReLU6 is hooked only with enable(relu6=True))
-            return "relu"
-        if isinstance(module, nn.MaxPool2d):
-            return "maxpool"
-        if isinstance(module, nn.AvgPool2d):
-            return "avgpool"
-        if isinstance(module, nn.Upsample):                 # (hooked only with enable(concat=True); bilinear mode: with bilinear=True)
-            return "bilinear" if module.mode == "bilinear" else "upsample"
-        if isinstance(module, nn.ChannelShuffle):           # (hooked only with enable(shuffle=True))
-            return "shuffle"
-        if _is_table_activation(module):                    # (hooked only with enable(activations=True))
-            return "act"
-        if isinstance(module, (nn.PixelShuffle, nn.PixelUnshuffle)):     # (hooked only with enable(pixelshuffle=True))
-            return "pixelshuffle"
-        name = type(module).__name__
-        return {"Concat": "concat", "NewAdd": "add", "Slice": "slice"}.get(name, "contraction")     # (Concat, Slice: likewise)
+        return _row(module).name
 
     def post(self, module, args, output):
         self.depth -= 1
         if not isinstance(output, torch.Tensor):
             return
-        kind = self._kind(module)
+        row = _row(module)
+        kind = row.name
         src = None
-        if kind == "act" and args and output is args[0]:
-            self.act_inplace.add(module)
-        if kind in ("relu", "maxpool", "avgpool", "upsample", "bilinear", "shuffle", "slice", "act", "pixelshuffle"):     # a value of these kinds exists only behind a traced value
+        if args and output is args[0]:
+            self.inplace.add(module)
+        if row.behind:                                      # a value of these kinds exists only behind a traced value
             if kind == "avgpool" and not self.avgpool:
                 return                                      # its output is an ordinary fp32 tensor
             src = self.values.get(id(args[0])) if args and isinstance(args[0], torch.Tensor) else None
@@ -814,15 +807,8 @@ def _clear(model):
         fwd = m.__dict__.get("forward")
         if isinstance(fwd, _InstanceForward):
             del m.__dict__["forward"]
-    model.__dict__.pop("_fq_resident_enabled", None)
-    model.__dict__.pop("_fq_resident_relu6", None)
-    model.__dict__.pop("_fq_resident_shuffle", None)
-    model.__dict__.pop("_fq_resident_act", None)
-    model.__dict__.pop("_fq_resident_avgpool", None)
-    model.__dict__.pop("_fq_resident_topdown", None)
-    model.__dict__.pop("_fq_resident_bilinear", None)
-    model.__dict__.pop("_fq_resident_requant", None)
-    model.__dict__.pop("_fq_resident_pixelshuffle", None)
+    for key in [k for k in model.__dict__ if k.startswith("_fq_resident_")]:     # (the per-switch keys of earlier versions too)
+        del model.__dict__[key]
 
 
 def disable(model):
@@ -835,36 +821,55 @@ def is_enabled(model):
     return bool(model.__dict__.get("_fq_resident_enabled"))
 
 
-_COUNTER = {"contraction": "resident_convs", "add": "resident_adds", "maxpool": "resident_pools", "concat": "resident_concats",
-            "upsample": "resident_upsamples", "shuffle": "resident_shuffles", "slice": "resident_slices",
-            "act": "resident_activations", "bilinear": "resident_bilinears", "pixelshuffle": "resident_pixelshuffles"}
-_FORWARD = {"maxpool": _MaxPoolResident, "concat": _ConcatResident, "upsample": _UpsampleResident, "shuffle": _ShuffleResident,
-            "slice": _SliceResident, "act": _ActTableResident, "bilinear": _BilinearResident, "pixelshuffle": _PixelShuffleResident}
-_MOVES = ("maxpool", "concat", "upsample", "shuffle", "slice", "pixelshuffle")       # what Quantity_b commutes with: data movement and max
-#                                                                      (not "bilinear": Quantity_b does not commute with interpolation)
+# enable()'s opt-in switches: (name, the summary keys it adds, the report attributes of describe() it fills), in the order in
+# which the keys enter the summary behind the six base keys (tests compare key lists)
+_SWITCH_TABLE = (
+    ("depthwise", ("resident_depthwise",), ()),
+    ("concat", ("resident_concats", "resident_upsamples"), ()),
+    ("flatten", ("flattened_concats",), ()),
+    ("avgpool", ("resident_avgpools",), ()),
+    ("sums", ("resident_sum_avgpools",), ("avgpool_left",)),
+    ("grouped", ("resident_grouped",), ()),
+    ("relu6", ("fused_relu6s",), ("relu6_left",)),
+    ("shuffle", ("resident_shuffles", "resident_slices"), ("shuffle_left",)),
+    ("activations", ("resident_activations",), ("activations_left",)),
+    ("topdown", ("topdown_adds", "topdown_sum_sources"), ("topdown_left",)),
+    ("bilinear", ("resident_bilinears",), ("bilinear_left",)),
+    ("requant", ("requant_concats", "requant_sum_sources"), ("requant_left",)),
+    ("pixelshuffle", ("resident_pixelshuffles", "resident_pixelunshuffles"), ("pixelshuffle_left",)),
+)
+_Switches = collections.namedtuple("_Switches", [name for name, _keys, _reports in _SWITCH_TABLE])
+# (switch, the switch it needs, enable()'s ValueError without it)
+_SWITCH_NEEDS = (
+    ("flatten", "concat", "resident.enable(flatten=True) needs concat=True: only planned Concats are flattened"),
+    ("sums", "avgpool", "resident.enable(sums=True) needs avgpool=True: only planned windowed pools read a NewAdd sum"),
+    ("topdown", "concat", "resident.enable(topdown=True) needs concat=True: the upsampling is hooked by that switch"),
+    ("bilinear", "concat", "resident.enable(bilinear=True) needs concat=True: the Concat behind a decoder's upsampling is planned by that switch"),
+    ("requant", "concat", "resident.enable(requant=True) needs concat=True: only a hooked Concat marker re-quantises"),
+)
+
+
+def _switches(**on):
+    """The switches of one enable() call as an immutable record: every one named in `on` by its truth value, the rest off."""
+    return _Switches(**dict((name, bool(on.pop(name, False))) for name in _Switches._fields), **on)     # (an unknown name: TypeError)
 
 
 class _Planning(object):
     """The plan of one traced forward.  enable() calls the passes below in order; they decide on the trace alone and change
     nothing on the model until install() writes the plans and the instance-level forwards to the modules."""
 
-    def __init__(self, tracer, depthwise, concat, avgpool, grouped, relu6=False, flatten=False, shuffle=False, activations=False,
-                 revoked=None, names=None, sums=False, topdown=False, revoked_up=None, bilinear=False, revoked_bil=None,
-                 requant=False, revoked_cat=None, pixelshuffle=False):
+    def __init__(self, tracer, switches, revoked=None, names=None):
         from .new_quantity_op import NewConv2d, NewAdd
         from .fabu_layer import Concat
         self.conv_type, self.concat_type = NewConv2d, Concat
         self.tracer = tracer
-        self.depthwise, self.grouped, self.relu6 = bool(depthwise), bool(grouped), bool(relu6)
-        self.relu6_left = {}             # (relu6=True) nn.ReLU6 module that stays torch's -> why
-        self.shuffle = bool(shuffle)
-        self.shuffle_left = {}           # (shuffle=True) nn.ChannelShuffle / Slice module that stays torch's -> why
-        self.perm = {}                   # (shuffle=True) planned nn.ChannelShuffle / Slice module -> (c_off, C, groups)
-        self.activations = bool(activations)
-        self.revoked = dict(revoked or {})   # (activations=True) module that an earlier round planned and verify_lossy() took back -> why
+        self.sw = switches               # the _Switches of this enable() call
+        self.revoked = dict(revoked or {})   # module that an earlier round planned and verify() took back -> why
         self.names = names or {}         # module -> its name in the model (for the reasons)
-        self.act_left = {}               # (activations=True) hooked table activation that stays torch's -> why
-        self.act_grids = {}              # (activations=True) planned table activation -> (source grid g, consumer bit b)
+        self.left = collections.defaultdict(dict)    # report attribute of describe() -> {module that stays torch's: why}
+        self.fields = {}                 # module -> the Plan fields that its format rule decided
+        self.forward_of = {}             # module -> its instance-level forward, where that is not its kind's
+        self.lossy = {}                  # planned table activation, bilinear upsampling or re-quantising Concat -> its readers' bit b
         self.value_of = dict((v.producer, v) for v in tracer.produced)
         self.relu_value = dict((id(c.src), c) for c in tracer.relu_values)
         self.fmt = {}                    # id(effective _Value) -> (bytes, grid)
@@ -877,55 +882,17 @@ class _Planning(object):
         self.add_resident = set()        # NewAdd modules whose operands arrive as integers
         self.int8_resident = set()       # nn.MaxPool2d, Concat, nearest-upsampling, nn.ChannelShuffle, Slice and nn.PixelShuffle / nn.PixelUnshuffle modules that run on the int8 integers
         self.avg_resident = {}           # windowed nn.AvgPool2d that runs on fq_avgpool_i8_nhwc -> (source grid g, consumer bit b)
-        self.sums = bool(sums)           # (avgpool=True, sums=True) a windowed pool may read a NewAdd's exact int16 sum
-        self.avg_sum = set()             # ... the pools of avg_resident that do (fq_avgpool_i16_nhwc)
-        self.avgpool_left = {}           # (sums=True) hooked windowed nn.AvgPool2d that stays torch's -> why
-        self.topdown = bool(topdown)     # (concat=True, topdown=True) a NewAdd reads its upsampled operand at (h / s, w / s)
-        self.revoked_up = dict(revoked_up or {})    # ... upsampling that an earlier round planned so and verify_topdown() took back -> why
-        self.topdown_ups = {}            # ... planned upsampling -> (bytes, grid) of its source
+        self.avg_sum = set()             # (avgpool=True, sums=True) the pools of avg_resident that read a NewAdd's exact int16 sum (fq_avgpool_i16_nhwc)
+        self.topdown_ups = {}            # (concat=True, topdown=True) upsampling that a NewAdd reads at (h / s, w / s) -> (bytes, grid) of its source
         self.topdown_adds = set()        # ... the NewAdd modules that take such an operand
-        self.topdown_left = {}           # ... hooked upsampling in front of a NewAdd that keeps its earlier plan -> why
-        self.bilinear = bool(bilinear)   # (concat=True, bilinear=True) bilinear upsampling by 2 or 4 on fq_upsample_bilinear_i8_nhwc
-        self.revoked_bil = dict(revoked_bil or {})  # ... module that an earlier round planned and verify_lossy_bilinear() took back -> why
-        self.bil_grids = {}              # ... planned bilinear upsampling -> (source grid g, consumer bit b)
-        self.bil_left = {}               # ... hooked bilinear-mode nn.Upsample that stays torch's -> why
-        self.requant = bool(requant)     # (concat=True, requant=True) a Concat re-quantises its operands on fq_concat_rq_i8_nhwc
-        self.revoked_cat = dict(revoked_cat or {})  # ... Concat that an earlier round planned so and verify_lossy_concat() took back -> why
-        self.rq_cats = {}                # ... planned re-quantising Concat -> (reader bit b, (format of operand 0, of operand 1))
-        self.rq_left = {}                # ... Concat that the plain rule does not fully serve and this one declines -> why
-        self.pixelshuffle = bool(pixelshuffle)      # (pixelshuffle=True) nn.PixelShuffle / nn.PixelUnshuffle on fq_pixel_shuffle_i8_nhwc
-        self.pixel_geo = {}              # ... planned module -> (r, ("d2s" | "s2d", C))
-        self.pixel_left = {}             # ... hooked module that stays torch's -> why
+        self.rq_cats = set()             # (concat=True, requant=True) the planned Concats that re-quantise their operands (fq_concat_rq_i8_nhwc)
         self.plans = {}                  # producer module -> Plan
         self.forwards = []               # (module, its instance-level forward)
         self.summary = {"resident_convs": 0, "resident_adds": 0, "resident_pools": 0, "fused_relus": 0, "fp32_outputs": 0,
                         "int_only_outputs": 0}
-        if depthwise:
-            self.summary["resident_depthwise"] = 0
-        if concat:
-            self.summary["resident_concats"] = self.summary["resident_upsamples"] = 0
-        if flatten:
-            self.summary["flattened_concats"] = 0
-        if avgpool:
-            self.summary["resident_avgpools"] = 0
-        if sums:
-            self.summary["resident_sum_avgpools"] = 0
-        if grouped:
-            self.summary["resident_grouped"] = 0
-        if relu6:
-            self.summary["fused_relu6s"] = 0
-        if shuffle:
-            self.summary["resident_shuffles"] = self.summary["resident_slices"] = 0
-        if activations:
-            self.summary["resident_activations"] = 0
-        if topdown:
-            self.summary["topdown_adds"] = self.summary["topdown_sum_sources"] = 0
-        if bilinear:
-            self.summary["resident_bilinears"] = 0
-        if requant:
-            self.summary["requant_concats"] = self.summary["requant_sum_sources"] = 0
-        if pixelshuffle:
-            self.summary["resident_pixelshuffles"] = self.summary["resident_pixelunshuffles"] = 0
+        for name, keys, _reports in _SWITCH_TABLE:
+            if getattr(switches, name):
+                self.summary.update((key, 0) for key in keys)
 
     # ---- what a value is and what a module can do
 
@@ -935,7 +902,7 @@ class _Planning(object):
 
     def effective(self, v):
         """(value the consumers see, fused ReLU / ReLU6 module or None)"""
-        if v.kind not in ("maxpool", "shuffle", "slice", "act", "pixelshuffle") and not v.foreign and len(v.consumers) == 1 and isinstance(v.consumers[0][0], (nn.ReLU, nn.ReLU6)):
+        if _KIND[v.kind].fuse_relu and not v.foreign and len(v.consumers) == 1 and isinstance(v.consumers[0][0], (nn.ReLU, nn.ReLU6)):
             act = v.consumers[0][0]
             after = self.relu_value.get(id(v))
             if after is not None and (isinstance(act, nn.ReLU) or self.takes_relu6(v)):
@@ -950,7 +917,7 @@ class _Planning(object):
         that is no integer convolution of this plan, and a ReLU6 behind a NewAdd, a Concat, a pool or an upsampling.  16-bit
         models have no plan at all.  The summary then gains `fused_relu6s`; describe() names what was left."""
         m = v.producer
-        if not self.relu6 or v.kind != "contraction" or not self.conv_can_emit(m):
+        if not self.sw.relu6 or v.kind != "contraction" or not self.conv_can_emit(m):
             return False
         return _native.relu6_clip(m.output_bit) is not None
 
@@ -960,7 +927,7 @@ class _Planning(object):
         source = {}
         for r in self.tracer.relu_values:
             source.setdefault(r.producer, r.src)
-        for act in self.tracer.relu6_seen:
+        for act in self.tracer.seen["relu6_left"]:
             if act in fused:
                 continue
             v = source.get(act)
@@ -977,14 +944,14 @@ class _Planning(object):
                 why = "the convolution's output has other readers"
             else:
                 why = "the ReLU6 was called more than once"
-            self.relu6_left[act] = why
+            self.left["relu6_left"][act] = why
 
     def is_dw(self, m):
         """A depthwise layer that this plan runs on fq_dwconv2d_i8_resident: `depthwise=True` plans depthwise NewConv2d layers
         (groups == in_channels == out_channels, 3x3 / 5x5, stride 1 / 2, shift in [1, 16]: NewConv2d._depthwise_ok) as integer
         producers and consumers; without it they stay fp32 producers, as every other grouped convolution does.  The summary then
         counts them as `resident_depthwise`."""
-        return self.depthwise and isinstance(m, self.conv_type) and self.once(m) and m._depthwise_ok(m.Conv, True)
+        return self.sw.depthwise and isinstance(m, self.conv_type) and self.once(m) and m._depthwise_ok(m.Conv, True)
 
     def is_gc(self, m):
         """A grouped layer that this plan runs on fq_gconv2d_i8_resident: `grouped=True` plans grouped NewConv2d layers
@@ -992,7 +959,7 @@ class _Planning(object):
         [1, 16]: NewConv2d._grouped_ok) as integer producers and consumers.  Such a layer is never run inside a NewAdd's kernel;
         an add reads its integers like any other operand.  Without the argument they stay fp32 producers.  The summary then counts
         them as `resident_grouped`."""
-        return self.grouped and isinstance(m, self.conv_type) and self.once(m) and m._grouped_ok(m.Conv, True)
+        return self.sw.grouped and isinstance(m, self.conv_type) and self.once(m) and m._grouped_ok(m.Conv, True)
 
     def conv_can_emit(self, m):
         return isinstance(m, self.conv_type) and self.once(m) and (m._int8_ok(m.Conv) or self.is_dw(m) or self.is_gc(m))
@@ -1017,46 +984,49 @@ class _Planning(object):
         for v in self.tracer.produced:
             e, relu_mod = self.effective(v)
             self.eff_of[id(v)] = (e, relu_mod)
-            m = v.producer
-            f = None
-            if v.kind == "contraction":
-                if self.conv_can_emit(m):
-                    f = (1, m.output_bit)
-            elif v.kind == "maxpool":
-                f = self._int8_source(v) if _maxpool_supported(m) else None
-            elif v.kind == "upsample":
-                s = _upsample_factor(m)
-                f = self._int8_source(v) if s is not None and len(v.shape) == 4 else None
-                if f is not None and not _native.concat_supported([v.shape[1]], [s]):
-                    f = None
-                if self.topdown:
-                    f = self._topdown_format(v, relu_mod, f)
-            elif v.kind == "bilinear":
-                f = self._bilinear_format(v)
-            elif v.kind == "avgpool":
-                self._plan_avgpool_window(v, e)             # (the value itself has no integer format)
-            elif v.kind == "concat":
-                f = self._concat_format(v)
-            elif v.kind in ("shuffle", "slice"):
-                f = self._shuffle_format(v)
-            elif v.kind == "act":
-                f = self._act_format(v)
-            elif v.kind == "pixelshuffle":
-                f = self._pixelshuffle_format(v)
-            else:
-                f = self._add_format(v)
-                ops = self.operands.get(m) or ()
-                if f is not None and any(o is not None and o.kind == "upsample" and o.producer in self.topdown_ups for o in ops):
-                    self.topdown_adds.add(m)
+            row = _KIND[v.kind]
+            f = row.rule(self, v)                           # (the rule also notes what else it decided: fields, forward_of, left)
             if f is not None:
                 self.fmt[id(e)] = f
-                if v.kind != "contraction":
-                    (self.add_resident if v.kind == "add" else self.int8_resident).add(m)
+                if row.forward is not None:                 # (a module that is no integer layer itself: it runs on its source's int8)
+                    self.int8_resident.add(v.producer)
+
+    def _conv_format(self, v):
+        """A NewConv2d / NewLinear that this plan runs on integers emits int8 at its own output bit."""
+        m = v.producer
+        if not self.conv_can_emit(m):
+            return None
+        if self.is_dw(m):
+            self.fields.setdefault(m, {})["depthwise"] = True
+            self.summary["resident_depthwise"] += 1
+        if self.is_gc(m):
+            self.fields.setdefault(m, {})["grouped"] = True
+            self.summary["resident_grouped"] += 1
+        return (1, m.output_bit)
 
     def _int8_source(self, v):
         """The format of the value that a max-pool / upsampling / average pool called once reads, if that is int8."""
         f = self.fmt.get(id(v.src))
         return f if f is not None and f[0] == 1 and self.once(v.producer) else None
+
+    def _maxpool_format(self, v):
+        return self._int8_source(v) if _maxpool_supported(v.producer) else None
+
+    def _upsample_format(self, v):
+        """A nearest upsampling by 2 or 4 (`concat=True`, _concat_format) repeats the int8 integers of its source; with
+        `topdown=True` one in front of a NewAdd launches nothing (_topdown_format)."""
+        m = v.producer
+        s = _upsample_factor(m)
+        f = self._int8_source(v) if s is not None and len(v.shape) == 4 else None
+        if f is not None and not _native.concat_supported([v.shape[1]], [s]):
+            f = None
+        if self.sw.topdown:
+            f = self._topdown_format(v, self.eff_of[id(v)][1], f)
+        self.fields[m] = {"up": s}
+        if m in self.topdown_ups:                           # (nothing is launched: the adds behind it read the coarse tensor)
+            self.fields[m].update(defer=True, emit_int=True, emit_f32=False)
+            self.forward_of[m] = _UpsampleTopDown
+        return f
 
     def _topdown_format(self, v, relu_mod, f_off):
         """`concat=True, topdown=True` plans a nearest upsampling by 2 or 4 whose readers are NewAdds -- the FPN top-down step
@@ -1100,18 +1070,18 @@ class _Planning(object):
             why = "a NewAdd that reads it was called more than once"
         elif not _native.add_up_supported(s, v.shape[2], v.shape[3], _native.pad16(v.shape[1])):
             why = "the %dx%d plane is not divisible by the factor %d" % (v.shape[2], v.shape[3], s)
-        elif m in self.revoked_up:
-            why = self.revoked_up[m]
+        elif m in self.revoked:
+            why = self.revoked[m]
         if why is None:
             self.topdown_ups[m] = src
             return src
-        self.topdown_left[m] = why
+        self.left["topdown_left"][m] = why
         return f_off
 
     def verify_topdown(self):
         """{upsampling: why} for every one planned by _topdown_format whose adds, after all passes, cannot take it: an add that
         is not resident (its other operand has no integer form, or the grid does not fit int16), or one whose operands are both
-        upsampled.  enable() plans again without them, as it does for verify_lossy()."""
+        upsampled.  Part of verify(): enable() plans again without them."""
         bad = {}
         for v in self.tracer.produced:
             m = v.producer
@@ -1135,7 +1105,7 @@ class _Planning(object):
                 ups = [o.producer for o in self.operands[v.producer] if o.kind == "upsample" and o.producer in self.topdown_ups]
                 self.summary["topdown_sum_sources"] += sum(1 for u in ups if self.topdown_ups[u][0] == 2)
 
-    def _plan_avgpool_window(self, v, e):
+    def _plan_avgpool_window(self, v):
         """`avgpool=True` plans a windowed nn.AvgPool2d (the pool branch of an Inception block, the 2x2 pool of a transition) that
         reads an int8 activation on a grid g and is read by NewConv2d layers only, all at one input bit b: DeQuantity -> pool ->
         the nn.ReLU behind it -> the consumers' Quantity run as one kernel on the integers (fq_avgpool_i8_nhwc), so the pool's
@@ -1153,15 +1123,16 @@ class _Planning(object):
         fq_avgpool_global_nhwc and a re-quantisation); where they are not (the head's pool in front of View) it keeps the
         whole-plane path.  The summary gains `resident_sum_avgpools`, and describe().avgpool_left names every hooked windowed
         pool that stays torch's with its reason."""
-        m = v.producer
+        m, e = v.producer, self.eff_of[id(v)][0]
         if self.avg_can_read(m):                            # the whole-plane pool: _AvgPoolResident ...
             f = self.fmt.get(id(v.src))
-            if self.sums and f is not None and f[0] == 2:   # ... unless it reads a sum and convolutions read it
+            if self.sw.sums and f is not None and f[0] == 2:    # ... unless it reads a sum and convolutions read it
                 self._avgpool_window_declined(v, e)
-            return
+            return None                                     # (the value itself has no integer format)
         why = self._avgpool_window_declined(v, e)
-        if why is not None and self.sums:
-            self.avgpool_left[m] = why
+        if why is not None and self.sw.sums:
+            self.left["avgpool_left"][m] = why
+        return None
 
     def _avgpool_window_declined(self, v, e):
         """None when the windowed pool is planned (avg_resident), else why not."""
@@ -1171,7 +1142,7 @@ class _Planning(object):
             return "the module was called more than once"
         if f is None:
             return "its source has no integer form in this plan (fp32 form)"
-        if f[0] != 1 and not (self.sums and f[0] == 2):
+        if f[0] != 1 and not (self.sw.sums and f[0] == 2):
             return "its source is a NewAdd sum (int16): needs sums=True (fp32 form)"
         if m.ceil_mode:
             return "ceil_mode=True: only floor-mode pools are taken (fp32 form)"
@@ -1215,11 +1186,11 @@ class _Planning(object):
         Concats are flattened by defer_concats, `flatten=True`), the `size=` form and other factors of an upsampling; a bare torch.cat stays foreign, as a bare
         `+` does.  The summary then gains `resident_concats`, `resident_upsamples` and `fused_upsamples` (defer_upsamples)."""
         plain = self._concat_plain(v)
-        if not self.requant:
+        if not self.sw.requant:
             return plain
         f, why = self._concat_requant(v, plain)
         if f is None and why is not None:
-            self.rq_left[v.producer] = why
+            self.left["requant_left"][v.producer] = why
         return f if f is not None else plain
 
     def _concat_plain(self, v):
@@ -1242,7 +1213,7 @@ class _Planning(object):
         int16 sum of a resident NewAdd ((2, g_i), with that add's fused ReLU; the add counts the Concat as a reader of its exact
         integers, _readers), or a lossy int8 value -- a table activation, a bilinear upsampling, another such Concat -- at bit b
         exactly.  The output is Quantity_b(cat(...)), a lossy value: planned with format (1, b) only where every transitive reader
-        through _MOVES is an integer convolution at b (_lossy_walk) and |b - g_i| <= 8; verify_lossy_concat() takes it back where
+        through _MOVES is an integer convolution at b (_lossy_walk) and |b - g_i| <= 8; verify() takes it back where
         a later pass left a reader in fp32 form.  The plain rule keeps every Concat it fully serves (operands int8 on one grid g,
         every convolution that reads it directly at g; a mover behind it takes its int8 as it is): this rule takes what that one
         refuses, or plans but has to emit fp32 for.  Returns (format, None) when planned, (None, why) when declined --
@@ -1259,8 +1230,8 @@ class _Planning(object):
             return None, "dim != 1, or its operands are not two 4-D tensors"
         if ops is None or ops[0] is None or ops[1] is None:
             return None, "an operand is not the output of a planned layer (no integer source)"
-        if m in self.revoked_cat:
-            return None, self.revoked_cat[m]
+        if m in self.revoked:
+            return None, self.revoked[m]
         if fp32_reader is not None:
             return None, fp32_reader
         if len(bits) != 1:
@@ -1286,18 +1257,13 @@ class _Planning(object):
             fmts.append(f)
         if not _native.concat_rq_supported([o.shape[1] for o in ops], [1, 1], [f[0] for f in fmts], [b - f[1] for f in fmts]):
             return None, "fq_concat_rq_i8_nhwc does not take operands of %s channels (unsupported geometry)" % [o.shape[1] for o in ops]
-        self.rq_cats[m] = (b, tuple(fmts))
+        self.rq_cats.add(m)
+        self.lossy[m] = b                                   # (also the plan's narrow_bit: the value's format)
+        self.fields[m] = {"grid": tuple(f[1] for f in fmts)}
+        self.forward_of[m] = _ConcatRequant
+        self.summary["requant_concats"] += 1
+        self.summary["requant_sum_sources"] += sum(1 for f in fmts if f[0] == 2)
         return (1, b), None
-
-    def verify_lossy_concat(self):
-        """verify_lossy() for the planned re-quantising Concats: {module: why} for every one whose value, after all passes,
-        somebody would read in fp32 form.  enable() plans again without them: the Concat keeps the plain rule's plan."""
-        bad = {}
-        for m, (b, _fmts) in self.rq_cats.items():
-            why = self._lossy_violation(self.value_of[m], b)
-            if why is not None:
-                bad[m] = "revoked by the lossy rule: " + why
-        return bad
 
     def _shuffle_format(self, v):
         """`shuffle=True` plans nn.ChannelShuffle and the Slice marker (fabu_layer.Slice, x[:, start:stop]), both served by
@@ -1331,9 +1297,9 @@ class _Planning(object):
                 why = "fq_shuffle_i8_nhwc does not take (c_off, C, groups) = %r of %d channels (nothing to do, or C > 65536)" % (
                     geo, channels)
             else:
-                self.perm[m] = geo
+                self.fields[m] = {"perm": geo}
                 return src
-        self.shuffle_left[m] = why
+        self.left["shuffle_left"][m] = why
         return None
 
     def _pixelshuffle_format(self, v):
@@ -1369,9 +1335,9 @@ class _Planning(object):
             if geo is None or not _native.pixel_shuffle_supported(geo[1][1], geo[0], geo[1][0] == "s2d"):
                 why = "fq_pixel_shuffle_i8_nhwc does not take r = %d on an input of shape %s (unsupported geometry)" % (r, tuple(v.src.shape))
             else:
-                self.pixel_geo[m] = geo
+                self.fields[m] = {"up": geo[0], "perm": geo[1]}
                 return src
-        self.pixel_left[m] = why
+        self.left["pixelshuffle_left"][m] = why
         return None
 
     def _name(self, m):
@@ -1386,7 +1352,7 @@ class _Planning(object):
         enable().  The table's output is Quantity_b(f(x)), not f(x) (the lossy-value rule): it is planned as an
         int8 value on grid b only where every transitive reader -- through max-pools, Concats, nearest upsamplings, shuffles
         and slices, with which Quantity_b commutes -- is an integer convolution with input_bit == b (_lossy_walk), and
-        verify_lossy() takes it back where a later pass left one of those readers in fp32 form.  Left to torch, each named with
+        verify() takes it back where a later pass left one of those readers in fp32 form.  Left to torch, each named with
         its reason by describe().activations_left: a module called twice, a NewAdd sum (int16) as the source, a non-4-D input, a
         per-channel nn.PReLU, a source without an integer form, readers at two bits, any fp32 reader (an average pool, a NewAdd, a
         second table activation, a model output, foreign code), and `inplace=True` modules: the planned forward returns a new
@@ -1397,7 +1363,7 @@ class _Planning(object):
         why = None
         if not self.once(m):
             why = "the module was called more than once"
-        elif m in self.tracer.act_inplace or getattr(m, "inplace", False):
+        elif m in self.tracer.inplace or getattr(m, "inplace", False):
             why = "inplace=True: the module rewrites its input tensor, a table activation returns a new one (fp32 form)"
         elif isinstance(m, nn.PReLU) and m.num_parameters != 1:
             why = "a per-channel nn.PReLU (%d weights) is no function of the integer alone" % m.num_parameters
@@ -1416,9 +1382,10 @@ class _Planning(object):
             if why is None and len(bits) != 1:
                 why = "its readers quantise at different bits %s" % sorted(bits)
             if why is None:
-                self.act_grids[m] = (src[1], bits.pop())
-                return (1, self.act_grids[m][1])
-        self.act_left[m] = why
+                self.lossy[m] = bits.pop()
+                self.fields[m] = {"grid": src[1]}
+                return (1, self.lossy[m])
+        self.left["activations_left"][m] = why
         return None
 
     def _bilinear_format(self, v):
@@ -1428,7 +1395,7 @@ class _Planning(object):
         function (weights are odd multiples of 1 / (2 up): one rounding of S * 2^(b - g) / (2 up)^2, include/fq.h).  Its output is
         Quantity_b(up(x)), not up(x): the lossy-value rule of _act_format applies word for word -- planned as an int8 value on grid
         b only where every transitive reader through _MOVES is an integer convolution with input_bit == b (_lossy_walk), taken
-        back by verify_lossy_bilinear() where a later pass left one of those readers in fp32 form.  The kind is NOT one of _MOVES:
+        back by verify() where a later pass left one of those readers in fp32 form.  The kind is NOT one of _MOVES:
         Quantity_b does not commute with interpolation, so a table activation (or another bilinear upsampling) in front of one
         is left by _lossy_walk.  An nn.ReLU directly behind the module is the kernel's `relu` flag (effective, _take).  Left to
         torch, each named with its reason by describe().bilinear_left: align_corners=True, the `size=` form, another or a
@@ -1451,8 +1418,8 @@ class _Planning(object):
             why = "its source has no integer form in this plan (fp32 form)"
         elif src[0] != 1:
             why = "its source is a NewAdd sum (int16): only int8 activations are interpolated (fp32 form)"
-        elif m in self.revoked_bil:
-            why = self.revoked_bil[m]
+        elif m in self.revoked:
+            why = self.revoked[m]
         else:
             bits, why = self._lossy_walk(v)
             if why is None and len(bits) != 1:
@@ -1462,9 +1429,10 @@ class _Planning(object):
                 if not _native.upsample_bilinear_supported(_bilinear_factor(m), b - src[1]):
                     why = "|b - g| = |%d - %d| > 8: not taken by the kernel (fp32 form)" % (b, src[1])
                 else:
-                    self.bil_grids[m] = (src[1], b)
+                    self.lossy[m] = b
+                    self.fields[m] = {"up": _bilinear_factor(m), "grid": src[1]}
                     return (1, b)
-        self.bil_left[m] = why
+        self.left["bilinear_left"][m] = why
         return None
 
     def _lossy_origin(self, v, depth=0):
@@ -1485,16 +1453,6 @@ class _Planning(object):
         if v.kind == "relu" or v.kind in _MOVES:
             return self._lossy_origin(v.src, depth + 1)
         return None
-
-    def verify_lossy_bilinear(self):
-        """verify_lossy() for the planned bilinear upsamplings: {module: why} for every one whose value, after all passes, somebody
-        would read in fp32 form.  enable() plans again without them."""
-        bad = {}
-        for m, (_g, b) in self.bil_grids.items():
-            why = self._lossy_violation(self.value_of[m], b)
-            if why is not None:
-                bad[m] = "revoked by the lossy rule: " + why
-        return bad
 
     def _lossy_walk(self, v):
         """({input bits of the convolutions that read v, directly or through _MOVES}, None), or (_, why not): the first reader
@@ -1522,16 +1480,18 @@ class _Planning(object):
             return bits, "read as fp32 by %s %s" % (what, self._name(c))
         return bits, None
 
-    def verify_lossy(self):
-        """{table activation: why} for every planned one whose value, after all passes, somebody would read in fp32 form: a
-        producer on the way that emits fp32, or a reader that turned out unplanned (a Concat whose other operand sits on another
-        grid).  enable() plans again without them: the activation stays torch's and its source leaves as fp32, as without the
-        switch.  At most one round per activation."""
+    def verify(self):
+        """{module: why} for every planned lossy producer -- table activation, bilinear upsampling, re-quantising Concat -- whose
+        value, after all passes, somebody would read in fp32 form: a producer on the way that emits fp32, or a reader that turned
+        out unplanned (a Concat whose other operand sits on another grid); and for the upsamplings that verify_topdown() names.
+        enable() plans again without them: the module stays torch's (a Concat keeps the plain rule's plan) and its source leaves
+        as fp32, as without the switch.  At most one round per module."""
         bad = {}
-        for m, (_g, b) in self.act_grids.items():
+        for m, b in self.lossy.items():
             why = self._lossy_violation(self.value_of[m], b)
             if why is not None:
                 bad[m] = "revoked by the lossy rule: " + why
+        bad.update(self.verify_topdown())
         return bad
 
     def _lossy_violation(self, v, b):
@@ -1553,13 +1513,17 @@ class _Planning(object):
 
     def _add_format(self, v):
         """A NewAdd of two integer operands: the exact sum as int16 on the finer of their grids, where that fits."""
-        ops = self._integer_operands(v.producer)
+        m = v.producer
+        ops = self._integer_operands(m)
         if ops is None:
             return None
         gx, gy = ops[2][1], ops[3][1]
         g = max(0, gx, gy)
         if g > MAX_WIDE_GRID or min(gx, gy) < -16:
             return None
+        self.add_resident.add(m)
+        if any(o.kind == "upsample" and o.producer in self.topdown_ups for o in ops[:2]):
+            self.topdown_adds.add(m)
         return (2, g)
 
     # ---- pass 2: what every producer has to emit
@@ -1572,8 +1536,8 @@ class _Planning(object):
                     plan = Plan()
                     plan.emit_int, plan.emit_f32 = True, False
                     plan.grid, plan.narrow_bit = self.avg_resident[v.producer]
-                    self._take(v.producer, plan, relu_mod, _AvgPoolWindowResident)
-                    self.summary["resident_avgpools"] += 1
+                    self._take(v.producer, plan, relu_mod, _KIND[v.kind].forward)
+                    self.summary[_KIND[v.kind].counter] += 1
                     if v.producer in self.avg_sum:
                         self.summary["resident_sum_avgpools"] += 1
             elif id(e) in self.fmt:                         # (anything else stays a plain fp32 producer)
@@ -1628,32 +1592,11 @@ class _Planning(object):
             plan.want_wide = True                           # fp32 leaves through the exact int16 sum
         plan.emit_int = exact + int8 + served > 0
         plan.emit_f32 = need_f32 or not plan.emit_int
-        if v.kind == "contraction" and self.is_dw(m):
-            plan.depthwise = True
-            self.summary["resident_depthwise"] += 1
-        if v.kind == "contraction" and self.is_gc(m):
-            plan.grouped = True
-            self.summary["resident_grouped"] += 1
-        if v.kind == "upsample":
-            plan.up = _upsample_factor(m)
-        forward = _FORWARD.get(v.kind)
-        if v.kind == "upsample" and m in self.topdown_ups:  # (nothing is launched: the adds behind it read the coarse tensor)
-            plan.defer, plan.emit_int, plan.emit_f32, forward = True, True, False, _UpsampleTopDown
-        if v.kind in ("shuffle", "slice"):
-            plan.perm = self.perm[m]
-        if v.kind == "act":
-            plan.grid = self.act_grids[m][0]
-        if v.kind == "pixelshuffle":
-            plan.up, plan.perm = self.pixel_geo[m]
-        if v.kind == "bilinear":
-            plan.up, plan.grid = _bilinear_factor(m), self.bil_grids[m][0]
-        if v.kind == "concat" and m in self.rq_cats:        # (narrow_bit is the readers' bit b already: the value's format)
-            fmts = self.rq_cats[m][1]
-            plan.grid, forward = tuple(f[1] for f in fmts), _ConcatRequant
-            self.summary["requant_concats"] += 1
-            self.summary["requant_sum_sources"] += sum(1 for f in fmts if f[0] == 2)
-        self._take(m, plan, relu_mod, forward)
-        self.summary["resident_pixelunshuffles" if isinstance(m, nn.PixelUnshuffle) else _COUNTER[v.kind]] += 1
+        for field, value in self.fields.get(m, {}).items():    # (what the format rule decided for this module)
+            setattr(plan, field, value)
+        row = _KIND[v.kind]
+        self._take(m, plan, relu_mod, self.forward_of.get(m, row.forward))
+        self.summary[row.counter(m) if callable(row.counter) else row.counter] += 1
 
     # ---- fusion passes (in this order: fuse_projections reads the fuse_next that fuse_block_tails sets)
 
@@ -1803,74 +1746,129 @@ class _Planning(object):
         for m, forward in self.forwards:
             m.__dict__["forward"] = forward
         model.__dict__["_fq_resident_enabled"] = True
-        if self.relu6:
+        names = dict((m, name) for name, m in model.named_modules())
+        report = model.__dict__["_fq_resident_report"] = {}      # what describe() hands out besides the plans: attribute -> value
+        for row in _KINDS:                                  # a hooked module that ran and has neither a plan nor a reason yet
+            if row.default is not None and getattr(self.sw, row.switch):
+                for m in self.tracer.seen[row.report]:
+                    if m not in self.plans and m not in self.left[row.report]:
+                        self.left[row.report][m] = row.default(m) if callable(row.default) else row.default
+        if self.sw.relu6:
             self._relu6_reasons()
-            names = dict((m, name) for name, m in model.named_modules())
-            model.__dict__["_fq_resident_relu6"] = (self.summary["fused_relu6s"],
-                                                    dict((names.get(m, "?"), why) for m, why in self.relu6_left.items()))
-        if self.shuffle:
-            for m in self.tracer.shuffle_seen:
-                if m not in self.plans and m not in self.shuffle_left:
-                    self.shuffle_left[m] = "its input is not the output of a planned layer"
-            names = dict((m, name) for name, m in model.named_modules())
-            model.__dict__["_fq_resident_shuffle"] = dict((names.get(m, "?"), why) for m, why in self.shuffle_left.items())
-        if self.sums:
-            for m in self.tracer.calls:                     # (every hooked module that ran, a pool behind foreign code included)
-                if (isinstance(m, nn.AvgPool2d) and m not in self.plans and m not in self.avgpool_left
-                        and not self.avg_can_read(m)):
-                    self.avgpool_left[m] = "its input is not the output of a planned layer (no integer source)"
-            names = dict((m, name) for name, m in model.named_modules())
-            model.__dict__["_fq_resident_avgpool"] = dict((names.get(m, "?"), why) for m, why in self.avgpool_left.items())
-        if self.topdown:
-            for m in model.modules():                       # (what _trace did not hook: foreign code, named all the same)
-                if isinstance(m, nn.Upsample) and _upsample_factor(m) is None and m not in self.bil_grids:
-                    self.topdown_left[m] = ("no nearest upsampling by one integer scale_factor of 2 or 4 (a `size=` form, another "
-                                            "factor or another mode): foreign code")
-            names = dict((m, name) for name, m in model.named_modules())
-            model.__dict__["_fq_resident_topdown"] = dict((names.get(m, "?"), why) for m, why in self.topdown_left.items())
-        if self.bilinear:
-            for m in self.tracer.bilinear_seen:
-                if m not in self.plans and m not in self.bil_left:
-                    self.bil_left[m] = _bilinear_form_left(m) or "its input is not the output of a planned layer (no integer source)"
-            names = dict((m, name) for name, m in model.named_modules())
-            model.__dict__["_fq_resident_bilinear"] = dict((names.get(m, "?"), why) for m, why in self.bil_left.items())
-        if self.requant:
-            names = dict((m, name) for name, m in model.named_modules())
-            model.__dict__["_fq_resident_requant"] = dict((names.get(m, "?"), why) for m, why in self.rq_left.items())
-        if self.pixelshuffle:
-            for m in self.tracer.pixel_seen:
-                if m not in self.plans and m not in self.pixel_left:
-                    self.pixel_left[m] = "its input is not the output of a planned layer (no integer source)"
-            names = dict((m, name) for name, m in model.named_modules())
-            model.__dict__["_fq_resident_pixelshuffle"] = dict((names.get(m, "?"), why) for m, why in self.pixel_left.items())
-        if self.activations:
-            for m, (g, b) in self.act_grids.items():
-                self.plans[m].table = _native.build_act_table(m, g, b)
-            for m in self.tracer.act_seen:
-                if m not in self.plans and m not in self.act_left:
-                    self.act_left[m] = "its input is not the output of a planned layer (no integer source)"
-            names = dict((m, name) for name, m in model.named_modules())
-            model.__dict__["_fq_resident_act"] = (dict((names.get(m, "?"), why) for m, why in self.act_left.items()),
-                                                  tuple(names.get(m, "?") for m in self.revoked))
+            report["fused_relu6s"] = self.summary["fused_relu6s"]
+        if self.sw.sums:
+            self._unplanned_avgpools()
+        if self.sw.topdown:
+            self._foreign_upsamples(model)
+        if self.sw.activations:
+            for m, plan in self.plans.items():
+                if _is_table_activation(m):
+                    plan.table = _native.build_act_table(m, plan.grid, plan.narrow_bit)
+            report["activations_revoked"] = tuple(names.get(m, "?") for m in self.revoked if _is_table_activation(m))
+        for switch, _keys, attributes in _SWITCH_TABLE:
+            for attribute in attributes if getattr(self.sw, switch) else ():
+                report[attribute] = dict((names.get(m, "?"), why) for m, why in self.left[attribute].items())
+
+    def _unplanned_avgpools(self):
+        """(`sums=True`) avgpool_left also names every hooked pool that ran without a plan, one behind foreign code included."""
+        for m in self.tracer.calls:
+            if (isinstance(m, nn.AvgPool2d) and m not in self.plans and m not in self.left["avgpool_left"]
+                    and not self.avg_can_read(m)):
+                self.left["avgpool_left"][m] = "its input is not the output of a planned layer (no integer source)"
+
+    def _foreign_upsamples(self, model):
+        """(`topdown=True`) topdown_left also names what _trace did not hook: foreign code."""
+        for m in model.modules():
+            if isinstance(m, nn.Upsample) and _upsample_factor(m) is None and m not in self.lossy:
+                self.left["topdown_left"][m] = ("no nearest upsampling by one integer scale_factor of 2 or 4 (a `size=` form, another "
+                                                "factor or another mode): foreign code")
 
 
-def _trace(model, example_input, concat, avgpool, relu6=False, shuffle=False, activations=False, bilinear=False, pixelshuffle=False):
+def _named(*names):
+    """Recognises the library's own layers by class name (new_quantity_op imports this module, so it is not imported up here)."""
+    return lambda m: any(c.__name__ in names for c in type(m).__mro__)
+
+
+def _instance_of(*types):
+    return lambda m: isinstance(m, types)
+
+
+def _pixel_counter(m):
+    return "resident_pixelunshuffles" if isinstance(m, nn.PixelUnshuffle) else "resident_pixelshuffles"
+
+
+_NO_SOURCE = "its input is not the output of a planned layer (no integer source)"
+_Kind = collections.namedtuple("_Kind", "name match rule switch behind fuse_relu moves forward counter report default")
+_Kind.__new__.__defaults__ = (None, False, True, False, None, None, None, None)      # (of `switch` ... `default`)
+# One row per traced kind; the first row that matches a hooked module is its kind, the last row is what any other hooked module
+# is.  Everything that tells kinds apart reads this table -- to add an op: a row, its format rule, its forward, its enable() switch.
+#   name      : _Value.kind
+#   match     : recognises the module
+#   rule      : its format rule, rule(planning, value) -> (bytes, grid) or None (_Planning.plan_formats); the docstring of the rule
+#               is the specification of its switch
+#   switch    : the enable() switch that hooks it in _trace (None: always hooked; without its switch a module stays foreign code)
+#   behind    : its value exists only behind a traced value (_Tracer.post)
+#   fuse_relu : an nn.ReLU that is its only reader may be fused into it (_Planning.effective)
+#   moves     : Quantity_b commutes with it -- data movement and max --, so a lossy value walks through it (_MOVES).  Not the
+#               bilinear upsampling: Quantity_b does not commute with interpolation
+#   forward   : its instance-level forward where planned (None: an integer layer, which reads its plan itself)
+#   counter   : the summary key that counts the planned ones, or a function of the module that gives it
+#   report    : the attribute of describe() that names the hooked ones that stay torch's (and the key of _Tracer.seen)
+#   default   : the reason given to one that ran without a plan and without a reason of its own (a text, or a function of the
+#               module; None: its report is written by a function of its own)
+_KINDS = (
+    _Kind("relu", _instance_of(nn.ReLU), None, behind=True),
+    _Kind("relu", _instance_of(nn.ReLU6), None, "relu6", behind=True, report="relu6_left"),
+    _Kind("maxpool", _instance_of(nn.MaxPool2d), _Planning._maxpool_format, behind=True, fuse_relu=False, moves=True,
+          forward=_MaxPoolResident, counter="resident_pools"),
+    _Kind("avgpool", _instance_of(nn.AvgPool2d), _Planning._plan_avgpool_window, behind=True, forward=_AvgPoolWindowResident,
+          counter="resident_avgpools"),
+    _Kind("bilinear", lambda m: isinstance(m, nn.Upsample) and m.mode == "bilinear", _Planning._bilinear_format, "bilinear",
+          behind=True, forward=_BilinearResident, counter="resident_bilinears", report="bilinear_left",
+          default=lambda m: _bilinear_form_left(m) or _NO_SOURCE),
+    _Kind("upsample", lambda m: _upsample_factor(m) is not None, _Planning._upsample_format, "concat", behind=True, moves=True,
+          forward=_UpsampleResident, counter="resident_upsamples"),
+    _Kind("shuffle", _instance_of(nn.ChannelShuffle), _Planning._shuffle_format, "shuffle", behind=True, fuse_relu=False, moves=True,
+          forward=_ShuffleResident, counter="resident_shuffles", report="shuffle_left",
+          default="its input is not the output of a planned layer"),
+    _Kind("act", _is_table_activation, _Planning._act_format, "activations", behind=True, fuse_relu=False,
+          forward=_ActTableResident, counter="resident_activations", report="activations_left", default=_NO_SOURCE),
+    _Kind("pixelshuffle", _instance_of(nn.PixelShuffle, nn.PixelUnshuffle), _Planning._pixelshuffle_format, "pixelshuffle",
+          behind=True, fuse_relu=False, moves=True, forward=_PixelShuffleResident, counter=_pixel_counter,
+          report="pixelshuffle_left", default=_NO_SOURCE),
+    _Kind("concat", _named("Concat"), _Planning._concat_format, "concat", moves=True, forward=_ConcatResident,
+          counter="resident_concats"),
+    _Kind("add", _named("NewAdd"), _Planning._add_format, counter="resident_adds"),
+    _Kind("slice", _named("Slice"), _Planning._shuffle_format, "shuffle", behind=True, fuse_relu=False, moves=True,
+          forward=_SliceResident, counter="resident_slices", report="shuffle_left",
+          default="its input is not the output of a planned layer"),
+    _Kind("contraction", _named("NewConv2d", "NewLinear"), _Planning._conv_format, counter="resident_convs"),
+)
+_KIND = dict((row.name, row) for row in reversed(_KINDS))    # (by name; the two rows of "relu" differ in how they are hooked only)
+_MOVES = tuple(row.name for row in _KINDS if row.moves)     # what Quantity_b commutes with: data movement and max
+
+
+def _row(module):
+    """The row of _KINDS that a hooked module belongs to."""
+    for row in _KINDS:
+        if row.match(module):
+            return row
+    return _KINDS[-1]
+
+
+def _trace(model, example_input, switches):
     """One forward of `model` in eval mode under the tracer: (tracer, the outputs of that forward)."""
-    from .new_quantity_op import NewConv2d, NewLinear, NewAdd
-    from .fabu_layer import Concat, Slice
-    planned_types = (NewConv2d, NewLinear, NewAdd, nn.ReLU, nn.MaxPool2d, nn.AvgPool2d) + ((nn.ReLU6,) if relu6 else ()) \
-        + ((nn.ChannelShuffle, Slice) if shuffle else ()) \
-        + ((nn.PixelShuffle, nn.PixelUnshuffle) if pixelshuffle else ())       # (without their switch these stay foreign code)
-    tracer = _Tracer(avgpool)
+    tracer = _Tracer(switches.avgpool)
     hooks = []
     for m in model.modules():
-        if (isinstance(m, planned_types) or (concat and _upsample_factor(m) is not None) or (activations and _is_table_activation(m))
-                or (bilinear and isinstance(m, nn.Upsample) and m.mode == "bilinear")):     # (any other nn.Upsample stays foreign code)
-            hooks.append(m.register_forward_pre_hook(tracer.pre))
-            hooks.append(m.register_forward_hook(tracer.post))
-        elif concat and isinstance(m, Concat):
+        row = _row(m)
+        if not row.match(m) or (row.switch is not None and not getattr(switches, row.switch)):
+            continue                                        # (foreign code: no kind, or one whose switch is off)
+        if row.name == "concat":                            # (`dim`, and the operands themselves, may be given by name)
             hooks.append(m.register_forward_pre_hook(tracer.pre_concat, with_kwargs=True))
-            hooks.append(m.register_forward_hook(tracer.post))
+        else:
+            hooks.append(m.register_forward_pre_hook(tracer.pre))
+        hooks.append(m.register_forward_hook(tracer.post))
     was_training = model.training
     model.eval()
     try:
@@ -1919,46 +1917,36 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
     `pixelshuffle=True` also plans nn.PixelShuffle(r) and nn.PixelUnshuffle(r), r in {2, 3, 4}, on the int8 integers
     (fq_pixel_shuffle_i8_nhwc; _Planning._pixelshuffle_format).  It needs no other switch."""
     from .new_quantity_op import QUANTIZE_BIT
-    if flatten and not concat:
-        raise ValueError("resident.enable(flatten=True) needs concat=True: only planned Concats are flattened")
-    if sums and not avgpool:
-        raise ValueError("resident.enable(sums=True) needs avgpool=True: only planned windowed pools read a NewAdd sum")
-    if topdown and not concat:
-        raise ValueError("resident.enable(topdown=True) needs concat=True: the upsampling is hooked by that switch")
-    if bilinear and not concat:
-        raise ValueError("resident.enable(bilinear=True) needs concat=True: the Concat behind a decoder's upsampling is planned by that switch")
-    if requant and not concat:
-        raise ValueError("resident.enable(requant=True) needs concat=True: only a hooked Concat marker re-quantises")
+    switches = _switches(depthwise=depthwise, concat=concat, avgpool=avgpool, grouped=grouped, relu6=relu6, flatten=flatten,
+                         shuffle=shuffle, activations=activations, sums=sums, topdown=topdown, bilinear=bilinear, requant=requant,
+                         pixelshuffle=pixelshuffle)
+    for switch, needed, message in _SWITCH_NEEDS:
+        if getattr(switches, switch) and not getattr(switches, needed):
+            raise ValueError(message)
     _clear(model)
     if QUANTIZE_BIT != 8:
         raise _native.FqError("resident activations are defined for QUANTIZE_BIT = 8")
-    tracer, traced_out = _trace(model, example_input, concat, avgpool, relu6, shuffle, activations, bilinear, pixelshuffle)
-    names = dict((m, name) for name, m in model.named_modules()) if activations or sums or topdown or bilinear or requant else None
-    revoked, revoked_up, revoked_bil, revoked_cat = {}, {}, {}, {}
+    tracer, traced_out = _trace(model, example_input, switches)
+    names = dict((m, name) for name, m in model.named_modules())
+    revoked = {}
     while True:
-        planning = _Planning(tracer, depthwise, concat, avgpool, grouped, relu6, flatten, shuffle, activations, revoked, names,
-                             sums, topdown, revoked_up, bilinear, revoked_bil, requant, revoked_cat, pixelshuffle)
+        planning = _Planning(tracer, switches, revoked, names)
         planning.plan_formats()
         planning.plan_outputs()
         planning.defer_convs()
         planning.fuse_block_tails()
         planning.fuse_projections()
-        if concat:
+        if switches.concat:
             planning.defer_upsamples()
-        if flatten:
+        if switches.flatten:
             planning.defer_concats()
         planning.hook_global_pools()
-        bad = planning.verify_lossy() if activations else {}
-        bad_up = planning.verify_topdown() if topdown else {}
-        bad_bil = planning.verify_lossy_bilinear() if bilinear else {}
-        bad_cat = planning.verify_lossy_concat() if requant else {}
-        if not bad and not bad_up and not bad_bil and not bad_cat:
+        bad = planning.verify()
+        if not bad:
             break
-        revoked_cat.update(bad_cat)                         # (... or one re-quantising Concat)
-        revoked_bil.update(bad_bil)                         # (... or one bilinear upsampling)
-        revoked.update(bad)                                 # (each round takes at least one activation out: it ends)
-        revoked_up.update(bad_up)                           # (... or one upsampling)
-    if topdown:
+        revoked.update(bad)                                 # (each round takes at least one module out -- a table activation, an
+        #                                                      upsampling, a re-quantising Concat --: it ends)
+    if switches.topdown:
         planning.count_topdown()
     planning.install(model)
     if verify:
@@ -1987,30 +1975,21 @@ class _Description(dict):
     rule does not fully serve -- it has no integer plan, or emits fp32 for a reader -- and the re-quantising rule declines.  After
     enable(pixelshuffle=True) `pixelshuffle_left` is {module name: why} for every hooked nn.PixelShuffle / nn.PixelUnshuffle that
     stays torch's."""
-    pixelshuffle_left = {}
-    activations_left = {}
-    bilinear_left = {}
-    requant_left = {}
-    avgpool_left = {}
-    topdown_left = {}
     activations_revoked = ()
     fused_relu6s = 0
-    relu6_left = {}
-    shuffle_left = {}
     flattened_concats = ()       # names of the Concats that enable(flatten=True) deferred into their consumer's launch
+
+
+for _switch, _keys, _attributes in _SWITCH_TABLE:           # every `*_left` report: empty while its switch is off
+    for _attribute in _attributes:
+        setattr(_Description, _attribute, {})
 
 
 def describe(model):
     """{module name: Plan} of the current plan (for logs and tests); see _Description for the ReLU6 report."""
     d = _Description((name, m.__dict__["_resident"]) for name, m in model.named_modules() if "_resident" in m.__dict__)
-    d.fused_relu6s, d.relu6_left = model.__dict__.get("_fq_resident_relu6", (0, {}))
-    d.shuffle_left = model.__dict__.get("_fq_resident_shuffle", {})
-    d.activations_left, d.activations_revoked = model.__dict__.get("_fq_resident_act", ({}, ()))
-    d.avgpool_left = model.__dict__.get("_fq_resident_avgpool", {})
-    d.topdown_left = model.__dict__.get("_fq_resident_topdown", {})
-    d.bilinear_left = model.__dict__.get("_fq_resident_bilinear", {})
-    d.requant_left = model.__dict__.get("_fq_resident_requant", {})
-    d.pixelshuffle_left = model.__dict__.get("_fq_resident_pixelshuffle", {})
+    for attribute, value in model.__dict__.get("_fq_resident_report", {}).items():
+        setattr(d, attribute, value)
     d.flattened_concats = tuple(name for name, m in model.named_modules()
                                 if type(m).__name__ == "Concat" and name in d and d[name].defer)
     return d

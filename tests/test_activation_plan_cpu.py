@@ -266,18 +266,20 @@ def test_the_concat_case_passes_the_walk_and_fails_the_verification():
     with ad.installed():
         model = an.RefusalNet("cat_grid").eval()
         x = torch.randn(2, 3, 8, 8, generator=torch.Generator().manual_seed(1))
-        tracer, _out = resident._trace(model, x, True, False, activations=True)
+        switches = resident._switches(concat=True, activations=True)
+        tracer, _out = resident._trace(model, x, switches)
         names = dict((m, n) for n, m in model.named_modules())
-        first = resident._Planning(tracer, False, True, False, False, activations=True, names=names)
+        first = resident._Planning(tracer, switches, names=names)
         first.plan_formats()
         first.plan_outputs()
-        assert first.act_grids == {model.act: (4, 4)} and not first.act_left and model.act in first.plans      # accepted ...
+        assert first.lossy == {model.act: 4} and first.plans[model.act].grid == 4                             # accepted (g, b) = (4, 4) ...
+        assert not first.left["activations_left"] and model.act in first.plans
         assert model.cat not in first.int8_resident                                                           # ... the Concat is not
-        assert first.verify_lossy() == {model.act: "revoked by the lossy rule: read as fp32 by cat"}
-        second = resident._Planning(tracer, False, True, False, False, activations=True, revoked=first.verify_lossy(), names=names)
+        assert first.verify() == {model.act: "revoked by the lossy rule: read as fp32 by cat"}
+        second = resident._Planning(tracer, switches, revoked=first.verify(), names=names)
         second.plan_formats()
         second.plan_outputs()
-        assert not second.act_grids and not second.verify_lossy() and model.act not in second.plans
+        assert not second.lossy and not second.verify() and model.act not in second.plans
 
 
 def test_the_same_net_with_the_operands_on_one_grid_is_planned_through_the_concat():

@@ -181,7 +181,7 @@ def test_the_pool_behind_a_sum_is_declined_without_sums_and_planned_with_it():
             h.to_f32()
         resident.disable(net)
         assert not _plans(net) and not _plans(net).avgpool_left and all("forward" not in m.__dict__ for m in net.modules())
-        assert "_fq_resident_avgpool" not in net.__dict__
+        assert "avgpool_left" not in net.__dict__.get("_fq_resident_report", {})
         spy.i16[:] = []
         _check_forwards(net, x, plain)
         assert not spy.i16
@@ -360,7 +360,7 @@ def test_the_default_call_is_the_parents():
             assert a == b and rows == _rows(net) and set(a) == an.DEFAULT_KEYS
             c = resident.enable(net, x, avgpool=True)
             assert set(c) == an.DEFAULT_KEYS | {"resident_avgpools"} and rows == _rows(net)
-            assert not _plans(net).avgpool_left and "_fq_resident_avgpool" not in net.__dict__
+            assert not _plans(net).avgpool_left and "avgpool_left" not in net.__dict__.get("_fq_resident_report", {})
             assert set(resident.Plan.__slots__) == set(next(iter(_plans(net).values())).__slots__)
     # no field was added to Plan: a plan pickled before this change loads as it is
     assert resident.Plan.__slots__ == ("relu", "emit_f32", "emit_int", "narrow_bit", "want_wide", "grid", "resident_add", "defer", "fuse_arg",

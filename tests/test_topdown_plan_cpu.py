@@ -141,7 +141,7 @@ def test_the_two_step_pathway(tag):
         assert all(float(p.abs().max()) > 0 for p in plain)
         off = resident.enable(net, x, concat=True)
         plans = _plans(net)
-        assert "topdown_adds" not in off and not plans.topdown_left and "_fq_resident_topdown" not in net.__dict__
+        assert "topdown_adds" not in off and not plans.topdown_left and "topdown_left" not in net.__dict__.get("_fq_resident_report", {})
         assert plans["add1"].emit_f32 and plans["add1"].resident_add and "up2" not in plans and "add2" not in plans
         assert plans["up1"].up == net.factor and not plans["up1"].defer
         spy.clear()
@@ -246,7 +246,7 @@ def test_the_default_call_has_no_new_key_and_plan_slots_are_unchanged():
         rows_b = _rows(net)
         assert resident.enable(net, x, concat=True, topdown=False) == b and rows_b == _rows(net)
         assert not any(k.startswith("topdown") for k in list(a) + list(b)) and not _plans(net).topdown_left
-        assert "_fq_resident_topdown" not in net.__dict__
+        assert "topdown_left" not in net.__dict__.get("_fq_resident_report", {})
         assert set(next(iter(_plans(net).values())).__slots__) == set(SLOTS)
     assert resident.Plan.__slots__ == SLOTS
 
