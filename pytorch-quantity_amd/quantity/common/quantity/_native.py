@@ -1543,12 +1543,13 @@ def maxpool_i8_nhwc(x, kernel, stride, padding):
     return y
 
 
-def _concat_supported(entry, Cs, ups):
-    n = len(Cs)
-    if n != len(ups) or n < 1:
+def _concat_supported(entry, *lists):
+    """entry_supported over per-source lists of one length (Cs, ups and, where the entry point has them, nbytes, shifts)."""
+    n = len(lists[0])
+    if n < 1 or any(len(v) != n for v in lists):
         return False
     ci = ctypes.c_int * n
-    return bool(getattr(lib(), entry + "_supported")(ci(*[int(c) for c in Cs]), ci(*[int(u) for u in ups]), n))
+    return bool(getattr(lib(), entry + "_supported")(*[ci(*[int(x) for x in v]) for v in lists], n))
 
 
 def concat_supported(Cs, ups):
@@ -1563,15 +1564,17 @@ def concat_n_supported(Cs, ups):
     return _concat_supported("fq_concat_n_i8_nhwc", Cs, ups)
 
 
-def _concat_operands(entry, struct, srcs, out):
-    """What both concat entry points do in front of the call: srcs = [(q, C, up, relu or None), ...] checked and packed into an
-    array of `struct` (relu only where the struct has the field), the operands' output planes compared, `out` allocated or
-    checked.  Returns (arr, n, out, cpad, N, H, W)."""
+def _concat_operands(entry, struct, srcs, out, dtypes=(torch.int8,)):
+    """What every concat entry point does in front of the call: srcs = [(q, C, up, relu or None, shift or None), ...] checked and
+    packed into an array of `struct` (relu, shift and the element size only where the struct has the field), q of one of `dtypes`,
+    the operands' output planes compared, `out` allocated or checked.  Returns (arr, n, out, cpad, N, H, W)."""
     n = len(srcs)
     arr = (struct * max(n, 1))()
     plane, total = None, 0
-    for i, (q, C, up, relu) in enumerate(srcs):
-        _need_cuda(q, torch.int8, entry)
+    for i, (q, C, up, relu, shift) in enumerate(srcs):
+        if len(dtypes) > 1 and q.dtype not in dtypes:
+            raise FqError("%s: an operand is %s, not int8 or int16" % (entry, q.dtype))
+        _need_cuda(q, q.dtype if len(dtypes) > 1 else dtypes[0], entry)
         assert q.dim() == 4 and q.is_contiguous()
         here = (int(q.shape[0]), int(q.shape[1]) * int(up), int(q.shape[2]) * int(up))
         if plane is None:
@@ -1581,6 +1584,8 @@ def _concat_operands(entry, struct, srcs, out):
         arr[i].q, arr[i].C, arr[i].Cpad, arr[i].up = q.data_ptr(), int(C), int(q.shape[3]), int(up)
         if relu is not None:
             arr[i].relu = 1 if relu else 0
+        if shift is not None:
+            arr[i].bytes, arr[i].shift = q.element_size(), int(shift)
         total += int(C)
     if plane is None:
         raise FqError("%s: no operand" % entry)
@@ -1599,7 +1604,7 @@ def concat_i8_nhwc(srcs, relu, out=None):
     channels each, `up` the nearest-upsampling factor of that operand.  Returns int8 [N, H, W, pad16(sum C)]: the operands one
     behind the other along the channels, the padding channels zero, max(., 0) applied when relu.  `out`: write there instead
     (that shape, dense, 16-byte aligned).  Launches on the current stream and does not synchronise."""
-    arr, n, out, cpad, N, H, W = _concat_operands("fq_concat_i8_nhwc", _CatSrc, [(q, C, up, None) for q, C, up in srcs], out)
+    arr, n, out, cpad, N, H, W = _concat_operands("fq_concat_i8_nhwc", _CatSrc, [(q, C, up, None, None) for q, C, up in srcs], out)
     _check(lib().fq_concat_i8_nhwc(arr, n, out.data_ptr(), cpad, 1 if relu else 0, N, H, W, _stream(out)), "fq_concat_i8_nhwc")
     return out
 
@@ -1609,7 +1614,7 @@ def concat_n_i8_nhwc(srcs, out=None):
     real channels each, `up` the nearest-upsampling factor of that operand and `relu` whether max(., 0) is applied to ITS bytes.
     Returns int8 [N, H, W, pad16(sum C)]: the operands one behind the other along the channels, the padding channels zero.
     `out`: write there instead (that shape, dense, 16-byte aligned).  Launches on the current stream and does not synchronise."""
-    arr, n, out, cpad, N, H, W = _concat_operands("fq_concat_n_i8_nhwc", _CatSrcN, [(q, C, up, bool(relu)) for q, C, up, relu in srcs], out)
+    arr, n, out, cpad, N, H, W = _concat_operands("fq_concat_n_i8_nhwc", _CatSrcN, [(q, C, up, bool(relu), None) for q, C, up, relu in srcs], out)
     _check(lib().fq_concat_n_i8_nhwc(arr, n, out.data_ptr(), cpad, N, H, W, _stream(out)), "fq_concat_n_i8_nhwc")
     return out
 
@@ -1618,12 +1623,7 @@ def concat_rq_supported(Cs, ups, nbytes, shifts):
     """True when fq_concat_rq_i8_nhwc takes sources of these channel counts, nearest-upsampling factors, element sizes (1: int8,
     2: int16) and shifts = consumer bit - source grid (include/fq.h): one to eight sources, every C >= 1, every factor 1, 2 or 4,
     every |shift| <= 8, at most 65536 channels in all.  Pure host arithmetic (no GPU needed)."""
-    n = len(Cs)
-    if n < 1 or len(ups) != n or len(nbytes) != n or len(shifts) != n:
-        return False
-    ci = ctypes.c_int * n
-    return bool(lib().fq_concat_rq_i8_nhwc_supported(ci(*[int(c) for c in Cs]), ci(*[int(u) for u in ups]),
-                                                     ci(*[int(b) for b in nbytes]), ci(*[int(s) for s in shifts]), n))
+    return _concat_supported("fq_concat_rq_i8_nhwc", Cs, ups, nbytes, shifts)
 
 
 def concat_rq_i8_nhwc(srcs, out=None):
@@ -1634,31 +1634,8 @@ def concat_rq_i8_nhwc(srcs, out=None):
     channels, the padding channels zero.  `out`: write there instead (that shape, dense, 16-byte aligned).  Launches on the
     current stream and does not synchronise."""
     entry = "fq_concat_rq_i8_nhwc"
-    n = len(srcs)
-    arr = (_CatSrcRq * max(n, 1))()
-    plane, total = None, 0
-    for i, (q, C, up, relu, shift) in enumerate(srcs):
-        if q.dtype not in (torch.int8, torch.int16):
-            raise FqError("%s: an operand is %s, not int8 or int16" % (entry, q.dtype))
-        _need_cuda(q, q.dtype, entry)
-        assert q.dim() == 4 and q.is_contiguous()
-        here = (int(q.shape[0]), int(q.shape[1]) * int(up), int(q.shape[2]) * int(up))
-        if plane is None:
-            plane = here
-        elif here != plane:
-            raise FqError("%s: the operands give different output planes (%s, %s)" % (entry, plane, here))
-        arr[i].q, arr[i].bytes, arr[i].C, arr[i].Cpad = q.data_ptr(), q.element_size(), int(C), int(q.shape[3])
-        arr[i].up, arr[i].relu, arr[i].shift = int(up), 1 if relu else 0, int(shift)
-        total += int(C)
-    if plane is None:
-        raise FqError("%s: no operand" % entry)
-    N, H, W = plane
-    cpad = pad16(total)
-    if out is None:
-        out = torch.empty(N, H, W, cpad, dtype=torch.int8, device=srcs[0][0].device)
-    else:
-        _need_cuda(out, torch.int8, entry)
-        assert tuple(out.shape) == (N, H, W, cpad) and out.is_contiguous()
+    arr, n, out, cpad, N, H, W = _concat_operands(entry, _CatSrcRq, [(q, C, up, bool(relu), int(shift)) for q, C, up, relu, shift in srcs], out,
+                                                  dtypes=(torch.int8, torch.int16))
     _check(lib().fq_concat_rq_i8_nhwc(arr, n, out.data_ptr(), cpad, N, H, W, _stream(out)), entry)
     return out
 

@@ -29,6 +29,11 @@ MOVED = [
     # the two concat kernels became the MAXSRC = 8 and MAXSRC = 2 instantiations of one template
     (r"concat_n_i8_kernel<(\w+), (\w+)>\(signed char\*, fq::CatNParams\)", r"concat_i8_kernel<8, \1, \2>(signed char*, fq::CatParams<8>)"),
     (r"concat_i8_kernel<(true|false), (\w+)>\(signed char\*, fq::CatParams\)", r"concat_i8_kernel<2, \1, \2>(signed char*, fq::CatParams<2>)"),
+    # ... and with the re-quantising kernel the two element policies of one skeleton
+    (r"concat_i8_kernel<(\d), (\w+), (\w+)>\(signed char\*, fq::CatParams<\d>\)",
+     r"concat_kernel<fq::CatMove, \1, \2, \3>(signed char*, fq::CatParams<fq::CatMove, \1>)"),
+    (r"concat_rq_i8_kernel<(\w+), (\w+)>\(signed char\*, fq::CrqParams\)",
+     r"concat_kernel<fq::CatRequant, 8, \1, \2>(signed char*, fq::CatParams<fq::CatRequant, 8>)"),
 ]
 
 

@@ -1,6 +1,6 @@
 """The nets and case lists of the re-quantising-Concat tests (test infrastructure, no product code).
 
-  kernel_cases() / sources() / case_arg()   the cases of tests/test_gpu_concat_rq_i8.py; scripts/concat_rq_geom_check.cpp walks the
+  kernel_cases() / sources() / case_arg()   the cases of tests/test_gpu_concat_rq_i8.py; scripts/concat_geom_check.cpp walks the
                        same shapes.
   ToyNet(variant)      one small integer-simulation net per cause for which the plain rule does not serve a Concat and
                        enable(concat=True, requant=True) does; built from NewConv2d info dicts, no calibration.
@@ -83,7 +83,7 @@ def kernel_cases(nsrc, plane):
 
 
 def case_arg(case):
-    """The case as scripts/concat_rq_geom_check.cpp reads it: N,H,W/C.../up.../bytes..."""
+    """The case as scripts/concat_geom_check.cpp reads it: N,H,W/C.../up.../bytes..."""
     N, H, W, Cs, ups, by = case[:6]
     return "%d,%d,%d/%s/%s/%s" % (N, H, W, ",".join(map(str, Cs)), ",".join(map(str, ups)), ",".join(map(str, by)))
 

@@ -1,5 +1,5 @@
 """The closed form of the re-quantising concatenation (include/fq.h: fq_concat_rq_i8_nhwc) in NumPy -- test infrastructure, no
-product code.  Written apart from the kernel's packed-int16 steps (csrc/fq_concat_rq_i8_geom.h, crq_requant): the quotient, the
+product code.  Written apart from the kernel's packed-int16 steps (csrc/fq_concat_i8_geom.h, crq_requant): the quotient, the
 dropped bits compared with one half, the tie by the quotient's parity, in int64.
 
   requant(v, shift, relu)      integer array (any int8 / int16 value) -> int64 array in [-128, 127]

@@ -221,7 +221,8 @@ def test_kernel_address_arithmetic_stays_inside_its_tensors(tmp_path):
     launch that holds anything but 16-byte loads -- over its built-in list and over the GPU tests' shape list.  The list reaches
     each path (16-byte, aligned dwords, byte-shifted dwords, chunks of two or more sources) without and with an upsampled source."""
     exe = str(tmp_path / "concat_geom_check")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "scripts", "concat_geom_check.cpp")])
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
+                           os.path.join(ROOT, "scripts", "concat_geom_check.cpp")])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.startswith("ok,"), out.stdout + out.stderr
     out = subprocess.run([exe] + [nn_.case_arg(c) for c in nn_.KERNEL_CASES], capture_output=True, text=True)

@@ -76,7 +76,8 @@ def test_one_and_two_sources_equal_the_two_source_kernel(nat, case):
 
 def test_the_case_list_covers_each_path_it_claims(tmp_path):
     exe = str(tmp_path / "concat_geom_check")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "scripts", "concat_geom_check.cpp")])
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
+                           os.path.join(ROOT, "scripts", "concat_geom_check.cpp")])
     out = subprocess.run([exe] + [nn_.case_arg(c) for c in nn_.KERNEL_CASES], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     nn_.check_paths_reached(nn_.class_rows(out.stdout.splitlines()))

@@ -1,4 +1,4 @@
-"""The re-quantising concatenation (fq_concat_rq_i8_nhwc, csrc/fq_concat_rq_i8.hip) against the closed form in NumPy
+"""The re-quantising concatenation (fq_concat_rq_i8_nhwc, csrc/fq_concat_i8.hip) against the closed form in NumPy
 (tests/requant_ref.py, which test_requant_plan_cpu.py holds against the reference's literal chain).  Everything is integers: every
 comparison is exact.   pytest -m gpu"""
 import ctypes
@@ -71,6 +71,25 @@ def test_a_launch_large_enough_that_lanes_take_a_second_item(nat):
     aligned = (4, 96, 96, (64, 128, 64), (1, 2, 1), (2, 1, 1), (-2, 3, 0), (1, 0, 0))      # the aligned family, strided too
     assert aligned[0] * aligned[1] * aligned[2] * 16 > 2048 * 256
     _run(nat, aligned, np.random.default_rng(6))
+
+
+# (N, H, W, Cs, ups, ReLU flags): the aligned family with an upsampled source; byte-shifted parts and chunks that straddle; one
+# source and the tail mask
+IDENTITY_CASES = ((2, 4, 4, (16, 32), (1, 2), (0, 1)), (2, 4, 4, (1, 3, 16, 19), (1, 1, 2, 1), (0, 1, 0, 1)), (2, 4, 4, (5,), (1,), (1,)))
+
+
+@pytest.mark.parametrize("case", IDENTITY_CASES, ids=lambda c: "C" + "_".join(map(str, c[3])))
+def test_int8_sources_at_shift_0_give_the_bytes_of_the_moving_kernel(nat, case):
+    """Both entry points are one kernel skeleton with two element policies: with every source int8 and every shift 0 the
+    re-quantisation is the identity, and the output is fq_concat_n_i8_nhwc's on the same sources, factors and ReLU flags, byte
+    for byte."""
+    N, H, W, Cs, ups, relus = case
+    zeros = (0,) * len(Cs)
+    arrays = rn.sources(np.random.default_rng(sum(Cs)), (N, H, W, Cs, ups, (1,) * len(Cs), zeros, relus))
+    dev = [torch.from_numpy(a).cuda() for a in arrays]
+    moved = nat.concat_n_i8_nhwc([(d, C, up, relu) for d, C, up, relu in zip(dev, Cs, ups, relus)])
+    requantised = nat.concat_rq_i8_nhwc([(d, C, up, relu, 0) for d, C, up, relu in zip(dev, Cs, ups, relus)])
+    assert moved.shape == requantised.shape == (N, H, W, rn.pad16(sum(Cs))) and torch.equal(moved, requantised)
 
 
 # ---------------------------------------------------------------- 2. what the entry point declines

@@ -2,7 +2,7 @@
 
 The closed form (requant_ref.py) is held against the reference's literal chain -- the oracle's DeQuantity, torch.cat, ReLU, the
 oracle's Quantity -- for every int8 and int16 value; the plan runs on doubles that take that chain literally (requant_doubles.py);
-the kernel's index arithmetic, its rounding and its guards are walked on the host (scripts/concat_rq_geom_check.cpp); golden G26
+the kernel's index arithmetic, its rounding and its guards are walked on the host (scripts/concat_geom_check.cpp); golden G26
 pins a calibrated net with a residual skip to the reference; forty random nets run under three plans.  Every comparison is exact."""
 import ctypes
 import io
@@ -222,12 +222,12 @@ def test_the_host_side_guards_and_their_return_codes(L, buf):
 
 # ---------------------------------------------------------------- 3. the walker
 def test_kernel_address_arithmetic_rounding_and_guards_on_the_host(tmp_path):
-    """csrc/fq_concat_rq_i8_geom.h holds the kernel's lane -> (sources, offsets, masks, loads) functions, its rounding and its
-    guards, and compiles as host code: scripts/concat_rq_geom_check.cpp, built with the address and undefined-behaviour sanitizers,
+    """csrc/fq_concat_i8_geom.h holds the kernel's lane -> (sources, offsets, masks, loads) functions, its rounding and its
+    guards, and compiles as host code: scripts/concat_geom_check.cpp, built with the address and undefined-behaviour sanitizers,
     walks every lane of every launch of the GPU tests' cases and of the two models' launch shapes."""
-    exe = str(tmp_path / "concat_rq_geom_check")
+    exe = str(tmp_path / "concat_geom_check")
     subprocess.check_call(["c++", "-O2", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                           os.path.join(ROOT, "scripts", "concat_rq_geom_check.cpp")])
+                           os.path.join(ROOT, "scripts", "concat_geom_check.cpp")])
     cases = [c for n in rn.KERNEL_NSRC for p in rn.KERNEL_PLANES for c in rn.kernel_cases(n, p)] + [rn.BIG_CASE] + rn.model_launches()
     args = sorted(set(rn.case_arg(c) for c in cases))
     out = subprocess.run([exe] + args, capture_output=True, text=True)
@@ -246,8 +246,19 @@ def test_kernel_address_arithmetic_rounding_and_guards_on_the_host(tmp_path):
     assert len(mixed) == 10 and all(int(r[r.index("general") + 1]) > 0 for r in mixed)       # (int16 sources at unaligned channel offsets)
     for bad in ("1,4,4/16/3/1", "1,4,4/16,16/1,1/1,3", "1,5,4/16/2/1", "1,4,4/16"):
         assert subprocess.run([exe, bad], capture_output=True, text=True).returncode in (1, 2), bad
-    header = open(os.path.join(ROOT, "pytorch-quantity_amd", "csrc", "fq_concat_rq_i8_geom.h")).read()
+    header = open(os.path.join(ROOT, "pytorch-quantity_amd", "csrc", "fq_concat_i8_geom.h")).read()
     assert re.search(r"kCrqMaxSrc = 8;", header) and re.search(r"kCrqMaxShift = 8;", header) and re.search(r"kCrqMaxBytes = 0x7ffffffeL;", header)
+
+
+def test_int8_sources_at_shift_0_are_the_moving_concat_on_the_doubles():
+    """The identity tests/test_gpu_concat_rq_i8.py holds the kernels to, on the two doubles."""
+    import concat_n_doubles
+    from test_gpu_concat_rq_i8 import IDENTITY_CASES
+    for N, H, W, Cs, ups, relus in IDENTITY_CASES:
+        arrays = rn.sources(np.random.default_rng(sum(Cs)), (N, H, W, Cs, ups, (1,) * len(Cs), (0,) * len(Cs), relus))
+        qs = [torch.from_numpy(a) for a in arrays]
+        moved = concat_n_doubles.concat_n_i8_nhwc([(q, C, up, relu) for q, C, up, relu in zip(qs, Cs, ups, relus)])
+        assert torch.equal(moved, rd.concat_rq_i8_nhwc([(q, C, up, relu, 0) for q, C, up, relu in zip(qs, Cs, ups, relus)]))
 
 
 def test_the_gpu_tests_case_list_meets_every_value_it_claims():
