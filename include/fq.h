@@ -61,7 +61,8 @@ int fq_last_hip_error(void);      /* thread-local hipError_t of the last FQ_ERR_
  * (256-pixel tiles, eight waves), 4 conv3x3_i8_halo, 5 / 6 conv2d_i8_dma with a ring of 2 / 3, 7 / 8 / 9 conv2d_i8_kernel
  * (C % 128 / C = 64 / general path), 10 stem_conv_i8, 11 block_tail_i8 (fq_block_tail_i8), 12 the same with the projection
  * shortcut computed in the kernel (fq_block_tail_proj_i8), 13 linear_i8_wave (a linear layer, one wave per 32 x 32 tile), 14 dwconv_i8
- * (fq_dwconv2d_i8_resident, a depthwise layer), 15 gconv_i8 (fq_gconv2d_i8_resident, a grouped layer), 0 nothing launched; bits
+ * (fq_dwconv2d_i8_resident, a depthwise layer), 15 gconv_i8 (fq_gconv2d_i8_resident, a grouped layer), 16 deconv_i8
+ * (fq_deconv2d_i8_resident, a transposed convolution), 0 nothing launched; bits
  * 8-15: output-channel
  * tile (64 / 128).  Lets a test assert that the dispatch it checked against a golden is the dispatch a benchmark timed. */
 int fq_conv2d_i8_last_variant(void);
@@ -665,6 +666,41 @@ int fq_gconv2d_i8_resident_pcs(const int8_t* x_nhwc, const int8_t* w_pack, const
                                int groups, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
                                int ob, fq_stream_t stream);
 
+/* Transposed convolution (nn.ConvTranspose2d, groups 1, dilation 1) on a resident activation: what NewConvTranspose2d.forward
+ * computes after Quantity.  The integer rule, part of this ABI:
+ *   P = (H-1)*stride_h - 2*pad_h + R + outpad_h          Q = (W-1)*stride_w - 2*pad_w + S + outpad_w
+ *   acc[n][oh][ow][k] = sum x[n][ih][iw][c] * w[c][k][r][s]                                              (int32, exact)
+ *       over c < C and the taps (r, s) with (oh + pad_h - r) = ih*stride_h, (ow + pad_w - s) = iw*stride_w, 0 <= ih < H, 0 <= iw < W
+ *   q_nhwc = clamp(RightShift(acc, rs) + qbias[k])       (= fq_conv2d_i8_resident's tail; ReLU fused when relu != 0)
+ * An output pixel no tap reaches (kernel < stride, or a row that exists only through outpad) is tail(0, qbias[k]).
+ * x_nhwc int8 [N][H][W][Cpad], Cpad = pad16(C); q_nhwc int8 [N][P][Q][Kpad], Kpad = pad16(K); both 16-byte aligned.  Channels
+ *   [K, Kpad) of q_nhwc are written as zeros; channels [C, Cpad) of x may hold anything (they meet zero weights).
+ * w_pack int8, fq_deconv2d_i8_packed_bytes(C, K, R, S) = Kpad*R*S*Cpad bytes, 16-byte aligned, w the layer's torch-layout
+ *   [C][K][R][S] weights packed per sub-pixel phase.  Phase f = fh*stride_w + fw (fh < stride_h, fw < stride_w: the output
+ *   pixels oh = fh (mod stride_h), ow = fw (mod stride_w)) owns the kernel rows r = a + stride_h*th, a = (fh + pad_h) % stride_h,
+ *   th < Th = ceil((R - a) / stride_h) (0 for a >= R), and the columns s = b + stride_w*tw likewise.  The phases follow one
+ *   another in the order of f, each [Kpad][Th*Tw][Cpad]: byte ((k*Th*Tw + th*Tw + tw)*Cpad + c) of its block is w[c][k][r][s],
+ *   zero for k >= K or c >= C.
+ * qbias fp32 [K], integer valued, of any magnitude (saturation as in fq_conv2d_i8).  ob: the output grid, as in
+ *   fq_conv2d_i8_resident (the integers do not depend on it).  Only int8 NHWC is written; a caller that needs fp32 NCHW follows
+ *   with fq_dequant_nhwc_to_nchw(q_nhwc, 1, ob, ...).
+ * fq_deconv2d_i8_supported (host arithmetic only): 1 for C, K >= 1, groups 1, dilation 1, 1 <= R, S <= 8, 1 <= stride <= 4,
+ *   0 <= pad < kernel and 0 <= outpad < stride per axis, every shift in [1, 16] (the integer tail of fq_int_tail.h only) and an
+ *   accumulator that stays in int32: ceil(R/stride_h)*ceil(S/stride_w)*C*2^14 + 2^16 + (255 << rs_max) < 2^31 - 1.
+ * Return codes, scalars judged before pointers: FQ_ERR_INVALID_ARG for an Sp range outside -128 <= lo <= 0 <= hi <= 127, rs or ob
+ *   outside [-120, 120], N < 0 or a non-positive size, kernel or stride or a negative pad or outpad; then FQ_ERR_UNSUPPORTED for
+ *   whatever fq_deconv2d_i8_supported refuses; then FQ_ERR_INVALID_ARG for Cpad != pad16(C), Kpad != pad16(K) or P, Q < 1; then
+ *   FQ_ERR_UNSUPPORTED for N*H*W*Cpad or Kpad*R*S*Cpad >= 2^31 - 1 or N*P*Q*Kpad >= 2^30 - 1 (32-bit offsets): callers keep the
+ *   fp32 form there.  N == 0 is then FQ_OK without a launch; with N > 0 a null or misaligned pointer is FQ_ERR_INVALID_ARG.
+ *   Nothing is written unless FQ_OK is returned.  fq_conv2d_i8_last_variant: 16.
+ * _act: the Sp range in place of relu, as for every integer producer (below).  No per-channel (_pcs) form. */
+int fq_deconv2d_i8_supported(int C, int K, int groups, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int outpad_h,
+                             int outpad_w, int dil_h, int dil_w, int rs_min, int rs_max);
+size_t fq_deconv2d_i8_packed_bytes(int C, int K, int R, int S);
+int fq_deconv2d_i8_resident(const int8_t* x_nhwc, const int8_t* w_pack, const float* qbias, int8_t* q_nhwc, int Cpad, int Kpad,
+                            int relu, int N, int H, int W, int C, int K, int R, int S, int stride_h, int stride_w, int pad_h,
+                            int pad_w, int outpad_h, int outpad_w, int rs, int ob, fq_stream_t stream);
+
 /* ---- a fused activation other than nn.ReLU: the `_act` entry points ---------------------------------------------
  * Each integer producer above has a sibling that takes the Sp range of its output integers, `int act_lo, int act_hi`, in the place
  * of `int relu`:   q = min(max(RightShift(acc, rs) + qbias[k], act_lo), act_hi)   (RightShift still saturates to [-128, 127]).
@@ -704,6 +740,9 @@ int fq_gconv2d_i8_resident_pcs_act(const int8_t* x_nhwc, const int8_t* w_pack, c
                                    int rs_max, int8_t* q_nhwc, int Cpad, int Kpad, int act_lo, int act_hi, int N, int H, int W,
                                    int C, int K, int groups, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
                                    int dil_h, int dil_w, int ob, fq_stream_t stream);
+int fq_deconv2d_i8_resident_act(const int8_t* x_nhwc, const int8_t* w_pack, const float* qbias, int8_t* q_nhwc, int Cpad, int Kpad,
+                                int act_lo, int act_hi, int N, int H, int W, int C, int K, int R, int S, int stride_h, int stride_w,
+                                int pad_h, int pad_w, int outpad_h, int outpad_w, int rs, int ob, fq_stream_t stream);
 
 /* Channel concatenation (the Concat marker layer, torch.cat along dim 1) and nearest upsampling (nn.UpsamplingNearest2d with an
  * integer factor) of resident int8 NHWC activations that share ONE grid: moving the integers is concatenating the values, and

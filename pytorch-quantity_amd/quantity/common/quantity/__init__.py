@@ -39,6 +39,7 @@ BiasAdd = _ops.BiasAdd
 NewConv2d = _ops.NewConv2d
 NewAdd = _ops.NewAdd
 NewLinear = _ops.NewLinear
+NewConvTranspose2d = _ops.NewConvTranspose2d      # (not in the reference: its ReconModel leaves nn.ConvTranspose2d float)
 QuanDequan = _ops.QuanDequan
 TestConv = _ops.TestConv
 TestLinear = _ops.TestLinear
@@ -49,5 +50,5 @@ __all__ = [
     "DistributionCollector", "Quantizer", "BitReader", "merge_bn", "walk_dirs", "tid",
     "Eltwise", "Concat", "Identity", "View", "Slice",
     "RightShift", "Sp", "BiasAdd", "NewConv2d", "NewAdd", "NewLinear", "QuanDequan",
-    "TestConv", "TestLinear", "Quantity", "DeQuantity",
+    "TestConv", "TestLinear", "Quantity", "DeQuantity", "NewConvTranspose2d",
 ]

@@ -233,9 +233,16 @@ def lib():
     L.fq_gconv2d_i8_resident.argtypes = [vp, vp, vp, vp] + [ci] * 19 + [vp]
     L.fq_gconv2d_i8_resident_pcs.restype = ci
     L.fq_gconv2d_i8_resident_pcs.argtypes = [vp, vp, vp, vp, ci, ci, vp] + [ci] * 18 + [vp]
+    L.fq_deconv2d_i8_supported.restype = ci
+    L.fq_deconv2d_i8_supported.argtypes = [ci] * 15
+    L.fq_deconv2d_i8_packed_bytes.restype = sz
+    L.fq_deconv2d_i8_packed_bytes.argtypes = [ci] * 4
+    L.fq_deconv2d_i8_resident.restype = ci
+    L.fq_deconv2d_i8_resident.argtypes = [vp, vp, vp, vp] + [ci] * 18 + [vp]
     # the `_act` siblings of the integer producers: `int act_lo, int act_hi` where those take `int relu`
     for name in ("fq_conv2d_i8_resident", "fq_conv2d_i8_resident_pcs", "fq_conv2d_i8_stem", "fq_conv2d_i8_stem_pcs",
-                 "fq_dwconv2d_i8_resident", "fq_dwconv2d_i8_resident_pcs", "fq_gconv2d_i8_resident", "fq_gconv2d_i8_resident_pcs"):
+                 "fq_dwconv2d_i8_resident", "fq_dwconv2d_i8_resident_pcs", "fq_gconv2d_i8_resident", "fq_gconv2d_i8_resident_pcs",
+                 "fq_deconv2d_i8_resident"):
         getattr(L, name + "_act").restype = ci
         plain = getattr(L, name).argtypes                     # (..., int relu, ints ..., stream) -> (..., int act_lo, int act_hi, ints ..., stream)
         getattr(L, name + "_act").argtypes = plain[:-1] + [ci, plain[-1]]
@@ -1115,7 +1122,7 @@ def pack_weight_krsc(w, cpad=None):
 # kernel there by name -- tests and bench.py assert with it that the dispatch they checked is the dispatch they time.
 CONV_VARIANTS = {0: "none", 1: "c64_halo", 2: "stream", 3: "halo8", 4: "halo", 5: "dma2", 6: "dma3", 7: "tile_c128", 8: "tile_c64",
                  9: "tile_general", 10: "stem", 11: "block_tail", 12: "block_tail_proj", 13: "linear_wave", 14: "depthwise",
-                 15: "grouped"}
+                 15: "grouped", 16: "deconv"}
 conv_variant_log = None
 
 
@@ -1859,6 +1866,73 @@ def quantize_i8_unfold_w(x, ib, S, stride_w, pad_w, dil_w, cpad2):
     _check(lib().fq_quantize_i8_unfold_w(xc.data_ptr(), y.data_ptr(), N, C, H, W, int(S), int(stride_w), int(pad_w),
                                          int(dil_w), int(cpad2), int(ib), _stream(xc)), "fq_quantize_i8_unfold_w")
     return y
+
+
+def _out_hw_deconv(H, W, R, S, stride, padding, output_padding):
+    """(P, Q): the output plane of nn.ConvTranspose2d with dilation 1."""
+    return ((H - 1) * stride[0] - 2 * padding[0] + R + output_padding[0], (W - 1) * stride[1] - 2 * padding[1] + S + output_padding[1])
+
+
+def deconv_supported(C, K, groups, R, S, stride, padding, output_padding, dilation, rs):
+    """True when fq_deconv2d_i8_resident takes a transposed convolution of this geometry and shift (include/fq.h): groups 1,
+    dilation 1, kernel 1 .. 8, stride 1 .. 4, pad < kernel, output_padding < stride, the shift in [1, 16], an accumulator inside
+    int32.  Pure host arithmetic (no GPU needed); rs: an int or a ShiftVec (every shift must lie in [1, 16]; the entry point itself
+    has no per-channel form)."""
+    lo, hi = _bounds(rs)
+    return bool(lib().fq_deconv2d_i8_supported(int(C), int(K), int(groups), int(R), int(S), int(stride[0]), int(stride[1]),
+                                               int(padding[0]), int(padding[1]), int(output_padding[0]), int(output_padding[1]),
+                                               int(dilation[0]), int(dilation[1]), lo, hi))
+
+
+def pack_weight_deconv(w, stride, padding):
+    """Integer-valued fp32 transposed-convolution weights [C, K, R, S] (torch's layout, groups 1) -> the flat int8 pack of
+    fq_deconv2d_i8_resident (include/fq.h): sub-pixel phase after phase, each [Kpad][taps of the phase][Cpad], zeros in the channel
+    padding.  Every tap lies in exactly one phase: Kpad * R * S * Cpad bytes."""
+    C, K, R, S = w.shape
+    sh, sw, ph, pw = int(stride[0]), int(stride[1]), int(padding[0]), int(padding[1])
+    cpad, kpad = pad16(C), pad16(K)
+    parts = []
+    for fh in range(sh):
+        for fw in range(sw):
+            a, b = (fh + ph) % sh, (fw + pw) % sw
+            sub = w[:, :, a::sh, b::sw]                                          # [C, K, Th, Tw]: the taps r = a + sh th, s = b + sw tw
+            blk = torch.zeros(kpad, sub.shape[2], sub.shape[3], cpad, dtype=torch.int8, device=w.device)
+            blk[:K, :, :, :C] = sub.permute(1, 2, 3, 0).to(torch.int8)
+            parts.append(blk.reshape(-1))
+    out = torch.cat(parts).contiguous()
+    assert out.numel() == int(lib().fq_deconv2d_i8_packed_bytes(C, K, R, S))
+    return out
+
+
+def deconv2d_i8_resident(xq, wq, qbias, C, kernel, stride, padding, output_padding, rs, ob, relu, clip=None, out=None):
+    """fq_deconv2d_i8_resident: xq int8 [N,H,W,Cpad], wq int8 flat (pack_weight_deconv), qbias fp32 [K]; C the real input channels,
+    kernel = (R, S).  Returns q int8 [N,P,Q,Kpad], the integers before DeQuantity(ob) with the ReLU folded in.  rs: an int (no
+    per-channel form).  clip = (lo, hi): the `_act` entry point with that Sp range in place of relu.  out: a contiguous int8
+    [N,P,Q,Kpad] tensor to write instead of a fresh one."""
+    entry = "fq_deconv2d_i8_resident"
+    _need_cuda(xq, torch.int8, entry)
+    _need_cuda(wq, torch.int8, entry)
+    _need_cuda(qbias, torch.float32, entry)
+    if isinstance(rs, ShiftVec):
+        raise FqError(entry + ": no per-channel form")
+    N, H, W, cpad = xq.shape
+    R, S = int(kernel[0]), int(kernel[1])
+    C, K = int(C), qbias.numel()
+    kpad = pad16(K)
+    assert cpad == pad16(C) and xq.is_contiguous() and wq.is_contiguous() and wq.numel() == kpad * R * S * cpad
+    P, Q = _out_hw_deconv(H, W, R, S, stride, padding, output_padding)
+    if P <= 0 or Q <= 0:
+        raise FqError(entry + ": the output plane is empty")
+    if out is None:
+        q = torch.empty(N, P, Q, kpad, dtype=torch.int8, device=xq.device)
+    else:
+        _need_cuda(out, torch.int8, entry)
+        assert tuple(out.shape) == (N, P, Q, kpad) and out.is_contiguous()
+        q = out
+    _conv_i8(entry, xq, wq, qbias, rs, K, (q.data_ptr(), cpad, kpad),
+             (N, H, W, C, K, R, S, stride[0], stride[1], padding[0], padding[1], output_padding[0], output_padding[1]), (int(ob),),
+             (relu, clip))
+    return q
 
 
 def pack_weight_unfold_w(w, cpad2):

@@ -30,7 +30,7 @@ QUANTIZE_BIT = 8
 DUMP_VISUALIZATION = os.environ.get("FQ_DUMP_VISUALIZATION", "0") not in ("", "0", "false", "False")
 
 __all__ = ["RightShift", "Sp", "BiasAdd", "NewConv2d", "NewAdd", "NewLinear", "QuanDequan", "TestConv",
-           "TestLinear", "Quantity", "DeQuantity", "QUANTIZE_BIT"]
+           "TestLinear", "Quantity", "DeQuantity", "QUANTIZE_BIT", "NewConvTranspose2d"]
 
 
 def _check_width(bits):
@@ -178,7 +178,7 @@ def _own_kernel_candidate(layer, switch):
 
 
 # Weights as a kernel reads them, cached on the integer layer by _IntegerSimLayer._packed: attribute -> what packs it
-_WEIGHT_SLOTS = ("_w_i8", "_w_stem", "_w_dw", "_w_gc")
+_WEIGHT_SLOTS = ("_w_i8", "_w_stem", "_w_dw", "_w_gc", "_w_dc")
 
 
 def _pack_dense(layer):                     # _w_i8: fq_conv2d_i8 and its kin (a stem-like layer: its width folded into the channels)
@@ -196,6 +196,15 @@ def _pack_depthwise(layer):                 # _w_dw: fq_dwconv2d_i8_resident
 
 def _pack_grouped(layer):                   # _w_gc: fq_gconv2d_i8_resident
     return _native.pack_weight_grouped(layer.weight.detach(), layer.groups)
+
+
+def _pack_deconv(layer):                    # _w_dc: fq_deconv2d_i8_resident (sub-pixel phase after phase)
+    return _native.pack_weight_deconv(layer.weight.detach(), layer.stride, layer.padding)
+
+
+def _launch_deconv(self, conv, xq, wq, relu, **act):
+    return _native.deconv2d_i8_resident(xq, wq, self.quantized_bias, conv.in_channels, conv.kernel_size, conv.stride, conv.padding,
+                                        conv.output_padding, self._rs(), self.output_bit, relu, **act)
 
 
 def _launch_depthwise(self, conv, xq, wq, relu, **act):
@@ -416,6 +425,68 @@ class NewConv2d(_IntegerSimLayer):
         if h.exact is not None and h.exact.dtype == torch.int8 and h.grid == self.input_bit and h.exact.shape[-1] == cpad:
             return h.exact
         return None
+
+
+class NewConvTranspose2d(_IntegerSimLayer):
+    """Integer simulation of a transposed convolution (nn.ConvTranspose2d): NewConv2d's chain word for word -- Quantity(input_bit)
+    -> the exact integer contraction with the quantised weights -> RightShift -> BiasAdd -> Sp -> DeQuantity.  (Not in the
+    reference, whose ReconModel leaves the module float; its calibration flow takes the layer up to the tables: golden G28.)
+
+    The wrapped module is kept as `.Conv`, as NewConv2d keeps its own.  Default forward, the reference-shaped form: the Quantity
+    kernel, the module's own forward on the integer-valued fp32 tensor (exact below 2^24 per partial sum), the fused tail kernel.
+    `use_deconv_i8 = True` (off by default; settable per instance) runs a layer that fq_deconv2d_i8_resident takes (_deconv_ok)
+    on that kernel instead: the same fp32 tensor, bit for bit.  resident.enable(..., deconv=True) plans such layers as integer
+    producers / consumers.  Per-tensor bits only: a list-valued weight_bit raises ValueError."""
+
+    use_deconv_i8 = False
+
+    def __init__(self, deconv_module, quantize_infor, name=None):
+        super(NewConvTranspose2d, self).__init__()
+        if isinstance(quantize_infor["weight_bit"], (list, tuple)):
+            raise ValueError("NewConvTranspose2d %s: per-channel weight bits are not defined for a transposed convolution (its "
+                             "weights are [in, out, R, S]); give the layer one weight_bit" % (name if name else repr(deconv_module)))
+        self.Conv = deconv_module
+        self._setup(deconv_module, quantize_infor, deconv_module.out_channels, False)
+
+    def _deconv_left(self, layer):
+        """None when fq_deconv2d_i8_resident takes `layer` at this module's shift, else the reason (describe().deconv_left)."""
+        if not isinstance(layer, nn.ConvTranspose2d) or layer.padding_mode != "zeros":
+            return "no zero-padded nn.ConvTranspose2d"
+        if layer.groups != 1:
+            return "groups %d: the kernel takes groups 1 only (fp32 form)" % layer.groups
+        if tuple(layer.dilation) != (1, 1):
+            return "dilation %s: the kernel takes dilation 1 only (fp32 form)" % (tuple(layer.dilation),)
+        if isinstance(self.rs_bit, list):
+            return "per-channel weight bits (fp32 form)"
+        k = layer.kernel_size
+        if _native.deconv_supported(layer.in_channels, layer.out_channels, 1, k[0], k[1], layer.stride, layer.padding,
+                                    layer.output_padding, (1, 1), self.rs_bit):
+            return None
+        if not 1 <= self.rs_bit <= 16:
+            return "shift %d outside [1, 16]: the integer tail does not take it (fp32 form)" % self.rs_bit
+        return ("a geometry the kernel refuses: kernel %s, stride %s, padding %s, output_padding %s, %d input channels (kernel 1 .. 8, "
+                "stride 1 .. 4, padding < kernel, an accumulator inside int32; fp32 form)"
+                % (tuple(k), tuple(layer.stride), tuple(layer.padding), tuple(layer.output_padding), layer.in_channels))
+
+    def _deconv_ok(self, layer, switch=None):
+        """True when `layer` is a transposed convolution that fq_deconv2d_i8_resident takes: the switch (use_deconv_i8, or the
+        caller's `switch`), QUANTIZE_BIT == 8, and the kernel's own limits (_deconv_left)."""
+        if not (self.use_deconv_i8 if switch is None else switch) or QUANTIZE_BIT != 8:
+            return False
+        return self._deconv_left(layer) is None
+
+    def forward(self, input):
+        conv = self.Conv
+        plan = self.__dict__.get("_resident")             # set by common.quantity.resident.enable(deconv=True): only where _deconv_ok
+        if plan is not None or (self.use_deconv_i8 and self._deconv_ok(conv)):
+            return self._forward_own_kernel(conv, input, plan, self._packed("_w_dc", conv, _pack_deconv),
+                                            _native.pad16(conv.in_channels), _launch_deconv)
+        q = self.Quan(as_f32(input))
+        acc = conv(q)               # integer-valued fp32 in, exact below 2^24 per partial sum
+        return self._tail(acc)
+
+    _forward_own_kernel = NewConv2d._forward_own_kernel
+    _resident_input = NewConv2d._resident_input
 
 
 class NewLinear(_IntegerSimLayer):

@@ -837,6 +837,7 @@ _SWITCH_TABLE = (
     ("bilinear", ("resident_bilinears",), ("bilinear_left",)),
     ("requant", ("requant_concats", "requant_sum_sources"), ("requant_left",)),
     ("pixelshuffle", ("resident_pixelshuffles", "resident_pixelunshuffles"), ("pixelshuffle_left",)),
+    ("deconv", ("resident_deconvs",), ("deconv_left",)),
 )
 _Switches = collections.namedtuple("_Switches", [name for name, _keys, _reports in _SWITCH_TABLE])
 # (switch, the switch it needs, enable()'s ValueError without it)
@@ -859,9 +860,9 @@ class _Planning(object):
     nothing on the model until install() writes the plans and the instance-level forwards to the modules."""
 
     def __init__(self, tracer, switches, revoked=None, names=None):
-        from .new_quantity_op import NewConv2d, NewAdd
+        from .new_quantity_op import NewConv2d, NewAdd, NewConvTranspose2d
         from .fabu_layer import Concat
-        self.conv_type, self.concat_type = NewConv2d, Concat
+        self.conv_type, self.concat_type, self.deconv_type = NewConv2d, Concat, NewConvTranspose2d
         self.tracer = tracer
         self.sw = switches               # the _Switches of this enable() call
         self.revoked = dict(revoked or {})   # module that an earlier round planned and verify() took back -> why
@@ -961,12 +962,36 @@ class _Planning(object):
         them as `resident_grouped`."""
         return self.sw.grouped and isinstance(m, self.conv_type) and self.once(m) and m._grouped_ok(m.Conv, True)
 
+    def is_dc(self, m):
+        """A transposed convolution that this plan runs on fq_deconv2d_i8_resident: `deconv=True` plans NewConvTranspose2d layers
+        (groups 1, dilation 1, kernel 1 .. 8, stride 1 .. 4, zero padding below the kernel size, output_padding below the stride,
+        shift in [1, 16], per-tensor bits: NewConvTranspose2d._deconv_ok) as integer producers at their output_bit and integer
+        consumers at their input_bit, the third own-kernel family beside depthwise and grouped.  An nn.ReLU behind one is fused,
+        with `relu6=True` an nn.ReLU6 as well; wherever a lossy value (a table activation, a bilinear upsampling, a re-quantising
+        Concat) requires integer convolutions at one bit of its readers, it is one.  Such a layer is never run inside a NewAdd's
+        kernel and never part of a block tail or a fused projection; an add reads its integers like any other operand.  Without
+        the argument it stays an fp32 producer, as a grouped convolution does without `grouped=True`.  The summary then counts
+        them as `resident_deconvs`; describe().deconv_left names the ones left with the reason: groups, dilation, a geometry or
+        shift the kernel refuses, called more than once."""
+        return self.sw.deconv and isinstance(m, self.deconv_type) and self.once(m) and m._deconv_ok(m.Conv, True)
+
     def conv_can_emit(self, m):
+        if isinstance(m, self.deconv_type):
+            return self.is_dc(m)
         return isinstance(m, self.conv_type) and self.once(m) and (m._int8_ok(m.Conv) or self.is_dw(m) or self.is_gc(m))
 
     def conv_can_read(self, m):
+        if isinstance(m, self.deconv_type):
+            return self.is_dc(m)
         return isinstance(m, self.conv_type) and ((m._int8_ok(m.Conv) and not m._stem_fold(m.Conv)) or self.is_dw(m)
                                                   or self.is_gc(m))
+
+    def _deconv_reasons(self):
+        """Why each traced NewConvTranspose2d without a plan stays an fp32 producer (for describe().deconv_left)."""
+        for m in self.tracer.calls:
+            if isinstance(m, self.deconv_type) and m not in self.plans:
+                self.left["deconv_left"][m] = ("the module was called more than once" if not self.once(m)
+                                               else m._deconv_left(m.Conv) or "its output has no integer form in this plan")
 
     def avg_can_read(self, m):
         """The whole-plane nn.AvgPool2d in front of the head, which reads the exact integers of its source (_AvgPoolResident)."""
@@ -1002,6 +1027,8 @@ class _Planning(object):
         if self.is_gc(m):
             self.fields.setdefault(m, {})["grouped"] = True
             self.summary["resident_grouped"] += 1
+        if self.is_dc(m):
+            self.summary["resident_deconvs"] += 1
         return (1, m.output_bit)
 
     def _int8_source(self, v):
@@ -1635,7 +1662,7 @@ class _Planning(object):
                 # (not cp.clip: the second tail of fq_block_tail_i8 has the plain ReLU's range only; a 1x1 with a fused ReLU6
                 #  stays a launch of its own)
                 if (cp is not None and not cp.defer and not cp.grouped and not cp.clip and cp.emit_int and not cp.emit_f32
-                        and self.once(c)
+                        and self.once(c) and isinstance(c, self.conv_type)
                         and _pointwise_conv(c.Conv) and c.input_bit == plan.narrow_bit
                         and conv3.Conv.out_channels == c.Conv.in_channels
                         and _native.block_tail_supported(conv3.Conv.in_channels, conv3.Conv.out_channels, c.Conv.out_channels,
@@ -1756,6 +1783,8 @@ class _Planning(object):
         if self.sw.relu6:
             self._relu6_reasons()
             report["fused_relu6s"] = self.summary["fused_relu6s"]
+        if self.sw.deconv:
+            self._deconv_reasons()
         if self.sw.sums:
             self._unplanned_avgpools()
         if self.sw.topdown:
@@ -1842,7 +1871,7 @@ _KINDS = (
     _Kind("slice", _named("Slice"), _Planning._shuffle_format, "shuffle", behind=True, fuse_relu=False, moves=True,
           forward=_SliceResident, counter="resident_slices", report="shuffle_left",
           default="its input is not the output of a planned layer"),
-    _Kind("contraction", _named("NewConv2d", "NewLinear"), _Planning._conv_format, counter="resident_convs"),
+    _Kind("contraction", _named("NewConv2d", "NewLinear", "NewConvTranspose2d"), _Planning._conv_format, counter="resident_convs"),
 )
 _KIND = dict((row.name, row) for row in reversed(_KINDS))    # (by name; the two rows of "relu" differ in how they are hooked only)
 _MOVES = tuple(row.name for row in _KINDS if row.moves)     # what Quantity_b commutes with: data movement and max
@@ -1885,7 +1914,7 @@ def _trace(model, example_input, switches):
 
 def enable(model, example_input, verify=True, depthwise=False, concat=False, avgpool=False, grouped=False, relu6=False,
            flatten=False, shuffle=False, activations=False, sums=False, topdown=False, bilinear=False, requant=False,
-           pixelshuffle=False):
+           pixelshuffle=False, deconv=False):
     """Trace one forward of `model` (an integer-simulation model built by Reconstruction.ReconModel,
     on the GPU) and switch every eligible NewConv2d / NewAdd (and the nn.ReLU / nn.MaxPool2d / global
     nn.AvgPool2d between them) to resident integer activations.  Returns a summary dict.
@@ -1915,11 +1944,13 @@ def enable(model, example_input, verify=True, depthwise=False, concat=False, avg
     ResNet-encoder U-Net -- on fq_concat_rq_i8_nhwc, which re-quantises every source to the readers' bit: a lossy value too
     (_Planning._concat_requant);
     `pixelshuffle=True` also plans nn.PixelShuffle(r) and nn.PixelUnshuffle(r), r in {2, 3, 4}, on the int8 integers
-    (fq_pixel_shuffle_i8_nhwc; _Planning._pixelshuffle_format).  It needs no other switch."""
+    (fq_pixel_shuffle_i8_nhwc; _Planning._pixelshuffle_format).  It needs no other switch;
+    `deconv=True` also plans NewConvTranspose2d layers -- the learned upsampling of a U-Net, a pix2pix / DCGAN head, a LinkNet
+    decoder -- as integer producers and consumers on fq_deconv2d_i8_resident (_Planning.is_dc).  It needs no other switch."""
     from .new_quantity_op import QUANTIZE_BIT
     switches = _switches(depthwise=depthwise, concat=concat, avgpool=avgpool, grouped=grouped, relu6=relu6, flatten=flatten,
                          shuffle=shuffle, activations=activations, sums=sums, topdown=topdown, bilinear=bilinear, requant=requant,
-                         pixelshuffle=pixelshuffle)
+                         pixelshuffle=pixelshuffle, deconv=deconv)
     for switch, needed, message in _SWITCH_NEEDS:
         if getattr(switches, switch) and not getattr(switches, needed):
             raise ValueError(message)
@@ -1974,7 +2005,8 @@ class _Description(dict):
     stays torch's.  After enable(concat=True, requant=True) `requant_left` is {module name: why} for every Concat that the plain
     rule does not fully serve -- it has no integer plan, or emits fp32 for a reader -- and the re-quantising rule declines.  After
     enable(pixelshuffle=True) `pixelshuffle_left` is {module name: why} for every hooked nn.PixelShuffle / nn.PixelUnshuffle that
-    stays torch's."""
+    stays torch's.  After enable(deconv=True) `deconv_left` is {module name: why} for every NewConvTranspose2d that stays an fp32
+    producer."""
     activations_revoked = ()
     fused_relu6s = 0
     flattened_concats = ()       # names of the Concats that enable(flatten=True) deferred into their consumer's launch

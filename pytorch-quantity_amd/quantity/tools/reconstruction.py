@@ -1,5 +1,7 @@
 """Rebuild a calibrated model as its integer-simulation (ReconModel) or fake-quant (ReconTest)
-counterpart by swapping Conv2d / Linear / Eltwise modules for the quantize-op modules.
+counterpart by swapping Conv2d / Linear / Eltwise modules for the quantize-op modules.  ReconModel also swaps an
+nn.ConvTranspose2d for NewConvTranspose2d (an extension: the reference leaves the module float in both); ReconTest leaves it as
+it is, float, as the reference does -- there is no TestConv for a transposed convolution.
 
 Drop-in for reference quantity/tools/reconstruction.py (Reconstruction :93, load_configs :101-105,
 get_quantity_information :107-172, ReconModel :175-241, ReconTest :243-324, merge_bn :326-332):
@@ -15,7 +17,7 @@ import torch
 import yaml
 
 from common.quantity import BitReader, Eltwise, Concat, Identity  # noqa: F401
-from common.quantity import NewConv2d, NewAdd, NewLinear, TestConv, TestLinear
+from common.quantity import NewConv2d, NewAdd, NewLinear, TestConv, TestLinear, NewConvTranspose2d
 from common.quantity import merge_bn
 
 __all__ = ["Reconstruction"]
@@ -89,14 +91,16 @@ class Reconstruction(object):
             info[name]["weight_bit"] = list(bits)
         return info
 
-    def _rebuild(self, all_quantize_infor, new_model_path, make_conv, make_linear, label):
+    def _rebuild(self, all_quantize_infor, new_model_path, make_conv, make_linear, label, make_deconv=None):
         for name, module in list(self.model.named_modules()):
             kind = type(module).__name__
-            if kind not in ("Conv2d", "Linear", "Eltwise"):
+            if kind not in ("Conv2d", "Linear", "Eltwise") and not (kind == "ConvTranspose2d" and make_deconv is not None):
                 continue
             assert all_quantize_infor[name]["layer_type"] == kind, "layer type wrong"
             if kind == "Conv2d":
                 new = make_conv(name, module, all_quantize_infor[name])
+            elif kind == "ConvTranspose2d":
+                new = make_deconv(name, module, all_quantize_infor[name])
             elif kind == "Linear":
                 new = make_linear(name, module, all_quantize_infor[name])
             else:
@@ -108,9 +112,11 @@ class Reconstruction(object):
         return self.model
 
     def ReconModel(self, all_quantize_infor, new_model_path):
-        """Quantity -> integer conv/linear -> RightShift -> BiasAdd -> Sp -> DeQuantity per layer."""
+        """Quantity -> integer conv/linear -> RightShift -> BiasAdd -> Sp -> DeQuantity per layer; an nn.ConvTranspose2d becomes a
+        NewConvTranspose2d, the same chain (a per-channel weight_bit list for it raises ValueError naming the layer)."""
         return self._rebuild(all_quantize_infor, new_model_path,
-                             lambda n, m, q: NewConv2d(m, q), lambda n, m, q: NewLinear(m, q), "ReconModel")
+                             lambda n, m, q: NewConv2d(m, q), lambda n, m, q: NewLinear(m, q), "ReconModel",
+                             make_deconv=lambda n, m, q: NewConvTranspose2d(m, q, name=n))
 
     def make_resident(self, example_input, verify=True):
         """Extension: keep the integer-simulation model's activations as integers between its layers
@@ -120,7 +126,8 @@ class Reconstruction(object):
         return resident.enable(self.model, example_input, verify=verify)
 
     def ReconTest(self, all_quantize_infor, new_model_path):
-        """Fake-quant evaluation model: w, b fake-quantised once; every output fake-quantised."""
+        """Fake-quant evaluation model: w, b fake-quantised once; every output fake-quantised.  An nn.ConvTranspose2d is left as
+        it is (float), as in the reference."""
         return self._rebuild(all_quantize_infor, new_model_path,
                              lambda n, m, q: TestConv(n, m, q, new_model_path),
                              lambda n, m, q: TestLinear(n, m, q, new_model_path), "ReconTest")
