@@ -464,6 +464,40 @@ int fq_gconv_f32(const float* x, const float* w_kcrs, const float* bias, float* 
 int fq_gconv_qd_f32(const float* x, const float* w_kcrs, const float* bias, float* y, int N, int C, int H, int W, int K, int groups,
                     int R, int S, int stride, int pad, int bit, int bitwidth, fq_stream_t stream);
 
+/* The transposed float convolutions of the calibration forward (nn.ConvTranspose2d with groups 1 and dilation 1: the
+ * up-convolutions of model/unet/UNet_fabu.py with up="deconv"), on the fp32 matrix cores, same epilogue contract as
+ * fq_conv1x1_f32 / fq_conv_kxk_f32 (bias may be NULL; relu_out may be NULL; with relu_out given y may be NULL and its statistic
+ * is still taken; exactly one of {max_inout, hist_row + interval} or neither):
+ *   y[n][k][oh][ow] = bias[k] + sum_{r,s,c} w[c][k][r][s] * x[n][c][(oh + pad - r)/stride][(ow + pad - s)/stride]
+ *   over the taps with (oh + pad - r) % stride == 0 and (ow + pad - s) % stride == 0 whose source pixel lies inside the image.
+ * x: fp32 [N][Cin][Hin][Win] contiguous; y / relu_out: fp32 [N][Cout][Ho][Wo], Ho = (Hin - 1) stride - 2 pad + R + outpad.
+ * wt: fp32 [(r*S + s)*Cin + c][Cout] = W[c][co][r][s] (the module's weight is [Cin][Cout][R][S]), 16-byte aligned:
+ *   fq_conv_kxk_f32's layout, w.permute(2, 3, 0, 1).reshape(R*S*Cin, Cout) -- there is no pack function.  The other pointers
+ *   need only their type's alignment (a y that is a view at an odd float offset is stored with narrower stores).
+ * Taken (fq_deconv_f32_supported, host arithmetic only; geometrically what fq_deconv2d_i8_supported takes, so that the
+ *   calibration and the resident plan agree on what the layer is): groups 1, dilation 1, 1 <= R, S <= 8, stride_h == stride_w in
+ *   1 .. 4, pad_h == pad_w with 0 <= pad < min(R, S), outpad_h == outpad_w < stride, Cin % 16 == 0, Cout % 4 == 0, an output
+ *   plane of at least 1 x 1, and x, y and w below 2^30 elements.  FQ_ERR_UNSUPPORTED for everything else: callers keep the
+ *   library there.  FQ_ERR_INVALID_ARG for a null or misaligned pointer, sizes below 1, both statistics at once, or a histogram
+ *   without its interval.  Nothing is launched in either case.  N == 0 is FQ_OK.
+ * Numerics (part of the contract: the plain, abs-max, histogram and ReLU forms see the same bits).  Per output:
+ *   acc = +0.0f
+ *   for r ascending with (oh + pad - r) % stride == 0:
+ *     for s ascending with (ow + pad - s) % stride == 0:
+ *       for c in 0 .. Cin-1:
+ *         acc = fmaf(w[c][k][r][s], x[n][c][(oh + pad - r)/stride][(ow + pad - s)/stride], acc)
+ *   y = acc + bias[k]                      (bias == NULL: acc + 0.0f)
+ *   A tap whose source pixel lies outside the image is the operand +0.0f.  It is never a value loaded from a neighbouring row
+ *   or plane.  An output with no tap at all (kernel smaller than stride) is +0.0f + bias[k].  There is no K split, no
+ *   workspace, and no float atomics other than the abs-max publish.  The value depends on neither N nor the tile, lane or code
+ *   path.  Image i of a batch gets the bits of the same image alone.  Exact zeros are not counted by the histogram.  The
+ *   abs-max ignores NaN. */
+int fq_deconv_f32_supported(int Cin, int Cout, int groups, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                            int outpad_h, int outpad_w, int dil_h, int dil_w, int H, int W);
+int fq_deconv_f32(const float* x, const float* wt, const float* bias, float* y, float* relu_out, int N, int Cin, int Hin, int Win,
+                  int Cout, int R, int S, int stride, int pad, int outpad, float* max_inout, const float* interval,
+                  int64_t* hist_row, fq_stream_t stream);
+
 /* The last 1x1 convolution of a residual block together with the `Eltwise` that consumes it and the ReLU behind that
  * (fabu_layer.py:5-11 called from the model the reference runs at pytorch_quantizer.py:288-296), calibration pass 1, in ONE
  * kernel:  v = conv1x1(x) + bias  (abs-max folded into *max_y; stored to y unless y is NULL),  s = v + res  (abs-max folded

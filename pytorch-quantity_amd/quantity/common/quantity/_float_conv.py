@@ -3,7 +3,7 @@ reference calls torch's Conv2d.forward -- pytorch_quantizer.py:288-296 inside th
 inside TestConv): 1x1 layers on fq_conv1x1_f32, R x S layers with zero padding (the 3x3 ones) on fq_conv_kxk_f32, the 7x7
 stride-2 stem on fq_conv_stem_f32 (csrc/) -- every convolution of a ResNet -- and, opt-in, the depthwise 3x3 / 5x5 layers of a
 separable network on fq_dwconv_f32 (FQ_OWN_DWCONV=1) and the grouped 1x1 / 3x3 layers of a ResNeXt-shaped one on fq_gconv_f32
-(FQ_OWN_GCONV=1), so that the calibration forward is deterministic
+(FQ_OWN_GCONV=1) and the nn.ConvTranspose2d layers of a decoder on fq_deconv_f32 (FQ_OWN_DECONV=1), so that the calibration forward is deterministic
 and never enters the convolution library (whose first-use solver search costs seconds in a fresh process).  Which call qualifies, the
 weights in the kernels' layout (cached on the module), the once-per-process check of every module against an independent
 implementation of the same fp32 mathematics, and the plain (no statistic) forward.  Shared by tools.Quantity (which adds the
@@ -19,7 +19,8 @@ import torch
 
 from . import _native
 
-__all__ = ["enabled", "depthwise_enabled", "grouped_enabled", "kind", "weight", "runner", "dw_reference", "g_reference", "verified", "plain", "call", "call_qd",
+__all__ = ["enabled", "depthwise_enabled", "grouped_enabled", "deconv_enabled", "kind", "weight", "runner", "dw_reference", "g_reference",
+           "dc_reference", "verified", "plain", "call", "call_qd",
            "call_linear_qd", "state", "is_verified", "is_off", "forget", "kernel_key", "own_convs", "TOL"]
 
 TOL = 1e-5                                      # |own - torch| <= TOL * (|W| * |x| + |b|): summation order only
@@ -112,6 +113,33 @@ def _g_ok(m, h, w):
             and m.out_channels * cgi * m.kernel_size[0] * m.kernel_size[1] < 2 ** 30)
 
 
+def deconv_enabled():
+    """FQ_OWN_DECONV=1 (read at call time; default off): nn.ConvTranspose2d layers run on fq_deconv_f32 instead of the library's
+    transposed convolution."""
+    return os.environ.get("FQ_OWN_DECONV", "0") == "1"
+
+
+def _dc_out_hw(m, h, w):
+    """Output plane of the nn.ConvTranspose2d m (dilation 1) on an h x w plane."""
+    return ((h - 1) * m.stride[0] - 2 * m.padding[0] + m.kernel_size[0] + m.output_padding[0],
+            (w - 1) * m.stride[1] - 2 * m.padding[1] + m.kernel_size[1] + m.output_padding[1])
+
+
+def _dc_ok(m, x):
+    """Does fq_deconv_f32 take the nn.ConvTranspose2d m on the input x?  Host arithmetic on the module alone (what
+    fq_deconv_f32_supported answers for the same numbers, plus what the C ABI cannot see: the bias, the padding mode, and the
+    2^30-element limits, which need the batch)."""
+    k, s, p, op = m.kernel_size, m.stride, m.padding, m.output_padding
+    if (m.bias is None or m.padding_mode != "zeros" or isinstance(p, str) or m.groups != 1 or tuple(m.dilation) != (1, 1)
+            or not (1 <= k[0] <= 8 and 1 <= k[1] <= 8) or s[0] != s[1] or not 1 <= s[0] <= 4 or p[0] != p[1]
+            or not 0 <= p[0] < min(k) or op[0] != op[1] or not 0 <= op[0] < s[0] or m.in_channels % 16 or m.out_channels % 4
+            or x.shape[1] != m.in_channels):
+        return False
+    ho, wo = _dc_out_hw(m, x.shape[2], x.shape[3])
+    return (ho >= 1 and wo >= 1 and x.numel() < 2 ** 30 and x.shape[0] * m.out_channels * ho * wo < 2 ** 30
+            and k[0] * k[1] * m.in_channels * m.out_channels < 2 ** 30)
+
+
 def _out_plane(m, h, w):
     """Output pixels per image and channel of the nn.Conv2d m (no dilation, integer padding) on an h x w plane; 0 where the
     padded plane is smaller than the kernel.  The kernels' hosts refuse 2^30 OUTPUT elements: the stem at stride 2 writes a
@@ -125,13 +153,20 @@ def _is_depthwise(m):
     return m.groups == m.in_channels
 
 
-def kind(m, x, wino=True, depthwise=None, grouped=None):
+def kind(m, x, wino=True, depthwise=None, grouped=None, deconv=None):
     """"c1" (fq_conv1x1_f32), "kxk" (fq_conv_kxk_f32), "wino" (fq_conv3x3_wino_f32: the Winograd form of the stride-1 3x3
     layers; wino=False or FQ_CONV_WINO=0 keeps them on "kxk"), "stem" (fq_conv_stem_f32), "dw" (fq_dwconv_f32: a depthwise 3x3 /
     5x5 layer, only with depthwise=True; None reads FQ_OWN_DWCONV), "g" (fq_gconv_f32: a grouped 1x1 / 3x3 layer with 4 .. 64
     channels per group, only with grouped=True; None reads FQ_OWN_GCONV) or None: which own kernel takes this call of the nn.Conv2d m.
     Every kind has the plain, the statistic and the QuanDequan form, so TestConv's two ways through a layer (fused with
-    QuanDequan, or not when somebody watches the module) see the same sums."""
+    QuanDequan, or not when somebody watches the module) see the same sums.
+    "dc" (fq_deconv_f32) for a `type(m) is nn.ConvTranspose2d` that kernel takes, only with deconv=True (None reads
+    FQ_OWN_DECONV): the plain, statistic and ReLU forms, no QuanDequan one."""
+    if isinstance(m, torch.nn.modules.conv._ConvTransposeNd):  # (a subclass may override forward: never taken, and never an nn.Conv2d kind)
+        if (type(m) is not torch.nn.ConvTranspose2d or not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or m.weight.dtype != torch.float32 or is_off(m)
+                or x.dim() != 4 or not x.is_contiguous() or not (deconv_enabled() if deconv is None else deconv)):
+            return None
+        return "dc" if _dc_ok(m, x) else None
     if (not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or m.weight.dtype != torch.float32 or m.bias is None
             or is_off(m) or m.dilation != (1, 1) or m.stride[0] != m.stride[1] or x.dim() != 4
             or not x.is_contiguous() or isinstance(m.padding, str) or m.padding[0] != m.padding[1] or m.padding_mode != "zeros"
@@ -167,7 +202,8 @@ def kind(m, x, wino=True, depthwise=None, grouped=None):
 def weight(m, k):
     """The weights in the layout the kernel reads (Wt [Cin][Cout] / the packed stem matrix / the transformed Winograd
     weights), one entry per kind, rebuilt when the parameter was written to or replaced.  "dw" and "g": the parameter itself
-    ([C][1][R][S] and [K][C / groups][R][S] are the layouts fq_dwconv_f32 and fq_gconv_f32 read)."""
+    ([C][1][R][S] and [K][C / groups][R][S] are the layouts fq_dwconv_f32 and fq_gconv_f32 read).  "dc": the transposed layer's
+    [Cin][Cout][R][S] as [(r*S + s)*Cin + c][Cout], fq_conv_kxk_f32's layout."""
     w = m.weight
     if k == "dw" or k == "g":
         return w.detach() if w.is_contiguous() else w.detach().contiguous()
@@ -177,6 +213,7 @@ def weight(m, k):
     if cached is None or cached[0] != tag:
         sb = _uses_sb(m, k)
         packed = (_native.pack_sb_weight(w) if sb                # (opt-in: the split-bf16 form of the 1x1 kernels takes this pack)
+                  else w.detach().permute(2, 3, 0, 1).reshape(w.shape[2] * w.shape[3] * w.shape[0], w.shape[1]).contiguous() if k == "dc"
                   else w.detach().view(w.shape[0], w.shape[1]).t().contiguous() if k == "c1"
                   else _native.pack_kxk_weight(w) if k == "kxk"
                   else _native.pack_wino_weight(w) if k == "wino" else _native.pack_stem_weight(w))
@@ -198,6 +235,8 @@ def runner(m, k, x):
         return lambda **kw: _native.dwconv_f32(x, wq, m.bias, m.kernel_size, s, m.padding[0], **kw)
     if k == "g":
         return lambda **kw: _native.gconv_f32(x, wq, m.bias, m.groups, m.kernel_size, s, m.padding[0], **kw)
+    if k == "dc":
+        return lambda **kw: _native.deconv_f32(x, wq, m.bias, m.kernel_size, s, m.padding[0], m.output_padding[0], **kw)
     return lambda **kw: _native.conv_stem_f32(x, wq, m.bias, m.out_channels, m.kernel_size, s, m.padding[0], **kw)
 
 
@@ -228,6 +267,26 @@ def g_reference(x, w, bias, groups, kernel, stride, padding):
     return ref, bound
 
 
+def dc_reference(x, w, bias, kernel, stride, padding, output_padding):
+    """(reference, bound) of a transposed convolution (groups 1, dilation 1) WITHOUT the convolution library, on CPU or CUDA
+    tensors: one matmul of W [Cin, Cout, R, S] seen as [Cout * R * S, Cin] with x seen as [n, Cin, H * W] -- every input pixel's
+    contribution to each (output channel, tap) --, F.fold to scatter them (col2im: sums of at most ceil(R / stride) *
+    ceil(S / stride) columns per output), then the bias -- the same fp32 mathematics as fq_deconv_f32 in another order; bound is
+    the same expression with absolute values, [n, Cout, Ho, Wo] both."""
+    n, cin, h, wd = x.shape
+    cout = w.shape[1]
+    ho = (h - 1) * stride[0] - 2 * padding[0] + kernel[0] + output_padding[0]
+    wo = (wd - 1) * stride[1] - 2 * padding[1] + kernel[1] + output_padding[1]
+    wv = w.reshape(cin, cout * kernel[0] * kernel[1]).t()
+    xv = x.reshape(n, cin, h * wd)
+
+    def fold(cols):
+        return torch.nn.functional.fold(cols, (ho, wo), kernel, padding=padding, stride=stride)
+    ref = fold(torch.matmul(wv, xv)) + bias.view(1, -1, 1, 1)
+    bound = fold(torch.matmul(wv.abs(), xv.abs())) + bias.abs().view(1, -1, 1, 1)
+    return ref, bound
+
+
 def verified(m, run, x, k=None):
     """Once per process, module and kernel (kernel_key(m, k); k = None: once per module, whatever kernel `run` is): the own
     kernel against torch on this very input.  Returns torch's result when the module fails (and marks it: it keeps the library
@@ -244,19 +303,30 @@ def verified(m, run, x, k=None):
     #  full-size temporary of `own.abs().max()` were allocator growth in a fresh process, most of the 0.16 s these checks cost a
     #  one-shot calibration of ResNet-50; round 5)
     n_all = int(x.shape[0])
-    if m.kernel_size == (1, 1) and m.groups == 1:               # 1x1: a GEMM (rocBLAS through torch.matmul), 16 + 16 images
+    rs = m.kernel_size[0] * m.kernel_size[1]
+    library = torch.nn.Conv2d.forward                           # what a module that fails keeps
+    if type(m) is torch.nn.ConvTranspose2d:                     # matmul + fold: Cout * R * S columns per input pixel, 8 + 8 images
+        per = max(1, min(8, (1 << 27) // max(x[0].numel() // m.in_channels * m.out_channels * rs, 1)))
+        library, w2 = torch.nn.ConvTranspose2d.forward, None
+    elif m.kernel_size == (1, 1) and m.groups == 1:             # 1x1: a GEMM (rocBLAS through torch.matmul), 16 + 16 images
         per = 16
     else:                                                       # R x S (the stem, depthwise and grouped layers included): im2col (unfold) + GEMM, 8 + 8 images
-        per = max(1, min(8, (1 << 27) // max(x[0].numel() * m.kernel_size[0] * m.kernel_size[1], 1)))
+        per = max(1, min(8, (1 << 27) // max(x[0].numel() * rs, 1)))
     groups = [(0, n_all)] if n_all <= 2 * per else [(0, per), (n_all - per, n_all)]
-    w2 = m.weight.view(m.out_channels, -1)
+    if library is torch.nn.Conv2d.forward:
+        w2 = m.weight.view(m.out_channels, -1)
     scratch = torch.zeros(1, dtype=torch.float32, device=x.device)
     own = run(max_dev=scratch, row=0)
     # (vector_norm(inf) = max |.| in one pass, no temporary; NaN propagates as in abs().max())
     ok = scratch[0] == torch.linalg.vector_norm(own.reshape(-1), float("inf"))
     for lo, hi in groups:
         xh = x[lo:hi]
-        if m.groups != 1:                                       # depthwise: no GEMM to lean on, the products summed per channel
+        if w2 is None:                                          # transposed: one GEMM, then col2im (F.fold)
+            ref, bound = dc_reference(xh, m.weight, m.bias, m.kernel_size, m.stride, m.padding, m.output_padding)
+            ok = ok & ((own[lo:hi] - ref).abs() <= TOL * bound).all()
+            del ref, bound
+            continue
+        if m.groups != 1:                                     # depthwise: no GEMM to lean on, the products summed per channel
             if _is_depthwise(m):
                 ref, bound = dw_reference(xh, m.weight, m.bias, m.kernel_size, m.stride, m.padding)
             else:                                               # grouped: one batched GEMM over the groups
@@ -278,7 +348,7 @@ def verified(m, run, x, k=None):
     # (one device-side verdict, one host synchronisation: the first forward of a process checks 53 modules)
     if not bool(ok):
         state(m)["off"] = True
-        return torch.nn.Conv2d.forward(m, x)
+        return library(m, x)
     state(m).setdefault("verified", set()).add(kernel_key(m, k))
     return None
 
@@ -354,7 +424,7 @@ def call_qd(m, x, bit, bitwidth):
     if not (enabled() and not torch.is_grad_enabled() and "forward" not in m.__dict__) or _hooked(m):
         return None
     k = kind(m, x)
-    if k is None:
+    if k is None or k == "dc":                                  # (fq_deconv_f32 has no QuanDequan form)
         return None
     run = runner(m, k, x)
     if not is_verified(m, k) and verified(m, run, x, k) is not None:

@@ -258,6 +258,10 @@ def lib():
     L.fq_gconv_f32.argtypes = [vp, vp, vp, vp, vp] + [ci] * 10 + [vp, vp, vp, vp]
     L.fq_gconv_qd_f32.restype = ci
     L.fq_gconv_qd_f32.argtypes = [vp, vp, vp, vp] + [ci] * 12 + [vp]
+    L.fq_deconv_f32_supported.restype = ci
+    L.fq_deconv_f32_supported.argtypes = [ci] * 15
+    L.fq_deconv_f32.restype = ci
+    L.fq_deconv_f32.argtypes = [vp, vp, vp, vp, vp] + [ci] * 10 + [vp, vp, vp, vp]
     L.fq_concat_i8_nhwc_supported.restype = ci
     L.fq_concat_i8_nhwc_supported.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci), ci]
     L.fq_concat_i8_nhwc.restype = ci
@@ -853,6 +857,31 @@ def gconv_f32(x, w, bias, groups, kernel, stride, pad, max_dev=None, interval_de
     shape = (N, K, (H + 2 * pd - R) // st + 1, (W + 2 * pd - S) // st + 1)
     return _conv_f32("fq_gconv_f32", x, w.data_ptr(), bias, shape, (N, C, H, W, K, G, R, S, st, pd), max_dev, interval_dev, hist_dev,
                      row, relu_out, out, qd)
+
+
+def deconv_f32_supported(cin, cout, groups, kernel, stride, pad, outpad, dilation, h, w):
+    """fq_deconv_f32_supported: does fq_deconv_f32 take this transposed geometry (cin -> cout channels on an h x w input plane)?
+    kernel, stride, pad, outpad, dilation: (h, w) pairs."""
+    return bool(lib().fq_deconv_f32_supported(int(cin), int(cout), int(groups), int(kernel[0]), int(kernel[1]), int(stride[0]),
+                                              int(stride[1]), int(pad[0]), int(pad[1]), int(outpad[0]), int(outpad[1]),
+                                              int(dilation[0]), int(dilation[1]), int(h), int(w)))
+
+
+def deconv_f32(x, wt, bias, kernel, stride, pad, outpad, max_dev=None, interval_dev=None, hist_dev=None, row=None, relu_out=None,
+               out=None):
+    """fq_deconv_f32: the float transposed convolution (groups 1, dilation 1, zero padding `pad`, output padding `outpad`) of
+    x [N, Cin, H, W] with the weights wt [(r*S + s)*Cin + c][Cout] = W[c][co][r][s], i.e.
+    w.permute(2, 3, 0, 1).reshape(R*S*Cin, Cout).contiguous() of the module's [Cin, Cout, R, S]; statistics / relu_out / out as in
+    conv_kxk_f32.  Returns y."""
+    _need_cuda(x, torch.float32, "fq_deconv_f32")
+    _need_cuda(wt, torch.float32, "fq_deconv_f32")
+    R, S = int(kernel[0]), int(kernel[1])
+    assert x.dim() == 4 and x.is_contiguous() and wt.dim() == 2 and wt.is_contiguous() and wt.shape[0] == R * S * x.shape[1]
+    N, Cin, H, W = x.shape
+    Cout, st, pd, op = int(wt.shape[1]), int(stride), int(pad), int(outpad)
+    shape = (N, Cout, (H - 1) * st - 2 * pd + R + op, (W - 1) * st - 2 * pd + S + op)
+    return _conv_f32("fq_deconv_f32", x, wt.data_ptr(), bias, shape, (N, Cin, H, W, Cout, R, S, st, pd, op), max_dev, interval_dev,
+                     hist_dev, row, relu_out, out, None)
 
 
 def conv_wino_enabled():

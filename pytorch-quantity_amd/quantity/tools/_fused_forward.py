@@ -16,6 +16,9 @@ same call fires -- and each fusion is a small state machine over them.  States l
 | | deferred not empty | the forward ends | RuntimeError: the model left the path the probe saw (`_forward_with_stats`) |
 | the proofs | poison = _DeferralProbe, mode learn / poison | two probe forwards before the first batch | `_probe_forward`, `_prove_deferral` (NaN poisoning + the keeper scan, `_hook_state._DeferralProbe`) |
 
+With Quantity.own_deconv (off by default) an nn.ConvTranspose2d that fq_deconv_f32 takes goes through the first row as kind "dc"
+(and the two conv -> ReLU rows behind an nn.ReLU); it is never deferred into an Eltwise.
+
 An out-of-place nn.ReLU6 takes the two conv -> ReLU rows as well when Quantity.fuse_relu6 is on (off by default), behind the own
 1x1 / R x S / depthwise convolutions only: the producer is told which of the two activations to write (`act=6.0`).
 
@@ -103,6 +106,39 @@ class _FusedForward(object):
                 return y
             m.forward = forward
             patched.append(m)
+        # own_deconv: every nn.ConvTranspose2d with a bias that fq_deconv_f32 takes leaves its work to its hook in the same way
+        # (kind "dc": never deferred into an Eltwise, an nn.ReLU behind it served, an nn.ReLU6 left to torch); everything else --
+        # and every such module with the switch off, which is then not patched at all -- is torch's own forward
+        if self.own_deconv and self.own_conv1x1 and "ConvTranspose2d" in self._all_op_type and "ConvTranspose2d" in self._cared_op_type:
+            for m in model.modules():
+                if type(m) is not torch.nn.ConvTranspose2d or m.bias is None or m.padding_mode != "zeros" or "forward" in m.__dict__:
+                    continue
+
+                def forward(x, output_size=None, m=m):
+                    lib = torch.nn.ConvTranspose2d.forward
+                    if (output_size is not None or not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32
+                            or m.weight.dtype != torch.float32 or torch.is_grad_enabled()):
+                        return lib(m, x, output_size)
+                    if ctl.own_plain:                    # per-channel calibration: the convolution only, statistics by its hooks
+                        own = _float_conv.kind(m, x, deconv=True)
+                        if own is None:
+                            return lib(m, x)
+                        y = _float_conv.plain(m, own, x, check=ctl.own_plain != "unchecked")
+                        if ctl.poison is not None:
+                            y = ctl.poison.conv_done(m, y)
+                        return y
+                    if ctl.fuse_collector is None or ctl.fuse_off:
+                        return lib(m, x)
+                    if ctl.fuse_stat == "hist" and m not in ctl.fuse_verified:
+                        return lib(m, x)                 # pass 2 fuses verified modules only
+                    own = _float_conv.kind(m, x, deconv=True)       # (None for a module that failed its check)
+                    if own is None:
+                        return lib(m, x)
+                    ctl.fuse_bias = (m, (own, x))        # the hook of this very call runs the whole convolution
+                    ho, wo = _float_conv._dc_out_hw(m, x.shape[2], x.shape[3])
+                    return torch.empty((x.shape[0], m.out_channels, ho, wo), dtype=torch.float32, device=x.device)
+                m.forward = forward
+                patched.append(m)
         if "Eltwise" in self._all_op_type and "Eltwise" in self._cared_op_type:
             from common.quantity.fabu_layer import Eltwise
             for m in model.modules():
@@ -508,7 +544,7 @@ class _FusedForward(object):
         cared = set(self.net_info.keys())
         for elt, conv in (probe.pairs.items() if self.fuse_conv_add else ()):
             relu = ctl.relu_after.get(elt)
-            if (type(relu) is not torch.nn.ReLU or probe.keys.get(conv) not in cared or probe.keys.get(elt) not in cared
+            if (type(relu) is not torch.nn.ReLU or type(conv) is not torch.nn.Conv2d or probe.keys.get(conv) not in cared or probe.keys.get(elt) not in cared
                     or conv.kernel_size != (1, 1) or conv.padding != (0, 0)
                     or not _native.conv1x1_add_f32_supported(conv.in_channels, conv.out_channels)
                     or not (self._only_our_hook(conv) and self._only_our_hook(elt) and self._only_our_hook(relu))

@@ -124,6 +124,10 @@ class Quantity(_FusedForward, _FileInputs):
     # Opt-in (FQ_OWN_GCONV=1): the grouped 1x1 / 3x3 layers of a ResNeXt-shaped network (4 .. 64 channels per group) run on
     # fq_gconv_f32 in the same way
     own_grouped = _float_conv.grouped_enabled()
+    # Opt-in (FQ_OWN_DECONV=1): the nn.ConvTranspose2d layers of a decoder (groups 1, dilation 1, kernels up to 8, strides up to 4,
+    # input channels a multiple of 16) run on fq_deconv_f32 in the same way, instead of the library's transposed convolution and
+    # a separate statistic pass over their output
+    own_deconv = _float_conv.deconv_enabled()
     # A residual sum both of whose operands pass 2's cache keeps anyway (conv3's output; the shortcut = the previous block's ReLU
     # output or the projection) is not written by pass 1: the cache keeps the shortcut in the sum's place and pass 2 histograms
     # (conv3 output, conv3 output + shortcut) in one pass over the pair (fq_hist2048_pair_seg).  Same integers.
