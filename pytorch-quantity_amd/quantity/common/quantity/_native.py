@@ -995,6 +995,15 @@ def _out_like(x, out):
     return out
 
 
+def _out_i8(shape, device, out, entry):
+    """A fresh int8 tensor of `shape`, or the caller's `out` checked to be one: an int8 CUDA tensor of that shape, contiguous."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.int8, device=device)
+    _need_cuda(out, torch.int8, entry)
+    assert tuple(out.shape) == tuple(shape) and out.is_contiguous()
+    return out
+
+
 def _unary(fn_name, x, ints, out):
     _need_cuda(x, torch.float32, fn_name)
     xc = x if x.is_contiguous() else x.contiguous()
@@ -1627,12 +1636,7 @@ def _concat_operands(entry, struct, srcs, out, dtypes=(torch.int8,)):
         raise FqError("%s: no operand" % entry)
     N, H, W = plane
     cpad = pad16(total)
-    if out is None:
-        out = torch.empty(N, H, W, cpad, dtype=torch.int8, device=srcs[0][0].device)
-    else:
-        _need_cuda(out, torch.int8, entry)
-        assert tuple(out.shape) == (N, H, W, cpad) and out.is_contiguous()
-    return arr, n, out, cpad, N, H, W
+    return arr, n, _out_i8((N, H, W, cpad), srcs[0][0].device, out, entry), cpad, N, H, W
 
 
 def concat_i8_nhwc(srcs, relu, out=None):
@@ -1696,11 +1700,7 @@ def shuffle_i8_nhwc(x_q, c_in, c_off, c, groups, out=None):
     if int(c_off) + int(c) > int(c_in):
         raise FqError("fq_shuffle_i8_nhwc: channels [%d, %d) of a source of %d" % (c_off, int(c_off) + int(c), c_in))
     cpad = pad16(c)
-    if out is None:
-        out = torch.empty(N, H, W, cpad, dtype=torch.int8, device=x_q.device)
-    else:
-        _need_cuda(out, torch.int8, "fq_shuffle_i8_nhwc")
-        assert tuple(out.shape) == (N, H, W, cpad) and out.is_contiguous()
+    out = _out_i8((N, H, W, cpad), x_q.device, out, "fq_shuffle_i8_nhwc")
     _check(lib().fq_shuffle_i8_nhwc(x_q.data_ptr(), cpad_in, int(c_off), out.data_ptr(), cpad, int(c), int(groups), N, H, W,
                                     _stream(out)), "fq_shuffle_i8_nhwc")
     return out
@@ -1726,11 +1726,8 @@ def act_lut_i8_nhwc(x_q, c, table, out=None):
     N, H, W, cpad = (int(v) for v in x_q.shape)
     if cpad != pad16(c):
         raise FqError("fq_act_lut_i8_nhwc: an activation of %d channels is stored as %d, got %d" % (c, pad16(c), cpad))
-    if out is None:
-        out = torch.empty_like(x_q)
-    else:
-        _need_cuda(out, torch.int8, "fq_act_lut_i8_nhwc")
-        assert tuple(out.shape) == (N, H, W, cpad) and out.is_contiguous() and out.data_ptr() != x_q.data_ptr()
+    assert not isinstance(out, torch.Tensor) or out.data_ptr() != x_q.data_ptr()      # (anything else: _out_i8 allocates or raises)
+    out = _out_i8((N, H, W, cpad), x_q.device, out, "fq_act_lut_i8_nhwc")
     _check(lib().fq_act_lut_i8_nhwc(x_q.data_ptr(), out.data_ptr(), table.data_ptr(), N, H, W, int(c), cpad, _stream(out)),
            "fq_act_lut_i8_nhwc")
     return out
@@ -1779,42 +1776,43 @@ def pixel_shuffle_i8_nhwc(x, C, r, inverse, out=None):
         raise FqError("%s: a %d x %d plane is not divisible by r = %d" % (entry, Hx, Wx, r))
     H, W = (Hx // r, Wx // r) if inverse else (Hx, Wx)
     shape = (N, H, W, pad16(C * r * r)) if inverse else (N, H * r, W * r, pad16(C))
-    if out is None:
-        out = torch.empty(shape, dtype=torch.int8, device=x.device)
-    else:
-        _need_cuda(out, torch.int8, entry)
-        assert tuple(out.shape) == shape and out.is_contiguous()
+    out = _out_i8(shape, x.device, out, entry)
     _check(lib().fq_pixel_shuffle_i8_nhwc(x.data_ptr(), cpad_in, out.data_ptr(), shape[3], C, r, inverse, N, H, W, _stream(out)), entry)
+    return out
+
+
+def _avgpool_supported(entry, kernel, stride, padding, shift):
+    return bool(getattr(lib(), entry + "_supported")(int(kernel[0]), int(kernel[1]), int(stride[0]), int(stride[1]), int(padding[0]),
+                                                     int(padding[1]), int(shift)))
+
+
+def _avgpool_nhwc(entry, dtype, q, channels, kernel, stride, padding, count_include_pad, shift, relu, out):
+    """The body of both windowed average pools: `entry` on a source of `dtype`."""
+    _need_cuda(q, dtype, entry)
+    assert q.dim() == 4 and q.is_contiguous()
+    N, H, W, cpad = (int(v) for v in q.shape)
+    P = (H + 2 * int(padding[0]) - int(kernel[0])) // int(stride[0]) + 1
+    Q = (W + 2 * int(padding[1]) - int(kernel[1])) // int(stride[1]) + 1
+    if P < 1 or Q < 1:
+        raise FqError("%s: the window %s does not fit the padded %d x %d plane" % (entry, tuple(kernel), H, W))
+    out = _out_i8((N, P, Q, cpad), q.device, out, entry)
+    _check(getattr(lib(), entry)(q.data_ptr(), out.data_ptr(), N, H, W, int(channels), cpad, int(kernel[0]), int(kernel[1]),
+                                 int(stride[0]), int(stride[1]), int(padding[0]), int(padding[1]), 1 if count_include_pad else 0,
+                                 int(shift), 1 if relu else 0, _stream(out)), entry)
     return out
 
 
 def avgpool_supported(kernel, stride, padding, shift):
     """True when fq_avgpool_i8_nhwc takes this window, stride, padding and shift = consumer bit - source grid (include/fq.h):
     2 * padding <= kernel, at most 64 taps, |shift| <= 8.  Pure host arithmetic (no GPU needed)."""
-    return bool(lib().fq_avgpool_i8_nhwc_supported(int(kernel[0]), int(kernel[1]), int(stride[0]), int(stride[1]), int(padding[0]),
-                                                   int(padding[1]), int(shift)))
+    return _avgpool_supported("fq_avgpool_i8_nhwc", kernel, stride, padding, shift)
 
 
 def avgpool_i8_nhwc(q, channels, kernel, stride, padding, count_include_pad, shift, relu, out=None):
     """fq_avgpool_i8_nhwc: nn.AvgPool2d (floor mode) on int8 [N, H, W, Cpad] with `channels` real channels, re-quantised by
     2^shift for the convolution behind it, max(., 0) applied when relu -> int8 [N, P, Q, Cpad], padding channels zero.  `out`:
     write there instead (that shape, dense, 16-byte aligned).  Launches on the current stream and does not synchronise."""
-    _need_cuda(q, torch.int8, "fq_avgpool_i8_nhwc")
-    assert q.dim() == 4 and q.is_contiguous()
-    N, H, W, cpad = (int(v) for v in q.shape)
-    P = (H + 2 * int(padding[0]) - int(kernel[0])) // int(stride[0]) + 1
-    Q = (W + 2 * int(padding[1]) - int(kernel[1])) // int(stride[1]) + 1
-    if P < 1 or Q < 1:
-        raise FqError("fq_avgpool_i8_nhwc: the window %s does not fit the padded %d x %d plane" % (tuple(kernel), H, W))
-    if out is None:
-        out = torch.empty(N, P, Q, cpad, dtype=torch.int8, device=q.device)
-    else:
-        _need_cuda(out, torch.int8, "fq_avgpool_i8_nhwc")
-        assert tuple(out.shape) == (N, P, Q, cpad) and out.is_contiguous()
-    _check(lib().fq_avgpool_i8_nhwc(q.data_ptr(), out.data_ptr(), N, H, W, int(channels), cpad, int(kernel[0]), int(kernel[1]),
-                                    int(stride[0]), int(stride[1]), int(padding[0]), int(padding[1]), 1 if count_include_pad else 0,
-                                    int(shift), 1 if relu else 0, _stream(out)), "fq_avgpool_i8_nhwc")
-    return out
+    return _avgpool_nhwc("fq_avgpool_i8_nhwc", torch.int8, q, channels, kernel, stride, padding, count_include_pad, shift, relu, out)
 
 
 def upsample_bilinear_supported(up, shift):
@@ -1832,11 +1830,7 @@ def upsample_bilinear_i8_nhwc(q, channels, up, shift, relu, out=None):
     assert q.dim() == 4 and q.is_contiguous()
     N, H, W, cpad = (int(v) for v in q.shape)
     up = int(up)
-    if out is None:
-        out = torch.empty(N, up * H, up * W, cpad, dtype=torch.int8, device=q.device)
-    else:
-        _need_cuda(out, torch.int8, "fq_upsample_bilinear_i8_nhwc")
-        assert tuple(out.shape) == (N, up * H, up * W, cpad) and out.is_contiguous()
+    out = _out_i8((N, up * H, up * W, cpad), q.device, out, "fq_upsample_bilinear_i8_nhwc")
     _check(lib().fq_upsample_bilinear_i8_nhwc(q.data_ptr(), out.data_ptr(), N, H, W, int(channels), cpad, up, int(shift),
                                               1 if relu else 0, _stream(out)), "fq_upsample_bilinear_i8_nhwc")
     return out
@@ -1845,8 +1839,7 @@ def upsample_bilinear_i8_nhwc(q, channels, up, shift, relu, out=None):
 def avgpool_i16_supported(kernel, stride, padding, shift):
     """True when fq_avgpool_i16_nhwc takes this window, stride, padding and shift = consumer bit - grid of the sum (include/fq.h):
     2 * padding <= kernel, at most 64 taps, |shift| <= 8.  Pure host arithmetic (no GPU needed)."""
-    return bool(lib().fq_avgpool_i16_nhwc_supported(int(kernel[0]), int(kernel[1]), int(stride[0]), int(stride[1]), int(padding[0]),
-                                                    int(padding[1]), int(shift)))
+    return _avgpool_supported("fq_avgpool_i16_nhwc", kernel, stride, padding, shift)
 
 
 def avgpool_i16_nhwc(q16, channels, kernel, stride, padding, count_include_pad, shift, relu, out=None):
@@ -1854,22 +1847,7 @@ def avgpool_i16_nhwc(q16, channels, kernel, stride, padding, count_include_pad, 
     channels, re-quantised by 2^shift for the convolution behind it, max(., 0) applied when relu -> int8 [N, P, Q, Cpad], padding
     channels zero.  `out`: write there instead (that shape, dense, 16-byte aligned).  Launches on the current stream and does
     not synchronise."""
-    _need_cuda(q16, torch.int16, "fq_avgpool_i16_nhwc")
-    assert q16.dim() == 4 and q16.is_contiguous()
-    N, H, W, cpad = (int(v) for v in q16.shape)
-    P = (H + 2 * int(padding[0]) - int(kernel[0])) // int(stride[0]) + 1
-    Q = (W + 2 * int(padding[1]) - int(kernel[1])) // int(stride[1]) + 1
-    if P < 1 or Q < 1:
-        raise FqError("fq_avgpool_i16_nhwc: the window %s does not fit the padded %d x %d plane" % (tuple(kernel), H, W))
-    if out is None:
-        out = torch.empty(N, P, Q, cpad, dtype=torch.int8, device=q16.device)
-    else:
-        _need_cuda(out, torch.int8, "fq_avgpool_i16_nhwc")
-        assert tuple(out.shape) == (N, P, Q, cpad) and out.is_contiguous()
-    _check(lib().fq_avgpool_i16_nhwc(q16.data_ptr(), out.data_ptr(), N, H, W, int(channels), cpad, int(kernel[0]), int(kernel[1]),
-                                     int(stride[0]), int(stride[1]), int(padding[0]), int(padding[1]), 1 if count_include_pad else 0,
-                                     int(shift), 1 if relu else 0, _stream(out)), "fq_avgpool_i16_nhwc")
-    return out
+    return _avgpool_nhwc("fq_avgpool_i16_nhwc", torch.int16, q16, channels, kernel, stride, padding, count_include_pad, shift, relu, out)
 
 
 def avgpool_global_nhwc(q, g, channels):
@@ -1952,12 +1930,7 @@ def deconv2d_i8_resident(xq, wq, qbias, C, kernel, stride, padding, output_paddi
     P, Q = _out_hw_deconv(H, W, R, S, stride, padding, output_padding)
     if P <= 0 or Q <= 0:
         raise FqError(entry + ": the output plane is empty")
-    if out is None:
-        q = torch.empty(N, P, Q, kpad, dtype=torch.int8, device=xq.device)
-    else:
-        _need_cuda(out, torch.int8, entry)
-        assert tuple(out.shape) == (N, P, Q, kpad) and out.is_contiguous()
-        q = out
+    q = _out_i8((N, P, Q, kpad), xq.device, out, entry)
     _conv_i8(entry, xq, wq, qbias, rs, K, (q.data_ptr(), cpad, kpad),
              (N, H, W, C, K, R, S, stride[0], stride[1], padding[0], padding[1], output_padding[0], output_padding[1]), (int(ob),),
              (relu, clip))

@@ -1,5 +1,5 @@
 // Host check of the address arithmetic of the resident add with a nearest-upsampled operand (csrc/fq_add_up_geom.h; the pattern of
-// avgpool_i16_geom_check.cpp): every lane of every launch loads inside both sources, every access is 16-byte aligned, the coarse
+// avgpool_geom_check.cpp): every lane of every launch loads inside both sources, every access is 16-byte aligned, the coarse
 // pixel of an output pixel (h, w) is (h / up, w / up) at the same channels and image, the digit-wise walk (add_up_next) lands on
 // the item the flat index names, and every output element is written exactly once.
 //   c++ -O2 -std=c++17 -o add_up_geom_check scripts/add_up_geom_check.cpp

@@ -1,16 +1,20 @@
-// Host check of the windowed int8 average pool's address arithmetic (csrc/fq_avgpool_i8_geom.h): every lane of every launch loads
-// inside the source (16 bytes, aligned), the taps of an output are exactly window ∩ image, each once, the divisor is the rule's,
-// the channel mask keeps the real channels only, and every output chunk is written exactly once and inside the output.
+// Host check of the windowed average pool's address arithmetic (csrc/fq_avgpool_i8_geom.h) for both of its sources, int8 and the
+// int16 NewAdd sum: every lane of every launch loads inside the source (16 bytes, aligned) at the tap's address, the taps of an
+// output are exactly window ∩ image, each once, the divisor is the rule's, the channel mask keeps the real channels only, every
+// item is stored at its own address and every output byte is written exactly once and inside the output.
 //   c++ -O2 -std=c++17 -o avgpool_geom_check scripts/avgpool_geom_check.cpp
-//   ./avgpool_geom_check                                  the built-in shape list
-//   ./avgpool_geom_check N,H,W,C,kh,kw,sh,sw,ph,pw ...    these cases instead; tests pass the GPU tests' list
-//   ./avgpool_geom_check window=T <cases>                 a size-limit row (10^8 chunks): only the first and the last T output chunks
+//   ./avgpool_geom_check                                  the built-in shape list, walked for both sources
+//   ./avgpool_geom_check [src=i8|i16] N,H,W,C,kh,kw,sh,sw,ph,pw ...
+//                                                         these cases instead, for one source (default i8); tests pass the GPU
+//                                                         tests' list
+//   ./avgpool_geom_check [src=...] window=T <cases>       a size-limit row (10^8 items): only the first and the last T output items
 //                                                         are walked, by the lanes and in the order the kernel visits them (neither
 //                                                         tensor reaches 2^31 bytes: there is no boundary between)
-// Every case is walked with and without count_include_pad.  One line per case: "case ...: P p Q q chunks n blocks b", then
-// "ok, <loads> loads checked".  Exit status 1 at the first violation.
-// The walk below is the kernel's own: same launch size, same lane -> chunk stepping by the grid size, the same window cut and
-// the same offset stepping along a window row, on a model of memory in which each byte is its own address.
+// Every case is walked with and without count_include_pad.  One line per case: "case ...: P p Q q chunks n blocks b" ("items" for
+// src=i16), then "ok, <loads> loads checked".  Exit status 1 at the first violation.
+// The walk below is the kernel's own: same launch size, same lane -> item stepping by the grid size, the same window cut and the
+// same offset stepping along a window row, on a model of memory in which each byte is its own address: a load is 16 byte
+// addresses of the source, a store Src::kOutBytes byte addresses of the output, and each output byte counts its writes.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,40 +34,38 @@ static void fail(const char* what, const Case& c, int cip) {
     exit(1);
 }
 
-static unsigned long g_window = 0;          // window=T: chunks [T, nchunks - T) are skipped
+static unsigned long g_window = 0;          // window=T: items [T, nchunks - T) are skipped
 
+template <class Src>
 static long run(const Case& c, int cip, bool print) {
     if (c.N < 1 || c.H < 1 || c.W < 1 || c.C < 1 || c.kh < 1 || c.kw < 1 || c.sh < 1 || c.sw < 1 || c.ph < 0 || c.pw < 0 ||
         2 * c.ph > c.kh || 2 * c.pw > c.kw || c.kh * c.kw > kAvgMaxTaps)
         fail("not a case the entry point launches", c, cip);
-    AvgGeom g;
-    g.N = c.N; g.H = c.H; g.W = c.W; g.C = c.C;
-    g.Cpad = (c.C + 15) / 16 * 16;
-    g.CH = g.Cpad / 16;
-    g.P = avg_out_size(c.H, c.kh, c.sh, c.ph);
-    g.Q = avg_out_size(c.W, c.kw, c.sw, c.pw);
-    g.kh = c.kh; g.kw = c.kw; g.sh = c.sh; g.sw = c.sw; g.ph = c.ph; g.pw = c.pw;
-    g.cip = cip;
-    if (g.P < 1 || g.Q < 1) fail("empty output", c, cip);
-    if (g.P != (c.H + 2 * c.ph - c.kh) / c.sh + 1 || g.Q != (c.W + 2 * c.pw - c.kw) / c.sw + 1) fail("output size is not floor mode's", c, cip);
-    const long x_bytes = (long)c.N * c.H * c.W * g.Cpad, y_bytes = (long)c.N * g.P * g.Q * g.Cpad;
+    const int Cpad = (c.C + 15) / 16 * 16;
+    if (c.H + 2 * c.ph < c.kh || c.W + 2 * c.pw < c.kw) fail("empty output", c, cip);
+    const long P = (c.H + 2 * c.ph - c.kh) / c.sh + 1, Q = (c.W + 2 * c.pw - c.kw) / c.sw + 1;
+    const long x_bytes = (long)Src::kBytes * c.N * c.H * c.W * Cpad, y_bytes = c.N * P * Q * Cpad;
     if (x_bytes >= 0x7fffffffL || y_bytes >= 0x7fffffffL) fail("tensor too large for the entry point", c, cip);
-    g.nchunks = (unsigned)(y_bytes / 16);
+    const AvgGeom g = avg_geom<Src>(c.N, c.H, c.W, c.C, Cpad, c.kh, c.kw, c.sh, c.sw, c.ph, c.pw, cip);
+    if (g.P != P || g.Q != Q) fail("output size is not floor mode's", c, cip);
+    if (Src::kLane * Src::kBytes != 16 || g.CH * Src::kLane != Cpad || (long)g.nchunks * Src::kOutBytes != y_bytes)
+        fail("the items do not tile the output", c, cip);
     const long blocks = avg_blocks(g);
     if (blocks < 1 || blocks > kAvgMaxBlocks) fail("launch size", c, cip);
     if (print && cip)
-        printf("case %d,%d,%d,%d,%d,%d,%d,%d,%d,%d: P %d Q %d chunks %u blocks %ld\n", c.N, c.H, c.W, c.C, c.kh, c.kw, c.sh, c.sw, c.ph,
-               c.pw, g.P, g.Q, g.nchunks, blocks);
+        printf("case %d,%d,%d,%d,%d,%d,%d,%d,%d,%d: P %d Q %d %s %u blocks %ld\n", c.N, c.H, c.W, c.C, c.kh, c.kw, c.sh, c.sw, c.ph,
+               c.pw, g.P, g.Q, Src::kBytes == 1 ? "chunks" : "items", g.nchunks, blocks);
 
     const unsigned threads = (unsigned)blocks * kAvgBlock;
-    if ((unsigned long)g.nchunks + threads > 0xffffffffUL) fail("the 32-bit chunk index wraps in `i += stride`", c, cip);
+    if ((unsigned long)g.nchunks + threads > 0xffffffffUL) fail("the 32-bit item index wraps in `i += stride`", c, cip);
     const bool windowed = g_window && (unsigned long)g.nchunks > 2 * g_window;
     auto slot = [&](unsigned i) { return !windowed || i < g_window ? (size_t)i : (size_t)(g_window + (i - (g.nchunks - g_window))); };
-    std::vector<unsigned char> written(windowed ? 2 * g_window : g.nchunks, 0);
+    std::vector<unsigned char> written((windowed ? 2 * g_window : (size_t)g.nchunks) * Src::kOutBytes, 0);
+    const unsigned step = avg_tap_step<Src>(g);
     long loads = 0;
     for (unsigned gid = 0; gid < threads; ++gid) {
         for (unsigned i = gid; i < g.nchunks; i += threads) {
-            if (windowed && i >= g_window && i < g.nchunks - g_window) {       // jump to this lane's first chunk of the last window
+            if (windowed && i >= g_window && i < g.nchunks - g_window) {       // jump to this lane's first item of the last window
                 const unsigned long steps = ((unsigned long)(g.nchunks - g_window) - i + threads - 1) / threads;
                 const unsigned long next = i + steps * threads;
                 if (next >= g.nchunks) break;
@@ -72,18 +74,20 @@ static long run(const Case& c, int cip, bool print) {
             }
             const AvgChunk ch = avg_chunk(g, i);
             if (ch.n < 0 || ch.n >= c.N || ch.p < 0 || ch.p >= g.P || ch.q < 0 || ch.q >= g.Q || ch.k < 0 || ch.k >= g.CH)
-                fail("chunk index outside the output", c, cip);
-            if ((((long)ch.n * g.P + ch.p) * g.Q + ch.q) * g.CH + ch.k != (long)i) fail("chunk is not where it is stored", c, cip);
+                fail("item index outside the output", c, cip);
+            if ((((long)ch.n * g.P + ch.p) * g.Q + ch.q) * g.CH + ch.k != (long)i) fail("item is not where it is stored", c, cip);
             const AvgWindow w = avg_window(g, ch.p, ch.q);
             // the kernel's loads
             std::set<std::pair<int, int>> got;
             for (int ih = w.h0; ih < w.h1; ++ih) {
-                unsigned off = avg_tap_offset(g, ch.n, ih, w.w0, ch.k);
-                for (int iw = w.w0; iw < w.w1; ++iw, off += (unsigned)g.Cpad) {
+                unsigned off = avg_tap_offset<Src>(g, ch.n, ih, w.w0, ch.k);
+                for (int iw = w.w0; iw < w.w1; ++iw, off += step) {
                     const long o = (long)off;
                     if (o % 16 || o < 0 || o + 16 > x_bytes) fail("16-byte load outside the source or unaligned", c, cip);
                     if (ih < 0 || ih >= c.H || iw < 0 || iw >= c.W) fail("tap outside the image", c, cip);
-                    if (o != (((long)ch.n * c.H + ih) * c.W + iw) * g.Cpad + 16L * ch.k) fail("load is not the tap's address", c, cip);
+                    // the first of its kLane elements: channel kLane k of pixel (n, ih, iw)
+                    if (o != Src::kBytes * ((((long)ch.n * c.H + ih) * c.W + iw) * Cpad + (long)Src::kLane * ch.k))
+                        fail("load is not the tap's address", c, cip);
                     if (!got.insert(std::make_pair(ih, iw)).second) fail("tap loaded twice", c, cip);
                     ++loads;
                 }
@@ -102,24 +106,31 @@ static long run(const Case& c, int cip, bool print) {
             for (int b = 0; b < c.kw; ++b) cols += ch.q * c.sw - c.pw + b >= 0 && ch.q * c.sw - c.pw + b < c.W;
             if (avg_divisor(g, w) != (cip ? c.kh * c.kw : rows * cols) || avg_divisor(g, w) < 1 || avg_divisor(g, w) > kAvgMaxTaps)
                 fail("divisor", c, cip);
-            for (int t = 0; t < 4; ++t) {
-                const unsigned m = avg_dword_mask(g, ch.k, t);
+            for (int t = 0; t < Src::kOutBytes / 4; ++t) {
+                const unsigned m = avg_dword_mask<Src>(g, ch.k, t);
                 for (int j = 0; j < 4; ++j)
-                    if (((m >> (8 * j)) & 0xffu) != (16 * ch.k + 4 * t + j < c.C ? 0xffu : 0u)) fail("channel mask", c, cip);
+                    if (((m >> (8 * j)) & 0xffu) != (Src::kLane * ch.k + 4 * t + j < c.C ? 0xffu : 0u)) fail("channel mask", c, cip);
             }
-            if (((long)i + 1) * 16 > y_bytes) fail("store outside the output", c, cip);
-            if (written[slot(i)]++) fail("output chunk written twice", c, cip);
+            // the store: aligned, inside the output, at the item's own channels, every byte for the first time
+            const size_t so = avg_store_offset<Src>(i);
+            if (so % Src::kOutBytes || (long)so + Src::kOutBytes > y_bytes) fail("store outside the output or unaligned", c, cip);
+            if ((long)so != (((long)ch.n * g.P + ch.p) * g.Q + ch.q) * Cpad + (long)Src::kLane * ch.k) fail("store is not the item's address", c, cip);
+            for (int j = 0; j < Src::kOutBytes; ++j)
+                if (written[slot(i) * Src::kOutBytes + j]++) fail("output byte written twice", c, cip);
         }
     }
     for (unsigned char v : written)
-        if (v != 1) fail("output chunk not written", c, cip);
+        if (v != 1) fail("output byte not written", c, cip);
     return loads;
 }
 
 int main(int argc, char** argv) {
     std::vector<Case> cases;
+    int src = 0;                                // 0: not given, else the element size
     for (int a = 1; a < argc; ++a) {
         if (strncmp(argv[a], "window=", 7) == 0) { g_window = strtoul(argv[a] + 7, nullptr, 10); continue; }
+        if (strcmp(argv[a], "src=i8") == 0) { src = 1; continue; }
+        if (strcmp(argv[a], "src=i16") == 0) { src = 2; continue; }
         Case c;
         if (sscanf(argv[a], "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d", &c.N, &c.H, &c.W, &c.C, &c.kh, &c.kw, &c.sh, &c.sw, &c.ph, &c.pw) != 10) {
             printf("cannot read case %s\n", argv[a]);
@@ -127,9 +138,10 @@ int main(int argc, char** argv) {
         }
         cases.push_back(c);
     }
-    if (cases.empty()) {
+    const bool given = !cases.empty();
+    if (!given) {
         const int planes[][3] = {{1, 1, 1}, {1, 2, 2}, {2, 3, 5}, {3, 5, 7}, {1, 9, 11}};
-        const int chans[] = {1, 16, 19, 100};
+        const int chans[] = {1, 8, 9, 16, 19, 100};
         const int wins[][6] = {{3, 3, 1, 1, 1, 1}, {3, 3, 1, 1, 0, 0}, {2, 2, 2, 2, 0, 0}, {2, 2, 2, 2, 1, 1}, {3, 3, 2, 2, 1, 1}, {3, 3, 2, 2, 0, 0},
                                {5, 5, 1, 1, 2, 2}, {5, 5, 3, 3, 2, 2}, {2, 3, 1, 2, 1, 1}, {7, 7, 1, 1, 3, 3}, {8, 8, 8, 8, 4, 4}, {1, 1, 1, 1, 0, 0},
                                {1, 64, 1, 3, 0, 32}, {4, 1, 5, 1, 2, 0}};
@@ -139,12 +151,18 @@ int main(int argc, char** argv) {
                     if (pl[1] + 2 * k[4] < k[0] || pl[2] + 2 * k[5] < k[1]) continue;
                     cases.push_back(Case{pl[0], pl[1], pl[2], C, k[0], k[1], k[2], k[3], k[4], k[5]});
                 }
-        cases.push_back(Case{2, 130, 130, 256, 3, 3, 1, 1, 1, 1});     // more chunks than the launch has lanes: the stride over chunks
+        cases.push_back(Case{2, 130, 130, 256, 3, 3, 1, 1, 1, 1});     // more items than the launch has lanes: the stride over items
         cases.push_back(Case{8, 55, 55, 160, 2, 2, 2, 2, 0, 0});
+        cases.push_back(Case{2, 129, 129, 128, 3, 3, 1, 1, 1, 1});     // the same with 8 channels per lane, just above the launch
+        cases.push_back(Case{8, 56, 56, 256, 2, 2, 2, 2, 0, 0});       // the ResNet-D shortcut in front of stage 2
     }
+    const bool i8 = src != 2, i16 = src == 2 || (src == 0 && !given);
     long total = 0;
     for (const Case& c : cases)
-        for (int cip = 0; cip < 2; ++cip) total += run(c, cip, argc > 1);
+        for (int cip = 0; cip < 2; ++cip) {
+            if (i8) total += run<AvgSrcI8>(c, cip, given);
+            if (i16) total += run<AvgSrcI16>(c, cip, given);
+        }
     printf("ok, %ld loads checked\n", total);
     return 0;
 }

@@ -1,5 +1,5 @@
 // Timing probe only, never loaded by the product (scripts/avgpool_i16_lane_probe.py): the 16-channels-per-lane form of the average
-// pool over an int16 sum, to set against the library's 8-channel form (csrc/fq_avgpool_i16.hip).  Two 16-byte
+// pool over an int16 sum, to set against the library's 8-channel form (csrc/fq_avgpool_i8.hip, the AvgI16 source).  Two 16-byte
 // loads per tap, sixteen int32 accumulators and divisions per lane, one 16-byte store.  Same rule, same launch shape; the int8
 // pool's geometry header serves as it stands (a chunk of 16 channels is 32 source bytes: byte offsets are twice its offsets).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++20 -fPIC -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt \
@@ -27,7 +27,7 @@ __global__ __launch_bounds__(kAvgBlock) void avgpool_i16_c16_kernel(const int16_
 #pragma unroll
         for (int t = 0; t < 16; ++t) s[t] = 0;
         for (int ih = w.h0; ih < w.h1; ++ih) {
-            unsigned off = 2u * avg_tap_offset(g, c.n, ih, w.w0, c.k);
+            unsigned off = 2u * avg_tap_offset<AvgSrcI8>(g, c.n, ih, w.w0, c.k);
             for (int iw = w.w0; iw < w.w1; ++iw, off += step) {
                 const v4u a = *reinterpret_cast<const v4u*>(xb + off);
                 const v4u b = *reinterpret_cast<const v4u*>(xb + off + 16);
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(kAvgBlock) void avgpool_i16_c16_kernel(const int16_
         for (int t = 0; t < 4; ++t) {
             const unsigned v = rq(s[4 * t], div, p.scale, p.lo) | (rq(s[4 * t + 1], div, p.scale, p.lo) << 8) |
                                (rq(s[4 * t + 2], div, p.scale, p.lo) << 16) | (rq(s[4 * t + 3], div, p.scale, p.lo) << 24);
-            o[t] = v & avg_dword_mask(g, c.k, t);
+            o[t] = v & avg_dword_mask<AvgSrcI8>(g, c.k, t);
         }
         *reinterpret_cast<v4u*>(y + (size_t)i * 16) = o;
     }

@@ -34,6 +34,11 @@ MOVED = [
      r"concat_kernel<fq::CatMove, \1, \2, \3>(signed char*, fq::CatParams<fq::CatMove, \1>)"),
     (r"concat_rq_i8_kernel<(\w+), (\w+)>\(signed char\*, fq::CrqParams\)",
      r"concat_kernel<fq::CatRequant, 8, \1, \2>(signed char*, fq::CatParams<fq::CatRequant, 8>)"),
+    # the two windowed average pools became the two source policies of one kernel
+    (r"^fq::avgpool_i8_nhwc_kernel\(signed char const\*, signed char\*, fq::AvgParams\)",
+     r"void fq::avgpool_nhwc_kernel<fq::AvgI8>(fq::AvgI8::elem const*, signed char*, fq::AvgParams)"),
+    (r"^fq::avgpool_i16_nhwc_kernel\(short const\*, signed char\*, fq::Avg16Params\)",
+     r"void fq::avgpool_nhwc_kernel<fq::AvgI16>(fq::AvgI16::elem const*, signed char*, fq::AvgParams)"),
 ]
 
 

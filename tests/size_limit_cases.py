@@ -333,6 +333,9 @@ GPU_CASES = [
     # windowed int8 average pool: 32-bit byte offsets into the source, a 32-bit chunk index; args N H W C kh kw sh sw ph pw
     _g("avgi_top", "fq_avgpool_i8_nhwc", (4160, 127, 127, 19, 3, 3, 1, 1, 1, 1), "top", "fq_avgpool_i8.hip: fq_avgpool_i8_nhwc",
        "N*H*W*Cpad", prod(4160, 127, 127, 32), I31, prod(4160, 127, 127, 32), 2 * prod(4160, 127, 127, 32), ragged=(("C", 19, 16),)),
+    # ... and over an int16 sum: half the images give the same source bytes; 8 channels per lane, so item 2 holds 3 real channels
+    _g("avg16_top", "fq_avgpool_i16_nhwc", (2080, 127, 127, 19, 3, 3, 1, 1, 1, 1), "top", "fq_avgpool_i8.hip: fq_avgpool_i16_nhwc",
+       "2*N*H*W*Cpad", prod(2, 2080, 127, 127, 32), I31, prod(2, 2080, 127, 127, 32), 3 * prod(2080, 127, 127, 32), ragged=(("C", 19, 8),)),
     # int8 kernels with 64-bit indices: an operand above 2^31 bytes
     _g("stem_i8_b520", "fq_conv2d_i8_stem", (520, 3, 512, 512, 64, 7, 7, 2, 3), "bit31", "fq_stem.hip: stem_dispatch", "q bytes",
        prod(520, 256, 256, 64), None, prod(520, 256, 256, 64), 4 * prod(520, 3, 512, 512) + prod(520, 256, 256, 64)),
@@ -361,7 +364,8 @@ GPU_CASES = [
 WALKER_ROWS = {
     "cat_top": ("concat_geom_check.cpp", ["window=4096", "maxsrc=2", "520,254,254/20,44/2,1"]),
     "catn_top": ("concat_geom_check.cpp", ["window=4096", "520,254,254/20,3,41/2,1,1"]),
-    "avgi_top": ("avgpool_geom_check.cpp", ["window=65536", "4160,127,127,19,3,3,1,1,1,1"]),
+    "avgi_top": ("avgpool_geom_check.cpp", ["src=i8", "window=65536", "4160,127,127,19,3,3,1,1,1,1"]),
+    "avg16_top": ("avgpool_geom_check.cpp", ["src=i16", "window=65536", "2080,127,127,19,3,3,1,1,1,1"]),
     "dwf_top": ("dwconv_f32_geom_check.cpp", ["window=4096", "128,520,127,127,3,1,1"]),
     "gf_top": ("gconv_f32_geom_check.cpp", ["window=2048", "1109,5,4,12,127,127,3,1,1"]),
     "gci_top": ("gconv_geom_check.cpp", ["window=1024", "5,4,12,3,1,1,1040,127,127"]),

@@ -311,8 +311,8 @@ def test_avgpool_supported_is_host_arithmetic():
 def test_kernel_address_arithmetic_stays_inside_its_tensors(tmp_path):
     """csrc/fq_avgpool_i8_geom.h holds the kernel's lane -> (chunk, taps, divisor, addresses) functions and compiles as host code:
     scripts/avgpool_geom_check.cpp walks every lane of every launch and exits non-zero on a load outside the source, an unaligned
-    load, a tap that is not in window ∩ image or is loaded twice, a wrong divisor or an output chunk written twice or not at all --
-    over its built-in list and over the GPU tests' shape list."""
+    load, a tap that is not in window ∩ image or is loaded twice, a wrong divisor or an output byte written twice or not at all --
+    over its built-in list (walked for both sources, int8 and int16) and, at the default src=i8, over the GPU tests' shape list."""
     exe = str(tmp_path / "avgpool_geom_check")
     subprocess.check_call(["c++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "scripts", "avgpool_geom_check.cpp")])
     out = subprocess.run([exe], capture_output=True, text=True)

@@ -822,6 +822,34 @@ def test_avgpool_i8_nhwc_source_just_below_2_31_bytes(nat):
             del y
 
 
+@pytest.mark.gpu
+def test_avgpool_i16_nhwc_source_just_below_2_31_bytes(nat):
+    """The same window on 2080 planes of 127 x 127 x 32 int16 over all of int16 (the same source bytes), shift -8 and -7: int32
+    window sums below 2^24, so the fp32 reference is exact up to its ONE division, as in the row above."""
+    cid = "avg16_top"
+    with _Case(cid) as c:
+        n, h, w, ch, kh, kw, sh, sw, ph, pw = c.args
+        cpad = T.pad16(ch)
+        x = hashed((n, h, w, cpad), -32768, 32767, 173, dtype=torch.int16)
+        assert 2 * x.numel() == c.value and (kh, kw, sh, sw, ph, pw) == (3, 3, 1, 1, 1, 1)
+        ones = torch.nn.functional.pad(torch.ones((1, h, w, 1), dtype=torch.int32, device="cuda"), (0, 0, 1, 1, 1, 1))
+        taps = sum(ones[:, a:a + h, b:b + w] for a in range(3) for b in range(3)).to(torch.float32)
+        for cip, shift, relu in ((False, -7, True), (True, -8, False)):
+            y = nat.avgpool_i16_nhwc(x, ch, (kh, kw), (sh, sw), (ph, pw), cip, shift, relu)
+            div = torch.full_like(taps, 9.0) if cip else taps
+
+            def ref(a, b):
+                xp = torch.nn.functional.pad(x[a:b, :, :, :ch].to(torch.int32), (0, 0, 1, 1, 1, 1))
+                sums = sum(xp[:, i:i + h, j:j + w] for i in range(3) for j in range(3)).to(torch.float32)
+                v = torch.round(sums / div * float(2.0 ** shift)).clamp(0.0 if relu else -128.0, 127.0)
+                out = torch.zeros((b - a, h, w, cpad), dtype=torch.int8, device="cuda")
+                out[..., :ch] = v.to(torch.int8)
+                return out
+
+            check_chunks(y, ref, 64, "%s count_include_pad=%d" % (cid, cip))
+            del y
+
+
 # ---- int8 kernels with an operand above 2^31 bytes --------------------------------------------------------------------------
 
 @pytest.mark.gpu

@@ -1,4 +1,4 @@
-"""Windowed average pooling over the exact int16 sum of a resident NewAdd (fq_avgpool_i16_nhwc, csrc/fq_avgpool_i16.hip) against
+"""Windowed average pooling over the exact int16 sum of a resident NewAdd (fq_avgpool_i16_nhwc, csrc/fq_avgpool_i8.hip) against
 the rule of include/fq.h in NumPy float32 (avgpool_nets.numpy_rule, which tests/test_sum_pool_plan_cpu.py holds against torch's own
 chain on int16 sources).  Everything is integers: every comparison is exact.   pytest -m gpu"""
 import ctypes
@@ -98,6 +98,25 @@ def test_more_items_than_lanes(nat):
     x = sn.source16(np.random.default_rng(5), case)
     got = nat.avgpool_i16_nhwc(torch.from_numpy(x).cuda(), case[3], (3, 3), (1, 1), (1, 1), False, -7, True).cpu().numpy()
     np.testing.assert_array_equal(got, an.numpy_rule(x, case[3], (3, 3), (1, 1), (1, 1), False, -7, True))
+
+
+def test_the_two_sources_of_one_kernel_agree(nat):
+    """avgpool_nhwc_kernel's two source policies held to each other: the same integers in [-128, 127], stored once as int8 and once
+    as int16 (garbage in the padding channels of both), give equal bytes through fq_avgpool_i8_nhwc and fq_avgpool_i16_nhwc -- 16
+    channels per lane against 8, packed int16 sums against int32, a dwordx4 store against a dwordx2."""
+    rng = np.random.default_rng(37)
+    for C in (1, 8, 9, 16, 17):
+        x8 = rng.integers(-128, 128, (2, 5, 7, an.pad16(C))).astype(np.int8)
+        x8[0, 0, 0, 0], x8[1, 4, 6, C - 1] = -128, 127
+        d8, d16 = torch.from_numpy(x8).cuda(), torch.from_numpy(x8.astype(np.int16)).cuda()
+        for win in ((3, 3, 1, 1, 1, 1), (2, 2, 2, 2, 0, 0), (2, 3, 1, 2, 1, 1)):
+            kernel, stride, padding = win[0:2], win[2:4], win[4:6]
+            for cip in (False, True):
+                for shift in (-2, 0, 3):
+                    for relu in (False, True):
+                        y8 = nat.avgpool_i8_nhwc(d8, C, kernel, stride, padding, cip, shift, relu)
+                        y16 = nat.avgpool_i16_nhwc(d16, C, kernel, stride, padding, cip, shift, relu)
+                        assert y8.shape == y16.shape and torch.equal(y8, y16), (C, win, cip, shift, relu)
 
 
 # ---------------------------------------------------------------- 2. what the entry point declines

@@ -177,6 +177,18 @@ def test_the_host_predicates_answer_on_both_sides_of_their_limits(L):
     assert sb(128, 256) == 1
 
 
+@pytest.mark.parametrize("entry", ["fq_avgpool_i8_nhwc", "fq_avgpool_i16_nhwc"])
+def test_the_average_pools_refuse_a_product_that_does_not_fit_64_bits(L, buf, entry):
+    """include/fq.h: both windowed pools take tensors below 2^31 - 1 bytes.  N = H = W = 2^31 - 1 with Cpad = 2^31 - 16 is about
+    2^124 bytes: a guard that multiplies the four in 64 bits overflows (undefined for signed) and may land below the limit; the
+    entry points compare factor by factor."""
+    big, cpad = (1 << 31) - 1, (1 << 31) - 16
+    assert cpad % 16 == 0 and big * big * big * cpad > 1 << 64
+    for win in ((2, 2, 2, 2, 0, 0), (1, 1, 1, 1, 0, 0)):
+        assert getattr(L, entry)(buf[0], buf[1], big, big, big, cpad, cpad, *win, 0, 0, 0, None) == UNSUPPORTED
+    assert buf[2].raw == b"\0" * len(buf[2].raw)
+
+
 # ---- the table's GPU rows, held to the same numbers -------------------------------------------------------------------------
 
 def test_every_gpu_row_sits_where_the_table_says():

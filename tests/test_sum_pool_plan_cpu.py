@@ -2,7 +2,7 @@
 NewAdd -- the ResNet-D shortcut.  The tracer, the plan, the handles and the module glue run for real; the kernel entry points are
 oracle-backed doubles (tests/sum_pool_doubles.py on top of avgpool_doubles.py) that follow the reference's fp32 chain literally.
 Every comparison is exact.  The rule of include/fq.h (fq_avgpool_i16_nhwc) is held against torch's own chain on int16 sources, the
-kernel's address arithmetic is walked on the host over the GPU tests' shape list (scripts/avgpool_i16_geom_check.cpp), golden G23
+kernel's address arithmetic is walked on the host over the GPU tests' shape list (scripts/avgpool_geom_check.cpp, src=i16), golden G23
 pins a calibrated toy ResNet-D to the reference, and forty random ResNet-D-shaped nets run under three plans."""
 import io
 import json
@@ -431,16 +431,16 @@ def test_a_plan_pickled_before_this_change_still_loads():
 
 # ---------------------------------------------------------------- 3. the walker
 def test_kernel_address_arithmetic_stays_inside_its_tensors(tmp_path):
-    """csrc/fq_avgpool_i16_geom.h holds the kernel's lane -> (item, taps, divisor, byte offsets, mask) functions and compiles as host
-    code: scripts/avgpool_i16_geom_check.cpp walks every lane of every launch and exits non-zero on a load outside the source, an
+    """csrc/fq_avgpool_i8_geom.h holds the kernel's lane -> (item, taps, divisor, byte offsets, mask) functions and compiles as host
+    code: scripts/avgpool_geom_check.cpp walks with src=i16 every lane of every launch and exits non-zero on a load outside the source, an
     unaligned load, a tap that is not in window ∩ image or is loaded twice, a wrong divisor or mask, or an output byte written twice
     or not at all -- over its built-in list and over the GPU tests' shape list."""
-    exe = str(tmp_path / "avgpool_i16_geom_check")
-    subprocess.check_call(["c++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "scripts", "avgpool_i16_geom_check.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True)
+    exe = str(tmp_path / "avgpool_geom_check")
+    subprocess.check_call(["c++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "scripts", "avgpool_geom_check.cpp")])
+    out = subprocess.run([exe, "src=i16"], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.startswith("ok,"), out.stdout + out.stderr
     shapes = an.KERNEL_CASES + [sn.STRIDE_LOOP_CASE, (1, 6, 6, 16, 2, 2, 2, 2, 0, 0)]
-    out = subprocess.run([exe] + [an.case_arg(c) for c in shapes], capture_output=True, text=True)
+    out = subprocess.run([exe, "src=i16"] + [an.case_arg(c) for c in shapes], capture_output=True, text=True)
     lines = out.stdout.splitlines()
     assert out.returncode == 0 and lines[-1].startswith("ok,") and len(lines) == len(shapes) + 1, out.stdout + out.stderr
     stride_loop = [ln for ln in lines if ln.startswith("case " + an.case_arg(sn.STRIDE_LOOP_CASE))][0].split()
@@ -448,7 +448,7 @@ def test_kernel_address_arithmetic_stays_inside_its_tensors(tmp_path):
     # the smallest square plane of this family for 8 channels per lane: one row and column less gives every lane exactly one item
     n, h, w, c = sn.STRIDE_LOOP_CASE[:4]
     assert n * h * w * c // 8 > 2048 * 256 >= n * (h - 1) * (w - 1) * c // 8
-    bad = subprocess.run([exe, "1,4,4,16,9,9,1,1,4,4"], capture_output=True, text=True)     # 81 taps: not a case the entry point launches
+    bad = subprocess.run([exe, "src=i16", "1,4,4,16,9,9,1,1,4,4"], capture_output=True, text=True)     # 81 taps: not a case the entry point launches
     assert bad.returncode == 1
 
 
