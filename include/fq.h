@@ -969,6 +969,14 @@ int fq_block_tail_proj_i8(const int8_t* x_nhwc, const int8_t* w3_krsc, const flo
 int fq_add_resident(const void* x, int x_bytes, int gx, const void* y, int y_bytes, int gy, int16_t* wide,
                     int g_wide, int8_t* narrow, int ib, int relu, size_t n, fq_stream_t stream);
 
+/* A diagnostic for tests (host arithmetic, no GPU needed): which of its arithmetic forms the resident NewAdd runs for these operand
+ * types and grids -- in fq_add_resident, fq_add_up_resident, the epilogue of fq_conv2d_i8_add_resident (x_bytes 1, gx = ob) and
+ * fq_block_tail*_i8 (x_bytes 1, gx = ob3, gy = g_res / obp) alike: 0 the fp32 chain, 1 the 32-bit integer form with
+ * k = max(0, gx, gy) - ib <= 0, 2 the same with k > 0 (a rounding right shift), 3 the packed int16 form.  The forms compute the
+ * same integers; the number says which code did.  FQ_ERR_INVALID_ARG for x_bytes / y_bytes outside {1, 2} or a grid or bit
+ * outside [-16, 16].  (Whether a wide output is taken is a separate question: g_wide <= 8, above.) */
+int fq_add_resident_form(int x_bytes, int gx, int y_bytes, int gy, int ib, int relu);
+
 /* The same add with its second operand read through a nearest upsampling by `up` (2 or 4), which is never materialised: the FPN
  * top-down step Eltwise(lateral, up(top)).  x and both outputs are [N][H][W][Cpad], y is [N][H / up][W / up][Cpad]; each is int8
  * or int16 as in fq_add_resident (y_bytes = 2: the exact sum of the add one level up).  Per element

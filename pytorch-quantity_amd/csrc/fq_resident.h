@@ -5,26 +5,11 @@
 #include <type_traits>
 #include "fq_common.h"
 #include "fq_int_tail.h"
+#include "fq_add_params.h"       // AddResParams, make_add_params: the host side, free of HIP
 
 namespace fq {
 
 typedef int v4i_r __attribute__((ext_vector_type(4)));
-
-struct AddResParams {
-    float sx, sy;          // 2^-gx, 2^-gy: integer -> value
-    float lo, hi;          // NewAdd's Sp range; lo = 0 when the following ReLU is fused
-    float s_wide;          // 2^g_out   (exact value -> int16)
-    float s_narrow;        // 2^ib      (next layers' Quantity)
-    // the same function in integer arithmetic on the grid g = max(0, gx, gy) (int_ok: the host proved the ranges)
-    int int_ok;
-    int shx, shy;          // g - gx, g - gy: operand -> grid g
-    int ilo, ihi;          // Sp range on grid g
-    int k, half_m1;        // narrow = S * 2^(ib - g): k = g - ib; k > 0: round-half-even right shift with 2^(k-1) - 1
-    // the integer form on PAIRS of int16 (v_pk_*_i16: two elements per instruction) where every intermediate fits 16 bits:
-    // pk_ok8 / pk_ok16 for an int8 / int16 operand y; the constants below are the ones above, replicated in both halves
-    int pk_ok8, pk_ok16;
-    unsigned shx2, shy2, k2, ilo2, ihi2, half2;
-};
 
 template <typename T> struct Vec16;                       // 16 consecutive channels of one pixel
 template <> struct Vec16<int8_t> {
@@ -198,38 +183,6 @@ __device__ __forceinline__ void add_resident_16(const VX& vx, const VY& vy, int1
         *reinterpret_cast<v4i_r*>(wide + 8) = o.w1;
     }
     if (narrow) *reinterpret_cast<v4i_r*>(narrow) = o.n;
-}
-
-// host: parameters of one resident add; FQ_OK or an error code (ranges, exact-sum grid)
-inline int make_add_params(int gx, int gy, int g_wide, bool want_wide, int ib, int relu, AddResParams* p) {
-    if (gx < -16 || gx > 16 || gy < -16 || gy > 16 || ib < -16 || ib > 16) return FQ_ERR_INVALID_ARG;
-    if (want_wide) {
-        // the exact sum must fit: grid max(0, gx, gy), |s| <= 128  =>  |S| <= 2^(7 + g) <= 2^15
-        const int g_need = gx > gy ? (gx > 0 ? gx : 0) : (gy > 0 ? gy : 0);
-        if (g_wide != g_need || g_wide > 8) return FQ_ERR_UNSUPPORTED;
-    }
-    p->sx = ldexpf(1.0f, -gx); p->sy = ldexpf(1.0f, -gy);
-    p->lo = relu ? 0.0f : -128.0f; p->hi = 127.0f;
-    p->s_wide = ldexpf(1.0f, want_wide ? g_wide : 0); p->s_narrow = ldexpf(1.0f, ib);
-    // integer form: operands |x|, |y| <= 2^15 shifted by at most 12, the clamped sum |S| <= 2^(7+g) <= 2^15 shifted left by
-    // at most 15 -- nothing leaves int32.  FQ_ADD_FLOAT=1 keeps the fp32 chain (A/B timing).
-    static const bool force_float = [] { const char* e = getenv("FQ_ADD_FLOAT"); return e && e[0] && e[0] != '0'; }();
-    const int g = gx > gy ? (gx > 0 ? gx : 0) : (gy > 0 ? gy : 0);
-    p->shx = g - gx; p->shy = g - gy;
-    p->k = g - ib;
-    p->int_ok = !force_float && g <= 8 && p->shx <= 12 && p->shy <= 12 && p->k >= -15 && p->k <= 24;
-    p->half_m1 = p->k > 0 ? (1 << (p->k - 1)) - 1 : 0;
-    p->ilo = relu ? 0 : -(128 << g); p->ihi = 127 << g;
-    if (!p->int_ok) { p->shx = p->shy = 0; p->k = 0; }
-    // packed int16 form: every intermediate inside 16 bits (see add_resident_16_pk).  FQ_ADD_PACKED=0 keeps the 32-bit form.
-    static const bool no_pk = [] { const char* e = getenv("FQ_ADD_PACKED"); return e && e[0] == '0'; }();
-    const bool pk = p->int_ok && !no_pk && p->k >= 1 && p->k <= 8 && p->shx >= 0 && p->shx <= 8;
-    p->pk_ok8 = pk && p->shy >= 0 && p->shy <= 8;
-    p->pk_ok16 = pk && p->shy == 0;
-    auto rep = [](int v) { return ((unsigned)v & 0xffffu) * 0x10001u; };
-    p->shx2 = rep(p->shx); p->shy2 = rep(p->shy); p->k2 = rep(p->k); p->ilo2 = rep(p->ilo); p->ihi2 = rep(p->ihi);
-    p->half2 = rep(p->half_m1);
-    return FQ_OK;
 }
 
 }  // namespace fq

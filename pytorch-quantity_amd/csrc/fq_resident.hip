@@ -107,6 +107,13 @@ extern "C" int fq_add_resident(const void* x, int x_bytes, int gx, const void* y
     return FQ_OK;
 }
 
+extern "C" int fq_add_resident_form(int x_bytes, int gx, int y_bytes, int gy, int ib, int relu) {
+    if ((x_bytes != 1 && x_bytes != 2) || (y_bytes != 1 && y_bytes != 2)) return FQ_ERR_INVALID_ARG;
+    AddResParams p;
+    const int rc = make_add_params(gx, gy, 0, false, ib, relu, &p);
+    return rc != FQ_OK ? rc : add_resident_form(p, x_bytes, y_bytes);
+}
+
 extern "C" int fq_dequant_nhwc_to_nchw(const void* q_nhwc, int q_bytes, int g, float* y_nchw, int N, int C, int HW, int Cpad,
                                        fq_stream_t stream) {
     if ((q_bytes != 1 && q_bytes != 2) || g < -120 || g > 120) return FQ_ERR_INVALID_ARG;

@@ -302,6 +302,8 @@ def lib():
     L.fq_upsample_bilinear_i8_nhwc.argtypes = [vp, vp] + [ci] * 8 + [vp]
     L.fq_add_resident.restype = ci
     L.fq_add_resident.argtypes = [vp, ci, ci, vp, ci, ci, vp, ci, vp, ci, ci, sz, vp]
+    L.fq_add_resident_form.restype = ci
+    L.fq_add_resident_form.argtypes = [ci] * 6
     L.fq_add_up_resident.restype = ci
     L.fq_add_up_resident.argtypes = [vp, ci, ci, vp, ci, ci, ci, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp]
     L.fq_add_up_resident_supported.restype = ci
@@ -1533,6 +1535,17 @@ def add_resident(x, gx, y, gy, want_wide, g_wide, want_narrow, ib, relu):
                                  _ptr(wide), int(g_wide), _ptr(narrow), int(ib), 1 if relu else 0, x.numel(),
                                  _stream(x)), "fq_add_resident")
     return wide, narrow
+
+
+ADD_FORMS = {0: "fp32", 1: "int32", 2: "int32_shift", 3: "packed"}
+
+
+def add_resident_form(x_bytes, gx, y_bytes, gy, ib, relu):
+    """fq_add_resident_form: which arithmetic form of the resident NewAdd these operand types and grids run (a key of ADD_FORMS),
+    in fq_add_resident and in every kernel that fuses it.  Host arithmetic, no GPU needed; raises FqError where the add would."""
+    rc = int(lib().fq_add_resident_form(int(x_bytes), int(gx), int(y_bytes), int(gy), int(ib), 1 if relu else 0))
+    _check(min(rc, 0), "fq_add_resident_form")
+    return rc
 
 
 def add_up_supported(up, H, W, cpad):
