@@ -62,7 +62,8 @@ int fq_last_hip_error(void);      /* thread-local hipError_t of the last FQ_ERR_
  * (C % 128 / C = 64 / general path), 10 stem_conv_i8, 11 block_tail_i8 (fq_block_tail_i8), 12 the same with the projection
  * shortcut computed in the kernel (fq_block_tail_proj_i8), 13 linear_i8_wave (a linear layer, one wave per 32 x 32 tile), 14 dwconv_i8
  * (fq_dwconv2d_i8_resident, a depthwise layer), 15 gconv_i8 (fq_gconv2d_i8_resident, a grouped layer), 16 deconv_i8
- * (fq_deconv2d_i8_resident, a transposed convolution), 0 nothing launched; bits
+ * (fq_deconv2d_i8_resident, a transposed convolution), 17 dwconv_dil_i8 (fq_dwconv2d_dil_i8_resident, an atrous depthwise layer),
+ * 0 nothing launched; bits
  * 8-15: output-channel
  * tile (64 / 128).  Lets a test assert that the dispatch it checked against a golden is the dispatch a benchmark timed. */
 int fq_conv2d_i8_last_variant(void);
@@ -667,6 +668,37 @@ int fq_dwconv2d_i8_resident(const int8_t* x_nhwc, const int8_t* w_rsc, const flo
 int fq_dwconv2d_i8_resident_pcs(const int8_t* x_nhwc, const int8_t* w_rsc, const float* qbias, const int32_t* rs_k, int rs_min,
                                 int rs_max, int8_t* q_nhwc, int Cpad, int relu, int N, int H, int W, int C, int R, int S,
                                 int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int ob, fq_stream_t stream);
+
+/* Atrous depthwise convolution (a depthwise nn.Conv2d with dilation d > 1 at stride 1: the tail of a backbone that trades
+ * stride for dilation, the 3x3 branches of an atrous-separable ASPP) on a resident activation,
+ *   acc[n][c][p][q] = sum_{r,s} w[c][r][s] * x[n][p - pad_h + r*d][q - pad_w + s*d][c]                          (int32, exact)
+ *   q_nhwc          = clamp(RightShift(acc, rs) + qbias[c])     (the tail of fq_dwconv2d_i8_resident; ReLU fused when relu != 0)
+ * with P = H + 2*pad_h - d*(R - 1), Q = W + 2*pad_w - d*(S - 1).  Operands, layouts, alignment, the Cpad rule, the zeros in
+ *   channels [C, Cpad), qbias, ob and the _pcs / _act forms are fq_dwconv2d_i8_resident's, argument for argument; w_rsc is the
+ *   same [R][S][Cpad] array.  The kernel walks the d x d phases of the output as dense stride-1 convolutions on lattices of step
+ *   d (csrc/fq_dwconv_dil_i8.hip).
+ * fq_dwconv2d_dil_i8_supported: 1 for C >= 1, R == S in {3, 5}, stride 1 on both axes, dil_h == dil_w = d with 2 <= d <= 64 and
+ *   every shift in [1, 16]; 0 for d = 1 (fq_dwconv2d_i8_resident's layer), stride 2, unequal dilations, other kernel sizes.  The
+ *   entry points also need 0 <= pad_h, pad_w <= d*(R - 1) (any padding up to the window's span: atrous layers pad by d, not by
+ *   less than R), N*H*W*Cpad < 2^31 and N*P*Q*Cpad < 2^30, and return FQ_ERR_UNSUPPORTED otherwise, nothing launched: callers
+ *   keep the fp32 grouped convolution + fq_recon_epilogue there.  A padded plane smaller than the window (H + 2*pad_h < d*(R - 1)
+ *   + 1) is FQ_ERR_INVALID_ARG.  _pcs: one shift per channel, as fq_dwconv2d_i8_resident_pcs; a constant vector gives the bytes of
+ *   the per-tensor entry point.  fq_conv2d_i8_last_variant: 17. */
+int fq_dwconv2d_dil_i8_supported(int C, int R, int S, int stride_h, int stride_w, int dil_h, int dil_w, int rs_min, int rs_max);
+int fq_dwconv2d_dil_i8_resident(const int8_t* x_nhwc, const int8_t* w_rsc, const float* qbias, int8_t* q_nhwc, int Cpad, int relu,
+                                int N, int H, int W, int C, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                                int dil_h, int dil_w, int rs, int ob, fq_stream_t stream);
+int fq_dwconv2d_dil_i8_resident_pcs(const int8_t* x_nhwc, const int8_t* w_rsc, const float* qbias, const int32_t* rs_k, int rs_min,
+                                    int rs_max, int8_t* q_nhwc, int Cpad, int relu, int N, int H, int W, int C, int R, int S,
+                                    int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int ob,
+                                    fq_stream_t stream);
+int fq_dwconv2d_dil_i8_resident_act(const int8_t* x_nhwc, const int8_t* w_rsc, const float* qbias, int8_t* q_nhwc, int Cpad,
+                                    int act_lo, int act_hi, int N, int H, int W, int C, int R, int S, int stride_h, int stride_w,
+                                    int pad_h, int pad_w, int dil_h, int dil_w, int rs, int ob, fq_stream_t stream);
+int fq_dwconv2d_dil_i8_resident_pcs_act(const int8_t* x_nhwc, const int8_t* w_rsc, const float* qbias, const int32_t* rs_k,
+                                        int rs_min, int rs_max, int8_t* q_nhwc, int Cpad, int act_lo, int act_hi, int N, int H,
+                                        int W, int C, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                                        int dil_w, int ob, fq_stream_t stream);
 
 /* Grouped convolution (nn.Conv2d with 1 < groups < channels: the 3x3 of a ResNeXt / RegNet block, the grouped 1x1 of a
  * ShuffleNet) on a resident activation.  G = groups, Cgi = C / G input and Cgo = K / G output channels per group:

@@ -25,6 +25,7 @@
 #include "fq_common.h"
 #include "fq_int_tail.h"
 #include "fq_dwconv_i8_geom.h"
+#include "fq_dwconv_i8_lane.h"
 
 namespace fq {
 
@@ -36,16 +37,6 @@ struct DwParams {
     int rs, half_rs;                   // per-tensor shift (the per-channel form reads rs_k)
     int ilo, ihi, slo, shi;            // RightShift range, Sp range (slo = 0 with the fused ReLU)
 };
-
-// 4 pixels x 4 channels -> 4 channels x 4 pixels: t[c] = (d[0].byte c, d[1].byte c, d[2].byte c, d[3].byte c)
-__device__ __forceinline__ void transpose4(const unsigned (&d)[4], unsigned (&t)[4]) {
-    const unsigned a01 = __builtin_amdgcn_perm(d[1], d[0], 0x05010400u), b01 = __builtin_amdgcn_perm(d[1], d[0], 0x07030602u);
-    const unsigned a23 = __builtin_amdgcn_perm(d[3], d[2], 0x05010400u), b23 = __builtin_amdgcn_perm(d[3], d[2], 0x07030602u);
-    t[0] = __builtin_amdgcn_perm(a23, a01, 0x05040100u);
-    t[1] = __builtin_amdgcn_perm(a23, a01, 0x07060302u);
-    t[2] = __builtin_amdgcn_perm(b23, b01, 0x05040100u);
-    t[3] = __builtin_amdgcn_perm(b23, b01, 0x07060302u);
-}
 
 template <int R, int STRIDE, bool PCS>
 __global__ __launch_bounds__(kDwBlock) void dwconv_i8_kernel(const int8_t* __restrict__ x, const int8_t* __restrict__ w,
@@ -64,19 +55,7 @@ __global__ __launch_bounds__(kDwBlock) void dwconv_i8_kernel(const int8_t* __res
 
     // this lane's weights: wr[r][c] = taps 0..3 of row r (byte s), w4[r][c] = tap 4 in byte 0 (5x5)
     unsigned wr[R][4], w4[S == 5 ? R : 1][4];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        unsigned d[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-            d[s] = s < S ? *reinterpret_cast<const unsigned*>(w + (size_t)(r * S + s) * g.Cpad + 4 * c4) : 0u;
-        transpose4(d, wr[r]);
-        if constexpr (S == 5) {
-            const unsigned d4 = *reinterpret_cast<const unsigned*>(w + (size_t)(r * S + 4) * g.Cpad + 4 * c4);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) w4[r][c] = (d4 >> (8 * c)) & 0xffu;
-        }
-    }
+    dw_lane_weights<R>(w, g.Cpad, c4, wr, w4);
     // the tail of each channel: rounding constant with the bias in it, merged clamp bounds, shift
     int tB[4], tlo[4], thi[4], trs[4];
 #pragma unroll
@@ -124,10 +103,10 @@ __global__ __launch_bounds__(kDwBlock) void dwconv_i8_kernel(const int8_t* __res
 #pragma unroll
                 for (int j = 0; j < TQ; ++j) {
                     const int a = j * STRIDE;                 // first pixel of the window (compile time after unrolling)
-                    const int ga = a / 4, oa = a % 4;
-                    const unsigned win = oa == 0 ? T[ga][c] : __builtin_amdgcn_alignbyte(T[ga + (ga + 1 < NG ? 1 : 0)][c], T[ga][c], oa);
+                    const int ga = a / 4;
+                    const unsigned win = dw_window(T[ga][c], T[ga + (ga + 1 < NG ? 1 : 0)][c], a % 4);
                     unsigned fifth = 0u;
-                    if constexpr (S == 5) fifth = T[(a + 4) / 4][c] >> (8 * ((a + 4) % 4));
+                    if constexpr (S == 5) fifth = dw_fifth(T[(a + 4) / 4][c], (a + 4) % 4);
 #pragma unroll
                     for (int t = 0; t < TP; ++t) {
                         const int r = i - t * STRIDE;         // the kernel row through which input row i reaches output row t

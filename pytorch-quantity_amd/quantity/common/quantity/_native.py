@@ -227,6 +227,12 @@ def lib():
     L.fq_dwconv2d_i8_resident.argtypes = [vp, vp, vp, vp] + [ci] * 16 + [vp]
     L.fq_dwconv2d_i8_resident_pcs.restype = ci
     L.fq_dwconv2d_i8_resident_pcs.argtypes = [vp, vp, vp, vp, ci, ci, vp] + [ci] * 15 + [vp]
+    L.fq_dwconv2d_dil_i8_supported.restype = ci
+    L.fq_dwconv2d_dil_i8_supported.argtypes = [ci] * 9
+    L.fq_dwconv2d_dil_i8_resident.restype = ci
+    L.fq_dwconv2d_dil_i8_resident.argtypes = [vp, vp, vp, vp] + [ci] * 16 + [vp]
+    L.fq_dwconv2d_dil_i8_resident_pcs.restype = ci
+    L.fq_dwconv2d_dil_i8_resident_pcs.argtypes = [vp, vp, vp, vp, ci, ci, vp] + [ci] * 15 + [vp]
     L.fq_gconv2d_i8_supported.restype = ci
     L.fq_gconv2d_i8_supported.argtypes = [ci] * 11
     L.fq_gconv2d_i8_resident.restype = ci
@@ -242,7 +248,7 @@ def lib():
     # the `_act` siblings of the integer producers: `int act_lo, int act_hi` where those take `int relu`
     for name in ("fq_conv2d_i8_resident", "fq_conv2d_i8_resident_pcs", "fq_conv2d_i8_stem", "fq_conv2d_i8_stem_pcs",
                  "fq_dwconv2d_i8_resident", "fq_dwconv2d_i8_resident_pcs", "fq_gconv2d_i8_resident", "fq_gconv2d_i8_resident_pcs",
-                 "fq_deconv2d_i8_resident"):
+                 "fq_deconv2d_i8_resident", "fq_dwconv2d_dil_i8_resident", "fq_dwconv2d_dil_i8_resident_pcs"):
         getattr(L, name + "_act").restype = ci
         plain = getattr(L, name).argtypes                     # (..., int relu, ints ..., stream) -> (..., int act_lo, int act_hi, ints ..., stream)
         getattr(L, name + "_act").argtypes = plain[:-1] + [ci, plain[-1]]
@@ -1162,7 +1168,7 @@ def pack_weight_krsc(w, cpad=None):
 # kernel there by name -- tests and bench.py assert with it that the dispatch they checked is the dispatch they time.
 CONV_VARIANTS = {0: "none", 1: "c64_halo", 2: "stream", 3: "halo8", 4: "halo", 5: "dma2", 6: "dma3", 7: "tile_c128", 8: "tile_c64",
                  9: "tile_general", 10: "stem", 11: "block_tail", 12: "block_tail_proj", 13: "linear_wave", 14: "depthwise",
-                 15: "grouped", 16: "deconv"}
+                 15: "grouped", 16: "deconv", 17: "depthwise_dilated"}
 conv_variant_log = None
 
 
@@ -1335,6 +1341,35 @@ def dwconv2d_i8_resident(xq, wq, qbias, stride, padding, rs, ob, relu, clip=None
     q = torch.empty(N, P, Q, cpad, dtype=torch.int8, device=xq.device)
     _conv_i8("fq_dwconv2d_i8_resident", xq, wq, qbias, rs, C, (q.data_ptr(), cpad),
              (N, H, W, C, R, S, stride[0], stride[1], padding[0], padding[1], 1, 1), (int(ob),), (relu, clip))
+    return q
+
+
+def dwconv_dil_supported(C, R, S, stride, dilation, rs):
+    """True when fq_dwconv2d_dil_i8_resident takes an atrous depthwise layer of this geometry and shift (include/fq.h): 3x3 / 5x5,
+    stride 1, one dilation d on both axes with 2 <= d <= 64, every shift in [1, 16].  Never true where dwconv_supported is.  Pure
+    host arithmetic (no GPU needed); rs: an int or a ShiftVec."""
+    lo, hi = _bounds(rs)
+    return bool(lib().fq_dwconv2d_dil_i8_supported(int(C), int(R), int(S), int(stride[0]), int(stride[1]), int(dilation[0]),
+                                                   int(dilation[1]), lo, hi))
+
+
+def dwconv2d_dil_i8_resident(xq, wq, qbias, padding, dilation, rs, ob, relu, clip=None):
+    """fq_dwconv2d_dil_i8_resident (stride 1, dilation (d, d)): xq int8 [N,H,W,Cpad], wq int8 [R,S,Cpad] (pack_weight_dw), qbias
+    fp32 [C]; returns q int8 [N,P,Q,Cpad], the integers before DeQuantity(ob) with the ReLU folded in.  rs: an int, or a ShiftVec
+    (the _pcs entry point).  clip = (lo, hi): the `_act` entry point with that Sp range in place of relu."""
+    _need_cuda(xq, torch.int8, "fq_dwconv2d_dil_i8_resident")
+    _need_cuda(wq, torch.int8, "fq_dwconv2d_dil_i8_resident")
+    _need_cuda(qbias, torch.float32, "fq_dwconv2d_dil_i8_resident")
+    N, H, W, cpad = xq.shape
+    R, S, Cw = wq.shape
+    C = qbias.numel()
+    assert cpad == Cw and xq.is_contiguous() and wq.is_contiguous() and C <= cpad
+    P, Q = _out_hw(H, W, R, S, (1, 1), padding, dilation)
+    if P <= 0 or Q <= 0:
+        raise FqError("fq_dwconv2d_dil_i8_resident: the dilated kernel does not fit the padded image")
+    q = torch.empty(N, P, Q, cpad, dtype=torch.int8, device=xq.device)
+    _conv_i8("fq_dwconv2d_dil_i8_resident", xq, wq, qbias, rs, C, (q.data_ptr(), cpad),
+             (N, H, W, C, R, S, 1, 1, padding[0], padding[1], dilation[0], dilation[1]), (int(ob),), (relu, clip))
     return q
 
 

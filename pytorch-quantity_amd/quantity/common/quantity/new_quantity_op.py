@@ -212,6 +212,11 @@ def _launch_depthwise(self, conv, xq, wq, relu, **act):
                                         **act)
 
 
+def _launch_atrous(self, conv, xq, wq, relu, **act):
+    return _native.dwconv2d_dil_i8_resident(xq, wq, self.quantized_bias, conv.padding, conv.dilation, self._rs(), self.output_bit,
+                                            relu, **act)
+
+
 def _launch_grouped(self, conv, xq, wq, relu, **act):
     return _native.gconv2d_i8_resident(xq, wq, self.quantized_bias, conv.out_channels, conv.groups, conv.stride, conv.padding,
                                        self._rs(), self.output_bit, relu, **act)
@@ -235,6 +240,11 @@ class _IntegerSimLayer(nn.Module):
     # fq_gconv2d_i8_resident instead of the reference-shaped form below.  Same fp32 tensor, bit for bit.  Off by default;
     # settable per instance; resident.enable(..., grouped=True) plans such layers as integer producers / consumers.
     use_grouped_i8 = False
+    # True: an atrous depthwise nn.Conv2d (dilation (d, d), 2 <= d <= 64, stride 1, 3x3 / 5x5, padding up to the window's span)
+    # runs on fq_dwconv2d_dil_i8_resident instead of the reference-shaped form below.  Same fp32 tensor, bit for bit.  Off by
+    # default; settable per instance or class-wide.  It is also the plan's opt-in: resident.enable(..., depthwise=True) plans
+    # such a layer, like any depthwise one, only where this attribute is true (_Planning.is_dw).
+    use_atrous_i8 = False
 
     def _int8_ok(self, layer):
         if not self.use_int8_mfma or QUANTIZE_BIT != 8:
@@ -253,6 +263,33 @@ class _IntegerSimLayer(nn.Module):
             return False
         k = layer.kernel_size
         return _native.dwconv_supported(layer.out_channels, k[0], k[1], layer.stride, layer.dilation, self._rs())
+
+    def _atrous_left(self, layer):
+        """None when fq_dwconv2d_dil_i8_resident takes `layer` at this module's shift, else the reason it does not, as text.  (The
+        switch is not part of the answer: _atrous_ok asks it.)"""
+        if QUANTIZE_BIT != 8:
+            return "QUANTIZE_BIT is not 8"
+        if not isinstance(layer, nn.Conv2d) or not (layer.groups == layer.in_channels == layer.out_channels):
+            return "not a depthwise nn.Conv2d"
+        if layer.padding_mode != "zeros" or isinstance(layer.padding, str):
+            return "padding given as a string or in a non-zero mode"
+        if tuple(layer.stride) != (1, 1):
+            return "stride %s: the atrous kernel takes stride 1" % (tuple(layer.stride),)
+        d = layer.dilation[0]
+        if layer.dilation[0] != layer.dilation[1] or not 2 <= d <= 64:
+            return "dilation %s: one dilation in [2, 64] on both axes" % (tuple(layer.dilation),)
+        k = layer.kernel_size
+        if k[0] != k[1] or k[0] not in (3, 5):
+            return "kernel size %s: 3x3 or 5x5" % (tuple(k),)
+        if max(layer.padding) > d * (k[0] - 1):
+            return "padding %s beyond the window's span %d" % (tuple(layer.padding), d * (k[0] - 1))
+        if not _native.dwconv_dil_supported(layer.out_channels, k[0], k[1], layer.stride, layer.dilation, self._rs()):
+            return "a shift outside [1, 16]"
+        return None
+
+    def _atrous_ok(self, layer, switch=None):
+        """True when the switch (use_atrous_i8, or the caller's `switch`) is on and _atrous_left(layer) has nothing to say."""
+        return bool(self.use_atrous_i8 if switch is None else switch) and self._atrous_left(layer) is None
 
     def _grouped_ok(self, layer, switch=None):
         """True when `layer` is a grouped convolution that fq_gconv2d_i8_resident takes: the switch (use_grouped_i8, or the
@@ -361,7 +398,11 @@ class NewConv2d(_IntegerSimLayer):
         plan = self.__dict__.get("_resident")             # set by common.quantity.resident.enable()
         if (plan is not None and plan.depthwise) or (self.use_depthwise_i8 and self._depthwise_ok(conv)):
             wq = self._packed("_w_dw", conv, _pack_depthwise)
-            return self._forward_own_kernel(conv, input, plan, wq, wq.shape[-1], _launch_depthwise)
+            atrous = conv.dilation[0] > 1                 # (a planned layer: _Planning.is_dw asked _depthwise_ok or _atrous_ok)
+            return self._forward_own_kernel(conv, input, plan, wq, wq.shape[-1], _launch_atrous if atrous else _launch_depthwise)
+        if plan is None and self.use_atrous_i8 and self._atrous_ok(conv):
+            wq = self._packed("_w_dw", conv, _pack_depthwise)
+            return self._forward_own_kernel(conv, input, plan, wq, wq.shape[-1], _launch_atrous)
         if (plan is not None and plan.grouped) or (self.use_grouped_i8 and self._grouped_ok(conv)):
             return self._forward_own_kernel(conv, input, plan, self._packed("_w_gc", conv, _pack_grouped),
                                             _native.pad16(conv.in_channels), _launch_grouped)

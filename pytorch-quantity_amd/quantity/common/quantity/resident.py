@@ -951,8 +951,13 @@ class _Planning(object):
         """A depthwise layer that this plan runs on fq_dwconv2d_i8_resident: `depthwise=True` plans depthwise NewConv2d layers
         (groups == in_channels == out_channels, 3x3 / 5x5, stride 1 / 2, shift in [1, 16]: NewConv2d._depthwise_ok) as integer
         producers and consumers; without it they stay fp32 producers, as every other grouped convolution does.  The summary then
-        counts them as `resident_depthwise`."""
-        return self.sw.depthwise and isinstance(m, self.conv_type) and self.once(m) and m._depthwise_ok(m.Conv, True)
+        counts them as `resident_depthwise`.  An atrous depthwise layer (dilation 2 .. 64, stride 1: NewConv2d._atrous_ok) is
+        taken the same way, on fq_dwconv2d_dil_i8_resident, where the LAYER opts in (`use_atrous_i8`, off by default): it fuses
+        the ReLU / ReLU6 behind it, reads and emits int8 and stays out of a NewAdd's kernel like any depthwise producer, and
+        NewConv2d.forward picks the launch by the layer's dilation."""
+        if not (self.sw.depthwise and isinstance(m, self.conv_type) and self.once(m)):
+            return False
+        return m._depthwise_ok(m.Conv, True) or m._atrous_ok(m.Conv)
 
     def is_gc(self, m):
         """A grouped layer that this plan runs on fq_gconv2d_i8_resident: `grouped=True` plans grouped NewConv2d layers
