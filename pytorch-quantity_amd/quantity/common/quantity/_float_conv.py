@@ -2,7 +2,7 @@
 reference calls torch's Conv2d.forward -- pytorch_quantizer.py:288-296 inside the calibration forward, new_quantity_op.py:283-292
 inside TestConv): 1x1 layers on fq_conv1x1_f32, R x S layers with zero padding (the 3x3 ones) on fq_conv_kxk_f32, the 7x7
 stride-2 stem on fq_conv_stem_f32 (csrc/) -- every convolution of a ResNet -- and, opt-in, the depthwise 3x3 / 5x5 layers of a
-separable network on fq_dwconv_f32 (FQ_OWN_DWCONV=1) and the grouped 1x1 / 3x3 layers of a ResNeXt-shaped one on fq_gconv_f32
+separable network on fq_dwconv_f32 (FQ_OWN_DWCONV=1), its atrous depthwise layers on fq_dwconv_dil_f32 (FQ_OWN_ATROUS=1) and the grouped 1x1 / 3x3 layers of a ResNeXt-shaped one on fq_gconv_f32
 (FQ_OWN_GCONV=1) and the nn.ConvTranspose2d layers of a decoder on fq_deconv_f32 (FQ_OWN_DECONV=1), so that the calibration forward is deterministic
 and never enters the convolution library (whose first-use solver search costs seconds in a fresh process).  Which call qualifies, the
 weights in the kernels' layout (cached on the module), the once-per-process check of every module against an independent
@@ -19,7 +19,7 @@ import torch
 
 from . import _native
 
-__all__ = ["enabled", "depthwise_enabled", "grouped_enabled", "deconv_enabled", "kind", "weight", "runner", "dw_reference", "g_reference",
+__all__ = ["enabled", "depthwise_enabled", "atrous_enabled", "grouped_enabled", "deconv_enabled", "kind", "weight", "runner", "dw_reference", "g_reference",
            "dc_reference", "verified", "plain", "call", "call_qd",
            "call_linear_qd", "state", "is_verified", "is_off", "forget", "kernel_key", "own_convs", "TOL"]
 
@@ -94,6 +94,24 @@ def _dw_ok(m, h, w):
             and _window_ok(m, h, w, ((3, 3), (5, 5))))
 
 
+def atrous_enabled():
+    """FQ_OWN_ATROUS=1 (read at call time; default off): atrous depthwise layers run on fq_dwconv_dil_f32 instead of the library's
+    grouped convolution."""
+    return os.environ.get("FQ_OWN_ATROUS", "0") == "1"
+
+
+def _dwd_ok(m, h, w):
+    """Does fq_dwconv_dil_f32 take the nn.Conv2d m on an h x w plane?  Host arithmetic on the module alone (what
+    fq_dwconv_dil_f32_supported answers for the same numbers, plus what the C ABI cannot see: the bias, the padding mode)."""
+    k, s, p, d = m.kernel_size, m.stride, m.padding, m.dilation
+    if (m.groups < 1 or not m.groups == m.in_channels == m.out_channels or m.bias is None or isinstance(p, str)
+            or m.padding_mode != "zeros"):
+        return False
+    span = d[0] * (k[0] - 1)
+    return (tuple(k) in ((3, 3), (5, 5)) and tuple(s) == (1, 1) and d[0] == d[1] and 2 <= d[0] <= 64 and p[0] == p[1]
+            and 0 <= p[0] <= span and h >= 1 and w >= 1 and h + 2 * p[0] >= span + 1 and w + 2 * p[1] >= span + 1)
+
+
 def grouped_enabled():
     """FQ_OWN_GCONV=1 (read at call time; default off): grouped layers that are not depthwise run on fq_gconv_f32 instead of the
     library's grouped convolution."""
@@ -141,11 +159,11 @@ def _dc_ok(m, x):
 
 
 def _out_plane(m, h, w):
-    """Output pixels per image and channel of the nn.Conv2d m (no dilation, integer padding) on an h x w plane; 0 where the
-    padded plane is smaller than the kernel.  The kernels' hosts refuse 2^30 OUTPUT elements: the stem at stride 2 writes a
-    quarter of its input plane."""
-    ho = (h + 2 * m.padding[0] - m.kernel_size[0]) // m.stride[0] + 1
-    wo = (w + 2 * m.padding[1] - m.kernel_size[1]) // m.stride[1] + 1
+    """Output pixels per image and channel of the nn.Conv2d m (integer padding) on an h x w plane; 0 where the padded plane is
+    smaller than the dilated kernel.  The kernels' hosts refuse 2^30 OUTPUT elements: the stem at stride 2 writes a quarter of
+    its input plane."""
+    ho = (h + 2 * m.padding[0] - m.dilation[0] * (m.kernel_size[0] - 1) - 1) // m.stride[0] + 1
+    wo = (w + 2 * m.padding[1] - m.dilation[1] * (m.kernel_size[1] - 1) - 1) // m.stride[1] + 1
     return max(ho, 0) * max(wo, 0)
 
 
@@ -153,11 +171,13 @@ def _is_depthwise(m):
     return m.groups == m.in_channels
 
 
-def kind(m, x, wino=True, depthwise=None, grouped=None, deconv=None):
+def kind(m, x, wino=True, depthwise=None, grouped=None, deconv=None, atrous=None):
     """"c1" (fq_conv1x1_f32), "kxk" (fq_conv_kxk_f32), "wino" (fq_conv3x3_wino_f32: the Winograd form of the stride-1 3x3
     layers; wino=False or FQ_CONV_WINO=0 keeps them on "kxk"), "stem" (fq_conv_stem_f32), "dw" (fq_dwconv_f32: a depthwise 3x3 /
     5x5 layer, only with depthwise=True; None reads FQ_OWN_DWCONV), "g" (fq_gconv_f32: a grouped 1x1 / 3x3 layer with 4 .. 64
-    channels per group, only with grouped=True; None reads FQ_OWN_GCONV) or None: which own kernel takes this call of the nn.Conv2d m.
+    channels per group, only with grouped=True; None reads FQ_OWN_GCONV), "dwd" (fq_dwconv_dil_f32: a depthwise 3x3 / 5x5 layer
+    at stride 1 with a dilation of 2 .. 64, only with atrous=True; None reads FQ_OWN_ATROUS -- without it every dilated layer is
+    None) or None: which own kernel takes this call of the nn.Conv2d m.
     Every kind has the plain, the statistic and the QuanDequan form, so TestConv's two ways through a layer (fused with
     QuanDequan, or not when somebody watches the module) see the same sums.
     "dc" (fq_deconv_f32) for a `type(m) is nn.ConvTranspose2d` that kernel takes, only with deconv=True (None reads
@@ -168,10 +188,14 @@ def kind(m, x, wino=True, depthwise=None, grouped=None, deconv=None):
             return None
         return "dc" if _dc_ok(m, x) else None
     if (not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or m.weight.dtype != torch.float32 or m.bias is None
-            or is_off(m) or m.dilation != (1, 1) or m.stride[0] != m.stride[1] or x.dim() != 4
+            or is_off(m) or m.stride[0] != m.stride[1] or x.dim() != 4
             or not x.is_contiguous() or isinstance(m.padding, str) or m.padding[0] != m.padding[1] or m.padding_mode != "zeros"
             or x.numel() >= 2 ** 30 or x.shape[0] * m.out_channels * _out_plane(m, x.shape[2], x.shape[3]) >= 2 ** 30):
         return None
+    if tuple(m.dilation) != (1, 1):                             # only the atrous depthwise kernel takes a dilation
+        if m.groups == 1 or not _is_depthwise(m) or not (atrous_enabled() if atrous is None else atrous):
+            return None
+        return "dwd" if _dwd_ok(m, x.shape[2], x.shape[3]) else None
     if m.groups != 1:
         if not _is_depthwise(m):                                # (a depthwise layer is never "g": fewer than 4 channels per group)
             if not (grouped_enabled() if grouped is None else grouped):
@@ -201,11 +225,11 @@ def kind(m, x, wino=True, depthwise=None, grouped=None, deconv=None):
 
 def weight(m, k):
     """The weights in the layout the kernel reads (Wt [Cin][Cout] / the packed stem matrix / the transformed Winograd
-    weights), one entry per kind, rebuilt when the parameter was written to or replaced.  "dw" and "g": the parameter itself
-    ([C][1][R][S] and [K][C / groups][R][S] are the layouts fq_dwconv_f32 and fq_gconv_f32 read).  "dc": the transposed layer's
-    [Cin][Cout][R][S] as [(r*S + s)*Cin + c][Cout], fq_conv_kxk_f32's layout."""
+    weights), one entry per kind, rebuilt when the parameter was written to or replaced.  "dw", "dwd" and "g": the parameter itself
+    ([C][1][R][S] and [K][C / groups][R][S] are the layouts fq_dwconv_f32, fq_dwconv_dil_f32 and fq_gconv_f32 read).  "dc": the
+    transposed layer's [Cin][Cout][R][S] as [(r*S + s)*Cin + c][Cout], fq_conv_kxk_f32's layout."""
     w = m.weight
-    if k == "dw" or k == "g":
+    if k == "dw" or k == "dwd" or k == "g":
         return w.detach() if w.is_contiguous() else w.detach().contiguous()
     tag = (w._version, w.data_ptr(), w.device, _native.conv_sb_enabled())
     by_kind = state(m).setdefault("wt", {})
@@ -233,6 +257,8 @@ def runner(m, k, x):
         return lambda **kw: _native.conv_wino_f32(x, wq, m.bias, m.out_channels, **kw)
     if k == "dw":
         return lambda **kw: _native.dwconv_f32(x, wq, m.bias, m.kernel_size, s, m.padding[0], **kw)
+    if k == "dwd":
+        return lambda **kw: _native.dwconv_dil_f32(x, wq, m.bias, m.kernel_size, m.dilation[0], m.padding[0], **kw)
     if k == "g":
         return lambda **kw: _native.gconv_f32(x, wq, m.bias, m.groups, m.kernel_size, s, m.padding[0], **kw)
     if k == "dc":
@@ -240,13 +266,13 @@ def runner(m, k, x):
     return lambda **kw: _native.conv_stem_f32(x, wq, m.bias, m.out_channels, m.kernel_size, s, m.padding[0], **kw)
 
 
-def dw_reference(x, w, bias, kernel, stride, padding):
+def dw_reference(x, w, bias, kernel, stride, padding, dilation=1):
     """(reference, bound) of a depthwise convolution WITHOUT the convolution library, on CPU or CUDA tensors: unfold, then the
-    R * S products of each channel summed -- the same fp32 mathematics as fq_dwconv_f32 in another order; bound is the same
-    expression with absolute values, [n, C, L] both (L = Ho * Wo)."""
+    R * S products of each channel summed -- the same fp32 mathematics as fq_dwconv_f32 (fq_dwconv_dil_f32 with a dilation) in
+    another order; bound is the same expression with absolute values, [n, C, L] both (L = Ho * Wo)."""
     n, c = x.shape[0], x.shape[1]
     rs = kernel[0] * kernel[1]
-    cols = torch.nn.functional.unfold(x, kernel, padding=padding, stride=stride).view(n, c, rs, -1)
+    cols = torch.nn.functional.unfold(x, kernel, dilation=dilation, padding=padding, stride=stride).view(n, c, rs, -1)
     wv = w.reshape(1, c, rs, 1)
     ref = (cols * wv).sum(2) + bias.view(1, -1, 1)
     bound = (cols.abs() * wv.abs()).sum(2) + bias.abs().view(1, -1, 1)
@@ -328,7 +354,7 @@ def verified(m, run, x, k=None):
             continue
         if m.groups != 1:                                     # depthwise: no GEMM to lean on, the products summed per channel
             if _is_depthwise(m):
-                ref, bound = dw_reference(xh, m.weight, m.bias, m.kernel_size, m.stride, m.padding)
+                ref, bound = dw_reference(xh, m.weight, m.bias, m.kernel_size, m.stride, m.padding, m.dilation)
             else:                                               # grouped: one batched GEMM over the groups
                 ref, bound = g_reference(xh, m.weight, m.bias, m.groups, m.kernel_size, m.stride, m.padding)
             ok = ok & ((own[lo:hi].reshape(hi - lo, m.out_channels, -1) - ref).abs() <= TOL * bound).all()

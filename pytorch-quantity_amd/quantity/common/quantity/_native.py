@@ -258,6 +258,12 @@ def lib():
     L.fq_dwconv_f32.argtypes = [vp, vp, vp, vp, vp] + [ci] * 8 + [vp, vp, vp, vp]
     L.fq_dwconv_qd_f32.restype = ci
     L.fq_dwconv_qd_f32.argtypes = [vp, vp, vp, vp] + [ci] * 10 + [vp]
+    L.fq_dwconv_dil_f32_supported.restype = ci
+    L.fq_dwconv_dil_f32_supported.argtypes = [ci] * 11
+    L.fq_dwconv_dil_f32.restype = ci
+    L.fq_dwconv_dil_f32.argtypes = [vp, vp, vp, vp, vp] + [ci] * 8 + [vp, vp, vp, vp]
+    L.fq_dwconv_dil_qd_f32.restype = ci
+    L.fq_dwconv_dil_qd_f32.argtypes = [vp, vp, vp, vp] + [ci] * 10 + [vp]
     L.fq_gconv_f32_supported.restype = ci
     L.fq_gconv_f32_supported.argtypes = [ci] * 13
     L.fq_gconv_f32.restype = ci
@@ -323,7 +329,7 @@ def lib():
     L.fq_json_dump_i32.restype = ci
     L.fq_json_dump_i32.argtypes = [ctypes.c_char_p, vp, ci, vp, ci]
     # the `_act` siblings of the float convolutions: `float act_cap` behind relu_out
-    for name in ("fq_conv1x1_f32", "fq_conv1x1_sb_f32", "fq_conv_kxk_f32", "fq_dwconv_f32"):
+    for name in ("fq_conv1x1_f32", "fq_conv1x1_sb_f32", "fq_conv_kxk_f32", "fq_dwconv_f32", "fq_dwconv_dil_f32"):
         plain = getattr(L, name).argtypes
         getattr(L, name + "_act").restype = ci
         getattr(L, name + "_act").argtypes = plain[:5] + [ctypes.c_float] + plain[5:]
@@ -840,6 +846,30 @@ def dwconv_f32(x, w, bias, kernel, stride, pad, max_dev=None, interval_dev=None,
     shape = (N, C, (H + 2 * pd - R) // st + 1, (W + 2 * pd - S) // st + 1)
     return _conv_f32("fq_dwconv_f32", x, w.data_ptr(), bias, shape, (N, C, H, W, R, S, st, pd), max_dev, interval_dev, hist_dev, row,
                      relu_out, out, qd, act=act)
+
+
+def dwconv_dil_f32_supported(c, kernel, stride, padding, dilation, h, w):
+    """fq_dwconv_dil_f32_supported: does fq_dwconv_dil_f32 take this atrous depthwise geometry?  kernel, stride, padding,
+    dilation: (h, w) pairs."""
+    return bool(lib().fq_dwconv_dil_f32_supported(int(c), int(kernel[0]), int(kernel[1]), int(stride[0]), int(stride[1]),
+                                                  int(padding[0]), int(padding[1]), int(dilation[0]), int(dilation[1]), int(h),
+                                                  int(w)))
+
+
+def dwconv_dil_f32(x, w, bias, kernel, dilation, padding, max_dev=None, interval_dev=None, hist_dev=None, row=None, relu_out=None,
+                   out=None, qd=None, act=None):
+    """fq_dwconv_dil_f32: the float atrous depthwise convolution (groups == channels, stride 1, one `dilation` >= 2 and zero
+    padding `padding` on both axes) of x [N, C, H, W] with the module's own weight w [C, 1, R, S]; statistics / relu_out / out /
+    qd / act as in conv1x1_f32.  Returns y."""
+    _need_cuda(x, torch.float32, "fq_dwconv_dil_f32")
+    _need_cuda(w, torch.float32, "fq_dwconv_dil_f32")
+    R, S = int(kernel[0]), int(kernel[1])
+    assert x.dim() == 4 and x.is_contiguous() and w.is_contiguous() and tuple(w.shape) == (x.shape[1], 1, R, S)
+    N, C, H, W = x.shape
+    d, pd = int(dilation), int(padding)
+    shape = (N, C, H + 2 * pd - d * (R - 1), W + 2 * pd - d * (S - 1))
+    return _conv_f32("fq_dwconv_dil_f32", x, w.data_ptr(), bias, shape, (N, C, H, W, R, S, d, pd), max_dev, interval_dev, hist_dev,
+                     row, relu_out, out, qd, act=act)
 
 
 def gconv_f32_supported(c, k, groups, kernel, stride, pad, dilation, h, w):

@@ -19,8 +19,11 @@ same call fires -- and each fusion is a small state machine over them.  States l
 With Quantity.own_deconv (off by default) an nn.ConvTranspose2d that fq_deconv_f32 takes goes through the first row as kind "dc"
 (and the two conv -> ReLU rows behind an nn.ReLU); it is never deferred into an Eltwise.
 
+With Quantity.own_atrous (off by default) a depthwise nn.Conv2d with a dilation that fq_dwconv_dil_f32 takes goes through the first
+row as kind "dwd"; with the switch off every dilated layer keeps the library convolution + bias producer row.
+
 An out-of-place nn.ReLU6 takes the two conv -> ReLU rows as well when Quantity.fuse_relu6 is on (off by default), behind the own
-1x1 / R x S / depthwise convolutions only: the producer is told which of the two activations to write (`act=6.0`).
+1x1 / R x S / depthwise / atrous depthwise convolutions only: the producer is told which of the two activations to write (`act=6.0`).
 
 Every fusion falls back to the unfused form of the same arithmetic; none changes a table (tests/test_gpu_conv_add_fusion.py,
 tests/test_gpu_float_forward_kernels.py, tests/test_gpu_r50_tables.py)."""
@@ -42,7 +45,7 @@ class _StopForward(Exception):
 _RELU_VERIFIED = "relu_fusion_verified"
 _RELU6_VERIFIED = "relu6_fusion_verified"         # the clipped copy gave torch's nn.ReLU6 bits here
 # the own convolutions whose `_act` entry point writes nn.ReLU6's copy (_float_conv.kind): the others leave a ReLU6 to torch
-_RELU6_KINDS = ("c1", "kxk", "dw")
+_RELU6_KINDS = ("c1", "kxk", "dw", "dwd")
 _POOL_VERIFIED = "pool_verified"                  # the own pooling kernel gave torch's bits here
 _POOL_OFF = "pool_off"
 _FUSION_VERIFIED = "bias_fusion_verified"         # conv-without-bias + fq_bias_add_absmax_f32 == its forward
@@ -64,7 +67,8 @@ class _FusedForward(object):
         """Instance-level forwards for the duration of a GPU calibration (undo: del module.forward; returns the patched modules):
         every hooked nn.Conv2d with a bias leaves its work to its forward hook -- the whole convolution with the statistic in
         the epilogue where common.quantity._float_conv takes the layer (1x1, R x S with zero padding, the 7x7/2 stem, depthwise
-        3x3 / 5x5 with own_depthwise, grouped 1x1 / 3x3 with own_grouped -- never deferred into an Eltwise), else
+        3x3 / 5x5 with own_depthwise, atrous depthwise 3x3 / 5x5 with own_atrous, grouped 1x1 / 3x3 with own_grouped -- never
+        deferred into an Eltwise), else
         convolution-without-bias here and fq_bias_add_absmax_f32 / fq_bias_add_hist_f32 in the hook; `Eltwise` likewise
         (fq_add_absmax_f32 / fq_add_hist_f32); nn.MaxPool2d / a global nn.AvgPool2d run on fq_maxpool2d_f32 /
         fq_avgpool_global_f32; an out-of-place nn.ReLU fed by one of the producers hands out the copy that producer wrote."""
@@ -81,7 +85,7 @@ class _FusedForward(object):
                         or torch.is_grad_enabled()):
                     return torch.nn.Conv2d.forward(m, x)
                 if ctl.own_plain:                    # per-channel calibration: the convolution only, statistics by its hooks
-                    own = _float_conv.kind(m, x, depthwise=self.own_depthwise, grouped=self.own_grouped) if self.own_conv1x1 else None
+                    own = _float_conv.kind(m, x, depthwise=self.own_depthwise, grouped=self.own_grouped, atrous=self.own_atrous) if self.own_conv1x1 else None
                     if own is None:
                         return torch.nn.Conv2d.forward(m, x)
                     y = _float_conv.plain(m, own, x, check=ctl.own_plain != "unchecked")
@@ -92,15 +96,15 @@ class _FusedForward(object):
                     return torch.nn.Conv2d.forward(m, x)
                 if ctl.fuse_stat == "hist" and m not in ctl.fuse_verified:
                     return torch.nn.Conv2d.forward(m, x)    # pass 2 fuses verified modules only
-                own = _float_conv.kind(m, x, depthwise=self.own_depthwise, grouped=self.own_grouped) if self.own_conv1x1 else None
+                own = _float_conv.kind(m, x, depthwise=self.own_depthwise, grouped=self.own_grouped, atrous=self.own_atrous) if self.own_conv1x1 else None
                 if own is None and m not in ctl.fuse_warm and not _flag(m, _FUSION_VERIFIED):
                     ctl.fuse_warm.add(m)                 # the first call of a shape may run a one-off MIOpen kernel:
                     return torch.nn.Conv2d.forward(m, x)    # plain forward now, verification on the next batch
                 if own is not None:
                     ctl.fuse_bias = (m, (own, x))        # the hook of this very call runs the whole convolution
-                    s, p, k = m.stride[0], m.padding[0], m.kernel_size
-                    return torch.empty((x.shape[0], m.out_channels, (x.shape[2] + 2 * p - k[0]) // s + 1,
-                                        (x.shape[3] + 2 * p - k[1]) // s + 1), dtype=torch.float32, device=x.device)
+                    s, p, k, d = m.stride[0], m.padding[0], m.kernel_size, m.dilation      # (the window: d (k - 1) + 1)
+                    return torch.empty((x.shape[0], m.out_channels, (x.shape[2] + 2 * p - d[0] * (k[0] - 1) - 1) // s + 1,
+                                        (x.shape[3] + 2 * p - d[1] * (k[1] - 1) - 1) // s + 1), dtype=torch.float32, device=x.device)
                 y = m._conv_forward(x, m.weight, None)
                 ctl.fuse_bias = (m, x)                   # the hook of this very call adds the bias
                 return y

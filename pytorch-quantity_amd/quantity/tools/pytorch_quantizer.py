@@ -121,6 +121,9 @@ class Quantity(_FusedForward, _FileInputs):
     # Opt-in (FQ_OWN_DWCONV=1): the depthwise 3x3 / 5x5 layers of a separable network run on fq_dwconv_f32 with the statistic in
     # its epilogue, like the dense layers above, instead of the library's grouped convolution + the bias-add producer
     own_depthwise = _float_conv.depthwise_enabled()
+    # Opt-in (FQ_OWN_ATROUS=1): the atrous depthwise 3x3 / 5x5 layers of a DeepLabV3+-shaped network (stride 1, dilation 2 .. 64)
+    # run on fq_dwconv_dil_f32 in the same way; with fuse_relu6 the layer's nn.ReLU6 copy comes from its `_act` entry point
+    own_atrous = _float_conv.atrous_enabled()
     # Opt-in (FQ_OWN_GCONV=1): the grouped 1x1 / 3x3 layers of a ResNeXt-shaped network (4 .. 64 channels per group) run on
     # fq_gconv_f32 in the same way
     own_grouped = _float_conv.grouped_enabled()
