@@ -532,6 +532,48 @@ int fq_deconv_f32(const float* x, const float* wt, const float* bias, float* y, 
                   int Cout, int R, int S, int stride, int pad, int outpad, float* max_inout, const float* interval,
                   int64_t* hist_row, fq_stream_t stream);
 
+/* The atrous dense 3x3 float convolutions of the calibration forward (nn.Conv2d with groups 1 and a dilation: the 3x3s of layer3 /
+ * layer4 of a dilated ResNet and the dense ASPP branches of model/deeplab/DeepLabV3_fabu.py), on the fp32 matrix cores, same
+ * epilogue contract as fq_conv1x1_f32 (bias may be NULL; relu_out may be NULL; with relu_out given y may be NULL and its statistic
+ * is still taken; exactly one of {max_inout, hist_row + interval} or neither):
+ *   y[n][k][p][q] = bias[k] + sum_{c,r,s} W[k][c][r][s] * x[n][c][p - pad + r*dil][q - pad + s*dil]
+ * x: fp32 [N][Cin][H][W] contiguous; y / relu_out: fp32 [N][Cout][Ho][Wo], Ho = H + 2 pad - 2 dil.
+ * wq: fq_conv_kxk_f32's pack, fp32 [(r*3 + s)*Cin + c][Cout] (_native.pack_kxk_weight).  Pointers need only their type's
+ *   alignment: every store is a 4-byte store, so a y that is a view at an odd float offset is as good as any other.
+ * Taken (fq_conv_dil_f32_supported, host arithmetic only): groups 1, R == S == 3, stride 1, one dilation 2 <= dil <= 64 on both
+ *   axes, one zero padding 0 <= pad <= 2 dil on both axes, H + 2 pad >= 2 dil + 1 and the same for W, Cin % 16 == 0,
+ *   Cout % 4 == 0, and x, y and the weights below 2^30 elements.  FQ_ERR_UNSUPPORTED for everything else: callers keep the
+ *   library there.  FQ_ERR_INVALID_ARG for a null or misaligned pointer, sizes below 1, both statistics at once, a histogram
+ *   without its interval, or a bit / bitwidth outside fq_conv1x1_qd_f32's range.  Nothing is launched in either case.
+ * Numerics (part of the contract: the plain, abs-max, histogram, ReLU, `_act` and QuanDequan forms store the same bits).  Per
+ *   output:
+ *   acc = +0.0f
+ *   for c0 in 0, FQ_CONV_DIL_F32_CHUNK, .. < Cin:
+ *     for r in 0 .. 2:  for s in 0 .. 2:
+ *       for c in c0 .. c0 + FQ_CONV_DIL_F32_CHUNK - 1:
+ *         acc = fmaf(W[k][c][r][s], x[n][c][p - pad + r*dil][q - pad + s*dil], acc)
+ *   y = acc + bias[k]                      (bias == NULL: acc + 0.0f)
+ *   A tap whose source pixel lies outside the image is the operand +0.0f -- never a value loaded from a neighbouring row or
+ *   plane.  For a finite weight such a step leaves acc as it is (acc is never -0.0f), so the kernel may leave it out: it does
+ *   for a tap that is dead for every pixel of a tile, and runs a partly live tap against zeros.  A NON-FINITE weight on a tap
+ *   outside the image therefore gives either NaN (the step was taken: Inf * 0) or the chain without the step, depending on
+ *   the tile the output falls into; the contract covers finite weights only.  No K split, no workspace, no float atomics other
+ *   than the abs-max publish.  The value depends on neither N nor the tile or lane: image i of a batch gets the bits of that
+ *   image alone.  Exact zeros are not counted by the histogram; the abs-max ignores NaN.
+ * fq_conv_dil_f32_act: relu_out = clamp(y, 0, act_cap) as the `_act` entry points above (nn.ReLU6: act_cap = 6).
+ * fq_conv_dil_qd_f32: TestConv.forward of such a layer in one kernel, fq_quandequan_f32(bit, bitwidth) of the value
+ *   fq_conv_dil_f32 would have stored. */
+#define FQ_CONV_DIL_F32_CHUNK 8
+int fq_conv_dil_f32_supported(int Cin, int Cout, int groups, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                              int dil_h, int dil_w, int H, int W);
+int fq_conv_dil_f32(const float* x, const float* wq, const float* bias, float* y, float* relu_out, int N, int Cin, int H, int W,
+                    int Cout, int dil, int pad, float* max_inout, const float* interval, int64_t* hist_row, fq_stream_t stream);
+int fq_conv_dil_f32_act(const float* x, const float* wq, const float* bias, float* y, float* relu_out, float act_cap, int N, int Cin,
+                        int H, int W, int Cout, int dil, int pad, float* max_inout, const float* interval, int64_t* hist_row,
+                        fq_stream_t stream);
+int fq_conv_dil_qd_f32(const float* x, const float* wq, const float* bias, float* y, int N, int Cin, int H, int W, int Cout, int dil,
+                       int pad, int bit, int bitwidth, fq_stream_t stream);
+
 /* The last 1x1 convolution of a residual block together with the `Eltwise` that consumes it and the ReLU behind that
  * (fabu_layer.py:5-11 called from the model the reference runs at pytorch_quantizer.py:288-296), calibration pass 1, in ONE
  * kernel:  v = conv1x1(x) + bias  (abs-max folded into *max_y; stored to y unless y is NULL),  s = v + res  (abs-max folded

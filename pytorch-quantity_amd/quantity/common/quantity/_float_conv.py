@@ -2,7 +2,8 @@
 reference calls torch's Conv2d.forward -- pytorch_quantizer.py:288-296 inside the calibration forward, new_quantity_op.py:283-292
 inside TestConv): 1x1 layers on fq_conv1x1_f32, R x S layers with zero padding (the 3x3 ones) on fq_conv_kxk_f32, the 7x7
 stride-2 stem on fq_conv_stem_f32 (csrc/) -- every convolution of a ResNet -- and, opt-in, the depthwise 3x3 / 5x5 layers of a
-separable network on fq_dwconv_f32 (FQ_OWN_DWCONV=1), its atrous depthwise layers on fq_dwconv_dil_f32 (FQ_OWN_ATROUS=1) and the grouped 1x1 / 3x3 layers of a ResNeXt-shaped one on fq_gconv_f32
+separable network on fq_dwconv_f32 (FQ_OWN_DWCONV=1), its atrous depthwise layers on fq_dwconv_dil_f32 (FQ_OWN_ATROUS=1), the atrous
+dense 3x3 layers of a dilated ResNet or a DeepLabV3 head on fq_conv_dil_f32 (FQ_OWN_DILATED=1) and the grouped 1x1 / 3x3 layers of a ResNeXt-shaped one on fq_gconv_f32
 (FQ_OWN_GCONV=1) and the nn.ConvTranspose2d layers of a decoder on fq_deconv_f32 (FQ_OWN_DECONV=1), so that the calibration forward is deterministic
 and never enters the convolution library (whose first-use solver search costs seconds in a fresh process).  Which call qualifies, the
 weights in the kernels' layout (cached on the module), the once-per-process check of every module against an independent
@@ -19,8 +20,8 @@ import torch
 
 from . import _native
 
-__all__ = ["enabled", "depthwise_enabled", "atrous_enabled", "grouped_enabled", "deconv_enabled", "kind", "weight", "runner", "dw_reference", "g_reference",
-           "dc_reference", "verified", "plain", "call", "call_qd",
+__all__ = ["enabled", "depthwise_enabled", "atrous_enabled", "dilated_enabled", "grouped_enabled", "deconv_enabled", "kind", "weight", "runner", "dw_reference", "g_reference",
+           "dc_reference", "kd_reference", "verified", "plain", "call", "call_qd",
            "call_linear_qd", "state", "is_verified", "is_off", "forget", "kernel_key", "own_convs", "TOL"]
 
 TOL = 1e-5                                      # |own - torch| <= TOL * (|W| * |x| + |b|): summation order only
@@ -112,6 +113,23 @@ def _dwd_ok(m, h, w):
             and 0 <= p[0] <= span and h >= 1 and w >= 1 and h + 2 * p[0] >= span + 1 and w + 2 * p[1] >= span + 1)
 
 
+def dilated_enabled():
+    """FQ_OWN_DILATED=1 (read at call time; default off): atrous dense 3x3 layers run on fq_conv_dil_f32 instead of the library's
+    convolution."""
+    return os.environ.get("FQ_OWN_DILATED", "0") == "1"
+
+
+def _kd_ok(m, h, w):
+    """Does fq_conv_dil_f32 take the nn.Conv2d m on an h x w plane?  Host arithmetic on the module alone (what
+    fq_conv_dil_f32_supported answers for the same numbers, plus what the C ABI cannot see: the bias, the padding mode)."""
+    k, s, p, d = m.kernel_size, m.stride, m.padding, m.dilation
+    if m.groups != 1 or m.bias is None or isinstance(p, str) or m.padding_mode != "zeros":
+        return False
+    return (tuple(k) == (3, 3) and tuple(s) == (1, 1) and d[0] == d[1] and 2 <= d[0] <= 64 and p[0] == p[1]
+            and 0 <= p[0] <= 2 * d[0] and h >= 1 and w >= 1 and h + 2 * p[0] >= 2 * d[0] + 1 and w + 2 * p[1] >= 2 * d[0] + 1
+            and m.in_channels % 16 == 0 and m.out_channels % 4 == 0 and 9 * m.in_channels * m.out_channels < 2 ** 30)
+
+
 def grouped_enabled():
     """FQ_OWN_GCONV=1 (read at call time; default off): grouped layers that are not depthwise run on fq_gconv_f32 instead of the
     library's grouped convolution."""
@@ -171,13 +189,14 @@ def _is_depthwise(m):
     return m.groups == m.in_channels
 
 
-def kind(m, x, wino=True, depthwise=None, grouped=None, deconv=None, atrous=None):
+def kind(m, x, wino=True, depthwise=None, grouped=None, deconv=None, atrous=None, dilated=None):
     """"c1" (fq_conv1x1_f32), "kxk" (fq_conv_kxk_f32), "wino" (fq_conv3x3_wino_f32: the Winograd form of the stride-1 3x3
     layers; wino=False or FQ_CONV_WINO=0 keeps them on "kxk"), "stem" (fq_conv_stem_f32), "dw" (fq_dwconv_f32: a depthwise 3x3 /
     5x5 layer, only with depthwise=True; None reads FQ_OWN_DWCONV), "g" (fq_gconv_f32: a grouped 1x1 / 3x3 layer with 4 .. 64
     channels per group, only with grouped=True; None reads FQ_OWN_GCONV), "dwd" (fq_dwconv_dil_f32: a depthwise 3x3 / 5x5 layer
-    at stride 1 with a dilation of 2 .. 64, only with atrous=True; None reads FQ_OWN_ATROUS -- without it every dilated layer is
-    None) or None: which own kernel takes this call of the nn.Conv2d m.
+    at stride 1 with a dilation of 2 .. 64, only with atrous=True; None reads FQ_OWN_ATROUS -- without it every dilated depthwise layer
+    is None), "kd" (fq_conv_dil_f32: a dense 3x3 layer at stride 1 with a dilation of 2 .. 64, Cin % 16 == 0 and Cout % 4 == 0, only
+    with dilated=True; None reads FQ_OWN_DILATED -- without it every dilated dense layer is None) or None: which own kernel takes this call of the nn.Conv2d m.
     Every kind has the plain, the statistic and the QuanDequan form, so TestConv's two ways through a layer (fused with
     QuanDequan, or not when somebody watches the module) see the same sums.
     "dc" (fq_deconv_f32) for a `type(m) is nn.ConvTranspose2d` that kernel takes, only with deconv=True (None reads
@@ -192,8 +211,12 @@ def kind(m, x, wino=True, depthwise=None, grouped=None, deconv=None, atrous=None
             or not x.is_contiguous() or isinstance(m.padding, str) or m.padding[0] != m.padding[1] or m.padding_mode != "zeros"
             or x.numel() >= 2 ** 30 or x.shape[0] * m.out_channels * _out_plane(m, x.shape[2], x.shape[3]) >= 2 ** 30):
         return None
-    if tuple(m.dilation) != (1, 1):                             # only the atrous depthwise kernel takes a dilation
-        if m.groups == 1 or not _is_depthwise(m) or not (atrous_enabled() if atrous is None else atrous):
+    if tuple(m.dilation) != (1, 1):                             # only the two atrous kernels take a dilation
+        if m.groups == 1:
+            if not (dilated_enabled() if dilated is None else dilated):
+                return None
+            return "kd" if _kd_ok(m, x.shape[2], x.shape[3]) else None
+        if not _is_depthwise(m) or not (atrous_enabled() if atrous is None else atrous):
             return None
         return "dwd" if _dwd_ok(m, x.shape[2], x.shape[3]) else None
     if m.groups != 1:
@@ -227,7 +250,8 @@ def weight(m, k):
     """The weights in the layout the kernel reads (Wt [Cin][Cout] / the packed stem matrix / the transformed Winograd
     weights), one entry per kind, rebuilt when the parameter was written to or replaced.  "dw", "dwd" and "g": the parameter itself
     ([C][1][R][S] and [K][C / groups][R][S] are the layouts fq_dwconv_f32, fq_dwconv_dil_f32 and fq_gconv_f32 read).  "dc": the
-    transposed layer's [Cin][Cout][R][S] as [(r*S + s)*Cin + c][Cout], fq_conv_kxk_f32's layout."""
+    transposed layer's [Cin][Cout][R][S] as [(r*S + s)*Cin + c][Cout], fq_conv_kxk_f32's layout.  "kd": fq_conv_kxk_f32's pack of the
+    layer's own weight, under its own key."""
     w = m.weight
     if k == "dw" or k == "dwd" or k == "g":
         return w.detach() if w.is_contiguous() else w.detach().contiguous()
@@ -239,7 +263,7 @@ def weight(m, k):
         packed = (_native.pack_sb_weight(w) if sb                # (opt-in: the split-bf16 form of the 1x1 kernels takes this pack)
                   else w.detach().permute(2, 3, 0, 1).reshape(w.shape[2] * w.shape[3] * w.shape[0], w.shape[1]).contiguous() if k == "dc"
                   else w.detach().view(w.shape[0], w.shape[1]).t().contiguous() if k == "c1"
-                  else _native.pack_kxk_weight(w) if k == "kxk"
+                  else _native.pack_kxk_weight(w) if k == "kxk" or k == "kd"
                   else _native.pack_wino_weight(w) if k == "wino" else _native.pack_stem_weight(w))
         cached = (tag, packed)
         by_kind[k] = cached
@@ -259,6 +283,8 @@ def runner(m, k, x):
         return lambda **kw: _native.dwconv_f32(x, wq, m.bias, m.kernel_size, s, m.padding[0], **kw)
     if k == "dwd":
         return lambda **kw: _native.dwconv_dil_f32(x, wq, m.bias, m.kernel_size, m.dilation[0], m.padding[0], **kw)
+    if k == "kd":
+        return lambda **kw: _native.conv_dil_f32(x, wq, m.bias, m.dilation[0], m.padding[0], **kw)
     if k == "g":
         return lambda **kw: _native.gconv_f32(x, wq, m.bias, m.groups, m.kernel_size, s, m.padding[0], **kw)
     if k == "dc":
@@ -276,6 +302,18 @@ def dw_reference(x, w, bias, kernel, stride, padding, dilation=1):
     wv = w.reshape(1, c, rs, 1)
     ref = (cols * wv).sum(2) + bias.view(1, -1, 1)
     bound = (cols.abs() * wv.abs()).sum(2) + bias.abs().view(1, -1, 1)
+    return ref, bound
+
+
+def kd_reference(x, w, bias, dilation, padding):
+    """(reference, bound) of an atrous dense convolution (groups 1, stride 1) WITHOUT the convolution library, on CPU or CUDA
+    tensors: F.unfold with the dilation, one matmul with the weight seen as [Cout, Cin * R * S], the bias -- the same fp32
+    mathematics as fq_conv_dil_f32 in another order; bound is the same expression with absolute values, [n, Cout, L] both
+    (L = Ho * Wo)."""
+    cols = torch.nn.functional.unfold(x, tuple(w.shape[2:]), dilation=dilation, padding=padding)
+    w2 = w.reshape(w.shape[0], -1)
+    ref = torch.matmul(w2, cols) + bias.view(1, -1, 1)
+    bound = torch.matmul(w2.abs(), cols.abs()) + bias.abs().view(1, -1, 1)
     return ref, bound
 
 
@@ -357,6 +395,11 @@ def verified(m, run, x, k=None):
                 ref, bound = dw_reference(xh, m.weight, m.bias, m.kernel_size, m.stride, m.padding, m.dilation)
             else:                                               # grouped: one batched GEMM over the groups
                 ref, bound = g_reference(xh, m.weight, m.bias, m.groups, m.kernel_size, m.stride, m.padding)
+            ok = ok & ((own[lo:hi].reshape(hi - lo, m.out_channels, -1) - ref).abs() <= TOL * bound).all()
+            del ref, bound
+            continue
+        if tuple(m.dilation) != (1, 1):                         # atrous dense: unfold with the dilation, one GEMM
+            ref, bound = kd_reference(xh, m.weight, m.bias, m.dilation, m.padding)
             ok = ok & ((own[lo:hi].reshape(hi - lo, m.out_channels, -1) - ref).abs() <= TOL * bound).all()
             del ref, bound
             continue

@@ -264,6 +264,12 @@ def lib():
     L.fq_dwconv_dil_f32.argtypes = [vp, vp, vp, vp, vp] + [ci] * 8 + [vp, vp, vp, vp]
     L.fq_dwconv_dil_qd_f32.restype = ci
     L.fq_dwconv_dil_qd_f32.argtypes = [vp, vp, vp, vp] + [ci] * 10 + [vp]
+    L.fq_conv_dil_f32_supported.restype = ci
+    L.fq_conv_dil_f32_supported.argtypes = [ci] * 13
+    L.fq_conv_dil_f32.restype = ci
+    L.fq_conv_dil_f32.argtypes = [vp, vp, vp, vp, vp] + [ci] * 7 + [vp, vp, vp, vp]
+    L.fq_conv_dil_qd_f32.restype = ci
+    L.fq_conv_dil_qd_f32.argtypes = [vp, vp, vp, vp] + [ci] * 9 + [vp]
     L.fq_gconv_f32_supported.restype = ci
     L.fq_gconv_f32_supported.argtypes = [ci] * 13
     L.fq_gconv_f32.restype = ci
@@ -329,7 +335,7 @@ def lib():
     L.fq_json_dump_i32.restype = ci
     L.fq_json_dump_i32.argtypes = [ctypes.c_char_p, vp, ci, vp, ci]
     # the `_act` siblings of the float convolutions: `float act_cap` behind relu_out
-    for name in ("fq_conv1x1_f32", "fq_conv1x1_sb_f32", "fq_conv_kxk_f32", "fq_dwconv_f32", "fq_dwconv_dil_f32"):
+    for name in ("fq_conv1x1_f32", "fq_conv1x1_sb_f32", "fq_conv_kxk_f32", "fq_dwconv_f32", "fq_dwconv_dil_f32", "fq_conv_dil_f32"):
         plain = getattr(L, name).argtypes
         getattr(L, name + "_act").restype = ci
         getattr(L, name + "_act").argtypes = plain[:5] + [ctypes.c_float] + plain[5:]
@@ -869,6 +875,31 @@ def dwconv_dil_f32(x, w, bias, kernel, dilation, padding, max_dev=None, interval
     d, pd = int(dilation), int(padding)
     shape = (N, C, H + 2 * pd - d * (R - 1), W + 2 * pd - d * (S - 1))
     return _conv_f32("fq_dwconv_dil_f32", x, w.data_ptr(), bias, shape, (N, C, H, W, R, S, d, pd), max_dev, interval_dev, hist_dev,
+                     row, relu_out, out, qd, act=act)
+
+
+def conv_dil_f32_supported(cin, cout, groups, kernel, stride, padding, dilation, h, w):
+    """fq_conv_dil_f32_supported: does fq_conv_dil_f32 take this atrous dense geometry?  kernel, stride, padding, dilation:
+    (h, w) pairs."""
+    return bool(lib().fq_conv_dil_f32_supported(int(cin), int(cout), int(groups), int(kernel[0]), int(kernel[1]), int(stride[0]),
+                                                int(stride[1]), int(padding[0]), int(padding[1]), int(dilation[0]),
+                                                int(dilation[1]), int(h), int(w)))
+
+
+def conv_dil_f32(x, wq, bias, dilation, padding, max_dev=None, interval_dev=None, hist_dev=None, row=None, relu_out=None, out=None,
+                 qd=None, act=None):
+    """fq_conv_dil_f32: the float atrous dense 3x3 convolution (groups 1, stride 1, one `dilation` >= 2 and zero padding `padding`
+    on both axes) of x [N, Cin, H, W] with the weights packed by pack_kxk_weight [9 Cin, Cout]; statistics / relu_out / out / qd /
+    act as in conv1x1_f32.  Returns y."""
+    _need_cuda(x, torch.float32, "fq_conv_dil_f32")
+    _need_cuda(wq, torch.float32, "fq_conv_dil_f32")
+    assert x.dim() == 4 and x.is_contiguous() and wq.dim() == 2 and wq.is_contiguous() and wq.shape[0] == 9 * x.shape[1]
+    N, Cin, H, W = x.shape
+    Cout, d, pd = int(wq.shape[1]), int(dilation), int(padding)
+    if not conv_dil_f32_supported(Cin, Cout, 1, (3, 3), (1, 1), (pd, pd), (d, d), H, W):    # (before the output is shaped: its plane
+        _check(-4, "fq_conv_dil_f32")                                                         #  may not exist; FQ_ERR_UNSUPPORTED)
+    shape = (N, Cout, H + 2 * pd - 2 * d, W + 2 * pd - 2 * d)
+    return _conv_f32("fq_conv_dil_f32", x, wq.data_ptr(), bias, shape, (N, Cin, H, W, Cout, d, pd), max_dev, interval_dev, hist_dev,
                      row, relu_out, out, qd, act=act)
 
 

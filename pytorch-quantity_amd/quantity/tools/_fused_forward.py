@@ -22,6 +22,10 @@ With Quantity.own_deconv (off by default) an nn.ConvTranspose2d that fq_deconv_f
 With Quantity.own_atrous (off by default) a depthwise nn.Conv2d with a dilation that fq_dwconv_dil_f32 takes goes through the first
 row as kind "dwd"; with the switch off every dilated layer keeps the library convolution + bias producer row.
 
+With Quantity.own_dilated (off by default) a dense 3x3 nn.Conv2d with a dilation that fq_conv_dil_f32 takes goes through the first
+row as kind "kd" (and the two conv -> ReLU rows behind an nn.ReLU); with the switch off it keeps the library convolution + bias
+producer row.
+
 An out-of-place nn.ReLU6 takes the two conv -> ReLU rows as well when Quantity.fuse_relu6 is on (off by default), behind the own
 1x1 / R x S / depthwise / atrous depthwise convolutions only: the producer is told which of the two activations to write (`act=6.0`).
 
@@ -45,7 +49,7 @@ class _StopForward(Exception):
 _RELU_VERIFIED = "relu_fusion_verified"
 _RELU6_VERIFIED = "relu6_fusion_verified"         # the clipped copy gave torch's nn.ReLU6 bits here
 # the own convolutions whose `_act` entry point writes nn.ReLU6's copy (_float_conv.kind): the others leave a ReLU6 to torch
-_RELU6_KINDS = ("c1", "kxk", "dw", "dwd")
+_RELU6_KINDS = ("c1", "kxk", "dw", "dwd", "kd")
 _POOL_VERIFIED = "pool_verified"                  # the own pooling kernel gave torch's bits here
 _POOL_OFF = "pool_off"
 _FUSION_VERIFIED = "bias_fusion_verified"         # conv-without-bias + fq_bias_add_absmax_f32 == its forward
@@ -67,7 +71,7 @@ class _FusedForward(object):
         """Instance-level forwards for the duration of a GPU calibration (undo: del module.forward; returns the patched modules):
         every hooked nn.Conv2d with a bias leaves its work to its forward hook -- the whole convolution with the statistic in
         the epilogue where common.quantity._float_conv takes the layer (1x1, R x S with zero padding, the 7x7/2 stem, depthwise
-        3x3 / 5x5 with own_depthwise, atrous depthwise 3x3 / 5x5 with own_atrous, grouped 1x1 / 3x3 with own_grouped -- never
+        3x3 / 5x5 with own_depthwise, atrous depthwise 3x3 / 5x5 with own_atrous, atrous dense 3x3 with own_dilated, grouped 1x1 / 3x3 with own_grouped -- never
         deferred into an Eltwise), else
         convolution-without-bias here and fq_bias_add_absmax_f32 / fq_bias_add_hist_f32 in the hook; `Eltwise` likewise
         (fq_add_absmax_f32 / fq_add_hist_f32); nn.MaxPool2d / a global nn.AvgPool2d run on fq_maxpool2d_f32 /
@@ -85,7 +89,7 @@ class _FusedForward(object):
                         or torch.is_grad_enabled()):
                     return torch.nn.Conv2d.forward(m, x)
                 if ctl.own_plain:                    # per-channel calibration: the convolution only, statistics by its hooks
-                    own = _float_conv.kind(m, x, depthwise=self.own_depthwise, grouped=self.own_grouped, atrous=self.own_atrous) if self.own_conv1x1 else None
+                    own = _float_conv.kind(m, x, depthwise=self.own_depthwise, grouped=self.own_grouped, atrous=self.own_atrous, dilated=self.own_dilated) if self.own_conv1x1 else None
                     if own is None:
                         return torch.nn.Conv2d.forward(m, x)
                     y = _float_conv.plain(m, own, x, check=ctl.own_plain != "unchecked")
@@ -96,7 +100,7 @@ class _FusedForward(object):
                     return torch.nn.Conv2d.forward(m, x)
                 if ctl.fuse_stat == "hist" and m not in ctl.fuse_verified:
                     return torch.nn.Conv2d.forward(m, x)    # pass 2 fuses verified modules only
-                own = _float_conv.kind(m, x, depthwise=self.own_depthwise, grouped=self.own_grouped, atrous=self.own_atrous) if self.own_conv1x1 else None
+                own = _float_conv.kind(m, x, depthwise=self.own_depthwise, grouped=self.own_grouped, atrous=self.own_atrous, dilated=self.own_dilated) if self.own_conv1x1 else None
                 if own is None and m not in ctl.fuse_warm and not _flag(m, _FUSION_VERIFIED):
                     ctl.fuse_warm.add(m)                 # the first call of a shape may run a one-off MIOpen kernel:
                     return torch.nn.Conv2d.forward(m, x)    # plain forward now, verification on the next batch

@@ -124,6 +124,9 @@ class Quantity(_FusedForward, _FileInputs):
     # Opt-in (FQ_OWN_ATROUS=1): the atrous depthwise 3x3 / 5x5 layers of a DeepLabV3+-shaped network (stride 1, dilation 2 .. 64)
     # run on fq_dwconv_dil_f32 in the same way; with fuse_relu6 the layer's nn.ReLU6 copy comes from its `_act` entry point
     own_atrous = _float_conv.atrous_enabled()
+    # Opt-in (FQ_OWN_DILATED=1): the atrous dense 3x3 layers of a dilated ResNet or a DeepLabV3 head (stride 1, dilation 2 .. 64,
+    # Cin % 16 == 0) run on fq_conv_dil_f32 in the same way, live taps only
+    own_dilated = _float_conv.dilated_enabled()
     # Opt-in (FQ_OWN_GCONV=1): the grouped 1x1 / 3x3 layers of a ResNeXt-shaped network (4 .. 64 channels per group) run on
     # fq_gconv_f32 in the same way
     own_grouped = _float_conv.grouped_enabled()
